@@ -511,6 +511,58 @@ def cpu_baseline(lm, eos, y0, region0, dt, kits_per_newton, budget_s=45.0, gpu_s
     return out
 
 
+DUMP_BYTES = 64 * 10**6     # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SEED = 20251015
+
+
+def cell_keys(lm, dims):
+    """a global name for every owned cell, independent of partition and cell order: the (fracture) cell's natural index
+    (k * ny + j) * nx + i, + level x n_global for MINC matrix cells"""
+    ijk = np.asarray(lm.owned_ijk, dtype=np.int64)
+    key = (ijk[:, 2] * dims[1] + ijk[:, 1]) * dims[0] + ijk[:, 0]
+    lev = lm.extras.get("minc_level")
+    if lev is not None:
+        key = key + np.asarray(lev, dtype=np.int64) * int(np.prod(dims))
+    return key
+
+
+def dump_outputs(path, lm, dims, n_cells, bs, y, f, regions, last, dist, rank):
+    """What the timed path computed in its last Newton step, as a caller of wai_newton_step receives it: the state y, the
+    residual f and the cells' phase regions (rows of every owned cell, sorted by cell_keys), and the step's record. Above
+    DUMP_BYTES a fixed, seeded sample of the cells is written, the same cells whatever the partition or build."""
+    per_cell = 8 * (2 * bs + 2)          # solution + residual rows, region, key (float64)
+    keys = cell_keys(lm, dims)
+    room = DUMP_BYTES - 5 * 4096         # (the files' headers)
+    sampled = n_cells * per_cell > room
+    if sampled:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_cells, room // per_cell, replace=False))
+        rows = np.nonzero(np.isin(keys, pick))[0]
+    else:
+        rows = np.arange(lm.n_owned)
+    part = (keys[rows], y.reshape(-1, bs)[rows], f.reshape(-1, bs)[rows], np.asarray(regions)[rows])
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, part)
+    else:
+        parts = [part]
+    if rank != 0:
+        return
+    key = np.concatenate([q[0] for q in parts])
+    # every sampled (or every) cell found on exactly one rank: the keys are dense in 0 .. n_cells - 1
+    assert key.size == (room // per_cell if sampled else n_cells) and np.unique(key).size == key.size, (key.size, n_cells)
+    order = np.argsort(key, kind="stable")
+    os.makedirs(path, exist_ok=True)
+    out = {"cell": key[order].astype(np.float64),
+           "solution": np.concatenate([q[1] for q in parts])[order].astype(np.float64),
+           "residual": np.concatenate([q[2] for q in parts])[order].astype(np.float64),
+           "region": np.concatenate([q[3] for q in parts])[order].astype(np.float64),
+           # time step, dt, Newton iteration, Krylov iterations, reason, max scaled residual
+           "newton_step": np.asarray(last, dtype=np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    log("outputs of the last timed step: %d cells of %d in %s" % (key.size, n_cells, path))
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (one per device)."""
     import torch
@@ -569,7 +621,11 @@ def main():
     ap.add_argument("--profile", action="store_true", help="per-kernel-class HIP event timing (serialises)")
     ap.add_argument("--micro-only", action="store_true",
                     help="kernel A/B runs: assemble one Jacobian, set up the preconditioner, print the kernel microbench, exit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a))
@@ -774,6 +830,10 @@ def main():
     ls1 = sim.launch_stats()
     cs1 = sim.comm_stats()
     l1 = len(drv.log)
+    if a.dump_outputs:      # before the untimed tail moves the state on
+        n_dof = lm.n_owned * bs
+        dump_outputs(a.dump_outputs, lm, dims, n_cells, bs, drv.y[:n_dof].cpu().numpy(), drv.f[:n_dof].cpu().numpy(),
+                     sim.regions()[: lm.n_owned], drv.log[-1][:6], dist, rank)
     while drv.it >= 0:      # (untimed) how the last timed try ends
         drv.newton_step()
     if dist is not None:

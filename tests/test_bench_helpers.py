@@ -62,3 +62,44 @@ def test_byte_counts_and_host_description():
     assert b.resolve_brick_order("auto", (100, 100, 100), (1, 1, 1), (16, 16, 2)) == "x"
     assert b.resolve_brick_order("auto", (172, 172, 170), (1, 1, 1), (8, 4, 2)) == "tile4x4"
     assert b.resolve_brick_order("z", (216, 216, 216), (1, 1, 1), (16, 16, 2)) == "z"
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays sorted by the cells' global names, at most DUMP_BYTES in all; above that a seeded
+    sample of cells that does not depend on how the cells are numbered"""
+    import numpy as np
+    from waiwera_amd import mesh as M
+    b = _bench()
+    dims, bs = (8, 6, 4), 2
+    g = M.StructuredGrid(dims, brick=(4, 3, 2))
+    lm = g.local_mesh(0, top_bc=([1.0e5, 20.0], 1))
+    keys = b.cell_keys(lm, dims)
+    assert np.array_equal(np.sort(keys), np.arange(g.n_global))
+    y = np.repeat(keys.astype(np.float64), bs) + np.tile([0.0, 0.5], lm.n_owned)
+    f = -y
+    regions = (keys % 3).astype(np.int32)
+    last = [4, 1.0e4, 2, 17, 0, 3.5e-3]
+
+    def files(d):
+        return {n[:-4]: np.load(os.path.join(d, n)) for n in os.listdir(d)}
+
+    b.dump_outputs(str(tmp_path / "all"), lm, dims, g.n_global, bs, y, f, regions, last, None, 0)
+    out = files(tmp_path / "all")
+    assert set(out) == {"cell", "solution", "residual", "region", "newton_step"}
+    assert all(v.dtype == np.float64 for v in out.values())
+    assert np.array_equal(out["cell"], np.arange(g.n_global))
+    assert np.array_equal(out["solution"][:, 0], out["cell"]) and np.array_equal(out["residual"], -out["solution"])
+    assert np.array_equal(out["region"], out["cell"] % 3) and list(out["newton_step"]) == last
+
+    monkeypatch.setattr(b, "DUMP_BYTES", 5 * 4096 + 40 * 8 * (2 * bs + 2))     # room for 40 of the 192 cells
+    b.dump_outputs(str(tmp_path / "s1"), lm, dims, g.n_global, bs, y, f, regions, last, None, 0)
+    perm = np.random.default_rng(1).permutation(lm.n_owned)             # the same cells in another local order
+    lm.owned_ijk = lm.owned_ijk[perm]
+    b.dump_outputs(str(tmp_path / "s2"), lm, dims, g.n_global, bs, y.reshape(-1, bs)[perm].ravel(),
+                   f.reshape(-1, bs)[perm].ravel(), regions[perm], last, None, 0)
+    s1, s2 = files(tmp_path / "s1"), files(tmp_path / "s2")
+    assert s1["cell"].size == 40 and np.all(np.diff(s1["cell"]) > 0)
+    assert sum(os.path.getsize(tmp_path / "s1" / n) for n in os.listdir(tmp_path / "s1")) <= b.DUMP_BYTES
+    for k in s1:
+        assert np.array_equal(s1[k], s2[k]), k
+    assert np.array_equal(s1["solution"][:, 0], s1["cell"])

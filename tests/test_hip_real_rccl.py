@@ -1,6 +1,6 @@
 """The N > 1 path on REAL RCCL: one rank per GPU, no stand-in for librccl (WAI_RCCL_LIB unset), as the driver's
-multi-GPU bench launches it.  Every test here needs at least two visible devices and is skipped on the one-GPU test
-boxes -- it exists so that the first multi-GPU box does not execute the product's RCCL calls for the first time inside
+multi-GPU bench launches it, wherever at least two devices are visible (on a one-GPU box the same code runs as a dry run
+over the test transport, see DRYRUN below) -- it exists so that the first multi-GPU box does not execute the product's RCCL calls for the first time inside
 the scaling bench: ncclCommInitRank over N devices, grouped ncclSend / ncclRecv halo exchanges on the communication
 stream, the two all-reduces per BiCGStab iteration, `dist.init_process_group("nccl", device_id=...)` in bench.py.
 What it replaces in the reference: the DMPlex ghost updates (src/dm_utils.F90:480-498, global_to_local_vec_section /
@@ -11,6 +11,7 @@ import json
 import os
 import subprocess
 import sys
+import warnings
 
 import pytest
 import torch
@@ -23,19 +24,21 @@ from tests.test_hip_multirank import DIMS, BRICK, _problem, _run_steps, compare_
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NDEV = torch.cuda.device_count() if torch.cuda.is_available() else 0
-# WAI_REAL_RCCL_DRYRUN=1 (a one-GPU box): run THIS FILE's code -- workers, comparisons, the bench call -- with every rank on
-# device 0 over the test transport, so that a slip in the test itself is found before the first multi-GPU box runs it.
-# It proves nothing about RCCL and is not part of the suite.
-DRYRUN = os.environ.get("WAI_REAL_RCCL_DRYRUN", "") in ("1", "2", "4", "8") and NDEV == 1
+# Dry run (a one-GPU box): THIS FILE's code -- workers, comparisons, the bench call -- runs with every rank on device 0 over
+# the test transport (tests/loopback_rccl) instead of being skipped, so that a slip in the test itself is found before the
+# first multi-GPU box runs it.  It proves nothing about RCCL, and test_this_file_is_armed says so in the report.
+# 2 ranks there; WAI_REAL_RCCL_DRYRUN=4 adds the 4-rank cases (no more: the one test GPU is shared, and at most six
+# processes may hold it at once).
+DRYRUN = NDEV == 1
 if DRYRUN:
-    NDEV = max(2, int(os.environ["WAI_REAL_RCCL_DRYRUN"]))      # "8": the 4- and 8-rank cases too
-    from tests.test_hip_multirank import LOOPBACK, _own_cus
+    NDEV = 4 if os.environ.get("WAI_REAL_RCCL_DRYRUN") == "4" else 2
+    from tests.test_hip_multirank import LOOPBACK
 needs_two = pytest.mark.skipif(NDEV < 2, reason="real RCCL needs one device per rank: %d visible" % NDEV)
 WORLDS = [w for w in (2, 4, 8) if w <= max(NDEV, 2)]
 
 
-def _real_worker(rank, world, uid_q, q, dims, brick, nsteps, overlap):
-    if os.environ.get("WAI_REAL_RCCL_DRYRUN"):
+def _real_worker(rank, world, uid_q, q, dims, brick, nsteps, overlap, dryrun):
+    if dryrun:
         from tests.test_hip_multirank import LOOPBACK as lb, _own_cus as cus
         os.environ["WAI_RCCL_LIB"] = lb
         cus(rank, world)
@@ -54,7 +57,7 @@ def _real_worker(rank, world, uid_q, q, dims, brick, nsteps, overlap):
     else:
         uid = uid_q.get(timeout=300)
     g, lm, prim, region = _problem(M.partition_shape(world), rank, dims, brick)
-    sim = FlowSimulation(lm, eos="we", device=0 if os.environ.get("WAI_REAL_RCCL_DRYRUN") else rank)   # ONE DEVICE PER RANK
+    sim = FlowSimulation(lm, eos="we", device=0 if dryrun else rank)   # ONE DEVICE PER RANK
     sim.set_regions(region)
     sim.comm_init(rank, world, uid)
     assert sim.comm_size() == world, (sim.comm_size(), world)
@@ -83,7 +86,7 @@ def test_ranks_on_their_own_gpus_match_one_rank(world, overlap):
     dims, brick, nsteps = (DIMS, BRICK, 3) if world == 2 else ((16, 16, 16), (2, 2, 2), 1)
     ctx = mp.get_context("spawn")
     q, uid_q = ctx.Queue(), ctx.Queue()
-    procs = [ctx.Process(target=_real_worker, args=(r, world, uid_q, q, dims, brick, nsteps, overlap)) for r in range(world)]
+    procs = [ctx.Process(target=_real_worker, args=(r, world, uid_q, q, dims, brick, nsteps, overlap, DRYRUN)) for r in range(world)]
     for p in procs:
         p.start()
     res = [q.get(timeout=900) for _ in range(world)]
@@ -105,7 +108,7 @@ def test_bench_on_real_rccl(world):
     env = dict(os.environ, MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "WAI_RCCL_LIB", "WAI_BENCH_LOOPBACK", "HSA_CU_MASK", "WAI_HALO_OVERLAP"):
         env.pop(k, None)
-    if DRYRUN:      # (eight processes with two streams each time-slice the one GPU: in order there, as tests/test_hip_multirank.py does)
+    if DRYRUN:      # (several processes with two streams each time-slice the one GPU: in order there, as tests/test_hip_multirank.py does)
         env.update(WAI_RCCL_LIB=LOOPBACK, WAI_BENCH_LOOPBACK="1", WAI_HALO_OVERLAP="1" if world == 2 else "0")
     dims = (64, 64, 32) if world < 8 else (64, 64, 64)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--lead", "1",
@@ -117,7 +120,7 @@ def test_bench_on_real_rccl(world):
     out = json.loads(lines[0])
     assert out["n_gpus"] == world and out["value"] > 0 and out["scaling"] == "strong"
     c = out["comm"]
-    assert c["rccl_ranks"] == world and (DRYRUN or "librccl" in c["transport"]), c
+    assert c["rccl_ranks"] == world and (c["transport"] == LOOPBACK if DRYRUN else "librccl" in c["transport"]), c
     assert 2.0 <= c["allreduces_per_krylov_iteration"] < 3.5 and 2.0 <= c["exchanges_per_krylov_iteration"] < 3.5, c
     assert c["halo_neighbours"] == {2: 1, 4: 2, 8: 3}[world]
     assert c["collective_time_share"] is not None and c["ms_per_krylov_iteration_device_only"] > 0
@@ -126,7 +129,10 @@ def test_bench_on_real_rccl(world):
 
 
 def test_this_file_is_armed():
-    """on a one-GPU box everything above is skipped: say so in the report instead of passing silently"""
+    """on a one-GPU box everything above ran as the dry run: say so in the report instead of passing silently"""
     if NDEV < 2:
-        pytest.skip("one visible device: the real-RCCL tests above did not run (they run wherever >= 2 devices are visible)")
+        pytest.skip("no visible device: the real-RCCL tests above did not run")
     assert WORLDS and WORLDS[0] == 2
+    if DRYRUN:
+        warnings.warn("one visible device: the real-RCCL tests above ran every rank on device 0 over the test transport "
+                      "(tests/loopback_rccl), not over RCCL; they run on RCCL wherever >= 2 devices are visible")
