@@ -10,68 +10,41 @@
 namespace wai {
 
 // Element (s, r, k) of block row i in a block-ELL value array of n block rows (layout rationale:
-// kernels_linalg.hip, "Matrix entry addressing").  WAI_ELL_ROWS builds the block-row layout for every bs.
+// kernels_linalg.hip, "Matrix entry addressing").
 // The stride between the element planes of block sizes >= 3 is not n but n rounded up to 512 doubles (4 KB), and never a
 // multiple of 2 MB: how a slot's nine planes fall onto the memory channels depends on it.  MEASURED (C4's SpMV alone,
 // tools/micro/spmv3_stride.hip, nine strides x three fresh allocations on one box): stride n = 5 029 280 doubles
 // 71.8-72.3 % of HBM peak, a multiple of 2 MB 70.0-72.9 %, 4-KB multiples with 0-132 KB added 71.4-78.2 % (mean 75 %).
-// Every array indexed through ell_ix with bs >= 3 is allocated with ell_rows(bs, n) rows (-DWAI_ELL_NO_PAD: stride n).
-#if defined(WAI_ELL_NO_PAD) && !defined(WAI_ELL_PLANES)
-#define WAI_ELL_PLANES   // the 64-row groups inside a slot need a stride that is a multiple of 64
-#endif
+// Every array indexed through ell_ix with bs >= 3 is allocated with ell_rows(bs, n) rows.
 __host__ __device__ __forceinline__ size_t ell_ld(size_t n) {
-#ifdef WAI_ELL_NO_PAD
-  return n;
-#else
   size_t ld = (n + 511) & ~(size_t)511;
   if ((ld & 262143) == 0) ld += 512;
   return ld;
-#endif
 }
 __host__ __device__ __forceinline__ size_t ell_rows(int bs, size_t n) {
-#ifndef WAI_ELL_ROWS
   if (bs >= 3) return ell_ld(n);
-#endif
   return n;
 }
 // Block sizes >= 3: SELL-64 in slices of eight slots (round 5).  The bs^2 elements of 64 consecutive block rows of slot s
-// sit together (rounds 4's per-slot form), and the (up to) eight slots of those 64 rows follow one another: everything a
-// wave reads of its 64 rows -- 7 slots x 9 elements x 512 B = 32 KB for the 7-point stencil of 3 x 3 blocks -- is ONE
-// contiguous run (the eighth slot's 4.6 KB are a hole nobody reads), where the per-slot form had seven streams 360 MB
-// apart and the element planes of rounds 2-3 sixty-three.  What the memory channels make of many concurrent streams
-// depends on where the allocation lands: C4's k_spmv<3> ran at 64 % of HBM peak on one box and 74-76 % on others, and
-// between 72.6 and 85.5 % in eight processes on one box; SELL-64 measured 76.0 % in ten processes out of ten
-// (tools/micro/spmv3_variants.hip, profiles/spmv3_variants_r4.log).  Slot s of block row i, element e = r bs + k:
+// sit together, and the (up to) eight slots of those 64 rows follow one another: everything a wave reads of its 64 rows --
+// 7 slots x 9 elements x 512 B = 32 KB for the 7-point stencil of 3 x 3 blocks -- is ONE contiguous run (the eighth
+// slot's 4.6 KB are a hole nobody reads).  With one stream per slot, C4's k_spmv<3> ran at 64 % of HBM peak on one box
+// and 74-76 % on others, and between 72.6 and 85.5 % in eight processes on one box; SELL-64 measured 76.0 % in ten
+// processes out of ten.  The earlier layouts (one plane per element, one stream per slot, block rows) live on in
+// tools/micro/spmv3_variants.hip (profiles/spmv3_variants_r4.log).  Slot s of block row i, element e = r bs + k:
 //     (s / 8) * 8 bs^2 ld  +  (((i / 64) * 8 + s % 8) * bs^2 + e) * 64  +  i % 64,      ld = ell_ld(n)
 // so wider systems (ILU(k) fill: W > 8) take further slices of eight.  An array of ONE block per row (the inverted
 // pivots) keeps the per-slot form through ell_ix1.  Arrays indexed through ell_ix are allocated with ell_size doubles.
-// -DWAI_ELL_SLOTWISE builds round 4's per-slot form, -DWAI_ELL_PLANES one plane per element.
+// Block sizes 1 and 2: the block rows of a plane per (slot, row-in-block), element i of a plane the bs-vector of block row i.
 __host__ __device__ __forceinline__ size_t ell_ix1(int bs, size_t n, int r, int k, size_t i) {
-#ifndef WAI_ELL_ROWS
-  if (bs >= 3) {
-#ifdef WAI_ELL_PLANES
-    return ((size_t)(r * bs + k)) * ell_ld(n) + i;
-#else
-    return ((i >> 6) * (size_t)(bs * bs) + (size_t)(r * bs + k)) * 64 + (i & 63);
-#endif
-  }
-#endif
+  if (bs >= 3) return ((i >> 6) * (size_t)(bs * bs) + (size_t)(r * bs + k)) * 64 + (i & 63);
   return ((size_t)r * n + i) * bs + k;
 }
 __host__ __device__ __forceinline__ size_t ell_ix(int bs, size_t n, int s, int r, int k, size_t i) {
-#ifndef WAI_ELL_ROWS
   if (bs >= 3) {
-#ifdef WAI_ELL_PLANES
-    return ((size_t)((s * bs + r) * bs + k)) * ell_ld(n) + i;
-#elif defined(WAI_ELL_SLOTWISE)
-    const size_t bb = (size_t)(bs * bs);
-    return (size_t)s * bb * ell_ld(n) + ((i >> 6) * bb + (size_t)(r * bs + k)) * 64 + (i & 63);
-#else
     const size_t bb = (size_t)(bs * bs);
     return (size_t)(s >> 3) * 8 * bb * ell_ld(n) + ((((i >> 6) << 3) + (size_t)(s & 7)) * bb + (size_t)(r * bs + k)) * 64 + (i & 63);
-#endif
   }
-#endif
   // (2 x 2 blocks: the two block rows of 64 rows together inside a slot, the same idea, MEASURED without effect -- C3's
   // fused launch 0.5326 / 0.5406 / 0.5387 against 0.5409 / 0.5713 / 0.5388 ms, the 108^3 share 0.0826 against 0.0820;
   // profiles/group2_ab_r4.log -- two planes per slot are few enough)
@@ -79,9 +52,7 @@ __host__ __device__ __forceinline__ size_t ell_ix(int bs, size_t n, int s, int r
 }
 // doubles of a W-slot array indexed through ell_ix
 __host__ __device__ __forceinline__ size_t ell_size(int bs, size_t n, int W) {
-#if !defined(WAI_ELL_ROWS) && !defined(WAI_ELL_PLANES) && !defined(WAI_ELL_SLOTWISE)
   if (bs >= 3) return (size_t)((W + 7) / 8) * 8 * bs * bs * ell_ld(n);
-#endif
   return (size_t)W * bs * bs * ell_rows(bs, n);
 }
 
@@ -225,8 +196,8 @@ struct IluSchedule {
                             // the inverted pivot block
   double* dinv = nullptr;   // inverted pivot blocks, SoA [bb][n]
   bool diag_only = false;   // ILU(0) touches no off-diagonal block in any subdomain (== DILU)
-  bool scaled = true;       // diag_only: rows pre-scaled by the inverted pivots (WAI_ILU_NOSCALE: off)
-  bool park = true;         // k_pc_park: upper blocks parked in LDS (WAI_PC_PARK=0: off)
+  bool scaled = true;       // diag_only: rows pre-scaled by the inverted pivots
+  bool park = true;         // k_pc_park: upper blocks parked in LDS
   int* row_uoff = nullptr;  // first parked upper block of a row inside its subdomain
   int* row_tslot = nullptr; // per row: slot of A_ki in row k for each of its (<= 4) in-subdomain lower couplings k, 4 bits each (15: none)
   int max_nl = 0;           // most in-subdomain lower couplings of any row
@@ -413,13 +384,9 @@ struct wai_ctx {
   // halo exchange overlapped with the preconditioned operator on the bricks that touch no ghost
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_pack = nullptr, ev_halo = nullptr;
-  // WAI_FACE_STREAM=1: the face bricks' launch of the overlapped halo exchange on a stream of its own, ordered behind the
-  // unpack only (round 5; measured slower than behind the interior bricks on the compute stream: krylov.hip launch_pc_split)
-  hipStream_t face_stream = nullptr;
-  hipEvent_t ev_face = nullptr, ev_prior = nullptr;
   // run-time switches of the fused launches, read from the environment once per solve / set-up / probe (read_env),
-  // not per launch: WAI_FIN_SEPARATE, WAI_PC_STAGGER (-1: each kernel's default), WAI_WAVE_ROWPTR, WAI_NO_COL16 (k_pc_park on the int32 column planes)
-  struct EnvSw { bool fin_separate = false; int stagger = -1; bool wave_rowptr = false; bool no_col16 = false; int stage = -1; bool no_face_stream = false; bool scalar_kernels = false; } env;
+  // not per launch: WAI_FIN_SEPARATE, WAI_NO_COL16 (k_pc_park on the int32 column planes), WAI_BCGS_SCALAR_KERNELS
+  struct EnvSw { bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
   // halo
   int n_nbr = 0;

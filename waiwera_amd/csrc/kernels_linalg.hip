@@ -23,37 +23,6 @@
 
 namespace wai {
 
-// Phase timing of the fused preconditioner kernels (build with -DWAI_PC_PHASES; tools/pc_phases.sh): thread 0 of every
-// workgroup stamps the 100 MHz real-time counter at the phase boundaries and adds the differences to g_pc_phase
-// [0] row loads + products, [1] wait for the workgroup's slowest wave, [2] forward sweep, [3] backward sweep,
-// [4] store + reductions, [7] workgroups
-#ifdef WAI_PC_PHASES
-constexpr int PH_WG = 131072;
-__device__ unsigned int g_pc_phase_wg[8 * PH_WG];   // per workgroup of the LAST launch: plain stores, no contention
-#define PH_DECL unsigned long long ph_t = wall_clock64()
-#define PH(k)                                                                                    \
-  do {                                                                                           \
-    if (threadIdx.x == 0 && blockIdx.x < PH_WG) {                                                \
-      const unsigned long long t_ = wall_clock64();                                              \
-      g_pc_phase_wg[(size_t)blockIdx.x * 8 + k] = (unsigned int)(t_ - ph_t);                     \
-      ph_t = t_;                                                                                 \
-    }                                                                                            \
-  } while (0)
-#define PH_COUNT() do { if (threadIdx.x == 0 && blockIdx.x < PH_WG) g_pc_phase_wg[(size_t)blockIdx.x * 8 + 7] = 1u; } while (0)
-void pc_phases_fetch(unsigned long long out[8], bool reset) {
-  std::vector<unsigned int> h((size_t)8 * PH_WG);
-  (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_pc_phase_wg), sizeof(unsigned int) * h.size());
-  for (int k = 0; k < 8; k++) out[k] = 0;
-  for (int w = 0; w < PH_WG; w++)
-    if (h[(size_t)w * 8 + 7])
-      for (int k = 0; k < 8; k++) out[k] += h[(size_t)w * 8 + k];
-  if (reset) { std::fill(h.begin(), h.end(), 0u); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pc_phase_wg), h.data(), sizeof(unsigned int) * h.size()); }
-}
-#else
-#define PH_DECL
-#define PH(k)
-#define PH_COUNT()
-#endif
 
 
 constexpr int TPB = 256;
@@ -84,12 +53,7 @@ __device__ __forceinline__ double wave_sum(double v) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 #endif
 }
-#ifndef PC_MIN_WAVES
-#define PC_MIN_WAVES 4   // waves per SIMD k_pc is compiled for; 5 or 6 force spills and measured 1.2x / 3x slower (tools/ab_pc_waves.sh)
-#endif
-#ifndef WAI_PC_STAGE_DEFAULT
-#define WAI_PC_STAGE_DEFAULT 0
-#endif
+constexpr int PC_MIN_WAVES = 4;   // waves per SIMD k_pc is compiled for; 5 or 6 force spills and measured 1.2x / 3x slower
 constexpr int WMAX = 8;  // block-ELL width handled in registers (7-point stencil: 7, MINC: 8)
 
 
@@ -121,35 +85,21 @@ __device__ __forceinline__ size_t dix(int n, int e, int i) {
 // read once per launch and the result vector written once: these streams carry the non-temporal
 // hint so that they do not evict the vector segments the neighbour gathers want to find in L2
 // (MEASURED at 216^3, same box: k_spmv 0.557 -> 0.441 ms = 82 % of 8 TB/s, k_pc_park 0.684 ->
-// 0.654 ms, and with the BiCGStab vector updates hinted too 7.5 % per Newton step; -DWAI_NO_NT
-// builds without the hints).
+// 0.654 ms, and with the BiCGStab vector updates hinted too 7.5 % per Newton step).
 typedef double wai_d2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int load_col(const int* __restrict__ col, size_t idx) {
-#ifndef WAI_NO_NT
   return __builtin_nontemporal_load(col + idx);
-#else
-  return col[idx];
-#endif
 }
 __device__ __forceinline__ void store_z2(double* __restrict__ z, size_t i, double a, double b) {
-#ifndef WAI_NO_NT
   wai_d2 v = {a, b};
   __builtin_nontemporal_store(v, reinterpret_cast<wai_d2*>(z + i * 2));
-#else
-  *reinterpret_cast<double2*>(z + i * 2) = make_double2(a, b);
-#endif
 }
 template <int BS>
 __device__ __forceinline__ void load_block(const double* __restrict__ val, int n, int s, int i, double* b) {
   if constexpr (BS == 2) {
     const size_t i0 = ell_ix(2, (size_t)n, s, 0, 0, (size_t)i), i1 = ell_ix(2, (size_t)n, s, 1, 0, (size_t)i);
-#ifndef WAI_NO_NT
     const wai_d2 r0 = __builtin_nontemporal_load(reinterpret_cast<const wai_d2*>(val + i0));
     const wai_d2 r1 = __builtin_nontemporal_load(reinterpret_cast<const wai_d2*>(val + i1));
-#else
-    const double2 r0 = *reinterpret_cast<const double2*>(val + i0);
-    const double2 r1 = *reinterpret_cast<const double2*>(val + i1);
-#endif
     b[0] = r0.x; b[1] = r0.y; b[2] = r1.x; b[3] = r1.y;
   } else {
 #pragma unroll
@@ -169,14 +119,13 @@ __device__ __forceinline__ void load_pivot(const double* __restrict__ val, int n
 
 // a 16-byte pair of doubles at 8-byte alignment: gfx950 serves it with one global_load_dwordx4 (unaligned access
 // mode), so the three components of a 3 x 3 system's vector entry cost a dwordx4 + a dwordx2 instead of three
-// dwordx2 gathers through the same cache lines (-DWAI_X_SCALAR_GATHER: the three scalar gathers of rounds 1-2)
+// dwordx2 gathers through the same cache lines (the three scalar gathers of rounds 1-2)
 typedef double wai_d2u __attribute__((ext_vector_type(2), aligned(8)));
 template <int BS>
 __device__ __forceinline__ void load_x(const double* __restrict__ x, int col, double* xv) {
   if constexpr (BS == 2) {
     const double2 t = *reinterpret_cast<const double2*>(x + (size_t)col * 2);
     xv[0] = t.x; xv[1] = t.y;
-#ifndef WAI_X_SCALAR_GATHER
   } else if constexpr (BS == 3) {
     const double* p = x + (size_t)col * 3;
     const wai_d2u t = *reinterpret_cast<const wai_d2u*>(p);
@@ -185,7 +134,6 @@ __device__ __forceinline__ void load_x(const double* __restrict__ x, int col, do
     const double* p = x + (size_t)col * 4;
     const wai_d2u t = *reinterpret_cast<const wai_d2u*>(p), u = *reinterpret_cast<const wai_d2u*>(p + 2);
     xv[0] = t.x; xv[1] = t.y; xv[2] = u.x; xv[3] = u.y;
-#endif
   } else {
 #pragma unroll
     for (int k = 0; k < BS; k++) xv[k] = x[(size_t)col * BS + k];
@@ -211,11 +159,7 @@ __device__ __forceinline__ void load_xs(const double* __restrict__ in, const dou
 template <int BS>
 __device__ __forceinline__ void load_x_stream(const double* __restrict__ x, int col, double* xv) {   // read once
   if constexpr (BS == 2) {
-#ifndef WAI_NO_NT
     const wai_d2 t = __builtin_nontemporal_load(reinterpret_cast<const wai_d2*>(x + (size_t)col * 2));
-#else
-    const double2 t = *reinterpret_cast<const double2*>(x + (size_t)col * 2);
-#endif
     xv[0] = t.x; xv[1] = t.y;
   } else {
 #pragma unroll
@@ -270,14 +214,12 @@ __global__ __launch_bounds__(TPB) void k_spmv(int n, int W, int nblk, const int*
   for (int r = 0; r < BS; r++) acc[r] = 0.0;
   ell_row_mult<BS>(n, SHORT ? rowptr[i + 1] - rowptr[i] : W, i, col, val, x, acc);
   if constexpr (BS == 2) store_z2(y, (size_t)i, acc[0], acc[1]);
-#ifndef WAI_X_SCALAR_GATHER
   else if constexpr (BS == 3) {
     double* p = y + (size_t)i * 3;
     wai_d2u t = {acc[0], acc[1]};
     *reinterpret_cast<wai_d2u*>(p) = t;
     p[2] = acc[2];
   }
-#endif
   else {
 #pragma unroll
     for (int r = 0; r < BS; r++) y[(size_t)i * BS + r] = acc[r];
@@ -754,10 +696,7 @@ constexpr int FIN_MAXS = 5;   // reduction slots summed together (the merged BiC
 // workgroups, finaliser f sums slice f of every slot and stores the slice sums (second-level partials, same arrival
 // protocol), and the LAST finaliser adds the slice sums in slice order, derives and posts.  k_finalize (the separate
 // launch) forms the same slice sums and adds them in the same order: identical bits either way, independent of timing.
-#ifndef WAI_FIN_SLICE
-#define WAI_FIN_SLICE 1024
-#endif
-constexpr int FIN_SLICE = WAI_FIN_SLICE;
+constexpr int FIN_SLICE = 1024;
 __host__ __device__ __forceinline__ int fin_slices(int nb) { return nb <= FIN_SLICE ? 1 : (nb + FIN_SLICE - 1) / FIN_SLICE > FIN_MAXF ? FIN_MAXF : (nb + FIN_SLICE - 1) / FIN_SLICE; }
 __host__ __device__ __forceinline__ void fin_slice_range(int nb, int nf, int f, int& lo, int& hi) {
   const int per = (nb + nf - 1) / nf;
@@ -947,7 +886,7 @@ __device__ __forceinline__ bool fin_block(const Fin& f, const double* partials, 
 // 9 us nothing; a second box: 0.0899 -> 0.0840 at 108^3, 0.556-0.561 -> 0.546-0.551 at 216^3.  k_pc_wave (ten-odd one-wave
 // bricks per CU, in workgroups of four) gains 1.5 % with 4 us per cohort (C5 0.1981-0.1993 -> 0.1954-0.1959, C4's quarter
 // 0.1687-0.1695 -> 0.1661-0.1666).  (Round 3 tried the same on the all-loads-at-once experiment k_pc_rows3 and saw no
-// change: there a brick's loads ARE one burst.)  WAI_PC_STAGGER=<ticks> overrides, 0 switches it off.
+// change: there a brick's loads ARE one burst.)
 struct Stagger { int ticks = 0, ncu = 256, per_cu = 3; };
 __device__ __forceinline__ void stagger_start(const Stagger& st) {
   if (st.ticks > 0 && (int)blockIdx.x < st.ncu * st.per_cu) {
@@ -969,12 +908,11 @@ __device__ __forceinline__ void wg_reduce_store(double (&v)[NS], double* red, do
     if (lane == 0) red[s * 16 + w] = t;
   }
   __syncthreads();
-#ifndef WAI_PC_EPI_ONE_LANE
   // Round 6, one WAVE per slot: wave s's first lane adds the waves' sums of slot s (w = 0, 1, ... in order: same bits), the NS chains
   // side by side; the callers' slot numbers are consecutive, so slot = first + wave (an indexed or selected table went to scratch).
   // MEASURED (profiles/epiw_ab_r6_*.log, alternating same-box rounds): the composed launch with its five sums 0.6889 -> 0.6836 ms at
   // 216^3, 0.0977 -> 0.0961 at 108^3 (three rounds each, every round the same sign); one-sum launches and k_pc_wave unchanged.
-  // (-DWAI_PC_EPI_ONE_LANE: thread 0 adds all slots, rounds 1-5.)
+  // (Before: thread 0 added all slots, rounds 1-5.)
   if (nw >= NS) {      // (a workgroup of fewer waves than slots: the one-lane form below)
     if (lane == 0 && w < NS) {
       const int slot = slots[0] + w;   // the callers' slots are consecutive (S_D1 .. S_W2, context.hpp)
@@ -984,7 +922,6 @@ __device__ __forceinline__ void wg_reduce_store(double (&v)[NS], double* red, do
     }
     return;
   }
-#endif
   // MEASURED AND REMOVED (round 6): one lane per slot for these NS sums (side by side instead of one after the other, same
   // order inside each) -- the lane-indexed slot number sent the slot table to scratch memory (32 bytes per lane) and every
   // fused launch ran 10 % slower (0.533 -> 0.586 ms at 216^3, 0.083 -> 0.089 at 108^3: profiles/exp_ab_r6_*.log).
@@ -1370,14 +1307,9 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? PC_MIN_WAVES : 4)) void k_pc(int n
 // epilogue drains), and the dispatcher's hand-out -- whichever slot frees first -- decorrelates the bricks of a CU, which a
 // fixed stride never does: workgroups that started together stay in step, all loading, then all sweeping (the effect the
 // start-up cohorts were introduced against in round 4, now for the whole launch).
-// SL (round 6): the brick's OWN segment of the operand staged in LDS before the slot loop.  Each thread loads its row's
-// entry (coalesced; composed: R_i and V_i, S_i = fma(-alpha, V_i, R_i) formed once), stores it to the solution area and,
-// behind one barrier, the in-brick columns of a row -- slots [lfirst, ulast): the lower couplings, the diagonal, the
-// upper couplings, 79 % of a 16 x 16 x 2 brick's -- are read from there; only the off-brick columns are gathered from
-// memory (composed: two gathers each).  The solution area doubles as the stage (a stage of its own would be the 8 KB
-// that end three resident workgroups per CU), so one more barrier separates the last read of S from the store of t = A S.
-// The same fma on the same operands: identical bits.
-template <bool SPMV, bool AX, bool C16, bool SL = false>
+// (Staging the brick's own operand segment in LDS, the in-brick columns read from there, was slower at C3, the 108^3
+// share and C2 -- two more barriers per brick replace the gathers' latency: profiles/stage_ab_r6_*.log.)
+template <bool SPMV, bool AX, bool C16>
 __global__ __launch_bounds__(512, 6) void k_pc_park(
     int n, int W, int nsub, const int* __restrict__ sub_ptr, const int* __restrict__ sub_nlev,
     const int* __restrict__ row_info, const int* __restrict__ row_uoff, const int* __restrict__ col,
@@ -1401,7 +1333,6 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   const bool active = tid < R;
   const double nalpha = AX ? -scal[S_ALPHA] : 0.0;   // input = in - alpha in2 (uniform: a scalar load)
   stagger_start(stagger);
-  PH_DECL;
   double* ys = lds;
   double* upark = lds + (size_t)blockDim.x * BS + 80;
   double Lf[MLU][BB];
@@ -1451,12 +1382,7 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
         if (q < W) cgs[q] = load_col(col, (size_t)q * n + i);
       }
     }
-    if constexpr (SPMV && SL) {   // the row's own operand entry: staged for the brick's other rows
-      load_xs<BS, AX>(in, in2, nalpha, i, xin);
-      *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(xin[0], xin[1]);
-    }
   }
-  if constexpr (SPMV && SL) __syncthreads();
   double acc[BS] = {0.0, 0.0};
   if (active) {
 #pragma unroll
@@ -1467,12 +1393,7 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
         load_block<BS>(sval, n, q, i, blk);
         if constexpr (SPMV) {
           double xv[BS];
-          if constexpr (SL) {
-            if (q >= lfirst && q < ulast) {   // in the brick: lower couplings, diagonal, upper couplings
-              const double2 t = *reinterpret_cast<const double2*>(ys + (cg - lo) * 2);
-              xv[0] = t.x; xv[1] = t.y;
-            } else load_xs<BS, AX>(in, in2, nalpha, cg, xv);
-          } else load_xs<BS, AX>(in, in2, nalpha, cg, xv);
+          load_xs<BS, AX>(in, in2, nalpha, cg, xv);
           acc[0] += blk[0] * xv[0] + blk[1] * xv[1];
           acc[1] += blk[2] * xv[0] + blk[3] * xv[1];
         }
@@ -1499,14 +1420,11 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       acc[0] = dv[0] * r[0] + dv[1] * r[1];
       acc[1] = dv[2] * r[0] + dv[3] * r[1];
     }
-    if constexpr (!(SPMV && SL)) { if (dot == 2 || dot == 4) load_xs<BS, AX>(in, in2, nalpha, i, xin); }
+    if (dot == 2 || dot == 4) load_xs<BS, AX>(in, in2, nalpha, i, xin);
     if (dot == 1 || dot == 4) load_x_stream<BS>(aux, i, avp);   // the dot product's partner: in flight through the sweeps
   }
-  if constexpr (SPMV && SL) __syncthreads();   // the stage's last reader is through: the area takes t = A x
   if (active) *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(acc[0], acc[1]);
-  PH(0);
   __syncthreads();
-  PH(1);
   auto gather3 = [&](const int (&cc)[MLU], const double (&ff)[MLU][BB], double* sum) {
     double2 yk[MLU];
 #pragma unroll
@@ -1519,9 +1437,7 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       sum[r] = (part[0] + part[1]) + part[2];
     }
   };
-#ifdef WAI_PC_SETPRIO   // MEASURED (round 6, profiles/exp_ab_r6_*.log): the sweeps at raised wave priority -- 0.5333 -> 0.5345 ms first launch,
-  __builtin_amdgcn_s_setprio(3);   // 0.6663 -> 0.6741 composed at 216^3, no change at 108^3: instruction issue is 15 % busy, there is nothing to win a race for
-#endif
+  // (The sweeps at raised wave priority, s_setprio 3, measured slower: 0.6663 -> 0.6741 ms composed at 216^3, profiles/exp_ab_r6_*.log.)
   for (int lev = 1; lev < nlf; lev++) {  // forward: y_i = t_i - sum A'_ik y_k
     if (lf == lev) {
       const double2 a = *reinterpret_cast<const double2*>(ys + tid * 2);
@@ -1531,7 +1447,6 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
     }
     __syncthreads();
   }
-  PH(2);
   // the lower blocks are dead: their registers take the parked upper blocks
 #pragma unroll
   for (int p = 0; p < MLU; p++) {
@@ -1553,10 +1468,6 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
     }
     if (lev + 1 < nlb) __syncthreads();
   }
-  PH(3);
-#ifdef WAI_PC_SETPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
   if (active) store_z2(z, (size_t)i, out[0], out[1]);
   if (dot != 0) {
     double* red = lds + (size_t)blockDim.x * BS;
@@ -1580,16 +1491,13 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       v[0] = out[0] * out[0] + out[1] * out[1];
       slots[0] = S_DP2;
     }
-#ifndef WAI_PC_EPI_NOBAR
+    // the reduction scratch is touched by nothing before this point; dropping the barrier was not felt (0.5704 / 0.6942
+    // against 0.5714 / 0.6924 ms at 216^3, profiles/nobar_ab_r6_c3.log), so it stays
     __syncthreads();
-#endif   // (-DWAI_PC_EPI_NOBAR: the reduction scratch is touched by nothing before this point, the barrier is not needed -- and
-         // not felt: 0.5704 / 0.6942 against 0.5714 / 0.6924 ms at 216^3, profiles/nobar_ab_r6_c3.log; kept as it was)
     if (dot == 4) wg_reduce_store<5>(v, red, partials, nb_max, slots, s);
     else if (dot == 2) { double v2[2] = {v[0], v[1]}; wg_reduce_store<2>(v2, red, partials, nb_max, slots, s); }
     else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slots, s); }
   }
-  PH(4);
-  PH_COUNT();
 }
 
 // ---- K6+K8 fused, one thread per SCALAR row (any block size; pivot-scaled DILU) ---------------
@@ -1625,7 +1533,6 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
   const int nlf = nl & 0xffff, nlb = nl >> 16;
   const int tid = threadIdx.x;
   const double nalpha = AX ? -scal[S_ALPHA] : 0.0;   // input = in - alpha in2
-  PH_DECL;
   // component-major over the R1 leading (long) rows, then component-major over the short ones
   const int R1 = sub_split ? (sub_split[s] & 0xffff) : R;
   const bool shortrow = tid >= R1 * BS;
@@ -1699,12 +1606,10 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
     }
     ys[il * BS + r] = acc;
   }
-  PH(0);
   // the dot product's partner (block order, tid-linear): in flight through the sweeps
   double avp = 0.0;
   if (active && (dot == 1 || dot == 4)) avp = __builtin_nontemporal_load(aux + (size_t)lo * BS + tid);
   __syncthreads();
-  PH(1);
   for (int lev = 1; lev < nlf; lev++) {  // forward: y_i = t_i - sum A'_ik y_k
     if (lf == lev) {
       double a = ys[il * BS + r];
@@ -1716,7 +1621,6 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
     }
     __syncthreads();
   }
-  PH(2);
   for (int lev = 0; lev < nlb; lev++) {  // backward: x_i = y_i - sum A'_ij x_j
     if (lb == lev) {
       double a = ys[il * BS + r];
@@ -1728,7 +1632,6 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
     }
     __syncthreads();
   }
-  PH(3);
   // block-order, tid-linear epilogue: store the result, reduce the dot products
   double out = 0.0;
   const size_t g = (size_t)lo * BS + tid;
@@ -1758,8 +1661,6 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
     else if (dot == 2) { double v2[2] = {v[0], v[1]}; wg_reduce_store<2>(v2, red, partials, nb_max, slots, s); }
     else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slots, s); }
   }
-  PH(4);
-  PH_COUNT();
 }
 
 // ---- K6+K8 fused, one WAVE per brick of <= 64 block rows (block sizes 3, 4; pivot-scaled DILU) ------
@@ -1830,18 +1731,15 @@ __global__ __launch_bounds__(256) void k_pc_wave(
   // One uniform branch, inside it straight-line loads with a clamped index (per-lane conditions around the requests made
   // the compiler wait between them: the first attempt, profiles/wave_prefetch_ab_r4.log, gained nothing).  MEASURED
   // (profiles/wave_early_aux_ab_r4.log, alternating builds, three runs): the launch with one product 0.5686 -> 0.5475 ms at
-  // C4, 0.1889 -> 0.1826 at C5; an iteration -2.1 % / -1.9 %.  -DWAI_WAVE_LATE_AUX: in the epilogue again
+  // C4, 0.1889 -> 0.1826 at C5; an iteration -2.1 % / -1.9 %.
   double pav[BS];
 #pragma unroll
   for (int j = 0; j < BS; j++) pav[j] = 0.0;
-#ifndef WAI_WAVE_LATE_AUX
   if (dot == 1 || dot == 4) {
     const int totp = R * BS;
 #pragma unroll
     for (int j = 0; j < BS; j++) pav[j] = __builtin_nontemporal_load(aux + (size_t)lo * BS + min(lane + 64 * j, totp - 1));
   }
-#endif
-  PH_DECL;
   double* ys = lds + (size_t)wave * lds_per_brick;   // [64 * BS] solution in block order
   double* upark = ys + 64 * BS;                      // parked upper blocks, row-major BS x BS each
   double Lf[NL][BB];
@@ -1912,7 +1810,6 @@ __global__ __launch_bounds__(256) void k_pc_wave(
 #pragma unroll
     for (int r = 0; r < BS; r++) ys[lane * BS + r] = acc[r];
   }
-  PH(0);
   __builtin_amdgcn_wave_barrier();
   for (int lev = 1; lev < nlf; lev++) {  // forward: y_i = t_i - sum A'_ik y_k
     if (lf == lev) {
@@ -1934,8 +1831,6 @@ __global__ __launch_bounds__(256) void k_pc_wave(
     }
     __builtin_amdgcn_wave_barrier();
   }
-  PH(2);
-#ifndef WAI_WAVE_LATE_AUX
   // ... and the operand's own entries (block order) for the merged products a backward sweep early: the lower blocks'
   // registers are free now (requested at the start too they would cost the fourth wave per SIMD).  MEASURED on top of the
   // partner vector (profiles/wave_early_xi_ab_r4.log): the five-product launch 0.6177 -> 0.6015 ms at C4; an iteration
@@ -1952,7 +1847,6 @@ __global__ __launch_bounds__(256) void k_pc_wave(
       if constexpr (AX) pi2[j] = in2[gp];
     }
   }
-#endif
   for (int lev = 0; lev < nlb; lev++) {  // backward: x_i = y_i - sum A'_ij x_j, upper blocks from LDS
     if (lb == lev) {
       double a[BS];
@@ -1977,7 +1871,6 @@ __global__ __launch_bounds__(256) void k_pc_wave(
     }
     __builtin_amdgcn_wave_barrier();
   }
-  PH(3);
   // block-order, lane-linear epilogue: the wave's R * BS results leave coalesced; dot products on the way
   double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   const int tot = R * BS;
@@ -1988,22 +1881,10 @@ __global__ __launch_bounds__(256) void k_pc_wave(
       const size_t gi = (size_t)lo * BS + t;
       const double out = ys[t];
       __builtin_nontemporal_store(out, z + gi);
-#ifndef WAI_WAVE_LATE_AUX
       if (dot == 1) v[0] += out * pav[j];
-#else
-      if (dot == 1) v[0] += out * __builtin_nontemporal_load(aux + gi);
-#endif
-#ifndef WAI_WAVE_LATE_AUX
       else if (dot == 2) { const double xi = AX ? __builtin_fma(nalpha, pi2[j], pxi[j]) : pxi[j]; v[0] += xi * out; v[1] += out * out; }
-#else
-      else if (dot == 2) { const double xi = AX ? __builtin_fma(nalpha, in2[gi], in[gi]) : in[gi]; v[0] += xi * out; v[1] += out * out; }
-#endif
       else if (dot == 4) {
-#ifndef WAI_WAVE_LATE_AUX
         const double xi = AX ? __builtin_fma(nalpha, pi2[j], pxi[j]) : pxi[j], av = pav[j];
-#else
-        const double xi = AX ? __builtin_fma(nalpha, in2[gi], in[gi]) : in[gi], av = __builtin_nontemporal_load(aux + gi);
-#endif
         v[0] += xi * out; v[1] += out * out; v[2] += xi * xi; v[3] += xi * av; v[4] += out * av;
       } else if (dot == 3) v[0] += out * out;
     }
@@ -2028,8 +1909,6 @@ __global__ __launch_bounds__(256) void k_pc_wave(
     if (wave == 0 && lane < ns)
       store_partial(partials + (size_t)(slot0 + lane) * nb_max + pbase + g, ((wred[lane][0] + wred[lane][1]) + wred[lane][2]) + wred[lane][3]);
   }
-  PH(4);
-  PH_COUNT();
 }
 
 // ---- layout conversion (C ABI exchanges BCSR) -------------------------------------------------
@@ -2105,18 +1984,10 @@ __global__ void k_bcgs_scalars(double* s, int phase, double* post, int seq) {
 
 // streaming vector accesses of the BiCGStab updates: every element is touched once per launch
 __device__ __forceinline__ double ldv(const double* p) {
-#ifndef WAI_NO_NT
   return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ void stv(double* p, double v) {
-#ifndef WAI_NO_NT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 // P = R + beta*(P - omega_old*V)   [VecAXPBYPCZ(P, 1, -omega*beta, beta, R, V)]
 __global__ __launch_bounds__(TPB) void k_bcgs_p(double* __restrict__ P, const double* __restrict__ R,
@@ -2599,13 +2470,8 @@ int launch_lu_apply(wai_ctx* c, const double* r, double* z) {
 // the fused launches' run-time switches: read once per solve / set-up / probe (tests switch them between solves of one process)
 void read_env(wai_ctx* c) {
   c->env.fin_separate = getenv("WAI_FIN_SEPARATE") != nullptr;
-  const char* es = getenv("WAI_PC_STAGGER");
-  c->env.stagger = es ? atoi(es) : -1;
-  c->env.wave_rowptr = getenv("WAI_WAVE_ROWPTR") != nullptr;
   c->env.no_col16 = getenv("WAI_NO_COL16") != nullptr;
-  { const char* e = getenv("WAI_PC_STAGE"); c->env.stage = e ? atoi(e) : -1; }   // k_pc_park's operand stage: 0 off, 1 composed launch, 2 both launches; -1 default
   c->env.scalar_kernels = getenv("WAI_BCGS_SCALAR_KERNELS") != nullptr;   // several ranks: the one-thread kernels behind the all-reduces (rounds 3-4)
-  { const char* e = getenv("WAI_FACE_STREAM"); c->env.no_face_stream = !(e && e[0] == '1'); }   // measured slower: off unless asked for
 }
 int bcgs_post(wai_ctx* c, int seq);
 static inline int pc_threads(const IluSchedule& s) { return ((s.max_rows + 63) / 64) * 64; }
@@ -2722,16 +2588,6 @@ bool pc_axpy_default(const wai_ctx* c) {
   return (kind == 1 && c->ilu.col16 && !c->env.no_col16) || kind == 3;   // k_pc_park on col16, k_pc_wave: measured faster end to end
 }
 
-// k_pc_park: is the brick's own operand segment staged in LDS (template SL)?  WAI_PC_STAGE = 0 never, 1 the composed
-// launch only, 2 both launches
-static bool pc_stage(const wai_ctx* c, bool composed) {
-  const int m = c->env.stage >= 0 ? c->env.stage : WAI_PC_STAGE_DEFAULT;
-  return composed ? m >= 1 : m >= 2;
-}
-
-// ticks of the 100-MHz clock between the cohorts of a fused launch's first generation (stagger_start); WAI_PC_STAGGER overrides
-static int stagger_ticks(const wai_ctx* c, int dflt) { return c->env.stagger >= 0 ? c->env.stagger : dflt; }
-
 template <int BS>
 static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool spmv, const double* in, double* z,
                          int dot_mode, const double* aux, const int* list, int nrun, const Fin* finp, const double* in2) {
@@ -2770,11 +2626,11 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
       const int* rp = (size_t)J.nnzb * 10 < (size_t)J.n * J.W * 9 ? J.rowptr : nullptr;   // > 10 % padding
 #define PCW(SP, AXV)                                                                                \
       hipLaunchKernelGGL((k_pc_wave<BS, SP, AXV>), gridw, 256, lds_w, c->stream, J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, s.row_info, \
-                         s.row_uoffw, J.col, s.fval, s.dinv, in, in2, scal, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, list, rp, (c->env.wave_rowptr ? nullptr : s.sub_split), per, pbase, fin, stagger)
+                         s.row_uoffw, J.col, s.fval, s.dinv, in, in2, scal, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, list, rp, s.sub_split, per, pbase, fin, stagger)
       Stagger stagger;
       stagger.ncu = c->n_cu;
       stagger.per_cu = std::max(1, (int)((size_t)160 * 1024 / (lds_w + 864)));
-      stagger.ticks = stagger_ticks(c, 400);
+      stagger.ticks = 400;   // ticks of the 100-MHz clock between the cohorts (stagger_start)
       if (spmv) { if (in2) PCW(true, true); else PCW(true, false); }
       else PCW(false, false);
 #undef PCW
@@ -2799,21 +2655,19 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
     // upper blocks parked in LDS: three resident workgroups per CU
     if (kind == 1) {
       const size_t lds_park = lds + (size_t)s.max_ublocks * 4 * sizeof(double);
-#define PCP3(SP, AXV, C16V, SLV)                                                                   \
-      hipLaunchKernelGGL((k_pc_park<SP, AXV, C16V, SLV>), grid, T, lds_park, c->stream, J.n, J.W, nrun, s.sub_ptr, s.sub_nlev,  \
+#define PCP2(SP, AXV, C16V)                                                                        \
+      hipLaunchKernelGGL((k_pc_park<SP, AXV, C16V>), grid, T, lds_park, c->stream, J.n, J.W, nrun, s.sub_ptr, s.sub_nlev,  \
                          s.row_info, s.row_uoff, J.col, s.col16, s.sub_seg, s.fval, s.dinv, in, in2, scal, z, aux, c->ks.partials, \
                          c->ks.nb_max, dot_mode, list, fin, stagger)
-#define PCP2(SP, AXV, C16V) do { if (SP && pc_stage(c, AXV)) PCP3(SP, AXV, C16V, SP); else PCP3(SP, AXV, C16V, false); } while (0)
 #define PCP(SP, AXV) do { if (s.col16 && !c->env.no_col16) PCP2(SP, AXV, true); else PCP2(SP, AXV, false); } while (0)
       Stagger stagger;
       stagger.ncu = c->n_cu;
       stagger.per_cu = std::max(1, std::min(3, (int)((size_t)160 * 1024 / (lds_park + 704))));
-      stagger.ticks = stagger_ticks(c, 600);
+      stagger.ticks = 600;
       if (spmv) { if (in2) PCP(true, true); else PCP(true, false); }
       else PCP(false, false);
 #undef PCP
 #undef PCP2
-#undef PCP3
       return;
     }
   }

@@ -4,10 +4,6 @@
 
 using namespace wai;
 
-#ifdef WAI_PC_PHASES
-namespace wai { void pc_phases_fetch(unsigned long long out[8], bool reset); }
-#endif
-
 namespace {
 // What the memory system gives a plain stream on this box, for the bench line's roofline.copy_ceiling / read_ceiling:
 // 16-byte streaming loads (and stores), two per thread and trip, enough workgroups to fill the chip.
@@ -45,7 +41,6 @@ extern "C" {
 int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   if (!c || !ms_per_launch || reps <= 0) return -2;
   read_env(c);
-  if (which == 16 && ensure_face_stream(c)) return -1;
   if ((which == 20 || which == 21) && !c->ks.basis) { c->err = "wai_bench_kernel 20 / 21: no Krylov basis (ksp_type gmres)"; return -2; }
   if (which > 0 && !c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e < 0 ? -1 : e; }
   Krylov& k = c->ks;
@@ -149,18 +144,6 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
   *ms_per_launch = ms / reps;
   if (which == 20 || which == 21) *ms_per_launch /= (float)std::min(std::max(c->opts.gmres_restart, 1), k.basis_m);
-#ifdef WAI_PC_PHASES
-  {
-    unsigned long long ph[8];
-    pc_phases_fetch(ph, true);
-    if (ph[7]) {
-      const double n = (double)ph[7], us = 0.01;   // 100 MHz ticks; the last launch's workgroups
-      fprintf(stderr, "pc phases (which %d, %.0f workgroups, %.4f ms per launch): load %.2f wait %.2f forward %.2f backward %.2f epilogue %.2f us per workgroup; "
-              "resident workgroups on average %.1f\n", which, n, ms / reps, ph[0] * us / n, ph[1] * us / n, ph[2] * us / n, ph[3] * us / n, ph[4] * us / n,
-              (ph[0] + ph[1] + ph[2] + ph[3] + ph[4]) * us * 1e-3 / (double)(ms / reps));
-    }
-  }
-#endif
   return 0;
 }
 

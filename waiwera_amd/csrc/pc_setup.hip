@@ -171,9 +171,9 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       dev_upload(c, &s.row_uoff, uoff) || dev_upload(c, &s.row_uoffw, uoffw) || dev_upload(c, &s.row_tslot, tslot) ||
       dev_alloc(c, &s.fval, ell_size(np, N, W)) || dev_alloc(c, &s.dinv, (size_t)np * np * ell_rows(np, N)))
     return -1;
-  // Kernel-selection switches are build-time (A/B builds: WAI_EXTRA_HIPCC_FLAGS="-DWAI_ILU_GENERAL" ...); the
-  // run-time environment only steers what the tests compare in one process (WAI_BCGS_MERGED, WAI_JAC_PARK,
-  // WAI_HALO_OVERLAP) and the transport library (WAI_RCCL_LIB).
+  // Kernel-selection switches.  Build time, for the fallback build that drives the GPU tests through the generic kernels
+  // (tools/ci_fallback_kernels.sh): WAI_ILU_GENERAL, WAI_PC_ROWS, WAI_PC_WAVE.  Run time, for the tests that compare paths
+  // in one process: WAI_NO_COL16 (k_pc_park on the int32 column planes: read_env) and WAI_COL16_MAX_SEG (below).
   s.diag_only = !offdiag_fill && !s.big;
   s.level_sorted = !s.big;
   for (int sd = 0; sd < s.nsub && s.level_sorted; sd++)
@@ -184,19 +184,10 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
 #ifdef WAI_ILU_GENERAL
   s.diag_only = false;     // stored L / U factor everywhere
 #endif
-#ifdef WAI_ILU_NOFAST
-  s.fast3 = false;         // no compacted 3 + 3 couplings
-#endif
-#ifdef WAI_ILU_NOSCALE
-  s.scaled = false;        // DILU with the inverted pivots read per application
-#endif
   {
     // 160 KB of LDS per CU; a workgroup may use 64 KB
     const size_t need = ((size_t)(((s.max_rows + 63) / 64) * 64) * np + 32 + (size_t)s.max_ublocks * 4) * sizeof(double);
     s.park = need <= 64 * 1024;
-#ifdef WAI_PC_NOPARK
-    s.park = false;        // k_pc instead of k_pc_park
-#endif
   }
   {
     // one thread per scalar row: needs the pivot-scaled DILU form, <= 4 + 4 couplings and a brick whose
@@ -284,9 +275,6 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
         }
       }
     }
-#ifdef WAI_NO_COL16
-    ok = false;            // A/B builds: the int32 planes everywhere
-#endif
     if (ok) {
       if (hipMalloc(reinterpret_cast<void**>(&s.col16), c16.size() * sizeof(unsigned short)) != hipSuccess ||
           hipMemcpy(s.col16, c16.data(), c16.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) {
