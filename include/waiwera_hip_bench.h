@@ -29,6 +29,19 @@ int wai_test_drop_partials(wai_ctx *ctx, int n);
  * is enqueued WITHOUT waiting for the event behind the unpack on the communication stream.  Over a stream-asynchronous
  * transport a multi-rank solve must then go wrong (tests/test_hip_multirank.py); 0 restores the product's ordering */
 int wai_test_drop_stream_wait(wai_ctx *ctx, int which);
+/* one preconditioned-operator application exactly as the Krylov drivers issue it, for the tests (vectors: bs * n_owned doubles,
+ * host or device; scal_in / scal_out: the 16 device scalars S_RHO .. S_BREAK before / after).
+ * spmv 1: z = B^-1 A (x - alpha x2) through the drivers' pc_amul (x2 may be NULL; non-NULL only where wai_pc_axpy_capable);
+ * spmv 0: z = B^-1 x through pc_solve, x the partner of dot modes 2 and 4.  dot_mode 0 none, 1 (z,aux), 2 (x,z),(z,z),
+ * 3 (z,z), 4 (x,z),(z,z),(x,x),(x,aux),(z,aux) -- x meaning the operand x - alpha x2.  split 1: interior bricks, then face
+ * bricks (the overlapped halo exchange's two launches; one rank, meshes of seven-block rows only).  fin_phase >= -1: the
+ * reductions finished (and the BiCGStab scalars of that phase derived) as the drivers finish them; -2: left as partial sums
+ * and finished here by k_finalize without a derivation.  S_ALPHA is set to alpha.  A combination the library cannot serve
+ * (x2 on a kernel that cannot form its operand, split without interior / face lists) is an error (-1), not a result. */
+int wai_test_pc_operator(wai_ctx *ctx, int spmv, const double *x, const double *x2, double alpha, int dot_mode,
+                         const double *aux, int split, int fin_phase, const double *scal_in, double *z, double *scal_out);
+/* 1 when the fused preconditioned-operator launch can form its operand x - alpha x2 itself (wai_test_pc_operator's x2) */
+int wai_pc_axpy_capable(wai_ctx *ctx);
 /* bytes this rank sends per halo exchange of a dof-per-cell vector, and its number of neighbours */
 int wai_halo_size(wai_ctx *ctx, int dof, long long *bytes_sent, int *n_neighbours);
 

@@ -29,6 +29,8 @@ __global__ __launch_bounds__(256) void k_stream_read(const stream_d2* __restrict
   if (i < n2) { const stream_d2 a = __builtin_nontemporal_load(src + i); t += a.x + a.y; }
   if (t == 1.2345678e300) *sink = t;   // never: keeps the loads
 }
+// can pc_amul form its operand x - alpha x2 inside the launch?  (pc_axpy_ok without the switch and the default)
+bool pc_operand_composable(const wai_ctx* c) { return pc_fused(c) && !c->net.cp_valid && pc_axpy_capable(c); }
 }  // namespace
 
 extern "C" {
@@ -184,6 +186,61 @@ int wai_launch_stats(wai_ctx* c, long long* kernels, long long* copies) {
   return 0;
 }
 int wai_test_drop_partials(wai_ctx* c, int n) { return c ? test_drop_partials(c, n) : -2; }
+// one preconditioned-operator application as the drivers issue it (waiwera_hip_bench.h): the inputs into the Krylov work
+// vectors (halo room), the scalars seeded, the partial slots emptied as a driver empties them before its first producer,
+// then pc_amul / pc_solve / launch_pc_split unchanged
+int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2, double alpha, int dot_mode, const double* aux,
+                         int split, int fin_phase, const double* scal_in, double* z, double* scal_out) {
+  if (!c || !x || !z || !scal_in || !scal_out || dot_mode < 0 || dot_mode > 4 || fin_phase < -2) return -2;
+  if ((dot_mode == 1 || dot_mode == 4) && !aux) { c->err = "wai_test_pc_operator: dot modes 1 and 4 need aux"; return -2; }
+  read_env(c);
+  if (!c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e < 0 ? -1 : e; }
+  if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
+  if (split && (!spmv || !pc_fused(c) || c->net.cp_valid || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
+    c->err = "wai_test_pc_operator: no interior / face brick lists to split the launch over";
+    return -1;
+  }
+  Krylov& k = c->ks;
+  const size_t n = (size_t)k.n;
+  double s[16];
+  for (int i = 0; i < 16; i++) s[i] = scal_in[i];
+  s[S_ALPHA] = alpha;
+  HIPCHK(c, hipMemcpyAsync(k.R, x, n * sizeof(double), hipMemcpyDefault, c->stream));
+  if (x2) HIPCHK(c, hipMemcpyAsync(k.V, x2, n * sizeof(double), hipMemcpyDefault, c->stream));
+  if (aux) HIPCHK(c, hipMemcpyAsync(k.RP, aux, n * sizeof(double), hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k.scal, s, sizeof(s), hipMemcpyHostToDevice, c->stream));
+  partials_clear(c, S_D1, 5);
+  const double* a = aux ? k.RP : nullptr;
+  const double* v = x2 ? k.V : nullptr;
+  int e = 0;
+  if (split) {
+    Fin fin;
+    const Fin* fp = nullptr;
+    if (fin_phase >= -1 && dot_mode) {
+      int slot0, nslots;
+      mode_slots(dot_mode, slot0, nslots);
+      fin = make_fin(c, slot0, nslots, fin_phase);
+      fp = &fin;
+    }
+    e = launch_pc_split(c, k.R, k.T, dot_mode, a, fp, v, nullptr);
+  } else if (spmv) {
+    e = pc_amul(c, k.R, k.T, dot_mode, a, fin_phase, v, false);
+  } else {
+    e = pc_solve(c, k.R, k.T, dot_mode, k.R, a, fin_phase);
+  }
+  if (e) return e;
+  if (fin_phase == -2 && dot_mode) {   // the partial sums left behind, summed by k_finalize as the general path sums them
+    int slot0, nslots;
+    mode_slots(dot_mode, slot0, nslots);
+    vec_finalize(c, k.nb_pc, slot0, nslots, -1);
+  }
+  HIPCHK(c, hipMemcpyAsync(z, k.T, n * sizeof(double), hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipMemcpyAsync(s, k.scal, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 16; i++) scal_out[i] = s[i];
+  return 0;
+}
+int wai_pc_axpy_capable(wai_ctx* c) { return c ? (pc_operand_composable(c) ? 1 : 0) : -2; }
 int wai_test_drop_stream_wait(wai_ctx* c, int which) { if (!c) return -2; c->test_drop_wait = which; return 0; }
 int wai_bench_mute_comm(wai_ctx* c, int on) {
   if (!c) return -2;

@@ -355,6 +355,25 @@ class FlowSimulation:
     def pc_apply(self, r, z):
         return self._chk(LIB.wai_pc_apply(self.h, _lib.ptr(r), _lib.ptr(z)), "pc_apply")
 
+    def pc_operator(self, x, x2=None, alpha=0.0, dot_mode=0, aux=None, spmv=True, split=False, fin_phase=-2, scal_in=None):
+        """one preconditioned-operator application as the Krylov drivers issue it (tests): z = B^-1 A (x - alpha x2)
+        (spmv) or B^-1 x, with dot_mode's inner products finished in the launch (fin_phase >= -1: and that phase's
+        BiCGStab scalars derived) or by k_finalize (-2); (z, the 16 device scalars after)"""
+        xi = _lib._f64(x)
+        x2i = _lib._f64(x2) if x2 is not None else None
+        ai = _lib._f64(aux) if aux is not None else None
+        s_in = _lib._f64(np.zeros(16) if scal_in is None else scal_in)
+        assert xi.size == self.num_dof and s_in.size == 16
+        z, s_out = np.zeros(self.num_dof), np.zeros(16)
+        self._chk(LIB.wai_test_pc_operator(self.h, 1 if spmv else 0, _lib.ptr(xi), _lib.ptr(x2i), float(alpha), int(dot_mode),
+                                           _lib.ptr(ai), 1 if split else 0, int(fin_phase), s_in.ctypes.data_as(_lib.pd),
+                                           _lib.ptr(z), s_out.ctypes.data_as(_lib.pd)), "test_pc_operator")
+        return z, s_out
+
+    def pc_axpy_capable(self):
+        """can the fused launch form its operand x - alpha x2 itself (pc_operator's x2)?"""
+        return LIB.wai_pc_axpy_capable(self.h) == 1
+
     def ksp_solve(self, b, x):
         its, reason, rn = C.c_int(0), C.c_int(0), C.c_double(0)
         self._chk(LIB.wai_ksp_solve(self.h, _lib.ptr(b), _lib.ptr(x), C.byref(its), C.byref(reason),

@@ -146,6 +146,8 @@ def _load():
         "wai_bench_mute_comm": (i32, [vp, i32]),
         "wai_test_drop_partials": (i32, [vp, i32]),
         "wai_test_drop_stream_wait": (i32, [vp, i32]),
+        "wai_test_pc_operator": (i32, [vp, i32, vp, vp, d, i32, vp, i32, i32, pd, vp, pd]),
+        "wai_pc_axpy_capable": (i32, [vp]),
         "wai_halo_size": (i32, [vp, i32, C.POINTER(C.c_longlong), C.POINTER(i32)]),
         "wai_pc_kernel_name": (C.c_char_p, [vp]),
         "wai_pre_timestep": (i32, [vp]),
