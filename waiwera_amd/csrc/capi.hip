@@ -1028,7 +1028,7 @@ int wai_pc_apply(wai_ctx* c, const double* r, double* z) {
   if (ri.in(r, c->ks.n, 0) || zo.out_only(z, c->ks.n, 1)) return -1;
   {
     Prof p(c, KC_PC_APPLY);
-    if (pc_solve(c, ri.dev, zo.dev, 0, nullptr, nullptr)) return -1;
+    if (pc_solve(c, ri.dev, zo.dev, PC_DOT_NONE, nullptr, nullptr)) return -1;
   }
   return zo.back();
 }

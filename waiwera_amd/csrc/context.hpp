@@ -63,6 +63,23 @@ enum KClass { KC_EOS = 0, KC_RESIDUAL = 1, KC_JACOBIAN = 2, KC_SPMV = 3, KC_PC_A
 enum { S_RHO = 0, S_RHOOLD = 1, S_ALPHA = 2, S_OMEGA = 3, S_BETA = 4, S_D1 = 5, S_D2 = 6,
        S_DP2 = 7, S_RHONEW = 8, S_W2 = 9, S_BREAK = 15, S_H = 16 };
 
+// The inner products a preconditioned-operator application (launch_pc, pc_solve, pc_amul) reduces as it computes
+// z = B^-1 (A in) or z = B^-1 in, chosen by its dot mode.  A mode's products go to consecutive reduction slots, from
+// pc_dot_slot0(mode) on, in this order:
+//   PC_DOT_NONE   0  none
+//   PC_DOT_ZA     1  (z, aux)                                          S_D1
+//   PC_DOT_XZ     2  (in, z), (z, z)                                   S_D1, S_D2
+//   PC_DOT_ZZ     3  (z, z)                                            S_DP2
+//   PC_DOT_MERGED 4  (in, z), (z, z), (in, in), (in, aux), (z, aux)    S_D1, S_D2, S_DP2, S_RHONEW, S_W2
+// Mode 4 is BiCGStab's merged reductions (krylov.hip, bcgs_second_half): one application, five inner products.
+enum PcDot { PC_DOT_NONE = 0, PC_DOT_ZA = 1, PC_DOT_XZ = 2, PC_DOT_ZZ = 3, PC_DOT_MERGED = 4 };
+static_assert(S_D2 == S_D1 + 1 && S_DP2 == S_D1 + 2 && S_RHONEW == S_D1 + 3 && S_W2 == S_D1 + 4,
+              "the merged reductions' slots S_D1 .. S_W2 are consecutive: a reduction addresses them as slot0 + index");
+__host__ __device__ constexpr int pc_dot_slot0(int mode) { return mode == PC_DOT_ZZ ? S_DP2 : S_D1; }
+__host__ __device__ constexpr int pc_dot_nslots(int mode) {
+  return mode == PC_DOT_MERGED ? 5 : (mode == PC_DOT_XZ ? 2 : (mode == PC_DOT_NONE ? 0 : 1));
+}
+
 struct Comm;  // RCCL state (comm.cpp)
 
 struct DeviceMesh {
@@ -463,8 +480,7 @@ int launch_asm_scatter(wai_ctx* c, double* z);             // z[owned] <- as.r_e
 int vec_dots(wai_ctx* c, const double* a1, const double* b1, int slot1, const double* a2, const double* b2,
              int slot2, int n);
 // z = B^-1 r (spmv = false) or z = B^-1 (A x) (spmv = true: x is `in`, haloed by the caller).
-// dot_mode 0: none; 1: scal-partials S_D1 += (z, aux); 2: S_D1 += (in, z), S_D2 += (z, z);
-// 3: S_DP2 += (z, z)
+// dot_mode: the inner products reduced on the way (PcDot above), aux the partner of modes 1 and 4
 // list / nrun: run only the listed subdomains (null: all)
 // fin (optional): finalise the dot products in the kernel's last workgroup instead of a k_finalize launch
 int launch_pc(wai_ctx* c, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
@@ -472,6 +488,10 @@ int launch_pc(wai_ctx* c, bool spmv, const double* in, double* z, int dot_mode, 
 // finalisation descriptor for slots [slot0, slot0 + nslots) (the launcher fills in the workgroup counts);
 // post: mirror the scalars to the host with a fresh sequence number (left in ks.seq)
 Fin make_fin(wai_ctx* c, int slot0, int nslots, int phase, bool post = false);
+// the same for the slots of a dot mode (PcDot)
+inline Fin make_fin_dots(wai_ctx* c, int dot_mode, int phase, bool post = false) {
+  return make_fin(c, pc_dot_slot0(dot_mode), pc_dot_nslots(dot_mode), phase, post);
+}
 int launch_ell_to_bcsr(wai_ctx* c, const double* ell, double* bcsr);
 int launch_bcsr_to_ell(wai_ctx* c, const double* bcsr, double* ell);
 // reductions: partial sums live in ks.partials[slot][block]; finalize sums nb partials of

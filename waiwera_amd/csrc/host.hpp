@@ -120,7 +120,6 @@ int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof
 int do_pc_setup(wai_ctx* c);
 // ---- krylov.hip --------------------------------------------------------------------------------------------------
 int halo_exchange(wai_ctx* c, double* vec, int dof);
-void mode_slots(int dot_mode, int& slot0, int& nslots);   // the reduction slots a fused launch's dot mode fills
 // the two launches of the overlapped halo exchange on the compute stream: interior bricks, then face bricks behind `after`
 // (null: behind what the compute stream held when called)
 int launch_pc_split(wai_ctx* c, const double* x, double* z, int dot_mode, const double* aux, const Fin* fp, const double* x2,
@@ -131,7 +130,7 @@ int read_scal(wai_ctx* c, int first, int count);
 // products are summed into the device scalars (and the BiCGStab scalars of that phase derived); -2: left as partials
 int pc_solve(wai_ctx* c, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase = -2);
 // z = B^-1 A x (x has halo room); x2: the operand is x - alpha x2 (fused kernels); post: the scalars to the host
-int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode = 0, const double* aux = nullptr, int fin_phase = -2,
+int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode = PC_DOT_NONE, const double* aux = nullptr, int fin_phase = -2,
             const double* x2 = nullptr, bool post = false);
 int do_ksp(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm);
 int bcgs_mode(const wai_ctx* c);

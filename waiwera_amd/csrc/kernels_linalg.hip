@@ -804,13 +804,14 @@ __device__ __forceinline__ void sum_partials(const double* partials, int nb_max,
 // so that the workgroup that finishes a reduction can read it without any cache-wide fence
 // Fault injection for the tests (wai_test_drop_partials): while positive, workgroup 0 of a launch loses its partial sums
 // (and counts the variable down) -- the finaliser must then run into its bounded wait, report breakdown code 4, and the
-// solver must come back with KSP_DIVERGED_NANORINF instead of hanging or summing stale data.
+// solver must come back with KSP_DIVERGED_NANORINF instead of hanging or summing stale data.  Several waves of workgroup 0
+// store at once: the count taken decides, so that a request of n drops exactly n (a store that lost the race leaves the
+// variable below zero, which ends the injection as zero does).
 __device__ int g_drop_partials = 0;
 __device__ __forceinline__ void store_partial(double* p, double t) {
-  if (blockIdx.x == 0 && __hip_atomic_load(&g_drop_partials, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0) {
-    atomicSub(&g_drop_partials, 1);
+  if (blockIdx.x == 0 && __hip_atomic_load(&g_drop_partials, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0 &&
+      atomicSub(&g_drop_partials, 1) > 0)
     return;
-  }
   __hip_atomic_store(p, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // is this workgroup one of the launch's finalisers (the last f.nf workgroups)?  If so do its share (the caller returns)
@@ -897,9 +898,10 @@ __device__ __forceinline__ void stagger_start(const Stagger& st) {
 
 // ---- K6+K8 fused: z = U^-1 L^-1 (A x)  or  z = U^-1 L^-1 r ------------------------------------
 
+// the workgroup's sums of v[0 .. NS) into the partials of the consecutive slots slot0, slot0 + 1, ... (entry blk)
 template <int NS>
 __device__ __forceinline__ void wg_reduce_store(double (&v)[NS], double* red, double* partials,
-                                                int nb_max, const int* slots, int blk) {
+                                                int nb_max, int slot0, int blk) {
   // red: LDS scratch of NS * 16 doubles (up to 16 waves per workgroup)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll
@@ -909,16 +911,15 @@ __device__ __forceinline__ void wg_reduce_store(double (&v)[NS], double* red, do
   }
   __syncthreads();
   // Round 6, one WAVE per slot: wave s's first lane adds the waves' sums of slot s (w = 0, 1, ... in order: same bits), the NS chains
-  // side by side; the callers' slot numbers are consecutive, so slot = first + wave (an indexed or selected table went to scratch).
+  // side by side; slot = slot0 + wave (an indexed or selected table of slot numbers went to scratch).
   // MEASURED (profiles/epiw_ab_r6_*.log, alternating same-box rounds): the composed launch with its five sums 0.6889 -> 0.6836 ms at
   // 216^3, 0.0977 -> 0.0961 at 108^3 (three rounds each, every round the same sign); one-sum launches and k_pc_wave unchanged.
   // (Before: thread 0 added all slots, rounds 1-5.)
   if (nw >= NS) {      // (a workgroup of fewer waves than slots: the one-lane form below)
     if (lane == 0 && w < NS) {
-      const int slot = slots[0] + w;   // the callers' slots are consecutive (S_D1 .. S_W2, context.hpp)
       double t = 0.0;
       for (int q = 0; q < nw; q++) t += red[w * 16 + q];
-      store_partial(partials + (size_t)slot * nb_max + blk, t);
+      store_partial(partials + (size_t)(slot0 + w) * nb_max + blk, t);
     }
     return;
   }
@@ -930,8 +931,49 @@ __device__ __forceinline__ void wg_reduce_store(double (&v)[NS], double* red, do
     for (int s = 0; s < NS; s++) {
       double t = 0.0;
       for (int q = 0; q < nw; q++) t += red[s * 16 + q];
-      store_partial(partials + (size_t)slots[s] * nb_max + blk, t);
+      store_partial(partials + (size_t)(slot0 + s) * nb_max + blk, t);
     }
+  }
+}
+// the workgroup's partial sums of dot mode `mode`'s products (v: pc_row_dots), one per slot, into entry blk
+__device__ __forceinline__ void pc_reduce_dots(int mode, double (&v)[5], double* red, double* partials, int nb_max, int blk) {
+  const int slot0 = pc_dot_slot0(mode);
+  if (mode == PC_DOT_MERGED) wg_reduce_store<5>(v, red, partials, nb_max, slot0, blk);
+  else if (mode == PC_DOT_XZ) { double v2[2] = {v[0], v[1]}; wg_reduce_store<2>(v2, red, partials, nb_max, slot0, blk); }
+  else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slot0, blk); }
+}
+
+// One row's (k_pc_rows, k_pc_wave: one scalar's) terms of dot mode `mode`'s products (context.hpp, PcDot), for a mode
+// other than none: v[0 .. pc_dot_nslots(mode)) gain x.o, o.o, ... over N components, with o the result z, x the operand
+// and a the partner aux.  get_x(x) / get_a(a) fill in the operand and the partner inside the branch of a mode that
+// needs them, so that each kernel's loads stay where they were.  Modes 1 and 4 skip inactive rows; mode 2 skips them
+// where GUARD2, and mode 3 never does.  Each kernel keeps the arithmetic it always had, because the two forms round apart
+// once the compiler contracts them into FMAs:
+//   SUM = false (k_pc, k_pc_wave): term by term, v[q] += x[0] o[0]; v[q] += x[1] o[1]; ...
+//   SUM = true (k_pc_park, k_pc_rows): one sum per product, v[q] = x[0] o[0] + x[1] o[1] + ...
+template <int N, bool SUM, bool GUARD2, class GetX, class GetA>
+__device__ __forceinline__ void pc_row_dots(int mode, double (&v)[5], const double (&o)[N], bool active, GetX get_x,
+                                            GetA get_a) {
+  auto dot = [&](int q, const double (&p)[N], const double (&r)[N]) {
+    if constexpr (SUM) {
+      double t = p[0] * r[0];
+#pragma unroll
+      for (int k = 1; k < N; k++) t += p[k] * r[k];
+      v[q] = t;
+    } else {
+#pragma unroll
+      for (int k = 0; k < N; k++) v[q] += p[k] * r[k];
+    }
+  };
+  double x[N], a[N];
+  if (mode == PC_DOT_ZA) {
+    if (active) { get_a(a); dot(0, o, a); }
+  } else if (mode == PC_DOT_XZ) {
+    if (active || !GUARD2) { get_x(x); dot(0, x, o); dot(1, o, o); }
+  } else if (mode == PC_DOT_MERGED) {
+    if (active) { get_x(x); get_a(a); dot(0, x, o); dot(1, o, o); dot(2, x, x); dot(3, x, a); dot(4, o, a); }
+  } else {
+    dot(0, o, o);
   }
 }
 
@@ -1039,7 +1081,7 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? PC_MIN_WAVES : 4)) void k_pc(int n
         }
       }
       if constexpr (!SPMV) load_x<BS>(in, i, acc);
-      if (dot == 2 || dot == 4) load_x<BS>(in, i, xin);
+      if (dot == PC_DOT_XZ || dot == PC_DOT_MERGED) load_x<BS>(in, i, xin);
       if constexpr (!SC) load_pivot<BS>(dinv, n, i, dv);
       if constexpr (SC && !SPMV) {  // plain application to an unscaled vector: scale it first
         load_pivot<BS>(dinv, n, i, dv);
@@ -1058,7 +1100,7 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? PC_MIN_WAVES : 4)) void k_pc(int n
 #pragma unroll
         for (int r = 0; r < BS; r++) acc[r] = 0.0;
         ell_row_mult<BS>(n, W, i, col, aval, in, acc);
-        if (dot == 2 || dot == 4) load_x<BS>(in, i, xin);
+        if (dot == PC_DOT_XZ || dot == PC_DOT_MERGED) load_x<BS>(in, i, xin);
       } else {
         load_x<BS>(in, i, acc);
       }
@@ -1241,36 +1283,12 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? PC_MIN_WAVES : 4)) void k_pc(int n
   if (dot != 0) {
     double* red = lds + (size_t)blockDim.x * BS;
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    int slots[5] = {S_D1, S_D2, S_DP2, S_RHONEW, S_W2};
-    if (dot == 1) {  // (z, aux)
-      if (active) {
-        double av[BS];
-        load_x_stream<BS>(aux, i, av);
+    pc_row_dots<BS, false, false>(dot, v, out, active, [&](double (&x)[BS]) {
 #pragma unroll
-        for (int r = 0; r < BS; r++) v[0] += out[r] * av[r];
-      }
-    } else if (dot == 2) {  // (in, z), (z, z)
-#pragma unroll
-      for (int r = 0; r < BS; r++) { v[0] += xin[r] * out[r]; v[1] += out[r] * out[r]; }
-    } else if (dot == 4) {  // merged BiCGStab reductions: (in,z), (z,z), (in,in), (in,aux), (z,aux)
-      if (active) {
-        double av[BS];
-        load_x_stream<BS>(aux, i, av);
-#pragma unroll
-        for (int r = 0; r < BS; r++) {
-          v[0] += xin[r] * out[r]; v[1] += out[r] * out[r]; v[2] += xin[r] * xin[r];
-          v[3] += xin[r] * av[r]; v[4] += out[r] * av[r];
-        }
-      }
-    } else {  // (z, z)
-#pragma unroll
-      for (int r = 0; r < BS; r++) v[0] += out[r] * out[r];
-      slots[0] = S_DP2;
-    }
+      for (int r = 0; r < BS; r++) x[r] = xin[r];
+    }, [&](double (&a)[BS]) { load_x_stream<BS>(aux, i, a); });
     __syncthreads();
-    if (dot == 4) wg_reduce_store<5>(v, red, partials, nb_max, slots, s);
-    else if (dot == 2) { double v2[2] = {v[0], v[1]}; wg_reduce_store<2>(v2, red, partials, nb_max, slots, s); }
-    else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slots, s); }
+    pc_reduce_dots(dot, v, red, partials, nb_max, s);
   }
 }
 
@@ -1420,8 +1438,8 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       acc[0] = dv[0] * r[0] + dv[1] * r[1];
       acc[1] = dv[2] * r[0] + dv[3] * r[1];
     }
-    if (dot == 2 || dot == 4) load_xs<BS, AX>(in, in2, nalpha, i, xin);
-    if (dot == 1 || dot == 4) load_x_stream<BS>(aux, i, avp);   // the dot product's partner: in flight through the sweeps
+    if (dot == PC_DOT_XZ || dot == PC_DOT_MERGED) load_xs<BS, AX>(in, in2, nalpha, i, xin);
+    if (dot == PC_DOT_ZA || dot == PC_DOT_MERGED) load_x_stream<BS>(aux, i, avp);   // the dot product's partner: in flight through the sweeps
   }
   if (active) *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(acc[0], acc[1]);
   __syncthreads();
@@ -1472,31 +1490,12 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   if (dot != 0) {
     double* red = lds + (size_t)blockDim.x * BS;
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    int slots[5] = {S_D1, S_D2, S_DP2, S_RHONEW, S_W2};
-    if (dot == 1) {
-      if (active) v[0] = out[0] * avp[0] + out[1] * avp[1];
-    } else if (dot == 2) {
-      v[0] = xin[0] * out[0] + xin[1] * out[1];
-      v[1] = out[0] * out[0] + out[1] * out[1];
-    } else if (dot == 4) {  // merged BiCGStab reductions: (in,z), (z,z), (in,in), (in,aux), (z,aux)
-      if (active) {
-        const double* av = avp;
-        v[0] = xin[0] * out[0] + xin[1] * out[1];
-        v[1] = out[0] * out[0] + out[1] * out[1];
-        v[2] = xin[0] * xin[0] + xin[1] * xin[1];
-        v[3] = xin[0] * av[0] + xin[1] * av[1];
-        v[4] = out[0] * av[0] + out[1] * av[1];
-      }
-    } else {
-      v[0] = out[0] * out[0] + out[1] * out[1];
-      slots[0] = S_DP2;
-    }
+    pc_row_dots<BS, true, false>(dot, v, out, active, [&](double (&x)[BS]) { x[0] = xin[0]; x[1] = xin[1]; },
+                                 [&](double (&a)[BS]) { a[0] = avp[0]; a[1] = avp[1]; });
     // the reduction scratch is touched by nothing before this point; dropping the barrier was not felt (0.5704 / 0.6942
     // against 0.5714 / 0.6924 ms at 216^3, profiles/nobar_ab_r6_c3.log), so it stays
     __syncthreads();
-    if (dot == 4) wg_reduce_store<5>(v, red, partials, nb_max, slots, s);
-    else if (dot == 2) { double v2[2] = {v[0], v[1]}; wg_reduce_store<2>(v2, red, partials, nb_max, slots, s); }
-    else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slots, s); }
+    pc_reduce_dots(dot, v, red, partials, nb_max, s);
   }
 }
 
@@ -1608,7 +1607,7 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
   }
   // the dot product's partner (block order, tid-linear): in flight through the sweeps
   double avp = 0.0;
-  if (active && (dot == 1 || dot == 4)) avp = __builtin_nontemporal_load(aux + (size_t)lo * BS + tid);
+  if (active && (dot == PC_DOT_ZA || dot == PC_DOT_MERGED)) avp = __builtin_nontemporal_load(aux + (size_t)lo * BS + tid);
   __syncthreads();
   for (int lev = 1; lev < nlf; lev++) {  // forward: y_i = t_i - sum A'_ik y_k
     if (lf == lev) {
@@ -1642,24 +1641,10 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? 8 : (BS == 3 ? (NL <= 3 ? 7 : 5) :
   if (dot != 0) {
     double* red = lds + (size_t)R * BS + BS;
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    int slots[5] = {S_D1, S_D2, S_DP2, S_RHONEW, S_W2};
-    if (dot == 1) {
-      if (active) v[0] = out * avp;
-    } else if (dot == 2) {
-      if (active) { const double xi = AX ? __builtin_fma(nalpha, in2[g], in[g]) : in[g]; v[0] = xi * out; v[1] = out * out; }
-    } else if (dot == 4) {
-      if (active) {
-        const double xi = AX ? __builtin_fma(nalpha, in2[g], in[g]) : in[g], av = avp;
-        v[0] = xi * out; v[1] = out * out; v[2] = xi * xi; v[3] = xi * av; v[4] = out * av;
-      }
-    } else {
-      v[0] = out * out;
-      slots[0] = S_DP2;
-    }
+    pc_row_dots<1, true, true>(dot, v, {out}, active, [&](double (&x)[1]) { x[0] = AX ? __builtin_fma(nalpha, in2[g], in[g]) : in[g]; },
+                               [&](double (&a)[1]) { a[0] = avp; });
     __syncthreads();
-    if (dot == 4) wg_reduce_store<5>(v, red, partials, nb_max, slots, s);
-    else if (dot == 2) { double v2[2] = {v[0], v[1]}; wg_reduce_store<2>(v2, red, partials, nb_max, slots, s); }
-    else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slots, s); }
+    pc_reduce_dots(dot, v, red, partials, nb_max, s);
   }
 }
 
@@ -1735,7 +1720,7 @@ __global__ __launch_bounds__(256) void k_pc_wave(
   double pav[BS];
 #pragma unroll
   for (int j = 0; j < BS; j++) pav[j] = 0.0;
-  if (dot == 1 || dot == 4) {
+  if (dot == PC_DOT_ZA || dot == PC_DOT_MERGED) {
     const int totp = R * BS;
 #pragma unroll
     for (int j = 0; j < BS; j++) pav[j] = __builtin_nontemporal_load(aux + (size_t)lo * BS + min(lane + 64 * j, totp - 1));
@@ -1838,7 +1823,7 @@ __global__ __launch_bounds__(256) void k_pc_wave(
   double pxi[BS], pi2[BS];
 #pragma unroll
   for (int j = 0; j < BS; j++) { pxi[j] = 0.0; pi2[j] = 0.0; }
-  if (dot == 2 || dot == 4) {
+  if (dot == PC_DOT_XZ || dot == PC_DOT_MERGED) {
     const int totp = R * BS;
 #pragma unroll
     for (int j = 0; j < BS; j++) {
@@ -1881,12 +1866,9 @@ __global__ __launch_bounds__(256) void k_pc_wave(
       const size_t gi = (size_t)lo * BS + t;
       const double out = ys[t];
       __builtin_nontemporal_store(out, z + gi);
-      if (dot == 1) v[0] += out * pav[j];
-      else if (dot == 2) { const double xi = AX ? __builtin_fma(nalpha, pi2[j], pxi[j]) : pxi[j]; v[0] += xi * out; v[1] += out * out; }
-      else if (dot == 4) {
-        const double xi = AX ? __builtin_fma(nalpha, pi2[j], pxi[j]) : pxi[j], av = pav[j];
-        v[0] += xi * out; v[1] += out * out; v[2] += xi * xi; v[3] += xi * av; v[4] += out * av;
-      } else if (dot == 3) v[0] += out * out;
+      if (dot != 0)
+        pc_row_dots<1, false, false>(dot, v, {out}, true, [&](double (&x)[1]) { x[0] = AX ? __builtin_fma(nalpha, pi2[j], pxi[j]) : pxi[j]; },
+                                     [&](double (&a)[1]) { a[0] = pav[j]; });
     }
   }
   if (dot != 0) {
@@ -1896,8 +1878,7 @@ __global__ __launch_bounds__(256) void k_pc_wave(
     // interval (profiles/fin_jv_ab_r4.log, fin_sleep_ab_r4.log).  The workgroup's LDS is held until its last brick ends
     // anyway, so the barrier costs no residency.  Index: the workgroup's position in the launch's list + pbase (the
     // face bricks' launch continues where the interior bricks' ended)
-    const int ns = dot == 4 ? 5 : (dot == 2 ? 2 : 1);
-    const int slot0 = dot == 3 ? S_DP2 : S_D1;   // S_D1 .. S_W2 are consecutive
+    const int ns = pc_dot_nslots(dot), slot0 = pc_dot_slot0(dot);
 #pragma unroll
     for (int q = 0; q < 5; q++) {
       if (q < ns) {

@@ -55,30 +55,26 @@ int read_scal_end(wai_ctx* c) {
   return 0;
 }
 
-// dot products the Krylov drivers want of a preconditioner result (see launch_pc): general path
+// the dot mode's products of a preconditioner result (context.hpp, PcDot), reduced by separate launches: general path
 int pc_dots(wai_ctx* c, int dot_mode, const double* x, const double* z, const double* aux) {
-  const int n = c->ks.n;
-  if (dot_mode == 1) return vec_dots(c, z, aux, S_D1, nullptr, nullptr, 0, n);
-  if (dot_mode == 2) return vec_dots(c, x, z, S_D1, z, z, S_D2, n);
-  if (dot_mode == 4) {   // merged BiCGStab reductions: (x,z), (z,z), (x,x), (x,aux), (z,aux)
-    vec_dots(c, x, z, S_D1, z, z, S_D2, n);
-    vec_dots(c, x, x, S_DP2, x, aux, S_RHONEW, n);
-    return vec_dots(c, z, aux, S_W2, nullptr, nullptr, 0, n);
+  const int n = c->ks.n, s = pc_dot_slot0(dot_mode);
+  switch (dot_mode) {
+    case PC_DOT_ZA: return vec_dots(c, z, aux, s, nullptr, nullptr, 0, n);
+    case PC_DOT_XZ: return vec_dots(c, x, z, s, z, z, s + 1, n);
+    case PC_DOT_ZZ: return vec_dots(c, z, z, s, nullptr, nullptr, 0, n);
+    case PC_DOT_MERGED:
+      vec_dots(c, x, z, s, z, z, s + 1, n);
+      vec_dots(c, x, x, s + 2, x, aux, s + 3, n);
+      return vec_dots(c, z, aux, s + 4, nullptr, nullptr, 0, n);
   }
-  if (dot_mode == 3) return vec_dots(c, z, z, S_DP2, nullptr, nullptr, 0, n);
   return 0;
 }
 
-// the reduction slots a dot mode leaves partial sums in: first slot, count
-void mode_slots(int dot_mode, int& slot0, int& nslots) {
-  slot0 = dot_mode == 3 ? S_DP2 : S_D1;
-  nslots = dot_mode == 2 ? 2 : (dot_mode == 4 ? 5 : 1);
-}
-// sum the partials a preconditioner application left (general path: separate one-block launches)
+// sum the partials a preconditioner application left (general path: separate one-block launches; mode 4's five slots
+// as four, then the last one with the scalars derived)
 int pc_finalize(wai_ctx* c, int dot_mode, int phase) {
-  if (!dot_mode) return 0;
-  int slot0, nslots;
-  mode_slots(dot_mode, slot0, nslots);
+  if (dot_mode == PC_DOT_NONE) return 0;
+  const int slot0 = pc_dot_slot0(dot_mode), nslots = pc_dot_nslots(dot_mode);
   if (nslots == 5) { vec_finalize(c, c->ks.nb_pc, slot0, 4, -1); return vec_finalize(c, c->ks.nb_pc, slot0 + 4, 1, phase); }
   return vec_finalize(c, c->ks.nb_pc, slot0, nslots, phase);
 }
@@ -90,15 +86,13 @@ int pc_solve(wai_ctx* c, const double* r, double* z, int dot_mode, const double*
   if (pc_fused(c)) {
     // the fused kernels take the partner of modes 2 and 4 from their own input vector (the x of
     // z = B^-1 A x); here the input is r = (A + E) x, so those inner products are reduced separately
-    if (dot_mode == 2 || dot_mode == 4) {
-      if (launch_pc(c, false, r, z, 0, nullptr)) return -1;
+    if (dot_mode == PC_DOT_XZ || dot_mode == PC_DOT_MERGED) {
+      if (launch_pc(c, false, r, z, PC_DOT_NONE, nullptr)) return -1;
       if (pc_dots(c, dot_mode, x, z, aux)) return -1;
       return fin_phase >= -1 ? pc_finalize(c, dot_mode, fin_phase) : 0;
     }
     if (fin_phase >= -1 && dot_mode) {
-      int slot0, nslots;
-      mode_slots(dot_mode, slot0, nslots);
-      const Fin fin = make_fin(c, slot0, nslots, fin_phase);
+      const Fin fin = make_fin_dots(c, dot_mode, fin_phase);
       return launch_pc(c, false, r, z, dot_mode, aux, nullptr, 0, &fin);
     }
     return launch_pc(c, false, r, z, dot_mode, aux);
@@ -116,7 +110,7 @@ int pc_solve(wai_ctx* c, const double* r, double* z, int dot_mode, const double*
       launch_asm_gather(c, a.r_full);
     } else launch_asm_gather(c, r);
     if (a.sched.big) { if (launch_big_solve(c, a.E, a.sched, a.r_ext)) return -1; }
-    else if (launch_pc_on(c, a.E, a.sched, false, a.r_ext, a.r_ext, 0, nullptr)) return -1;
+    else if (launch_pc_on(c, a.E, a.sched, false, a.r_ext, a.r_ext, PC_DOT_NONE, nullptr)) return -1;
     launch_asm_scatter(c, z);
   } else {   // block Jacobi with subdomains of more than 1024 rows
     if (z != r) vec_copy(c, z, r, n);
@@ -144,9 +138,7 @@ int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode, const double* aux, i
   Fin fin;
   const Fin* fp = nullptr;
   if (fin_phase >= -1 && dot_mode) {
-    int slot0, nslots;
-    mode_slots(dot_mode, slot0, nslots);
-    fin = make_fin(c, slot0, nslots, fin_phase, post);
+    fin = make_fin_dots(c, dot_mode, fin_phase, post);
     fp = &fin;
   }
   const bool halo = c->comm && c->mesh.n_halo;
@@ -266,7 +258,7 @@ BcgsPlan bcgs_plan(const wai_ctx* c) {
 int bcgs_first_half(wai_ctx* c, const BcgsPlan& pl) {
   Krylov& k = c->ks;
   if (!pl.fused3) { Prof p(c, KC_VECTOR); bcgs_update_p(c); }
-  if (int e = pc_amul(c, k.P, k.V, 1, k.RP, pl.multi ? -1 : 2)) return e;
+  if (int e = pc_amul(c, k.P, k.V, PC_DOT_ZA, k.RP, pl.multi ? -1 : 2)) return e;
   Prof p(c, KC_VECTOR);
   if (pl.multi) {
     if (int e = allreduce_scal(c, S_D1, 1)) return e;
@@ -287,7 +279,7 @@ int bcgs_first_half(wai_ctx* c, const BcgsPlan& pl) {
 int bcgs_second_half(wai_ctx* c, const BcgsPlan& pl) {
   Krylov& k = c->ks;
   if (pl.fused3) {
-    if (int e = pc_amul(c, pl.axpy ? k.R : k.S, k.T, 4, k.RP, pl.multi ? -1 : 6, pl.axpy ? k.V : nullptr, !pl.multi)) return e;
+    if (int e = pc_amul(c, pl.axpy ? k.R : k.S, k.T, PC_DOT_MERGED, k.RP, pl.multi ? -1 : 6, pl.axpy ? k.V : nullptr, !pl.multi)) return e;
     Prof p(c, KC_VECTOR);
     if (pl.multi) {
       // omega, (R,R), rho, beta and the post: derived by the X / R / P update itself (k_bcgs_xrp<DERIVE>), no scalar kernel
@@ -299,7 +291,7 @@ int bcgs_second_half(wai_ctx* c, const BcgsPlan& pl) {
     bcgs_update_xrp(c);
     return 0;
   }
-  if (int e = pc_amul(c, k.S, k.T, pl.merged ? 4 : 2, pl.merged ? k.RP : nullptr, pl.merged ? -1 : 3)) return e;
+  if (int e = pc_amul(c, k.S, k.T, pl.merged ? PC_DOT_MERGED : PC_DOT_XZ, pl.merged ? k.RP : nullptr, pl.merged ? -1 : 3)) return e;
   Prof p(c, KC_VECTOR);
   if (pl.merged) {
     if (pl.multi) { if (int e = allreduce_scal(c, S_D1, 5)) return e; }
@@ -334,7 +326,7 @@ int ksp_bcgs(wai_ctx* c, const double* b, double* x, int* its, int* reason, doub
   vec_zero(c, k.scal + S_BREAK, 1);
   {
     Prof p(c, KC_PC_APPLY);
-    if (pc_solve(c, b, k.R, 3, nullptr, nullptr, multi ? -1 : 0)) return -1;  // R = B^-1 b, (R,R), first rho / beta
+    if (pc_solve(c, b, k.R, PC_DOT_ZZ, nullptr, nullptr, multi ? -1 : 0)) return -1;  // R = B^-1 b, (R,R), first rho / beta
   }
   {
     Prof p(c, KC_VECTOR);
@@ -404,14 +396,14 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
     double* v0 = k.basis;
     if (it == 0) {
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, b, v0, 0, nullptr, nullptr)) return -1;
+      if (pc_solve(c, b, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     } else {
       vec_copy(c, k.P, x, n);
       if (halo_exchange(c, k.P, c->np)) return -1;
       { Prof p(c, KC_SPMV); if (apply_operator(c, k.P, k.tmp)) return -1; }
       vec_waxpy(c, k.tmp, -1.0, k.tmp, b, n);
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, k.tmp, v0, 0, nullptr, nullptr)) return -1;
+      if (pc_solve(c, k.tmp, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     }
     {
       Prof p(c, KC_VECTOR);
@@ -526,14 +518,14 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
     double* v0 = k.basis;
     if (it == 0) {
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, b, v0, 0, nullptr, nullptr)) return -1;
+      if (pc_solve(c, b, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     } else {
       vec_copy(c, k.P, x, n);
       if (halo_exchange(c, k.P, c->np)) return -1;
       { Prof p(c, KC_SPMV); if (apply_operator(c, k.P, k.tmp)) return -1; }
       vec_waxpy(c, k.tmp, -1.0, k.tmp, b, n);
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, k.tmp, v0, 0, nullptr, nullptr)) return -1;
+      if (pc_solve(c, k.tmp, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     }
     {
       Prof p(c, KC_VECTOR);
@@ -656,7 +648,7 @@ int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
   const int maxits = c->opts.ksp_max_its;
   vec_zero(c, x, n);
   for (int j = 0; j <= L; j++) vec_zero(c, u[j], nl);
-  { Prof p(c, KC_PC_APPLY); if (pc_solve(c, b, r[0], 0, nullptr, nullptr)) return -1; }
+  { Prof p(c, KC_PC_APPLY); if (pc_solve(c, b, r[0], PC_DOT_NONE, nullptr, nullptr)) return -1; }
   vec_copy(c, rt, r[0], n);
   double d[2];
   if (host_dots(c, r[0], r[0], nullptr, nullptr, d)) return -1;

@@ -50,15 +50,13 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   auto run = [&]() {
     switch (which) {
       case 0: launch_spmv(c, k.P, k.tmp); break;
-      case 1: case 3: pc_solve(c, k.P, k.V, 0, nullptr, nullptr); break;
-      case 9: if (c->ilu.n_int > 0) launch_pc(c, true, k.P, k.V, 1, k.RP, c->ilu.sub_int, c->ilu.n_int); break;   // interior bricks only
-      case 10: if (c->ilu.n_bnd > 0) launch_pc(c, true, k.P, k.V, 1, k.RP, c->ilu.sub_bnd, c->ilu.n_bnd); break;  // face bricks only
+      case 1: case 3: pc_solve(c, k.P, k.V, PC_DOT_NONE, nullptr, nullptr); break;
+      case 9: if (c->ilu.n_int > 0) launch_pc(c, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_int, c->ilu.n_int); break;   // interior bricks only
+      case 10: if (c->ilu.n_bnd > 0) launch_pc(c, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_bnd, c->ilu.n_bnd); break;  // face bricks only
       case 16:  // interior + face bricks as the overlapped halo exchange launches them (no halo here): the split's cost against case 2
         if (c->ilu.n_int > 0 && c->ilu.n_bnd > 0) {
-          int slot0, nslots;
-          mode_slots(1, slot0, nslots);
-          const Fin fin = make_fin(c, slot0, nslots, 2);
-          launch_pc_split(c, k.P, k.V, 1, k.RP, &fin, nullptr, nullptr);
+          const Fin fin = make_fin_dots(c, PC_DOT_ZA, 2);
+          launch_pc_split(c, k.P, k.V, PC_DOT_ZA, k.RP, &fin, nullptr, nullptr);
         }
         break;
       case 5: {  // the launches (and, on several ranks, collectives) of one BiCGStab iteration back to back, no host in
@@ -74,7 +72,7 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
       case 17: {  // the second fused launch of the iteration exactly as bcgs_second_half issues it on one rank: operand S (or
                   // R - alpha V formed in the launch), five inner products, omega / (R,R) / rho / beta + the post in the finaliser
         const BcgsPlan pl = bcgs_plan(c);
-        pc_amul(c, pl.axpy ? k.R : k.S, k.T, 4, k.RP, 6, pl.axpy ? k.V : nullptr, true);
+        pc_amul(c, pl.axpy ? k.R : k.S, k.T, PC_DOT_MERGED, k.RP, 6, pl.axpy ? k.V : nullptr, true);
         break;
       }
       case 18:   // what a copy achieves on this box: hipMemcpy device to device, half of the perturbed-fluid scratch onto the other
@@ -100,16 +98,16 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
         break;
       }
       case 7:   // the second fused launch of the "fused" iteration: z = B^-1 A (R - alpha V) with the five inner products
-        pc_amul(c, k.R, k.T, 4, k.RP, -1, pc_axpy_ok(c) ? k.V : nullptr, false);
+        pc_amul(c, k.R, k.T, PC_DOT_MERGED, k.RP, -1, pc_axpy_ok(c) ? k.V : nullptr, false);
         break;
       // the fused launch by reduction mode: 11 none; 12 (z,aux) left as partials; 13 (x,z),(z,z) + omega in the launch;
       // 14 the five merged products left as partials; 15 the five + omega, (R,R), rho, beta in the launch
-      case 11: pc_amul(c, k.P, k.V, 0, nullptr, -2); break;
-      case 12: pc_amul(c, k.P, k.V, 1, k.RP, -2); break;
-      case 13: pc_amul(c, k.P, k.V, 2, nullptr, 3); break;
-      case 14: pc_amul(c, k.P, k.V, 4, k.RP, -2); break;
-      case 15: pc_amul(c, k.P, k.V, 4, k.RP, 6); break;
-      default: pc_amul(c, k.P, k.V, 1, k.RP, 2); break;   // what a BiCGStab half-iteration runs (no halo on one rank)
+      case 11: pc_amul(c, k.P, k.V, PC_DOT_NONE, nullptr, -2); break;
+      case 12: pc_amul(c, k.P, k.V, PC_DOT_ZA, k.RP, -2); break;
+      case 13: pc_amul(c, k.P, k.V, PC_DOT_XZ, nullptr, 3); break;
+      case 14: pc_amul(c, k.P, k.V, PC_DOT_MERGED, k.RP, -2); break;
+      case 15: pc_amul(c, k.P, k.V, PC_DOT_MERGED, k.RP, 6); break;
+      default: pc_amul(c, k.P, k.V, PC_DOT_ZA, k.RP, 2); break;   // what a BiCGStab half-iteration runs (no halo on one rank)
     }
   };
   c->dbg = (which == 3 || which == 4) && pc_fused(c) && !(c->J.bs == 2 && c->ilu.park) ? 1 : 0;
@@ -191,8 +189,8 @@ int wai_test_drop_partials(wai_ctx* c, int n) { return c ? test_drop_partials(c,
 // then pc_amul / pc_solve / launch_pc_split unchanged
 int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2, double alpha, int dot_mode, const double* aux,
                          int split, int fin_phase, const double* scal_in, double* z, double* scal_out) {
-  if (!c || !x || !z || !scal_in || !scal_out || dot_mode < 0 || dot_mode > 4 || fin_phase < -2) return -2;
-  if ((dot_mode == 1 || dot_mode == 4) && !aux) { c->err = "wai_test_pc_operator: dot modes 1 and 4 need aux"; return -2; }
+  if (!c || !x || !z || !scal_in || !scal_out || dot_mode < PC_DOT_NONE || dot_mode > PC_DOT_MERGED || fin_phase < -2) return -2;
+  if ((dot_mode == PC_DOT_ZA || dot_mode == PC_DOT_MERGED) && !aux) { c->err = "wai_test_pc_operator: dot modes 1 and 4 need aux"; return -2; }
   read_env(c);
   if (!c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e < 0 ? -1 : e; }
   if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
@@ -217,9 +215,7 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
     Fin fin;
     const Fin* fp = nullptr;
     if (fin_phase >= -1 && dot_mode) {
-      int slot0, nslots;
-      mode_slots(dot_mode, slot0, nslots);
-      fin = make_fin(c, slot0, nslots, fin_phase);
+      fin = make_fin_dots(c, dot_mode, fin_phase);
       fp = &fin;
     }
     e = launch_pc_split(c, k.R, k.T, dot_mode, a, fp, v, nullptr);
@@ -229,11 +225,8 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
     e = pc_solve(c, k.R, k.T, dot_mode, k.R, a, fin_phase);
   }
   if (e) return e;
-  if (fin_phase == -2 && dot_mode) {   // the partial sums left behind, summed by k_finalize as the general path sums them
-    int slot0, nslots;
-    mode_slots(dot_mode, slot0, nslots);
-    vec_finalize(c, k.nb_pc, slot0, nslots, -1);
-  }
+  if (fin_phase == -2 && dot_mode)   // the partial sums left behind, summed by k_finalize as the general path sums them
+    vec_finalize(c, k.nb_pc, pc_dot_slot0(dot_mode), pc_dot_nslots(dot_mode), -1);
   HIPCHK(c, hipMemcpyAsync(z, k.T, n * sizeof(double), hipMemcpyDefault, c->stream));
   HIPCHK(c, hipMemcpyAsync(s, k.scal, sizeof(s), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
