@@ -52,7 +52,14 @@ enum { WAI_PC_BJACOBI = 0, WAI_PC_ASM = 1, WAI_PC_NONE = 2, WAI_PC_LU = 3 };   /
  * src/timestepper.F90:1668-1669) as contiguous owned-row ranges; NULL = one block per rank, the
  * reference's layout.  Blocks of up to 1024 rows (bricks of the mesh) run on the fused
  * one-workgroup-per-block kernels; larger ones -- any size -- on the launch-per-dependency-level
- * path, which is general but several times slower per application. */
+ * path, which is general but several times slower per application.
+ * Limit: at most 16 faces per owned cell, boundary faces included, and at most 15 neighbouring
+ * cells, so at most 16 blocks per matrix row: a polygonal column of a middle layer may have up to 13
+ * lateral neighbours (14 with a boundary face above or below it, e.g. in the top layer).
+ * wai_ctx_create refuses a wider mesh with an error naming the cell and its count.
+ * Cells with 9 .. 16 faces run on wide variants of the SpMV and of the fused preconditioned operator
+ * (k_spmv_wide, k_pc_wide with the stored ILU(0) factor); meshes of at most 8 faces per cell keep
+ * their kernels. */
 typedef struct wai_mesh_desc {
   int n_owned, n_halo, n_bc, n_faces;
   const int *face_cells;

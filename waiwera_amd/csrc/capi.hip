@@ -324,6 +324,12 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
       if (cc < N) deg[cc]++;
     }
   m.max_deg = *std::max_element(deg.begin(), deg.end());
+  if (m.max_deg > MAX_CELL_FACES) {   // (documented beside wai_mesh_desc, include/waiwera_hip.h)
+    const int cell = (int)(std::max_element(deg.begin(), deg.end()) - deg.begin());
+    c->err = "cell " + std::to_string(cell) + " has " + std::to_string(m.max_deg) + " faces: at most " +
+             std::to_string(MAX_CELL_FACES) + " supported";
+    return -2;
+  }
   std::vector<int> adj_face((size_t)m.max_deg * N, -1), adj_other((size_t)m.max_deg * N, 0),
       adj_blk((size_t)m.max_deg * N, -1), fill(N, 0);
   for (int f = 0; f < NF; f++)
@@ -342,9 +348,13 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
     for (int s = 0; s < deg[i]; s++)
       if (adj_other[(size_t)s * N + i] < m.n_prim) cnt++;
     J.h_rowptr[i + 1] = J.h_rowptr[i] + cnt;
+    if (cnt > MAX_CELL_FACES) {   // 16 faces and none of them a boundary face: 15 neighbouring cells at most
+      c->err = "cell " + std::to_string(i) + " has " + std::to_string(cnt - 1) + " neighbouring cells (a matrix row of " +
+               std::to_string(cnt) + " blocks): at most 15 supported";
+      return -2;
+    }
     J.W = std::max(J.W, cnt);
   }
-  if (J.W > 8) { c->err = "more than 8 blocks in a matrix row not supported"; return -2; }
   J.nnzb = J.h_rowptr[N];
   J.h_colidx.resize(J.nnzb);
   std::vector<int> diag(N), ell_col((size_t)J.W * N);

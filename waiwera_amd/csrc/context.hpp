@@ -56,6 +56,10 @@ __host__ __device__ __forceinline__ size_t ell_size(int bs, size_t n, int W) {
   return (size_t)W * bs * bs * ell_rows(bs, n);
 }
 
+// most faces of an owned cell (boundary faces included) and most blocks of a matrix row -- the cell itself and at most 15
+// neighbouring cells (include/waiwera_hip.h)
+constexpr int MAX_CELL_FACES = 16;
+
 enum KClass { KC_EOS = 0, KC_RESIDUAL = 1, KC_JACOBIAN = 2, KC_SPMV = 3, KC_PC_APPLY = 4,
               KC_PC_SETUP = 5, KC_VECTOR = 6, KC_TRANSITIONS = 7, KC_COUNT = 8 };
 
@@ -208,7 +212,11 @@ struct IluSchedule {
   int* sub_ptr = nullptr;   // nsub+1 row ranges
   int* sub_nlev = nullptr;  // per subdomain: forward levels | backward levels << 16
   int* sub_split = nullptr; // per subdomain: leading rows longer than half the block-ELL width (k_pc_rows: MINC bricks), or null
-  int* row_info = nullptr;  // per row: lfirst | dslot<<4 | ulast<<8 | lev_f<<12 | lev_b<<22
+  int* row_info = nullptr;  // per row: lfirst | dslot<<4 | ulast<<8 | lev_f<<12 | lev_b<<22 (big, wide: lfirst | dslot<<8 | ulast<<16)
+  // rows of 9 .. 16 blocks in subdomains of <= 1024 rows (cells with up to 16 faces): k_ilu_factor_wide and k_pc_wide read
+  // the 64-bit descriptor, lfirst | dslot<<5 | ulast<<10 in the low word, lev_f | lev_b<<10 in the high one
+  bool wide = false;
+  unsigned long long* row_infow = nullptr;
   double* fval = nullptr;   // factor in the matrix' block-ELL layout; the diagonal slot holds
                             // the inverted pivot block
   double* dinv = nullptr;   // inverted pivot blocks, SoA [bb][n]

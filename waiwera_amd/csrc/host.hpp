@@ -113,7 +113,7 @@ inline bool pc_extended(const wai_ctx* c) {
 
 // ---- pc_setup.hip ------------------------------------------------------------------------------------------------
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts);
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true);
 void free_schedule(IluSchedule& s);
 void free_asm(AsmSystem& a);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell

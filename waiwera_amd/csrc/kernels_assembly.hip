@@ -22,6 +22,7 @@
 namespace wai {
 
 constexpr int MAXDEG = 8;   // faces per cell held in registers (structured: 6, MINC: 7)
+constexpr int MAXDEG_WIDE = MAX_CELL_FACES;   // k_tracer_assemble<K, MAXDEG_WIDE>: cells with 9 .. 16 faces
 constexpr int TPB = 256;
 
 // XCD-aware cell-block mapping for the gather-heavy sweeps: dispatch puts workgroup b on XCD
@@ -831,7 +832,8 @@ __device__ __forceinline__ double tracer_coef(const CellState<KIND>& s, const Ro
   return r.phi * sat * rho;  // cell_tracer_balance_coefs, cell.F90:146-164
 }
 
-template <int KIND>
+// WM: the most slots of a row (MAXDEG; MAXDEG_WIDE for cells with 9 .. 16 faces)
+template <int KIND, int WM = MAXDEG>
 __global__ __launch_bounds__(TPB) void k_tracer_assemble(MeshView m, const double* __restrict__ flu,
                                                          size_t stride, TracerForm tf, int n_prim, int W,
                                                          const double* __restrict__ alx1,
@@ -850,9 +852,9 @@ __global__ __launch_bounds__(TPB) void k_tracer_assemble(MeshView m, const doubl
   load_rock(m.rock, m.n_local, c, rown);
   const double vol = m.vol[c];
   const int dslot = m.diag_blk[c];
-  double row[MAXDEG];  // Ar by ELL slot
+  double row[WM];  // Ar by ELL slot
 #pragma unroll
-  for (int q = 0; q < MAXDEG; q++) row[q] = 0.0;
+  for (int q = 0; q < WM; q++) row[q] = 0.0;
   double diag = 0.0, br = 0.0;
   const double cf_own = tracer_coef<KIND>(own, rown, p);  // cell_diffusion_factor: the same product
   for (int s = 0; s < m.max_deg; s++) {
@@ -882,7 +884,7 @@ __global__ __launch_bounds__(TPB) void k_tracer_assemble(MeshView m, const doubl
     diag += to_own;
     if (blk >= 0) {
 #pragma unroll
-      for (int q = 0; q < MAXDEG; q++) row[q] += (q == blk) ? to_oth : 0.0;
+      for (int q = 0; q < WM; q++) row[q] += (q == blk) ? to_oth : 0.0;
     } else {
       br += to_oth * xbc[(size_t)(o - n_prim) * tf.nt + tf.it];
     }
@@ -930,7 +932,7 @@ __global__ __launch_bounds__(TPB) void k_tracer_assemble(MeshView m, const doubl
   const bool absent = !(((int)own.phases) & (1 << p));
   const size_t n = m.n_owned;
 #pragma unroll
-  for (int q = 0; q < MAXDEG; q++) {
+  for (int q = 0; q < WM; q++) {
     if (q < W) {
       double v = (q == dslot) ? diag : cA * row[q];
       if (absent) v = (q == dslot) ? 1.0 : 0.0;
@@ -1161,16 +1163,19 @@ static inline int grid_for(size_t n) { return (int)((n + TPB - 1) / TPB); }
 static inline int grid8_for(size_t n) { return ((grid_for(n) + 7) / 8) * 8; }  // xcd_cell kernels
 
 // launch KERNEL<kind>(...) for the context's EOS
-#define WAI_BY_EOS(c, KERNEL, grid, ...)                                                          \
-  do {                                                                                           \
-    if ((c)->kind == EOS_W) hipLaunchKernelGGL(KERNEL<EOS_W>, grid, TPB, 0, (c)->stream, __VA_ARGS__);        \
-    else if ((c)->kind == EOS_WE) hipLaunchKernelGGL(KERNEL<EOS_WE>, grid, TPB, 0, (c)->stream, __VA_ARGS__); \
-    else if ((c)->kind == EOS_WSE) hipLaunchKernelGGL(KERNEL<EOS_WSE>, grid, TPB, 0, (c)->stream, __VA_ARGS__); \
-    else if ((c)->kind == EOS_WAE) hipLaunchKernelGGL(KERNEL<EOS_WAE>, grid, TPB, 0, (c)->stream, __VA_ARGS__); \
-    else if ((c)->kind == EOS_WSCE) hipLaunchKernelGGL(KERNEL<EOS_WSCE>, grid, TPB, 0, (c)->stream, __VA_ARGS__); \
-    else if ((c)->kind == EOS_WSAE) hipLaunchKernelGGL(KERNEL<EOS_WSAE>, grid, TPB, 0, (c)->stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<EOS_WCE>, grid, TPB, 0, (c)->stream, __VA_ARGS__);                         \
+// KERNEL<eos of c TARGS> on grid x TPB; TARGS: further template arguments, each behind a WAI_COMMA (or nothing)
+#define WAI_BY_EOS_T(c, KERNEL, TARGS, grid, ...)                                                                       \
+  do {                                                                                                                 \
+    if ((c)->kind == EOS_W) hipLaunchKernelGGL((KERNEL<EOS_W TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__);          \
+    else if ((c)->kind == EOS_WE) hipLaunchKernelGGL((KERNEL<EOS_WE TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__);   \
+    else if ((c)->kind == EOS_WSE) hipLaunchKernelGGL((KERNEL<EOS_WSE TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__); \
+    else if ((c)->kind == EOS_WAE) hipLaunchKernelGGL((KERNEL<EOS_WAE TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__); \
+    else if ((c)->kind == EOS_WSCE) hipLaunchKernelGGL((KERNEL<EOS_WSCE TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__); \
+    else if ((c)->kind == EOS_WSAE) hipLaunchKernelGGL((KERNEL<EOS_WSAE TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<EOS_WCE TARGS>), grid, TPB, 0, (c)->stream, __VA_ARGS__);                           \
   } while (0)
+#define WAI_BY_EOS(c, KERNEL, grid, ...) WAI_BY_EOS_T(c, KERNEL, , grid, __VA_ARGS__)
+#define WAI_COMMA ,
 
 int launch_eos(wai_ctx* c, const double* y, int first, int count, bool perturbed) {
   if (count <= 0) return 0;
@@ -1235,7 +1240,6 @@ int launch_residual(wai_ctx* c, double dt, const double* lhs_old, double* f, dou
 
 int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
   const MeshView m = view(c);
-  if (m.max_deg > MAXDEG) { c->err = "cell with more than 8 faces not supported"; return -1; }
   const size_t stride = c->mesh.n_local;
   // No clearing pass and no read-modify-write: two cells share at most one face (wai_ctx_create refuses duplicate
   // connections), so every block of a row is produced by exactly one adjacency slot and is STORED; the padding slots of
@@ -1278,6 +1282,13 @@ int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
     if (hipError_t e = hipGetLastError(); e != hipSuccess) { c->err = std::string("k_jacobian_sym: ") + hipGetErrorString(e); return -1; }
     return 0;
   }
+  // the row-wise kernels hold the base terms of MAXDEG faces per cell in registers / LDS: cells with more faces (up to
+  // 16, wai_ctx_create) are assembled column-wise only
+  if (m.max_deg > MAXDEG) {
+    c->err = "the row-wise Jacobian (WAI_JAC_SYM=0) supports cells with at most 8 faces; this mesh has a cell with " +
+             std::to_string(m.max_deg) + " (the default column-wise Jacobian takes up to 16)";
+    return -1;
+  }
   if (park) {
 #define JP(K)                                                                                             \
     do {                                                                                                  \
@@ -1310,9 +1321,13 @@ int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
 int launch_tracer_assemble(wai_ctx* c, const TracerForm& tf, const double* alx_last,
                            const double* alx_last2, double* b) {
   const MeshView m = view(c);
-  if (m.max_deg > MAXDEG || c->J.W > MAXDEG) { c->err = "cell with more than 8 faces not supported"; return -1; }
-  WAI_BY_EOS(c, k_tracer_assemble, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
-             c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->tr.val, b);
+  // rows indexed by ELL slot: up to W of them (wai_ctx_create refuses rows of more than MAXDEG_WIDE blocks)
+  if (c->J.W > MAXDEG)
+    WAI_BY_EOS_T(c, k_tracer_assemble, WAI_COMMA MAXDEG_WIDE, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
+                 c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->tr.val, b);
+  else
+    WAI_BY_EOS(c, k_tracer_assemble, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
+               c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->tr.val, b);
   return 0;
 }
 

@@ -55,6 +55,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 constexpr int PC_MIN_WAVES = 4;   // waves per SIMD k_pc is compiled for; 5 or 6 force spills and measured 1.2x / 3x slower
 constexpr int WMAX = 8;  // block-ELL width handled in registers (7-point stencil: 7, MINC: 8)
+constexpr int WMAX_WIDE = MAX_CELL_FACES;  // widest row of the wide kernels (k_spmv_wide, k_pc_wide): cells with up to 16 faces
 
 
 __device__ __forceinline__ int xcd_remap(int b, int n) {
@@ -173,19 +174,20 @@ __device__ __forceinline__ void load_x_stream(const double* __restrict__ x, int 
 // of a row's blocks and gathers are requested before the first is used, is SLOWER -- 0.480-0.484 against 0.438-0.464 ms
 // at 216^3 (2 x 2 blocks), 0.565-0.575 against 0.496-0.510 at C4 (3 x 3) -- one slot's element planes at a time are 4 or
 // 9 concurrent streams through the memory channels, all seven slots' 28 or 63.
-template <int BS>
+// WM: the most slots a row may have (WMAX; WMAX_WIDE for the meshes whose cells have up to 16 faces)
+template <int BS, int WM = WMAX>
 __device__ __forceinline__ void ell_row_mult(int n, int W, int i, const int* __restrict__ col,
                                              const double* __restrict__ val,
                                              const double* __restrict__ x, double* acc) {
   constexpr int BB = BS * BS;
-  int cs[WMAX];   // all column indices first: one round trip instead of one per slot
+  int cs[WM];   // all column indices first: one round trip instead of one per slot
 #pragma unroll
-  for (int s = 0; s < WMAX; s++) {
+  for (int s = 0; s < WM; s++) {
     cs[s] = i;
     if (s < W) cs[s] = load_col(col, (size_t)s * n + i);
   }
 #pragma unroll
-  for (int s = 0; s < WMAX; s++) {
+  for (int s = 0; s < WM; s++) {
     if (s < W) {
       const int c = cs[s];
       double xv[BS], a[BS * BS];
@@ -202,17 +204,17 @@ __device__ __forceinline__ void ell_row_mult(int n, int W, int i, const int* __r
 // ---- K6: block SpMV --------------------------------------------------------------------------
 // rowptr (may be null): rows shorter than the block-ELL width (MINC matrix cells: 2 blocks of 8)
 // skip their padding slots instead of streaming zeros
-template <int BS, bool SHORT>
-__global__ __launch_bounds__(TPB) void k_spmv(int n, int W, int nblk, const int* __restrict__ col,
-                                              const double* __restrict__ val, const int* __restrict__ rowptr,
-                                              const double* __restrict__ x, double* __restrict__ y) {
+template <int BS, bool SHORT, int WM>
+__device__ __forceinline__ void spmv_row(int n, int W, int nblk, const int* __restrict__ col,
+                                         const double* __restrict__ val, const int* __restrict__ rowptr,
+                                         const double* __restrict__ x, double* __restrict__ y) {
   const int b = xcd_remap(blockIdx.x, nblk);
   const int i = b * TPB + threadIdx.x;
   if (b >= nblk || i >= n) return;
   double acc[BS];
 #pragma unroll
   for (int r = 0; r < BS; r++) acc[r] = 0.0;
-  ell_row_mult<BS>(n, SHORT ? rowptr[i + 1] - rowptr[i] : W, i, col, val, x, acc);
+  ell_row_mult<BS, WM>(n, SHORT ? rowptr[i + 1] - rowptr[i] : W, i, col, val, x, acc);
   if constexpr (BS == 2) store_z2(y, (size_t)i, acc[0], acc[1]);
   else if constexpr (BS == 3) {
     double* p = y + (size_t)i * 3;
@@ -224,6 +226,21 @@ __global__ __launch_bounds__(TPB) void k_spmv(int n, int W, int nblk, const int*
 #pragma unroll
     for (int r = 0; r < BS; r++) y[(size_t)i * BS + r] = acc[r];
   }
+}
+template <int BS, bool SHORT>
+__global__ __launch_bounds__(TPB) void k_spmv(int n, int W, int nblk, const int* __restrict__ col,
+                                              const double* __restrict__ val, const int* __restrict__ rowptr,
+                                              const double* __restrict__ x, double* __restrict__ y) {
+  spmv_row<BS, SHORT, WMAX>(n, W, nblk, col, val, rowptr, x, y);
+}
+// Rows of 9 .. 16 blocks (cells with up to 16 faces: polygonal columns, refined grids with hanging nodes).  The same
+// slot-at-a-time streaming as k_spmv, sixteen guarded slots instead of eight; such meshes have ragged rows, so the
+// launcher takes the rowptr form wherever padding exceeds 10 %.
+template <int BS, bool SHORT>
+__global__ __launch_bounds__(TPB) void k_spmv_wide(int n, int W, int nblk, const int* __restrict__ col,
+                                                   const double* __restrict__ val, const int* __restrict__ rowptr,
+                                                   const double* __restrict__ x, double* __restrict__ y) {
+  spmv_row<BS, SHORT, WMAX_WIDE>(n, W, nblk, col, val, rowptr, x, y);
 }
 
 // ---- small dense helpers ---------------------------------------------------------------------
@@ -278,6 +295,14 @@ __device__ __forceinline__ void unpack_info_wide(int info, int& lfirst, int& dsl
   lfirst = info & 255; dslot = (info >> 8) & 255; ulast = (info >> 16) & 255;
 }
 
+// descriptor of the brick schedules with rows of 9 .. 16 blocks (IluSchedule::row_infow: k_ilu_factor_wide, k_pc_wide):
+// low word lfirst | dslot << 5 | ulast << 10, high word lev_f | lev_b << 10
+__device__ __forceinline__ void unpack_info_w(unsigned long long info, int& lfirst, int& dslot, int& ulast, int& lf,
+                                              int& lb) {
+  const unsigned w0 = (unsigned)info, w1 = (unsigned)(info >> 32);
+  lfirst = w0 & 31; dslot = (w0 >> 5) & 31; ulast = (w0 >> 10) & 31;
+  lf = w1 & 1023; lb = (w1 >> 10) & 1023;
+}
 // ---- K7: block ILU(0) numeric factorisation (IKJ), one workgroup per subdomain ----------------
 // Works in place on fval (a copy of the matrix); rows of one dependency level are independent.
 // On exit the diagonal slot of every row holds the inverted pivot block.
@@ -301,6 +326,80 @@ __global__ void k_ilu_factor(int n, int nsub, const int* __restrict__ sub_ptr,
         const int k = col[(size_t)q * n + i];
         int kl, kd, ku, kf, kb;
         unpack_info(row_info[k], kl, kd, ku, kf, kb);
+        double w[BB], d[BB], t[BB];
+#pragma unroll
+        for (int z = 0; z < BB; z++) {
+          w[z] = fval[vix<BS>(n, q, z, i)];
+          d[z] = fval[vix<BS>(n, kd, z, k)];
+        }
+#pragma unroll
+        for (int r = 0; r < BS; r++)
+#pragma unroll
+          for (int c = 0; c < BS; c++) {
+            double acc = 0.0;
+#pragma unroll
+            for (int e = 0; e < BS; e++) acc += w[r * BS + e] * d[e * BS + c];
+            t[r * BS + c] = acc;
+          }
+#pragma unroll
+        for (int z = 0; z < BB; z++) fval[vix<BS>(n, q, z, i)] = t[z];
+        for (int r2 = kd + 1; r2 < ku; r2++) {
+          const int j = col[(size_t)r2 * n + k];
+          for (int q2 = q + 1; q2 < ulast; q2++) {
+            if (col[(size_t)q2 * n + i] != j) continue;
+            double u[BB];
+#pragma unroll
+            for (int z = 0; z < BB; z++) u[z] = fval[vix<BS>(n, r2, z, k)];
+#pragma unroll
+            for (int r = 0; r < BS; r++)
+#pragma unroll
+              for (int c = 0; c < BS; c++) {
+                double acc = 0.0;
+#pragma unroll
+                for (int e = 0; e < BS; e++) acc += t[r * BS + e] * u[e * BS + c];
+                fval[vix<BS>(n, q2, r * BS + c, i)] -= acc;
+              }
+            break;
+          }
+        }
+      }
+      double piv[BB], inv[BB];
+#pragma unroll
+      for (int z = 0; z < BB; z++) piv[z] = fval[vix<BS>(n, dslot, z, i)];
+      if (!block_inverse<BS>(piv, inv)) atomicMax(&flags[0], 1);
+#pragma unroll
+      for (int z = 0; z < BB; z++) {
+        fval[vix<BS>(n, dslot, z, i)] = inv[z];
+        dinv[dix<BS>(n, z, i)] = inv[z];
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+
+// The same for the schedules with rows of 9 .. 16 blocks, on their 64-bit row descriptor.  A copy rather than a body
+// shared with k_ilu_factor: compiled through a shared inline function, k_ilu_factor<4> spilled differently.
+template <int BS>
+__global__ void k_ilu_factor_wide(int n, int nsub, const int* __restrict__ sub_ptr,
+                                  const int* __restrict__ sub_nlev, const unsigned long long* __restrict__ row_info,
+                                  const int* __restrict__ col, double* fval, double* __restrict__ dinv,
+                                  int* flags) {
+  constexpr int BB = BS * BS;
+  const int s = xcd_remap(blockIdx.x, nsub);
+  if (s >= nsub) return;
+  const int lo = sub_ptr[s], R = sub_ptr[s + 1] - lo;
+  const int nlf = sub_nlev[s] & 0xffff;
+  const int i = lo + threadIdx.x;
+  const bool active = (int)threadIdx.x < R;
+  int lfirst = 0, dslot = 0, ulast = 0, lf = -1, lb = 0;
+  if (active) unpack_info_w(row_info[i], lfirst, dslot, ulast, lf, lb);
+  for (int lev = 0; lev < nlf; lev++) {
+    if (active && lf == lev) {
+      for (int q = lfirst; q < dslot; q++) {
+        const int k = col[(size_t)q * n + i];
+        int kl, kd, ku, kf, kb;
+        unpack_info_w(row_info[k], kl, kd, ku, kf, kb);
         double w[BB], d[BB], t[BB];
 #pragma unroll
         for (int z = 0; z < BB; z++) {
@@ -1292,6 +1391,149 @@ __global__ __launch_bounds__(1024, (BS <= 2 ? PC_MIN_WAVES : 4)) void k_pc(int n
   }
 }
 
+// ---- K6+K8 fused for rows of 9 .. 16 blocks (stored factor) ---------------------------------------
+// Meshes whose cells have up to 16 faces (polygonal columns, quad columns refined around the wells: a coarse column and
+// two fine neighbours along one side are pairwise adjacent) have triangles in their cell graph: ILU(0) fills
+// off-diagonal blocks, so the factor is stored (k_ilu_factor_wide) and the DILU forms never apply.  k_pc holds a row's
+// factor in registers; at 16 slots that is 64 doubles for 2 x 2 blocks and 144 for 3 x 3, beyond the register file.  Here
+// a thread keeps nothing of its row across the sweeps but the inverted pivot block:
+//   load phase  t = A x streamed slot by slot (ell_row_mult, 16 guarded slots); the row's in-subdomain upper blocks of the
+//               factor are parked in LDS behind the solution vector while the loads of the whole brick are in flight --
+//               as many rows as fit the 64 KB a workgroup may ask for (rows in order, a row parks all of its upper blocks
+//               or none: `ucap`); the others re-read theirs from memory in the backward sweep;
+//   forward     y_i = t_i - sum_k L_ik y_k at the row's level, each lower block read once from memory;
+//   backward    x_i = inv(D_i) (y_i - sum_j U_ij x_j), upper blocks from LDS where parked.
+// Every factor block is read once per application, so the launch moves about what the launch-per-level path moves
+// without its 2 x levels launches and the separate SpMV.  One workgroup per subdomain (<= 1024 rows), one thread per block
+// row; k_pc's interface: dot modes, finaliser workgroups, sub_list (the interior / face split of the halo exchange).
+template <int BS, bool SPMV>
+__global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const int* __restrict__ sub_ptr,
+                                                  const int* __restrict__ sub_nlev,
+                                                  const unsigned long long* __restrict__ row_infow,
+                                                  const int* __restrict__ row_uoffw, const int* __restrict__ col,
+                                                  const int* __restrict__ rowptr, const double* __restrict__ aval,
+                                                  const double* __restrict__ fval, const double* __restrict__ in,
+                                                  double* __restrict__ z, const double* __restrict__ aux, double* partials,
+                                                  int nb_max, int dot, int ucap, const int* __restrict__ sub_list, Fin fin) {
+  constexpr int BB = BS * BS;
+  extern __shared__ __attribute__((aligned(16))) double lds[];  // [T * BS] solution, 80 doubles reduction scratch, [ucap][BB] parked upper blocks
+  if (fin_block(fin, partials, nb_max)) return;
+  int s = xcd_remap(blockIdx.x, nsub);
+  if (s >= nsub) return;
+  if (sub_list) s = sub_list[s];
+  const int lo = sub_ptr[s], R = sub_ptr[s + 1] - lo;
+  const int nl = sub_nlev[s], nlf = nl & 0xffff, nlb = nl >> 16;
+  const int tid = threadIdx.x, i = lo + tid;
+  const bool active = tid < R;
+  double* ys = lds;
+  double* red = lds + (size_t)blockDim.x * BS;
+  double* park = red + 80;
+  int lfirst = 0, dslot = 0, ulast = 0, lf = -1, lb = -1, uo = 0;
+  bool parked = false;
+  if (active) {
+    unpack_info_w(row_infow[i], lfirst, dslot, ulast, lf, lb);
+    double acc[BS];
+    if constexpr (SPMV) {
+#pragma unroll
+      for (int r = 0; r < BS; r++) acc[r] = 0.0;
+      ell_row_mult<BS, WMAX_WIDE>(n, rowptr ? rowptr[i + 1] - rowptr[i] : W, i, col, aval, in, acc);
+    } else {
+      load_x<BS>(in, i, acc);
+    }
+    uo = row_uoffw[i];
+    parked = uo + (ulast - dslot - 1) <= ucap;
+    if (parked) {
+      for (int q = dslot + 1; q < ulast; q++) {
+        double blk[BB];
+        load_block<BS>(fval, n, q, i, blk);
+        double* p = park + (size_t)(uo + q - dslot - 1) * BB;
+#pragma unroll
+        for (int e = 0; e < BB; e++) p[e] = blk[e];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < BS; r++) ys[tid * BS + r] = acc[r];
+  }
+  __syncthreads();
+  for (int lev = 1; lev < nlf; lev++) {  // level-0 rows have no lower couplings
+    if (lf == lev) {
+      double a[BS];
+#pragma unroll
+      for (int r = 0; r < BS; r++) a[r] = ys[tid * BS + r];
+      for (int q = lfirst; q < dslot; q++) {
+        const int k = col[(size_t)q * n + i] - lo;
+        double m[BB], yk[BS];
+        load_block<BS>(fval, n, q, i, m);
+#pragma unroll
+        for (int c = 0; c < BS; c++) yk[c] = ys[k * BS + c];
+#pragma unroll
+        for (int r = 0; r < BS; r++)
+#pragma unroll
+          for (int c = 0; c < BS; c++) a[r] -= m[r * BS + c] * yk[c];
+      }
+#pragma unroll
+      for (int r = 0; r < BS; r++) ys[tid * BS + r] = a[r];
+    }
+    __syncthreads();
+  }
+  // the inverted pivot: fetched once the forward sweep is over, so that it does not hold registers through the load
+  // phase (4 x 4 blocks: 127 VGPRs and spills with it loaded there)
+  double out[BS], dv[BB];
+#pragma unroll
+  for (int r = 0; r < BS; r++) out[r] = 0.0;
+#pragma unroll
+  for (int e = 0; e < BB; e++) dv[e] = 0.0;
+  if (active) load_block<BS>(fval, n, dslot, i, dv);
+  for (int lev = 0; lev < nlb; lev++) {
+    if (lb == lev) {
+      double a[BS];
+#pragma unroll
+      for (int r = 0; r < BS; r++) a[r] = ys[tid * BS + r];
+      for (int q = dslot + 1; q < ulast; q++) {
+        const int k = col[(size_t)q * n + i] - lo;
+        double m[BB], xk[BS];
+        if (parked) {
+          const double* p = park + (size_t)(uo + q - dslot - 1) * BB;
+#pragma unroll
+          for (int e = 0; e < BB; e++) m[e] = p[e];
+        } else {
+          load_block<BS>(fval, n, q, i, m);
+        }
+#pragma unroll
+        for (int c = 0; c < BS; c++) xk[c] = ys[k * BS + c];
+#pragma unroll
+        for (int r = 0; r < BS; r++)
+#pragma unroll
+          for (int c = 0; c < BS; c++) a[r] -= m[r * BS + c] * xk[c];
+      }
+#pragma unroll
+      for (int r = 0; r < BS; r++) {
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < BS; c++) t += dv[r * BS + c] * a[c];
+        out[r] = t;
+      }
+#pragma unroll
+      for (int r = 0; r < BS; r++) ys[tid * BS + r] = out[r];
+    }
+    if (lev + 1 < nlb) __syncthreads();
+  }
+  if (active) {
+#pragma unroll
+    for (int r = 0; r < BS; r++) z[(size_t)i * BS + r] = out[r];
+  }
+  if (dot != 0) {
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    pc_row_dots<BS, false, false>(dot, v, out, active, [&](double (&x)[BS]) {   // the operand again (an L2 hit), not held
+#pragma unroll
+      for (int r = 0; r < BS; r++) x[r] = 0.0;
+      if (active) load_x<BS>(in, i, x);
+    }, [&](double (&a)[BS]) { load_x_stream<BS>(aux, i, a); });
+    __syncthreads();
+    pc_reduce_dots(dot, v, red, partials, nb_max, s);
+  }
+}
+
 // ---- K6+K8 fused, upper blocks parked in LDS (bs = 2, pivot-scaled DILU, <= 3+3 couplings) -----
 // k_pc holds a row's three lower and three upper blocks in registers through both sweeps (~100
 // VGPRs: two workgroups per CU), although the upper blocks are only needed once the forward sweep
@@ -2232,6 +2474,20 @@ int launch_spmv(wai_ctx* c, const double* x, double* y) {
   const int nblk = (J.n + TPB - 1) / TPB;
   const int grid = ((nblk + 7) / 8) * 8;
   const int* rp = (size_t)J.nnzb * 10 < (size_t)J.n * J.W * 9 ? J.rowptr : nullptr;   // > 10 % padding
+  if (J.W > WMAX) {   // cells with 9 .. 16 faces (wai_ctx_create refuses wider rows)
+    if (J.W > WMAX_WIDE) return -1;
+#define SPW(BSV) do { if (rp) hipLaunchKernelGGL((k_spmv_wide<BSV, true>), grid, TPB, 0, c->stream, J.n, J.W, nblk, J.col, J.val, rp, x, y); \
+                      else hipLaunchKernelGGL((k_spmv_wide<BSV, false>), grid, TPB, 0, c->stream, J.n, J.W, nblk, J.col, J.val, rp, x, y); } while (0)
+    switch (J.bs) {
+      case 1: SPW(1); break;
+      case 2: SPW(2); break;
+      case 3: SPW(3); break;
+      case 4: SPW(4); break;
+      default: return -1;
+    }
+#undef SPW
+    return 0;
+  }
   switch (J.bs) {
     case 1: if (rp) hipLaunchKernelGGL((k_spmv<1, true>), grid, TPB, 0, c->stream, J.n, J.W, nblk, J.col, J.val, rp, x, y); else hipLaunchKernelGGL((k_spmv<1, false>), grid, TPB, 0, c->stream, J.n, J.W, nblk, J.col, J.val, rp, x, y); break;
     case 2: if (rp) hipLaunchKernelGGL((k_spmv<2, true>), grid, TPB, 0, c->stream, J.n, J.W, nblk, J.col, J.val, rp, x, y); else hipLaunchKernelGGL((k_spmv<2, false>), grid, TPB, 0, c->stream, J.n, J.W, nblk, J.col, J.val, rp, x, y); break;
@@ -2509,6 +2765,15 @@ int launch_ilu_factor_on(wai_ctx* c, const Bcsr& J, IluSchedule& s) {
       case 4: hipLaunchKernelGGL((k_dilu_pivots<4, false>), grid, T, lds, c->stream, J.n, s.nsub, s.sub_ptr, s.sub_nlev, s.row_info, J.col, J.val, s.dinv, c->d_flags); break;
       default: return -1;
     }
+  } else if (s.wide) {
+    hipMemcpyAsync(s.fval, J.val, sizeof(double) * ell_size(J.bs, J.n, J.W), hipMemcpyDeviceToDevice, c->stream);
+    switch (J.bs) {
+      case 1: hipLaunchKernelGGL(k_ilu_factor_wide<1>, grid, T, 0, c->stream, J.n, s.nsub, s.sub_ptr, s.sub_nlev, s.row_infow, J.col, s.fval, s.dinv, c->d_flags); break;
+      case 2: hipLaunchKernelGGL(k_ilu_factor_wide<2>, grid, T, 0, c->stream, J.n, s.nsub, s.sub_ptr, s.sub_nlev, s.row_infow, J.col, s.fval, s.dinv, c->d_flags); break;
+      case 3: hipLaunchKernelGGL(k_ilu_factor_wide<3>, grid, T, 0, c->stream, J.n, s.nsub, s.sub_ptr, s.sub_nlev, s.row_infow, J.col, s.fval, s.dinv, c->d_flags); break;
+      case 4: hipLaunchKernelGGL(k_ilu_factor_wide<4>, grid, T, 0, c->stream, J.n, s.nsub, s.sub_ptr, s.sub_nlev, s.row_infow, J.col, s.fval, s.dinv, c->d_flags); break;
+      default: return -1;
+    }
   } else {
     hipMemcpyAsync(s.fval, J.val, sizeof(double) * ell_size(J.bs, J.n, J.W), hipMemcpyDeviceToDevice, c->stream);
     switch (J.bs) {
@@ -2553,16 +2818,18 @@ int launch_big_solve(wai_ctx* c, const Bcsr& J, const IluSchedule& s, double* z)
   return 0;
 }
 
-// which fused kernel serves (matrix, schedule): 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc.  The first
-// three can form their input on the fly (in - alpha in2: launch_pc_on's in2)
+// which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc.
+// Kinds 1 .. 3 can form their input on the fly (in - alpha in2: launch_pc_on's in2)
 static int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s) {
+  if (s.wide) return 4;   // rows of 9 .. 16 blocks: no other fused kernel reads their descriptor
   if (c->dbg) return 0;
   if (s.wave_kernel && J.bs >= 3) return 3;
   if (s.rows_kernel) return 2;
   if (J.bs == 2 && s.park && s.diag_only && s.scaled && s.fast3 && pc_threads(s) <= 512) return 1;
   return 0;
 }
-bool pc_axpy_capable(const wai_ctx* c) { return !c->ilu.big && pc_kernel_kind(c, c->J, c->ilu) != 0; }
+static bool kind_composes(int kind) { return kind >= 1 && kind <= 3; }
+bool pc_axpy_capable(const wai_ctx* c) { return !c->ilu.big && kind_composes(pc_kernel_kind(c, c->J, c->ilu)); }
 bool pc_axpy_default(const wai_ctx* c) {
   if (c->ilu.big) return false;
   const int kind = pc_kernel_kind(c, c->J, c->ilu);
@@ -2592,6 +2859,19 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
   } while (0)
   const int kind = pc_kernel_kind(c, J, s);
   const double* scal = c->ks.scal;
+  if (kind == 4) {
+    // rows of 9 .. 16 blocks: parked upper blocks within the 64 KB a workgroup may ask for
+    const size_t room = (size_t)64 * 1024 > lds ? (size_t)64 * 1024 - lds : 0;
+    const int ucap = (int)std::min((size_t)s.max_ublocks_w, room / ((size_t)BS * BS * sizeof(double)));
+    const size_t lds_w = lds + (size_t)ucap * BS * BS * sizeof(double);
+    const int* rp = (size_t)J.nnzb * 10 < (size_t)J.n * J.W * 9 ? J.rowptr : nullptr;   // > 10 % padding
+#define PCWD(SP) hipLaunchKernelGGL((k_pc_wide<BS, SP>), grid, T, lds_w, c->stream, J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, \
+                                    s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux, c->ks.partials, c->ks.nb_max, \
+                                    dot_mode, ucap, list, fin)
+    if (spmv) PCWD(true); else PCWD(false);
+#undef PCWD
+    return;
+  }
   // one wave per brick of <= 64 block rows (block sizes 3 and 4), four bricks per workgroup
   if (kind == 3) {
     if constexpr (BS >= 3) {
@@ -2666,7 +2946,7 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
 
 int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z,
                  int dot_mode, const double* aux, const int* list, int nrun, const Fin* fin, const double* in2) {
-  if (in2 && (!spmv || pc_kernel_kind(c, M, s) == 0)) { c->err = "composed input asked of a kernel that cannot form it"; return -1; }
+  if (in2 && (!spmv || !kind_composes(pc_kernel_kind(c, M, s)))) { c->err = "composed input asked of a kernel that cannot form it"; return -1; }
   const Fin* fin_later = nullptr;
   if (fin && dot_mode != 0 && c->env.fin_separate) { fin_later = fin; fin = nullptr; }
   c->ks.nb_pc = s.nsub;   // partial sums per slot this application leaves: one per brick (k_pc_wave: per workgroup, set there)

@@ -39,18 +39,24 @@ extern "C" {
 // 1 = ILU(0) apply z = B^-1 r, 2 = fused z = B^-1 (A x) with the (z, aux) reduction finished in the kernel,
 // 3/4 = probes of 1/2 with the substitution sweeps skipped (load/compute phase split), 5 = the five launches
 // of a whole BiCGStab iteration (overwrites the Krylov work vectors), 6 = its vector updates alone,
-// 9 / 10 = the fused kernel on the interior / face bricks only.
+// 9 / 10 = the fused kernel on the interior / face bricks only, 23 = z = B^-1 (A x) by the launch-per-level path on the
+// factor in force (k_spmv + k_lvl_solve per level: the path k_pc_wide replaces, on the same system).
 int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   if (!c || !ms_per_launch || reps <= 0) return -2;
   read_env(c);
   if ((which == 20 || which == 21) && !c->ks.basis) { c->err = "wai_bench_kernel 20 / 21: no Krylov basis (ksp_type gmres)"; return -2; }
   if (which > 0 && !c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e < 0 ? -1 : e; }
+  if (which == 23 && (!pc_fused(c) || !c->ilu.ord_f)) { c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh)"; return -2; }
   Krylov& k = c->ks;
   const size_t copy_n = (size_t)c->np * c->df * c->mesh.n_prim / 2;   // modes 18 / 19 (the scratch is rewritten by every Jacobian)
   auto run = [&]() {
     switch (which) {
       case 0: launch_spmv(c, k.P, k.tmp); break;
       case 1: case 3: pc_solve(c, k.P, k.V, PC_DOT_NONE, nullptr, nullptr); break;
+      case 23:   // the launch-per-level path on the schedule in force (wide schedules: the factor k_pc_wide applies), for comparison
+        launch_spmv(c, k.P, k.V);
+        launch_big_solve(c, c->J, c->ilu, k.V);
+        break;
       case 9: if (c->ilu.n_int > 0) launch_pc(c, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_int, c->ilu.n_int); break;   // interior bricks only
       case 10: if (c->ilu.n_bnd > 0) launch_pc(c, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_bnd, c->ilu.n_bnd); break;  // face bricks only
       case 16:  // interior + face bricks as the overlapped halo exchange launches them (no halo here): the split's cost against case 2
@@ -155,11 +161,13 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
   if (c->opts.pc_type == WAI_PC_LU) return "k_spmv + k_lu_apply (dense block inverses)";
   if (pc_extended(c)) {
     static thread_local char b3[96];
-    snprintf(b3, sizeof(b3), "k_spmv + %s on the extended system (%s, ILU(%d))", c->as.sched.big ? "k_lvl_solve per level" : "k_pc",
+    snprintf(b3, sizeof(b3), "k_spmv + %s on the extended system (%s, ILU(%d))",
+             c->as.sched.big ? "k_lvl_solve per level" : (c->as.sched.wide ? "k_pc_wide" : "k_pc"),
              c->opts.pc_type == WAI_PC_ASM ? "ASM" : "block Jacobi", std::max(c->opts.ilu_levels, 0));
     return b3;
   }
   if (s.big) return "k_spmv + k_lvl_solve per level";
+  if (s.wide) { static thread_local char bw[64]; snprintf(bw, sizeof(bw), "k_pc_wide<%d,spmv>", c->J.bs); return bw; }
   if (s.wave_kernel) { static thread_local char b4[64]; snprintf(b4, sizeof(b4), "k_pc_wave<%d,spmv>", c->J.bs); return b4; }
   if (s.rows_kernel) { static thread_local char b2[64]; snprintf(b2, sizeof(b2), "k_pc_rows<%d,spmv,%d+%d>", c->J.bs, s.max_nlu <= 3 ? 3 : 4, s.max_nlu <= 3 ? 3 : 4); return b2; }
   if (c->J.bs == 2 && s.park && s.diag_only && s.scaled && s.fast3 && s.max_rows <= 512)

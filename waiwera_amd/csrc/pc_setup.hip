@@ -14,7 +14,7 @@ namespace wai {
 // compact / parked kernel conditions -- or, for subdomains of more than 1024 rows, the level sets
 // of the launch-per-level path.  `ghosts`: rows may have columns >= n (partition ghosts).
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts) {
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide) {
   s.nsub = (int)sub.size() - 1;
   if (sub.front() != 0 || sub.back() != N) { c->err = "sub_ptr must cover [0, n_owned]"; return -2; }
   std::vector<int> diag(N);
@@ -98,12 +98,27 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
     nlf_all = std::max(nlf_all, nlf); nlb_all = std::max(nlb_all, nlb);
   }
   // the brick kernels hold a row's <= 8 blocks in registers and pack slot numbers in 4 bits: wider rows (ILU(k)
-  // fill) and subdomains of more than 1024 rows take the launch-per-level path, whose descriptor has 8-bit slots
-  s.big = s.max_rows > 1024 || W > 8;
+  // fill) and subdomains of more than 1024 rows take the launch-per-level path, whose descriptor has 8-bit slots.
+  // A mesh whose own rows are wider (cells with 9 .. 16 faces: c->J.W > 8) has k_pc_wide for its subdomains of <= 1024
+  // rows of <= 16 blocks: its own Jacobian's and the ILU(0) extended systems of PCASM built on it (`allow_wide`; ILU(k)
+  // fill stays on the launch-per-level path).  A mesh of at most 8 blocks per row keeps the schedule it always had.
+  s.wide = allow_wide && c->J.W > 8 && W > 8 && W <= 16 && s.max_rows <= 1024;
+  s.big = s.max_rows > 1024 || (W > 8 && !s.wide);
   if (!s.big && s.max_lev > 1023) { c->err = "more than 1023 dependency levels in a subdomain"; return -2; }
   for (int i = 0; i < N; i++)
-    info[i] = s.big ? (lfirst[i] | (diag[i] << 8) | (ulast[i] << 16))
-                    : (lfirst[i] | (diag[i] << 4) | (ulast[i] << 8) | (levf[i] << 12) | (levb[i] << 22));
+    info[i] = (s.big || s.wide) ? (lfirst[i] | (diag[i] << 8) | (ulast[i] << 16))
+                                : (lfirst[i] | (diag[i] << 4) | (ulast[i] << 8) | (levf[i] << 12) | (levb[i] << 22));
+  if (s.wide) {
+    std::vector<unsigned long long> infow(N);
+    for (int i = 0; i < N; i++)
+      infow[i] = (unsigned long long)(lfirst[i] | (diag[i] << 5) | (ulast[i] << 10)) |
+                 ((unsigned long long)(levf[i] | (levb[i] << 10)) << 32);
+    if (hipMalloc(reinterpret_cast<void**>(&s.row_infow), infow.size() * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemcpy(s.row_infow, infow.data(), infow.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
+      c->err = "hipMalloc of the wide row descriptors failed";
+      return -1;
+    }
+  }
   // Launch order.  Workgroup b of a fused launch runs on XCD b % 8 and takes position (b & 7) * per + (b >> 3) of the
   // list it is given, so each XCD works through one contiguous eighth in order.  Where bricks differ in cost (the
   // ragged bricks at the upper ends of a rank's box: fewer rows, fewer levels) the long ones go first inside each
@@ -155,8 +170,9 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       if (dev_upload(c, &s.sub_int, li) || dev_upload(c, &s.sub_bnd, lb)) return -1;
     }
   }
-  if (s.big) {
-    // level sets over all subdomains: rows of one level are independent wherever they live
+  if (s.big || s.wide) {
+    // level sets over all subdomains: rows of one level are independent wherever they live (wide schedules: for the
+    // measurement of the launch-per-level path on the same factor, wai_bench_kernel 23)
     s.nlev_f = nlf_all; s.nlev_b = nlb_all;
     std::vector<int> of(N), ob(N);
     s.lev_f_ptr.assign(nlf_all + 1, 0); s.lev_b_ptr.assign(nlb_all + 1, 0);
@@ -174,7 +190,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
   // Kernel-selection switches.  Build time, for the fallback build that drives the GPU tests through the generic kernels
   // (tools/ci_fallback_kernels.sh): WAI_ILU_GENERAL, WAI_PC_ROWS, WAI_PC_WAVE.  Run time, for the tests that compare paths
   // in one process: WAI_NO_COL16 (k_pc_park on the int32 column planes: read_env) and WAI_COL16_MAX_SEG (below).
-  s.diag_only = !offdiag_fill && !s.big;
+  s.diag_only = !offdiag_fill && !s.big && !s.wide;   // (wide rows: the stored factor alone, k_pc_wide)
   s.level_sorted = !s.big;
   for (int sd = 0; sd < s.nsub && s.level_sorted; sd++)
     for (int i = sub[sd] + 1; i < sub[sd + 1]; i++)
@@ -290,7 +306,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
 }
 
 void free_schedule(IluSchedule& s) {
-  hipFree(s.col16); hipFree(s.sub_seg);
+  hipFree(s.col16); hipFree(s.sub_seg); hipFree(s.row_infow);
   hipFree(s.sub_ptr); hipFree(s.sub_nlev); hipFree(s.sub_split); hipFree(s.row_info); hipFree(s.fval); hipFree(s.dinv);
   hipFree(s.row_uoff); hipFree(s.row_uoffw); hipFree(s.row_tslot); hipFree(s.sub_order); hipFree(s.sub_int); hipFree(s.sub_bnd); hipFree(s.ord_f); hipFree(s.ord_b);
   s = IluSchedule();
@@ -528,7 +544,7 @@ int build_asm(wai_ctx* c, int overlap, int levels, bool with_net) {
   if (dev_upload(c, &a.E.col, ell_col) || dev_upload(c, &a.gmap, gmap) || dev_upload(c, &a.ext_row, erow) ||
       dev_alloc(c, &a.E.val, ell_size(np, n_ext, W)) || dev_alloc(c, &a.r_ext, (size_t)np * n_ext + 16))
     return -1;
-  if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false)) return e;
+  if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0)) return e;
   a.with_net = with_net;
   a.n_net = 0;
   if (mnet > 0) {   // where the blocks of the network's E land in the extended planes

@@ -19,7 +19,9 @@ import numpy as np
 
 
 def read_geometry(path):
-    """returns (nodes (N, 3), cells [node index lists, gmsh hexahedron / prism order], 3)"""
+    """returns (nodes (N, 3), cells [node index lists, gmsh hexahedron / prism order], 3).  Columns of
+    any number of nodes: a column of n nodes gives n-gon prisms (lower ring, then upper ring, as for
+    hexahedra), which unstructured.build_mesh takes with two n-gon faces and n quads."""
     with open(path) as f:
         lines = [ln.rstrip("\n") for ln in f]
     sections, cur = {}, None
@@ -52,8 +54,8 @@ def read_geometry(path):
     cells = []
     for lay in range(len(bottoms)):
         for col in columns:
-            if len(col) not in (3, 4):
-                raise NotImplementedError("columns with %d nodes" % len(col))
+            if len(col) < 3:
+                raise ValueError("column with %d nodes" % len(col))
             xy = np.array([verts[nm] for nm in col])
             x, y = xy[:, 0], xy[:, 1]
             signed = 0.5 * np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y)

@@ -21,6 +21,27 @@ PRISM_FACES = [(0, 2, 1), (3, 4, 5), (0, 1, 4, 3), (1, 2, 5, 4), (2, 0, 3, 5)]
 TET_FACES = [(0, 2, 1), (0, 1, 3), (1, 2, 3), (2, 0, 3)]
 
 
+def prism_faces(k):
+    """faces of a k-gon prism given as its lower ring then its upper ring (the hexahedra's order):
+    the two k-gons and k quads.  k = 3, 4 give PRISM_FACES / HEX_FACES up to the order of the faces;
+    those tables stay in use for their shapes."""
+    lower = tuple(range(k - 1, -1, -1))
+    upper = tuple(range(k, 2 * k))
+    return [lower, upper] + [(q, (q + 1) % k, k + (q + 1) % k, k + q) for q in range(k)]
+
+
+def _cell_faces(nnodes):
+    """face table of a 3-D cell by its node count: hexahedra, prisms and tetrahedra as gmsh numbers
+    them, and 2k nodes for k >= 5 a k-gon prism (polygonal MULgraph columns)"""
+    table = {8: HEX_FACES, 6: PRISM_FACES, 4: TET_FACES}.get(nnodes)
+    if table is not None:
+        return table
+    if nnodes >= 10 and nnodes % 2 == 0:
+        return prism_faces(nnodes // 2)
+    raise ValueError("3-D cell with %d nodes: hexahedra (8), prisms (6), tetrahedra (4) or k-gon prisms "
+                     "(2k nodes, lower ring then upper ring)" % nnodes)
+
+
 def _polygon(xy):
     """area and centroid of a planar polygon given by its vertices in order (shoelace)"""
     x, y = xy[:, 0], xy[:, 1]
@@ -76,7 +97,7 @@ def build_mesh(nodes, cells, dim, thickness=1.0, radial=False, gravity=None, bou
                     nrm = np.array([t[1], -t[0], 0.0]) / length
                     fgeo[key] = [length, np.array([*(0.5 * (a0 + a1)), 0.0]), nrm]
         else:
-            table = {8: HEX_FACES, 6: PRISM_FACES, 4: TET_FACES}[len(nd)]
+            table = _cell_faces(len(nd))
             fl = []
             for f in table:
                 key = tuple(sorted(nd[k] for k in f))
