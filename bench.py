@@ -1,10 +1,19 @@
 #!/usr/bin/env python
 """Headline benchmark: Newton steps/s of the Newton-step hot path on the synthetic structured
-meshes of SURVEY.md section 8d (BASELINE.json metric), the roofline of the dominant kernel, and the
-CPU oracle timed on the same mesh.
+meshes of SURVEY.md section 8d (BASELINE.json metric); with --full also the correctness gate, the
+roofline of the dominant kernel, and the CPU oracle timed on the same mesh.
 
     python bench.py --gpus N --steps K --warmup W           # N > 1: spawns its own N ranks
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, lead-in, warm-up, the K timed steps,
+--dump-outputs if asked, and the result line (metric, value, ms_per_step, and what the timed steps'
+own records give: Krylov counts, the least-squares split, launch counts).  --full adds, after the
+timed steps and outside all timing: the device's clocks, how the last timed try ends and the
+accepted-step rate, the `check` gate (one more accepted time step and its balance; the oracle's
+residual and Jacobian at the window's first state), the kernel microbenchmarks and `roofline`, the
+collectives' exposed time (`comm`, N > 1), the reference's default preconditioner from the committed
+comparison, and the CPU baseline (`cpu_baseline`, unless --no-cpu).
 
 Workloads (--config): c3 (default) 216^3 = 10 077 696-cell eos we; c2 100^3 eos we; c4 172x172x170
 eos wce (3 x 3 blocks); c5 100^3 fracture cells + 1 MINC matrix level, eos wce.
@@ -616,8 +625,11 @@ def main():
                     help="relative permeability / capillary pressure: the reference's defaults (linear [0,1]/[0,1], zero) or "
                          "SURVEY.md section 8d's second series, Corey (0.3, 0.05)")
     ap.add_argument("--no-lens", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--spmv-reps", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: the correctness gate, "
+                         "kernel microbenchmarks and roofline, the collectives' cost, the CPU baseline (see the module docstring)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--spmv-reps", type=int, default=200, help="launches per kernel microbenchmark (--full, --micro-only)")
     ap.add_argument("--profile", action="store_true", help="per-kernel-class HIP event timing (serialises)")
     ap.add_argument("--micro-only", action="store_true",
                     help="kernel A/B runs: assemble one Jacobian, set up the preconditioner, print the kernel microbench, exit")
@@ -826,7 +838,7 @@ def main():
         drv.newton_step()
     barrier()
     el = time.perf_counter() - t0
-    dev_state = device_state(local_rank) if rank == 0 else None
+    dev_state = device_state(local_rank) if rank == 0 and a.full else None
     ls1 = sim.launch_stats()
     cs1 = sim.comm_stats()
     l1 = len(drv.log)
@@ -834,25 +846,26 @@ def main():
         n_dof = lm.n_owned * bs
         dump_outputs(a.dump_outputs, lm, dims, n_cells, bs, drv.y[:n_dof].cpu().numpy(), drv.f[:n_dof].cpu().numpy(),
                      sim.regions()[: lm.n_owned], drv.log[-1][:6], dist, rank)
-    while drv.it >= 0:      # (untimed) how the last timed try ends
-        drv.newton_step()
+    if a.full:
+        while drv.it >= 0:      # (untimed) how the last timed try ends
+            drv.newton_step()
     if dist is not None:
         tt = torch.tensor([el], dtype=torch.float64, device="cpu" if loopback else "cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     timed = drv.log[l0:l1]
     kits = sum(r[3] for r in timed)
-    # Newton iterations that belong to accepted time steps (tries that end converged), and their time
+    # Newton iterations that belong to accepted time steps (tries that end converged), and their time.  Without --full the
+    # last timed try is not run to its end: its steps are None, neither accepted nor thrown away
     acc_n, acc_s, ok = 0, 0.0, None
     for r in reversed(drv.log[l0:]):
         if r[4] != 0:
             ok = r[4] > 0
-        r.append(bool(ok))
+        r.append(ok)
     for r in timed:
         if r[7]:
             acc_n += 1
             acc_s += r[6]
-    last_ok = [r for r in drv.log if r[4] > 0][-1]
     prof = sim.profile_get() if a.profile else None
     sim.profile(False)
     for i, rec in enumerate(drv.log):
@@ -864,162 +877,165 @@ def main():
     b = np.array([r[6] for r in timed])
     fixed_s, iter_s = (np.linalg.lstsq(A, b, rcond=None)[0] if len(timed) > 2 and np.ptp(A[:, 1]) > 0 else (0.0, 0.0))
     k_med = float(np.median(A[:, 1])) if len(timed) else 0.0
-
-    # Correctness gate (`check` in the line).  (i) the last accepted time step's convergence measure, as
-    # SNES_convergence forms it; (ii) global balance of that step's discrete equations, per equation:
-    # sum_i V_i (L_i(y_new) - L_i(y_old) - dt R_i(y_new)) against sum_i V_i |L_i(y_new) - L_i(y_old)| -- wai_lhs /
-    # wai_rhs evaluated afresh on the accepted state, not Newton's own residual vector; (iii) in the CPU-baseline
-    # leg the oracle's residual and FD Jacobian at the window's first state against the device's (below).
-    check = {"max_scaled_residual_last_accepted_step": last_ok[5], "nonlinear_tolerance": 1e-5}
-    gpu_state = None
-    n_dof = lm.n_owned * bs
-    vol = torch.from_numpy(np.ascontiguousarray(lm.cell_geom[: lm.n_owned, 3])).cuda()
-    # one more accepted time step from where the trajectory stands, kept out of every timing
-    lhs0 = torch.zeros(n_dof, dtype=torch.float64, device="cuda")
-    r_chk = 0
-    for _ in range(60):
-        r_chk, _ = drv.newton_step()      # lhs_old = L(y_old) is set when a try begins and kept through it
-        if r_chk > 0:
-            lhs0.copy_(drv.lhs_old)
-            dt_chk = drv.log[-1][1]
-            t_old = drv.t - dt_chk
-            break
-    if r_chk > 0:
-        lhs1 = torch.zeros_like(lhs0)
-        rhs1 = torch.zeros_like(lhs0)
-        assert sim.pre_eval(t_old + dt_chk, y) == 0
-        sim.lhs(t_old + dt_chk, (t_old, t_old + dt_chk), y, lhs1)
-        sim.rhs(t_old + dt_chk, (t_old, t_old + dt_chk), y, rhs1)
-        torch.cuda.synchronize()
-        dl = (lhs1 - lhs0).view(-1, bs) * vol[:, None]
-        # per equation: sum_i V_i (dL_i - dt R_i) and sum_i V_i |dL_i| -- over ALL ranks' cells (the fluxes through a
-        # rank boundary cancel between the two ranks that compute them, as they do between two cells of one rank)
-        sums = torch.stack([(dl - dt_chk * rhs1.view(-1, bs) * vol[:, None]).sum(dim=0), dl.abs().sum(dim=0)])
-        if dist is not None:
-            sums_h = sums.cpu() if loopback else sums
-            dist.all_reduce(sums_h, op=dist.ReduceOp.SUM)
-            sums = sums_h
-        bal = sums[0].abs() / sums[1].clamp_min(1e-300)
-        check["step_balance_defect_per_equation"] = [float(v) for v in bal.cpu()]
-        check["step_balance_of"] = "accepted step at t = %.6g s, dt = %.4g s%s" % (t_old, dt_chk, ", summed over %d ranks" % world if world > 1 else "")
-        del lhs1, rhs1, dl
-    # the window's first state again: residual and Jacobian the oracle is compared with, and the matrix
-    # the kernel microbenchmarks run on
-    gpu_first_kits = drv.log[n_lead][3] if len(drv.log) > n_lead and drv.log[n_lead][2] == 1 else None   # the device's Krylov count on the window's first system
-    # ... and that whole Newton step on the device (warm-up's first step: outside the timed region, host-timed like the timed ones)
-    gpu_first_step = ({"krylov": int(drv.log[n_lead][3]), "seconds": float(drv.log[n_lead][6]), "reason": int(drv.log[n_lead][4])}
-                      if gpu_first_kits is not None else None)
-    drv.restore(start)
-    drv._begin()
-    sim.jacobian(drv.t + drv.dt, drv.dt, y, drv.lhs_old)
-    sim.pc_setup()
-    if world == 1 and not a.no_cpu:
-        gpu_state = dict(f=drv.f.cpu().numpy().copy(), J=sim.jacobian_values())
-    drv.it = -1
-
-    # Kernel roofline, measured live with HIP events on the library's stream on the Jacobian of the window's
-    # first Newton step.  Dominant kernel of a Newton step: the fused preconditioned operator
-    # k_pc (block SpMV t = A x, block-Jacobi ILU(0) solve z = U^-1 L^-1 t, dot (z, aux)), run
-    # twice per BiCGStab iteration.  Plain block SpMV is reported beside it.
-    nnzb = wl.LIB.wai_jacobian_nnzb(sim.h)
-    names = ["spmv", "ilu_apply", "fused_pc_amul"]
-    kb = {name: sim.bench_kernel(w, a.spmv_reps if w in (0, 2) else 20) for w, name in enumerate(names)}
-    if a.ksp == "gmres":
-        kb["fused_pc_plain"] = sim.bench_kernel(11, a.spmv_reps)
-    if world == 1 and not minc and a.pc == "bjacobi" and a.ilu_levels == 0:   # the two launches of the overlapped halo exchange, timed alone
-        kb["fused_interior_bricks"] = sim.bench_kernel(9, a.spmv_reps)
-        kb["fused_face_bricks"] = sim.bench_kernel(10, a.spmv_reps)
-        kb["fused_interior_and_face_bricks_as_launched"] = sim.bench_kernel(16, a.spmv_reps)
-    if world == 1 and a.ksp == "bcgs" and a.pc == "bjacobi" and a.ilu_levels == 0:   # the iteration's launches back to back, and its vector updates alone
-        kb["bicgstab_iteration_device_only"] = sim.bench_kernel(5, 50)
-        kb["bicgstab_vector_updates"] = sim.bench_kernel(6, 50)
-        # the iteration's SECOND fused launch exactly as it is issued (composed operand R - alpha V where that is the default,
-        # five inner products, the scalars and the post in the launch): since round 5 the launch with the larger share
-        kb["fused_pc_second_half"] = sim.bench_kernel(17, a.spmv_reps)
-    # what a copy achieves on this box (2 x bytes / time): hipMemcpy device to device and the library's own copy kernel
-    n_copy = (sim.n_prim * bs * sim.fluid_dof // 2) * 8
-    kb["copy_memcpy_d2d"] = sim.bench_kernel(18, 20)
-    kb["copy_kernel"] = sim.bench_kernel(19, 20)
-    kb["read_kernel"] = sim.bench_kernel(22, 20)
-    copy_gbs = {"hipMemcpyDtoD": 2.0 * n_copy / (kb["copy_memcpy_d2d"] * 1e-3) / 1e9, "copy_kernel": 2.0 * n_copy / (kb["copy_kernel"] * 1e-3) / 1e9,
-                "read_kernel": 2.0 * n_copy / (kb["read_kernel"] * 1e-3) / 1e9, "bytes_moved": 2 * n_copy}
-    comm = None
-    if world > 1:
-        # what the collectives cost per BiCGStab iteration: the iteration's launches and collectives back to back without
-        # the host (wai_bench_kernel 5), with RCCL at work and with every all-reduce / exchange muted (same kernels, same
-        # streams and events, no RCCL call) -- the difference is the collectives' EXPOSED time, overlap included
-        def maxr(v):
-            tt = torch.tensor([v], dtype=torch.float64, device="cpu" if loopback else "cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            return float(tt.item())
-        hb, nn = sim.halo_size()
-        comm = {"rccl_ranks": sim.comm_size(),
-                "allreduces_per_krylov_iteration": (cs1[0] - cs0[0]) / max(kits, 1),
-                "exchanges_per_krylov_iteration": (cs1[1] - cs0[1]) / max(kits, 1),
-                "counted_over": "every collective of the timed region (Newton protocol included) / its Krylov iterations",
-                "halo_bytes_per_exchange": int(maxr(hb)), "halo_neighbours": int(maxr(nn)),
-                "halo_exchange": "behind the interior bricks (communication stream)" if os.environ.get("WAI_HALO_OVERLAP", "1") != "0" else "in order",
-                "transport": os.environ.get("WAI_RCCL_LIB", "librccl (RCCL over xGMI)")}
-        if loopback:
-            comm["note"] = ("all %d ranks on ONE GPU%s over a test transport: the multi-rank code path and its collective counts, "
-                            "not a scaling measurement" % (world, (", %d compute units each (HSA_CU_MASK)" % (256 // world)) if "HSA_CU_MASK" in os.environ else ""))
-        if a.ksp == "bcgs" and a.pc == "bjacobi" and a.ilu_levels == 0:
-            barrier()
-            t_on = maxr(sim.bench_kernel(5, 30))
-            barrier()
-            sim.mute_comm(True)
-            t_off = maxr(sim.bench_kernel(5, 30))
-            sim.mute_comm(False)
-            barrier()
-            comm.update({"ms_per_krylov_iteration_device_only": t_on, "ms_per_krylov_iteration_collectives_muted": t_off,
-                         "ms_collectives_per_iteration": t_on - t_off, "collective_time_share": (t_on - t_off) / t_on if t_on > 0 else None})
-    log("kernel microbench (ms/launch): " + json.dumps(kb))
-    b_spmv = spmv_bytes(nnzb, lm.n_owned, bs)
-    b_pc = pc_bytes(nnzb, lm.n_owned, bs)
-    ms, ms_pc = kb["spmv"], kb["fused_pc_amul"]
-    achieved = b_spmv / (ms * 1e-3) / 1e9
-    achieved_pc = b_pc / (ms_pc * 1e-3) / 1e9
-    log("spmv: %.3f ms/launch, %.1f GB/s algorithmic (%.1f%% of %.0f); fused pc: %.3f ms, %.1f GB/s (%.1f%%)"
-        % (ms, achieved, 100 * achieved / HBM_PEAK_GBS, HBM_PEAK_GBS, ms_pc, achieved_pc, 100 * achieved_pc / HBM_PEAK_GBS))
     if prof:
         log("kernel-class time inside the timed region (ms, launches): " + json.dumps(prof))
-    # The dominant kernel.  A BiCGStab iteration issues the fused kernel twice: on P with one inner product (`first`), and on
-    # S = R - alpha V -- composed inside the launch where that is the default -- with the five merged products and the
-    # scalars (`second`).  Whichever launch takes longer is the line's `roofline`; the other one travels beside it.
-    composed = bool(sim.bcgs_composed()) if "fused_pc_second_half" in kb else False
-    halves = {"first": {"ms": ms_pc, "bytes": b_pc, "what": "fused BCSR SpMV + block ILU(0) apply + (z, r^)",
-                        "kernel": sim.pc_kernel_name(composed=False)}}
-    if "fused_pc_second_half" in kb:
-        b2 = b_pc + (8 * bs * lm.n_owned if composed else 0)       # composed: R and V are read where S was
-        halves["second"] = {"ms": kb["fused_pc_second_half"], "bytes": b2,
-                            "what": ("fused BCSR SpMV on S = R - alpha V formed in the launch" if composed else "fused BCSR SpMV on S")
-                                    + " + block ILU(0) apply + five inner products + scalars",
-                            "kernel": sim.pc_kernel_name(composed=composed)}
-    for h in halves.values():
-        h["gbs"] = h["bytes"] / (h["ms"] * 1e-3) / 1e9
-        h["frac"] = h["gbs"] / HBM_PEAK_GBS
-    if a.ksp == "gmres":
-        # GMRES(m), classical Gram-Schmidt: per Krylov iteration ONE fused operator application and, averaged over a restart
-        # cycle j = 0 .. m - 1, the inner products (w, v_0 .. v_j) (k_mdot<1..8>: j + 1 basis vectors + w once per pass of eight)
-        # and the update w -= sum h_j v_j with |w|^2 (k_maxpy_norm: j + 1 basis vectors, w read and written)
-        m_r = opts.gmres_restart
-        vec = 8 * bs * lm.n_owned
-        halves = {"operator": dict(halves["first"], ms=kb["fused_pc_plain"], what="fused BCSR SpMV + block ILU(0) apply, no inner product")}
-        halves["operator"]["bytes"] = b_pc - vec      # no dot-product partner
-        halves["gram_schmidt_dots"] = {"ms": sim.bench_kernel(20, 3), "bytes": vec * sum(j + 2 for j in range(m_r)) / m_r,
-                                       "what": "GMRES(%d) inner products (w, v_0..v_j), average over a restart cycle" % m_r, "kernel": "k_mdot<8>"}
-        halves["gram_schmidt_update"] = {"ms": sim.bench_kernel(21, 3), "bytes": vec * sum(j + 3 for j in range(m_r)) / m_r,
-                                         "what": "GMRES(%d) update w -= sum h_j v_j + |w|^2, average over a restart cycle" % m_r, "kernel": "k_maxpy_norm"}
+
+    # --full only: what the headline does not need, after the timed steps and outside their timing
+    kb, comm = {}, None
+    if a.full:
+        last_ok = [r for r in drv.log if r[4] > 0][-1]
+        # Correctness gate (`check` in the line).  (i) the last accepted time step's convergence measure, as
+        # SNES_convergence forms it; (ii) global balance of that step's discrete equations, per equation:
+        # sum_i V_i (L_i(y_new) - L_i(y_old) - dt R_i(y_new)) against sum_i V_i |L_i(y_new) - L_i(y_old)| -- wai_lhs /
+        # wai_rhs evaluated afresh on the accepted state, not Newton's own residual vector; (iii) in the CPU-baseline
+        # leg the oracle's residual and FD Jacobian at the window's first state against the device's (below).
+        check = {"max_scaled_residual_last_accepted_step": last_ok[5], "nonlinear_tolerance": 1e-5}
+        gpu_state = None
+        n_dof = lm.n_owned * bs
+        vol = torch.from_numpy(np.ascontiguousarray(lm.cell_geom[: lm.n_owned, 3])).cuda()
+        # one more accepted time step from where the trajectory stands, kept out of every timing
+        lhs0 = torch.zeros(n_dof, dtype=torch.float64, device="cuda")
+        r_chk = 0
+        for _ in range(60):
+            r_chk, _ = drv.newton_step()      # lhs_old = L(y_old) is set when a try begins and kept through it
+            if r_chk > 0:
+                lhs0.copy_(drv.lhs_old)
+                dt_chk = drv.log[-1][1]
+                t_old = drv.t - dt_chk
+                break
+        if r_chk > 0:
+            lhs1 = torch.zeros_like(lhs0)
+            rhs1 = torch.zeros_like(lhs0)
+            assert sim.pre_eval(t_old + dt_chk, y) == 0
+            sim.lhs(t_old + dt_chk, (t_old, t_old + dt_chk), y, lhs1)
+            sim.rhs(t_old + dt_chk, (t_old, t_old + dt_chk), y, rhs1)
+            torch.cuda.synchronize()
+            dl = (lhs1 - lhs0).view(-1, bs) * vol[:, None]
+            # per equation: sum_i V_i (dL_i - dt R_i) and sum_i V_i |dL_i| -- over ALL ranks' cells (the fluxes through a
+            # rank boundary cancel between the two ranks that compute them, as they do between two cells of one rank)
+            sums = torch.stack([(dl - dt_chk * rhs1.view(-1, bs) * vol[:, None]).sum(dim=0), dl.abs().sum(dim=0)])
+            if dist is not None:
+                sums_h = sums.cpu() if loopback else sums
+                dist.all_reduce(sums_h, op=dist.ReduceOp.SUM)
+                sums = sums_h
+            bal = sums[0].abs() / sums[1].clamp_min(1e-300)
+            check["step_balance_defect_per_equation"] = [float(v) for v in bal.cpu()]
+            check["step_balance_of"] = "accepted step at t = %.6g s, dt = %.4g s%s" % (t_old, dt_chk, ", summed over %d ranks" % world if world > 1 else "")
+            del lhs1, rhs1, dl
+        # the window's first state again: residual and Jacobian the oracle is compared with, and the matrix
+        # the kernel microbenchmarks run on
+        gpu_first_kits = drv.log[n_lead][3] if len(drv.log) > n_lead and drv.log[n_lead][2] == 1 else None   # the device's Krylov count on the window's first system
+        # ... and that whole Newton step on the device (warm-up's first step: outside the timed region, host-timed like the timed ones)
+        gpu_first_step = ({"krylov": int(drv.log[n_lead][3]), "seconds": float(drv.log[n_lead][6]), "reason": int(drv.log[n_lead][4])}
+                          if gpu_first_kits is not None else None)
+        drv.restore(start)
+        drv._begin()
+        sim.jacobian(drv.t + drv.dt, drv.dt, y, drv.lhs_old)
+        sim.pc_setup()
+        if world == 1 and not a.no_cpu:
+            gpu_state = dict(f=drv.f.cpu().numpy().copy(), J=sim.jacobian_values())
+        drv.it = -1
+
+        # Kernel roofline, measured live with HIP events on the library's stream on the Jacobian of the window's
+        # first Newton step.  Dominant kernel of a Newton step: the fused preconditioned operator
+        # k_pc (block SpMV t = A x, block-Jacobi ILU(0) solve z = U^-1 L^-1 t, dot (z, aux)), run
+        # twice per BiCGStab iteration.  Plain block SpMV is reported beside it.
+        nnzb = wl.LIB.wai_jacobian_nnzb(sim.h)
+        names = ["spmv", "ilu_apply", "fused_pc_amul"]
+        kb = {name: sim.bench_kernel(w, a.spmv_reps if w in (0, 2) else 20) for w, name in enumerate(names)}
+        if a.ksp == "gmres":
+            kb["fused_pc_plain"] = sim.bench_kernel(11, a.spmv_reps)
+        if world == 1 and not minc and a.pc == "bjacobi" and a.ilu_levels == 0:   # the two launches of the overlapped halo exchange, timed alone
+            kb["fused_interior_bricks"] = sim.bench_kernel(9, a.spmv_reps)
+            kb["fused_face_bricks"] = sim.bench_kernel(10, a.spmv_reps)
+            kb["fused_interior_and_face_bricks_as_launched"] = sim.bench_kernel(16, a.spmv_reps)
+        if world == 1 and a.ksp == "bcgs" and a.pc == "bjacobi" and a.ilu_levels == 0:   # the iteration's launches back to back, and its vector updates alone
+            kb["bicgstab_iteration_device_only"] = sim.bench_kernel(5, 50)
+            kb["bicgstab_vector_updates"] = sim.bench_kernel(6, 50)
+            # the iteration's SECOND fused launch exactly as it is issued (composed operand R - alpha V where that is the default,
+            # five inner products, the scalars and the post in the launch): since round 5 the launch with the larger share
+            kb["fused_pc_second_half"] = sim.bench_kernel(17, a.spmv_reps)
+        # what a copy achieves on this box (2 x bytes / time): hipMemcpy device to device and the library's own copy kernel
+        n_copy = (sim.n_prim * bs * sim.fluid_dof // 2) * 8
+        kb["copy_memcpy_d2d"] = sim.bench_kernel(18, 20)
+        kb["copy_kernel"] = sim.bench_kernel(19, 20)
+        kb["read_kernel"] = sim.bench_kernel(22, 20)
+        copy_gbs = {"hipMemcpyDtoD": 2.0 * n_copy / (kb["copy_memcpy_d2d"] * 1e-3) / 1e9, "copy_kernel": 2.0 * n_copy / (kb["copy_kernel"] * 1e-3) / 1e9,
+                    "read_kernel": 2.0 * n_copy / (kb["read_kernel"] * 1e-3) / 1e9, "bytes_moved": 2 * n_copy}
+        if world > 1:
+            # what the collectives cost per BiCGStab iteration: the iteration's launches and collectives back to back without
+            # the host (wai_bench_kernel 5), with RCCL at work and with every all-reduce / exchange muted (same kernels, same
+            # streams and events, no RCCL call) -- the difference is the collectives' EXPOSED time, overlap included
+            def maxr(v):
+                tt = torch.tensor([v], dtype=torch.float64, device="cpu" if loopback else "cuda")
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                return float(tt.item())
+            hb, nn = sim.halo_size()
+            comm = {"rccl_ranks": sim.comm_size(),
+                    "allreduces_per_krylov_iteration": (cs1[0] - cs0[0]) / max(kits, 1),
+                    "exchanges_per_krylov_iteration": (cs1[1] - cs0[1]) / max(kits, 1),
+                    "counted_over": "every collective of the timed region (Newton protocol included) / its Krylov iterations",
+                    "halo_bytes_per_exchange": int(maxr(hb)), "halo_neighbours": int(maxr(nn)),
+                    "halo_exchange": "behind the interior bricks (communication stream)" if os.environ.get("WAI_HALO_OVERLAP", "1") != "0" else "in order",
+                    "transport": os.environ.get("WAI_RCCL_LIB", "librccl (RCCL over xGMI)")}
+            if loopback:
+                comm["note"] = ("all %d ranks on ONE GPU%s over a test transport: the multi-rank code path and its collective counts, "
+                                "not a scaling measurement" % (world, (", %d compute units each (HSA_CU_MASK)" % (256 // world)) if "HSA_CU_MASK" in os.environ else ""))
+            if a.ksp == "bcgs" and a.pc == "bjacobi" and a.ilu_levels == 0:
+                barrier()
+                t_on = maxr(sim.bench_kernel(5, 30))
+                barrier()
+                sim.mute_comm(True)
+                t_off = maxr(sim.bench_kernel(5, 30))
+                sim.mute_comm(False)
+                barrier()
+                comm.update({"ms_per_krylov_iteration_device_only": t_on, "ms_per_krylov_iteration_collectives_muted": t_off,
+                             "ms_collectives_per_iteration": t_on - t_off, "collective_time_share": (t_on - t_off) / t_on if t_on > 0 else None})
+        log("kernel microbench (ms/launch): " + json.dumps(kb))
+        b_spmv = spmv_bytes(nnzb, lm.n_owned, bs)
+        b_pc = pc_bytes(nnzb, lm.n_owned, bs)
+        ms, ms_pc = kb["spmv"], kb["fused_pc_amul"]
+        achieved = b_spmv / (ms * 1e-3) / 1e9
+        achieved_pc = b_pc / (ms_pc * 1e-3) / 1e9
+        log("spmv: %.3f ms/launch, %.1f GB/s algorithmic (%.1f%% of %.0f); fused pc: %.3f ms, %.1f GB/s (%.1f%%)"
+            % (ms, achieved, 100 * achieved / HBM_PEAK_GBS, HBM_PEAK_GBS, ms_pc, achieved_pc, 100 * achieved_pc / HBM_PEAK_GBS))
+        # The dominant kernel.  A BiCGStab iteration issues the fused kernel twice: on P with one inner product (`first`), and on
+        # S = R - alpha V -- composed inside the launch where that is the default -- with the five merged products and the
+        # scalars (`second`).  Whichever launch takes longer is the line's `roofline`; the other one travels beside it.
+        composed = bool(sim.bcgs_composed()) if "fused_pc_second_half" in kb else False
+        halves = {"first": {"ms": ms_pc, "bytes": b_pc, "what": "fused BCSR SpMV + block ILU(0) apply + (z, r^)",
+                            "kernel": sim.pc_kernel_name(composed=False)}}
+        if "fused_pc_second_half" in kb:
+            b2 = b_pc + (8 * bs * lm.n_owned if composed else 0)       # composed: R and V are read where S was
+            halves["second"] = {"ms": kb["fused_pc_second_half"], "bytes": b2,
+                                "what": ("fused BCSR SpMV on S = R - alpha V formed in the launch" if composed else "fused BCSR SpMV on S")
+                                        + " + block ILU(0) apply + five inner products + scalars",
+                                "kernel": sim.pc_kernel_name(composed=composed)}
         for h in halves.values():
             h["gbs"] = h["bytes"] / (h["ms"] * 1e-3) / 1e9
             h["frac"] = h["gbs"] / HBM_PEAK_GBS
-        kb.update({"gmres_dots_per_iteration": halves["gram_schmidt_dots"]["ms"], "gmres_update_per_iteration": halves["gram_schmidt_update"]["ms"]})
-    dom = max(halves, key=lambda k: halves[k]["ms"])
-    other = [k for k in halves if k != dom]
-    traffic = None
-    if world == 1:
-        traffic = traffic_from_profiles(a.config, dims, brick, halves[dom]["kernel"], composed=(dom == "second" and composed),
-                                        brick_order=a.brick_order)
+        if a.ksp == "gmres":
+            # GMRES(m), classical Gram-Schmidt: per Krylov iteration ONE fused operator application and, averaged over a restart
+            # cycle j = 0 .. m - 1, the inner products (w, v_0 .. v_j) (k_mdot<1..8>: j + 1 basis vectors + w once per pass of eight)
+            # and the update w -= sum h_j v_j with |w|^2 (k_maxpy_norm: j + 1 basis vectors, w read and written)
+            m_r = opts.gmres_restart
+            vec = 8 * bs * lm.n_owned
+            halves = {"operator": dict(halves["first"], ms=kb["fused_pc_plain"], what="fused BCSR SpMV + block ILU(0) apply, no inner product")}
+            halves["operator"]["bytes"] = b_pc - vec      # no dot-product partner
+            halves["gram_schmidt_dots"] = {"ms": sim.bench_kernel(20, 3), "bytes": vec * sum(j + 2 for j in range(m_r)) / m_r,
+                                           "what": "GMRES(%d) inner products (w, v_0..v_j), average over a restart cycle" % m_r, "kernel": "k_mdot<8>"}
+            halves["gram_schmidt_update"] = {"ms": sim.bench_kernel(21, 3), "bytes": vec * sum(j + 3 for j in range(m_r)) / m_r,
+                                             "what": "GMRES(%d) update w -= sum h_j v_j + |w|^2, average over a restart cycle" % m_r, "kernel": "k_maxpy_norm"}
+            for h in halves.values():
+                h["gbs"] = h["bytes"] / (h["ms"] * 1e-3) / 1e9
+                h["frac"] = h["gbs"] / HBM_PEAK_GBS
+            kb.update({"gmres_dots_per_iteration": halves["gram_schmidt_dots"]["ms"], "gmres_update_per_iteration": halves["gram_schmidt_update"]["ms"]})
+        dom = max(halves, key=lambda k: halves[k]["ms"])
+        other = [k for k in halves if k != dom]
+        traffic = None
+        if world == 1:
+            traffic = traffic_from_profiles(a.config, dims, brick, halves[dom]["kernel"], composed=(dom == "second" and composed),
+                                            brick_order=a.brick_order)
 
     if rank == 0:
         ksp_name = {"bcgs": "BiCGStab", "gmres": "GMRES(30)"}.get(a.ksp, a.ksp)
@@ -1037,9 +1053,6 @@ def main():
             "value": a.steps / el, "unit": "Newton steps/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": 1e3 * el / a.steps, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            # Newton iterations of accepted time steps only / their time: what the window costs without the tries
-            # that are thrown away
-            "value_accepted_steps": (acc_n / acc_s) if acc_s > 0 else None,
             # `value` divides by whatever Krylov counts the window's tries happened to take, and one failed try (a thousand-odd
             # iterations, there or not depending on the rounding of an earlier step) moves it by tens of per cent.  The stable
             # pair is (ms_fixed_per_newton_step, ms_per_krylov_iteration) of the least-squares fit over the timed steps;
@@ -1047,9 +1060,6 @@ def main():
             # between rounds and boxes
             "value_normalised": (1.0 / (fixed_s + k_med * iter_s)) if iter_s > 0 else None,
             "value_normalised_at_krylov_iterations": k_med,
-            "accepted_newton_steps": acc_n,
-            "check": check,
-            "device_state_after_timed_region": dev_state,
             "config": {"workload": "%s%s: %dx%dx%d structured eos_%s mesh%s (%d cells), BE time steps %d-%d, %s (cyclic), "
                                    "%s + %s(%dx%dx%d bricks)/%s, rtol 1e-5"
                                    % ((a.config, share) + dims + (eos, (" + 1 MINC level" if minc else "") + (", Corey (0.3, 0.05) k_r" if a.curves == "corey" else ""), n_cells, a.lead,
@@ -1063,40 +1073,48 @@ def main():
                        "timed_newton_steps": [{"time_step": r[0], "dt": r[1], "newton": r[2], "krylov": r[3],
                                                "reason": r[4], "ms": 1e3 * r[6], "accepted": r[7]} for r in timed],
                        "partition": "x".join(str(p) for p in grid.part), "ksp": a.ksp, "pc": a.pc, "ilu_levels": a.ilu_levels,
-                       "brick_order": a.brick_order,
-                       # the reference's default preconditioner is PCASM overlap 1 / ILU(0); this line runs `pc` -- what the
-                       # default would cost on the same systems (committed measurement, not made in this run)
-                       "pc_reference_default": pc_reference_default(a.config, a.pc)},
-            "roofline": {"bound": "hbm", "kernel": "%s (%s; %s)" % (halves[dom]["kernel"], halves[dom]["what"], ("the iteration's %s fused launch" % dom) if dom in ("first", "second") else "per Krylov iteration"),
-                         "dominant_half": dom, "ms_per_krylov_iteration_by_kernel": {k: halves[k]["ms"] for k in halves},
-                         "achieved": halves[dom]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": halves[dom]["frac"],
-                         "traffic": traffic[0] if traffic else None,
-                         "traffic_source": traffic[1] if traffic else None,
-                         "traffic_over_algorithmic": (traffic[0] / halves[dom]["bytes"]) if traffic and traffic[0] else None,
-                         "algorithmic_bytes_per_launch": halves[dom]["bytes"], "ms_per_launch": halves[dom]["ms"],
-                         # what a copy achieves on this box, measured in this run (2 x bytes / time)
-                         "copy_ceiling_gbs": max(copy_gbs["hipMemcpyDtoD"], copy_gbs["copy_kernel"]), "read_ceiling_gbs": copy_gbs["read_kernel"],
-                         "copy_ceiling": copy_gbs,
-                         # the metric's second half, flat: BCSR SpMV achieved GB/s and fraction of HBM peak
-                         "spmv_gbs": achieved, "spmv_frac": achieved / HBM_PEAK_GBS, "spmv_ms_per_launch": ms,
-                         "spmv_algorithmic_bytes_per_launch": b_spmv, "spmv_kernel": "k_spmv<%d> (BCSR SpMV)" % bs},
+                       "brick_order": a.brick_order},
         }
-        for k in other:   # the iteration's other fused launch (GMRES: its other per-iteration kernels)
-            pre = k + ("_half" if k in ("first", "second") else "")
-            out["roofline"].update({"%s_kernel" % pre: "%s (%s)" % (halves[k]["kernel"], halves[k]["what"]), "%s_ms_per_launch" % pre: halves[k]["ms"],
-                                    "%s_algorithmic_bytes_per_launch" % pre: halves[k]["bytes"], "%s_achieved" % pre: halves[k]["gbs"],
-                                    "%s_frac" % pre: halves[k]["frac"]})
-        if "bicgstab_iteration_device_only" in kb:
-            out["config"]["ms_per_krylov_iteration_device_only"] = kb["bicgstab_iteration_device_only"]
-            out["config"]["ms_vector_updates_per_iteration"] = kb["bicgstab_vector_updates"]
-            out["config"]["ms_fused_per_iteration"] = sum(h["ms"] for h in halves.values())
-            # the whole iteration against the roofline: both fused launches' algorithmic bytes + the X / R / P update's
-            # eight vectors (+ S = R - alpha V's three where it is a launch of its own) over the iteration's device time
-            b_iter = sum(h["bytes"] for h in halves.values()) + (8 + (0 if composed else 3)) * 8 * bs * lm.n_owned
-            out["roofline"]["iteration_algorithmic_bytes"] = b_iter
-            out["roofline"]["iteration_frac"] = b_iter / (kb["bicgstab_iteration_device_only"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-            out["config"]["bicgstab_form"] = os.environ.get("WAI_BCGS", "fused") + " (WAI_BCGS=petsc | merged | fused)"
+        if a.full:
+            out.update({
+                # Newton iterations of accepted time steps only / their time: what the window costs without the tries
+                # that are thrown away
+                "value_accepted_steps": (acc_n / acc_s) if acc_s > 0 else None,
+                "accepted_newton_steps": acc_n,
+                "check": check,
+                "device_state_after_timed_region": dev_state})
+            # the reference's default preconditioner is PCASM overlap 1 / ILU(0); this line runs `pc` -- what the
+            # default would cost on the same systems (committed measurement, not made in this run)
+            out["config"]["pc_reference_default"] = pc_reference_default(a.config, a.pc)
+            out["roofline"] = {"bound": "hbm", "kernel": "%s (%s; %s)" % (halves[dom]["kernel"], halves[dom]["what"], ("the iteration's %s fused launch" % dom) if dom in ("first", "second") else "per Krylov iteration"),
+                             "dominant_half": dom, "ms_per_krylov_iteration_by_kernel": {k: halves[k]["ms"] for k in halves},
+                             "achieved": halves[dom]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": halves[dom]["frac"],
+                             "traffic": traffic[0] if traffic else None,
+                             "traffic_source": traffic[1] if traffic else None,
+                             "traffic_over_algorithmic": (traffic[0] / halves[dom]["bytes"]) if traffic and traffic[0] else None,
+                             "algorithmic_bytes_per_launch": halves[dom]["bytes"], "ms_per_launch": halves[dom]["ms"],
+                             # what a copy achieves on this box, measured in this run (2 x bytes / time)
+                             "copy_ceiling_gbs": max(copy_gbs["hipMemcpyDtoD"], copy_gbs["copy_kernel"]), "read_ceiling_gbs": copy_gbs["read_kernel"],
+                             "copy_ceiling": copy_gbs,
+                             # the metric's second half, flat: BCSR SpMV achieved GB/s and fraction of HBM peak
+                             "spmv_gbs": achieved, "spmv_frac": achieved / HBM_PEAK_GBS, "spmv_ms_per_launch": ms,
+                             "spmv_algorithmic_bytes_per_launch": b_spmv, "spmv_kernel": "k_spmv<%d> (BCSR SpMV)" % bs}
+            for k in other:   # the iteration's other fused launch (GMRES: its other per-iteration kernels)
+                pre = k + ("_half" if k in ("first", "second") else "")
+                out["roofline"].update({"%s_kernel" % pre: "%s (%s)" % (halves[k]["kernel"], halves[k]["what"]), "%s_ms_per_launch" % pre: halves[k]["ms"],
+                                        "%s_algorithmic_bytes_per_launch" % pre: halves[k]["bytes"], "%s_achieved" % pre: halves[k]["gbs"],
+                                        "%s_frac" % pre: halves[k]["frac"]})
+            if "bicgstab_iteration_device_only" in kb:
+                out["config"]["ms_per_krylov_iteration_device_only"] = kb["bicgstab_iteration_device_only"]
+                out["config"]["ms_vector_updates_per_iteration"] = kb["bicgstab_vector_updates"]
+                out["config"]["ms_fused_per_iteration"] = sum(h["ms"] for h in halves.values())
+                # the whole iteration against the roofline: both fused launches' algorithmic bytes + the X / R / P update's
+                # eight vectors (+ S = R - alpha V's three where it is a launch of its own) over the iteration's device time
+                b_iter = sum(h["bytes"] for h in halves.values()) + (8 + (0 if composed else 3)) * 8 * bs * lm.n_owned
+                out["roofline"]["iteration_algorithmic_bytes"] = b_iter
+                out["roofline"]["iteration_frac"] = b_iter / (kb["bicgstab_iteration_device_only"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+                out["config"]["bicgstab_form"] = os.environ.get("WAI_BCGS", "fused") + " (WAI_BCGS=petsc | merged | fused)"
         if comm:
             out["comm"] = comm
         if a.rank_share > 1:
@@ -1104,7 +1122,7 @@ def main():
                                  "ms_per_krylov_iteration": 1e3 * iter_s,
                                  "ms_per_krylov_iteration_device_only": kb.get("bicgstab_iteration_device_only"),
                                  "launches_per_krylov_iteration": launches}
-        if not a.no_cpu and world == 1:   # the CPU baseline is a single-GPU-run item
+        if a.full and not a.no_cpu and world == 1:   # the CPU baseline is a single-GPU-run item
             try:
                 cb = cpu_baseline(lm, eos, start["y"].cpu().numpy(), start["regions"], start["dt"],
                                   kits / max(a.steps, 1), gpu_state=gpu_state, minc=minc, brick=brick, curves=CURVES[a.curves],

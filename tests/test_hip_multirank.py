@@ -572,7 +572,7 @@ def test_bench_as_the_driver_launches_it(world, dims, brick, part):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "2", "--warmup", "1", "--lead", "1", "--window", "2", "--dims"] + [str(v) for v in dims] + \
-          ["--brick"] + [str(v) for v in brick] + ["--spmv-reps", "3", "--no-cpu"]
+          ["--brick"] + [str(v) for v in brick] + ["--spmv-reps", "3", "--no-cpu", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

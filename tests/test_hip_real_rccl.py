@@ -112,7 +112,7 @@ def test_bench_on_real_rccl(world):
         env.update(WAI_RCCL_LIB=LOOPBACK, WAI_BENCH_LOOPBACK="1", WAI_HALO_OVERLAP="1" if world == 2 else "0")
     dims = (64, 64, 32) if world < 8 else (64, 64, 64)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--lead", "1",
-           "--window", "2", "--dims"] + [str(v) for v in dims] + ["--spmv-reps", "5", "--no-cpu"]
+           "--window", "2", "--dims"] + [str(v) for v in dims] + ["--spmv-reps", "5", "--no-cpu", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

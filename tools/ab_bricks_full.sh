@@ -2,7 +2,7 @@
 # steps at 216^3); the transient is chaotic in its step failures, so repeat shapes to see the spread
 shapes=("8 8 8" "16 16 2" "20 12 2" "18 12 2" "12 18 2" "16 16 1" "32 16 1" "24 20 1" "12 12 3" "16 8 4" "8 8 4" "16 16 3")
 for b in "${shapes[@]}"; do
-  python bench.py --brick $b --steps 20 --warmup 10 --no-cpu 2>&1 | grep -E "^\{" | python -c "
+  python bench.py --brick $b --steps 20 --warmup 10 --no-cpu --full 2>&1 | grep -E "^\{" | python -c "
 import sys, json
 for line in sys.stdin:
     d = json.loads(line)
