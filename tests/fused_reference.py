@@ -6,7 +6,7 @@ launches (tests/test_hip_fused_operator.py) -- written from the definitions, not
   ILU(0) sub-solves computes), couplings that leave a subdomain dropped; pivot blocks inverted by Gauss-Jordan in
   long double (numpy.linalg has no long-double loops);
 - inner products in long double together with sum |a_i b_i| for the error bar;
-- the BiCGStab scalars the fused launches derive (derive_scalars, derive_merged, derive_rotate of kernels_linalg.hip),
+- the BiCGStab scalars the fused launches derive (derive_scalars, derive_merged, derive_rotate of reductions.hip.h),
   restated as formulas in double.
 
 Everything runs in numpy.longdouble: 80-bit extended precision on x86-64 hosts, so that the reference carries no fp64
@@ -179,7 +179,7 @@ class BlockILU0:
         return self.solve(spmv(self.rowptr, self.colidx, val, self.bs, x))
 
 
-# ---- the BiCGStab scalars of the in-launch finalisation (kernels_linalg.hip: derive_merged, derive_rotate, derive_scalars),
+# ---- the BiCGStab scalars of the in-launch finalisation (reductions.hip.h: derive_merged, derive_rotate, derive_scalars),
 # restated in double.  The breakdown codes are left to the kernels except where noted.
 def derive_merged(s):
     st, tt, ss, srp, trp = s[S_D1], s[S_D2], s[S_DP2], s[S_RHONEW], s[S_W2]

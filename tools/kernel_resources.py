@@ -2,7 +2,7 @@
 """Register / LDS / scratch table of the HIP kernels of one source file, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks (no GPU needed).
 
-    python tools/kernel_resources.py waiwera_amd/csrc/kernels_linalg.hip [name-filter] [-- extra hipcc flags]
+    python tools/kernel_resources.py waiwera_amd/csrc/kernels_fused.hip [name-filter] [-- extra hipcc flags]
 """
 import re
 import subprocess

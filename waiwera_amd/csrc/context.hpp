@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/waiwera_hip.h"
 #include "physics.hip.h"
@@ -10,7 +11,7 @@
 namespace wai {
 
 // Element (s, r, k) of block row i in a block-ELL value array of n block rows (layout rationale:
-// kernels_linalg.hip, "Matrix entry addressing").
+// linalg_device.hip.h, "Matrix entry addressing").
 // The stride between the element planes of block sizes >= 3 is not n but n rounded up to 512 doubles (4 KB), and never a
 // multiple of 2 MB: how a slot's nine planes fall onto the memory channels depends on it.  MEASURED (C4's SpMV alone,
 // tools/micro/spmv3_stride.hip, nine strides x three fresh allocations on one box): stride n = 5 029 280 doubles
@@ -259,6 +260,26 @@ struct IluSchedule {
   std::vector<int> lev_f_ptr, lev_b_ptr;   // host: row ranges of each level in ord_f / ord_b
   bool built = false;
 };
+// threads of a brick kernel's workgroup: one per row of the largest subdomain, whole waves
+inline int pc_threads(const IluSchedule& s) { return ((s.max_rows + 63) / 64) * 64; }
+
+// A run-time block size or flag turned into a template argument, once: f(std::integral_constant<int, BS>{}) for bs 1 .. 4
+// (else -1, f not called) and f(std::true_type{} / std::false_type{}).  Inside f: `constexpr int BS = decltype(bs)::value;`
+template <class F>
+int with_bs(int bs, F&& f) {
+  switch (bs) {
+    case 1: f(std::integral_constant<int, 1>{}); return 0;
+    case 2: f(std::integral_constant<int, 2>{}); return 0;
+    case 3: f(std::integral_constant<int, 3>{}); return 0;
+    case 4: f(std::integral_constant<int, 4>{}); return 0;
+    default: return -1;
+  }
+}
+template <class F>
+void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 // PCASM (restricted additive Schwarz) system: every subdomain's overlapped row set is stored as
 // its own block of an extended matrix E (couplings leaving the set dropped), so the block-Jacobi
@@ -318,7 +339,7 @@ struct TracerForm {
   double dt, ratio, decay, activation, diffusion;
 };
 
-// Finalisation of a producer kernel's partial sums inside its own launch (fin_block, kernels_linalg.hip): one
+// Finalisation of a producer kernel's partial sums inside its own launch (fin_block, reductions.hip.h): one
 // extra workgroup waits for the partials of `nslots` consecutive reduction slots, sums them into the device
 // scalars -- in the order k_finalize sums them --, derives the BiCGStab scalars of `phase` and, when asked,
 // posts the scalars to the pinned host mirror.  Replaces a one-block k_finalize launch (and the 128-byte
@@ -442,7 +463,7 @@ struct wai_ctx {
   int dbg = 0;                  // timing probes (wai_bench_kernel)
 };
 
-// ---- kernel launchers (kernels_assembly.hip / kernels_linalg.hip) --------------------------
+// ---- kernel launchers (kernels_assembly.hip / kernels_matrix.hip, kernels_factor.hip, kernels_fused.hip) --------------------------
 namespace wai {
 int launch_eos(wai_ctx* c, const double* y, int first, int count, bool perturbed);
 int launch_residual(wai_ctx* c, double dt, const double* lhs_old, double* f, double* lhs_out,
@@ -513,7 +534,7 @@ int vec_waxpy(wai_ctx* c, double* w, double alpha, const double* x, const double
 int bcgs_scalars(wai_ctx* c, int phase, bool post = false);
 int bcgs_update_xrp_derive(wai_ctx* c);
 int bcgs_post(wai_ctx* c, int seq);
-void read_env(wai_ctx* c);   // the launch switches above (kernels_linalg.hip)
+void read_env(wai_ctx* c);   // the launch switches above (kernels_fused.hip)
 int test_drop_partials(wai_ctx* c, int n);   // fault injection (tests): workgroup 0 loses its next n partial sums
 int bcgs_update_p(wai_ctx* c);
 int bcgs_update_s(wai_ctx* c);

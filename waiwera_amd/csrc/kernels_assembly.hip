@@ -410,7 +410,7 @@ __global__ __launch_bounds__(TPB) void k_jacobian(MeshView m, const double* __re
 
   // diagonal block: own state perturbed in component k
   // block-ELL planes: element (r, k) of the block in slot q of block-row c is val[ell_ix(np, n_owned, q, r, k, c)]
-  // (context.hpp; kernels_linalg.hip, "Matrix entry addressing")
+  // (context.hpp; linalg_device.hip.h, "Matrix entry addressing")
   const size_t nrow = m.n_owned;
   const int dq = m.diag_blk[c];
 #pragma unroll
@@ -581,7 +581,7 @@ __global__ __launch_bounds__(ParkT<KIND>::threads, (EosT<KIND>::np <= 2 ? 2 : 1)
 
   // diagonal block: own state perturbed in component k
   // block-ELL planes: element (r, k) of the block in slot q of block-row c is val[ell_ix(np, n_owned, q, r, k, c)]
-  // (context.hpp; kernels_linalg.hip, "Matrix entry addressing")
+  // (context.hpp; linalg_device.hip.h, "Matrix entry addressing")
   const size_t nrow = m.n_owned;
   const int dq = m.diag_blk[c];
 #pragma unroll

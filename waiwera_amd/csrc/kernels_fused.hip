@@ -1,0 +1,330 @@
+// Every kernel that stores or finalises a partial sum -- the five fused preconditioned-operator kernels and the K9 vector
+// kernels -- with their launchers, the run-time switches and the tests' fault-injection hook (reductions.hip.h says why
+// they share one translation unit).
+#include "pc_generic.hip.h"
+#include "pc_wide.hip.h"
+#include "pc_park.hip.h"
+#include "pc_rows.hip.h"
+#include "pc_wave.hip.h"
+#include "krylov_vec.hip.h"
+
+namespace wai {
+
+// ---- launchers -------------------------------------------------------------------------------
+static inline int vgrid(int n) {
+  int g = (n + TPB - 1) / TPB;
+  return g > 1024 ? 1024 : (g < 1 ? 1 : g);
+}
+
+// the fused launches' run-time switches: read once per solve / set-up / probe (tests switch them between solves of one process)
+void read_env(wai_ctx* c) {
+  c->env.fin_separate = getenv("WAI_FIN_SEPARATE") != nullptr;
+  c->env.no_col16 = getenv("WAI_NO_COL16") != nullptr;
+  c->env.scalar_kernels = getenv("WAI_BCGS_SCALAR_KERNELS") != nullptr;   // several ranks: the one-thread kernels behind the all-reduces (rounds 3-4)
+}
+
+// which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc.
+// Kinds 1 .. 3 can form their input on the fly (in - alpha in2: launch_pc_on's in2)
+static int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s) {
+  if (s.wide) return 4;   // rows of 9 .. 16 blocks: no other fused kernel reads their descriptor
+  if (c->dbg) return 0;
+  if (s.wave_kernel && J.bs >= 3) return 3;
+  if (s.rows_kernel) return 2;
+  if (J.bs == 2 && s.park && s.diag_only && s.scaled && s.fast3 && pc_threads(s) <= 512) return 1;
+  return 0;
+}
+static bool kind_composes(int kind) { return kind >= 1 && kind <= 3; }
+bool pc_axpy_capable(const wai_ctx* c) { return !c->ilu.big && kind_composes(pc_kernel_kind(c, c->J, c->ilu)); }
+bool pc_axpy_default(const wai_ctx* c) {
+  if (c->ilu.big) return false;
+  const int kind = pc_kernel_kind(c, c->J, c->ilu);
+  return (kind == 1 && c->ilu.col16 && !c->env.no_col16) || kind == 3;   // k_pc_park on col16, k_pc_wave: measured faster end to end
+}
+
+template <int BS>
+static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool spmv, const double* in, double* z,
+                         int dot_mode, const double* aux, const int* list, int nrun, const Fin* finp, const double* in2) {
+  if (!list) { nrun = s.nsub; list = s.sub_order; }   // all subdomains: in the schedule's launch order, if it has one
+  const bool with_fin = finp && dot_mode != 0;
+  Fin fin;
+  if (finp && dot_mode != 0) { fin = *finp; fin.count = nrun; fin.nb = s.nsub; fin.nf = fin_slices(s.nsub); }   // all subdomains' partials are summed
+  c->ks.n_launch++;
+  const int grid = ((nrun + 7) / 8) * 8 + (with_fin ? fin.nf : 0), T = pc_threads(s);   // + the finalisers (fin_block)
+  const size_t lds = ((size_t)T * BS + 80) * sizeof(double);
+  // the (SPMV, AX) pairs the composing kernels are built for: (true, true), (true, false), (false, false)
+  auto sp_ax = [&](auto&& go) {
+    if (spmv) with_flag(in2 != nullptr, [&](auto ax) { go(std::true_type{}, ax); });
+    else go(std::false_type{}, std::false_type{});
+  };
+  const int kind = pc_kernel_kind(c, J, s);
+  const double* scal = c->ks.scal;
+  const int* rp = (size_t)J.nnzb * 10 < (size_t)J.n * J.W * 9 ? J.rowptr : nullptr;   // > 10 % padding
+  if (kind == 4) {
+    // rows of 9 .. 16 blocks: parked upper blocks within the 64 KB a workgroup may ask for
+    const size_t room = (size_t)64 * 1024 > lds ? (size_t)64 * 1024 - lds : 0;
+    const int ucap = (int)std::min((size_t)s.max_ublocks_w, room / ((size_t)BS * BS * sizeof(double)));
+    const size_t lds_w = lds + (size_t)ucap * BS * BS * sizeof(double);
+    with_flag(spmv, [&](auto sp) {
+      hipLaunchKernelGGL((k_pc_wide<BS, decltype(sp)::value>), grid, T, lds_w, c->stream, J.n, J.W, nrun, s.sub_ptr, s.sub_nlev,
+                         s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux, c->ks.partials, c->ks.nb_max,
+                         dot_mode, ucap, list, fin);
+    });
+    return;
+  }
+  // one wave per brick of <= 64 block rows (block sizes 3 and 4), four bricks per workgroup
+  if (kind == 3) {
+    if constexpr (BS >= 3) {
+      // one partial sum per WORKGROUP (four bricks) and slot: the face bricks' launch of the overlapped halo exchange
+      // continues the interior bricks' indices, and its finalisers sum both
+      const int ngrp = (nrun + 3) / 4;
+      const int pbase = (list && list == s.sub_bnd) ? (s.n_int + 3) / 4 : 0, nb_w = pbase + ngrp;
+      if (with_fin) { fin.nb = nb_w; fin.nf = fin_slices(nb_w); }
+      c->ks.nb_pc = nb_w;
+      const int gridw = ((ngrp + 7) / 8) * 8 + (with_fin ? fin.nf : 0);
+      const int per = 64 * BS + s.max_ublocks_w * BS * BS;            // doubles per brick: solution + parked upper blocks
+      const size_t lds_w = (size_t)4 * per * sizeof(double);
+      Stagger stagger;
+      stagger.ncu = c->n_cu;
+      stagger.per_cu = std::max(1, (int)((size_t)160 * 1024 / (lds_w + 864)));
+      stagger.ticks = 400;   // ticks of the 100-MHz clock between the cohorts (stagger_start)
+      sp_ax([&](auto sp, auto ax) {
+        hipLaunchKernelGGL((k_pc_wave<BS, decltype(sp)::value, decltype(ax)::value>), gridw, 256, lds_w, c->stream, J.n, J.W, nrun,
+                           s.sub_ptr, s.sub_nlev, s.row_info, s.row_uoffw, J.col, s.fval, s.dinv, in, in2, scal, z, aux, c->ks.partials,
+                           c->ks.nb_max, dot_mode, list, rp, s.sub_split, per, pbase, fin, stagger);
+      });
+      return;
+    }
+  }
+  // one thread per scalar row: block sizes 3 and 4 (and 2 when asked for: WAI_PC_ROWS=1)
+  if (kind == 2) {
+    const int TR = ((s.max_rows * BS + 63) / 64) * 64;
+    const size_t lds_r = ((size_t)s.max_rows * BS + BS + 5 * 16 + 8) * sizeof(double);
+    auto rows = [&](auto nlu) {   // couplings per sweep held in registers: 3 or 4
+      sp_ax([&](auto sp, auto ax) {
+        constexpr int NLU = decltype(nlu)::value;
+        hipLaunchKernelGGL((k_pc_rows<BS, decltype(sp)::value, NLU, NLU, decltype(ax)::value>), grid, TR, lds_r, c->stream, J.n, J.W,
+                           nrun, s.sub_ptr, s.sub_nlev, s.row_info, J.col, s.fval, s.dinv, in, in2, scal, z, aux, c->ks.partials,
+                           c->ks.nb_max, dot_mode, list, rp, s.sub_split, fin);
+      });
+    };
+    if (s.max_nlu <= 3) rows(std::integral_constant<int, 3>{});
+    else rows(std::integral_constant<int, 4>{});
+    return;
+  }
+  if constexpr (BS == 2) {
+    // upper blocks parked in LDS: three resident workgroups per CU
+    if (kind == 1) {
+      const size_t lds_park = lds + (size_t)s.max_ublocks * 4 * sizeof(double);
+      Stagger stagger;
+      stagger.ncu = c->n_cu;
+      stagger.per_cu = std::max(1, std::min(3, (int)((size_t)160 * 1024 / (lds_park + 704))));
+      stagger.ticks = 600;
+      with_flag(s.col16 && !c->env.no_col16, [&](auto c16) {
+        sp_ax([&](auto sp, auto ax) {
+          hipLaunchKernelGGL((k_pc_park<decltype(sp)::value, decltype(ax)::value, decltype(c16)::value>), grid, T, lds_park, c->stream,
+                             J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, s.row_info, s.row_uoff, J.col, s.col16, s.sub_seg, s.fval, s.dinv,
+                             in, in2, scal, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, list, fin, stagger);
+        });
+      });
+      return;
+    }
+  }
+  auto generic = [&](auto di) {   // 0 stored factor, 1 DILU, 2 DILU on rows pre-scaled by the inverted pivots
+    with_flag(spmv, [&](auto sp) {
+      with_flag(s.fast3, [&](auto fast) {
+        hipLaunchKernelGGL((k_pc<BS, decltype(sp)::value, decltype(di)::value, decltype(fast)::value>), grid, T, lds, c->stream,
+                           J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, s.row_info, J.col, J.val, s.fval, s.dinv, in, z, aux,
+                           c->ks.partials, c->ks.nb_max, dot_mode, c->dbg, list, fin);
+      });
+    });
+  };
+  if (s.diag_only && s.scaled) generic(std::integral_constant<int, 2>{});
+  else if (s.diag_only) generic(std::integral_constant<int, 1>{});
+  else generic(std::integral_constant<int, 0>{});
+}
+
+int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z,
+                 int dot_mode, const double* aux, const int* list, int nrun, const Fin* fin, const double* in2) {
+  if (in2 && (!spmv || !kind_composes(pc_kernel_kind(c, M, s)))) { c->err = "composed input asked of a kernel that cannot form it"; return -1; }
+  const Fin* fin_later = nullptr;
+  if (fin && dot_mode != 0 && c->env.fin_separate) { fin_later = fin; fin = nullptr; }
+  c->ks.nb_pc = s.nsub;   // partial sums per slot this application leaves: one per brick (k_pc_wave: per workgroup, set there)
+  if (with_bs(M.bs, [&](auto bs) { launch_pc_bs<decltype(bs)::value>(c, M, s, spmv, in, z, dot_mode, aux, list, nrun, fin, in2); }) != 0)
+    return -1;
+  if (fin_later) {
+    vec_finalize(c, c->ks.nb_pc, fin_later->slot0, fin_later->nslots, fin_later->phase);
+    if (fin_later->seq > 0) bcgs_post(c, fin_later->seq);
+  }
+  return 0;
+}
+int launch_pc(wai_ctx* c, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
+              const int* list, int nrun, const Fin* fin, const double* in2) {
+  return launch_pc_on(c, c->J, c->ilu, spmv, in, z, dot_mode, aux, list, nrun, fin, in2);
+}
+Fin make_fin(wai_ctx* c, int slot0, int nslots, int phase, bool post) {
+  Fin f;   // count / nb: filled in by the launcher
+  f.slot0 = slot0; f.nslots = nslots; f.phase = phase;
+  f.scal = c->ks.scal; f.post = c->ks.d_post; f.part2 = c->ks.partials2;
+  f.seq = post ? ++c->ks.seq : 0;
+  return f;
+}
+
+int vec_finalize(wai_ctx* c, int nb, int slot0, int nslots, int phase) {
+  const int T = nb > 256 ? 1024 : 256;
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_finalize, 1, T, 0, c->stream, c->ks.partials, c->ks.nb_max, nb, slot0, nslots, c->ks.scal, phase);
+  return 0;
+}
+
+int vec_dot(wai_ctx* c, const double* a, const double* b, int n, int slot) {
+  const int g = vgrid(n);
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_dot, g, TPB, 0, c->stream, a, b, n, c->ks.partials, c->ks.nb_max, slot);
+  return vec_finalize(c, g, slot, 1, -1);
+}
+int vec_dots(wai_ctx* c, const double* a1, const double* b1, int slot1, const double* a2, const double* b2,
+             int slot2, int n) {
+  const int g = vgrid(n);
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_dots, g, TPB, 0, c->stream, a1, b1, slot1, a2, b2, slot2, n, c->ks.partials, c->ks.nb_max);
+  c->ks.nb_pc = g;
+  return 0;
+}
+int partials_clear(wai_ctx* c, int slot0, int nslots) {
+  const size_t tot = (size_t)nslots * std::max(c->ks.nb_max, (int)FIN_MAXF);   // both arrays: the slices' sums too
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_partials_clear, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, c->ks.partials, c->ks.partials2, c->ks.nb_max, slot0, nslots);
+  return 0;
+}
+int vec_copy(wai_ctx* c, double* dst, const double* src, size_t n) {
+  c->ks.n_copy++;
+  return hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream) == hipSuccess ? 0 : -1;
+}
+int vec_zero(wai_ctx* c, double* dst, size_t n) {
+  return hipMemsetAsync(dst, 0, n * sizeof(double), c->stream) == hipSuccess ? 0 : -1;
+}
+int vec_waxpy(wai_ctx* c, double* w, double alpha, const double* x, const double* y, int n) {
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_waxpy, vgrid(n), TPB, 0, c->stream, w, alpha, x, y, n);
+  return 0;
+}
+int bcgs_scalars(wai_ctx* c, int phase, bool post) {
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_bcgs_scalars, 1, 64, 0, c->stream, c->ks.scal, phase, c->ks.d_post, post ? ++c->ks.seq : 0);
+  return 0;
+}
+int test_drop_partials(wai_ctx* c, int n) {
+  return hipMemcpyToSymbolAsync(HIP_SYMBOL(g_drop_partials), &n, sizeof(int), 0, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+         hipStreamSynchronize(c->stream) == hipSuccess ? 0 : -1;
+}
+int bcgs_post(wai_ctx* c, int seq) {   // the device scalars as they stand, under a sequence number already handed out
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_bcgs_scalars, 1, 64, 0, c->stream, c->ks.scal, -1, c->ks.d_post, seq);
+  return 0;
+}
+
+int bcgs_update_p(wai_ctx* c) {
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_bcgs_p, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.P, c->ks.R, c->ks.V, c->ks.n, c->ks.scal);
+  return 0;
+}
+int bcgs_update_s(wai_ctx* c) {
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_bcgs_s, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.S, c->ks.R, c->ks.V, c->ks.n, c->ks.scal);
+  return 0;
+}
+int bcgs_update_xr(wai_ctx* c, bool dots, int fin_phase, bool post) {
+  const int g = vgrid(c->ks.n);
+  Fin fin;
+  if (dots && fin_phase >= -1) { fin = make_fin(c, S_DP2, 2, fin_phase, post); fin.count = g; fin.nb = g; fin.nf = fin_slices(g); }
+  c->ks.n_launch++;
+  if (dots && fin.count > 0 && c->env.fin_separate) {
+    Fin none;
+    hipLaunchKernelGGL(k_bcgs_xr<true>, g, TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.S, c->ks.T,
+                       c->ks.RP, c->ks.n, c->ks.scal, c->ks.partials, c->ks.nb_max, none);
+    c->ks.nblocks = g;
+    vec_finalize(c, g, S_DP2, 2, fin_phase);
+    if (fin.seq > 0) bcgs_post(c, fin.seq);
+    return 0;
+  }
+  if (dots)
+    hipLaunchKernelGGL(k_bcgs_xr<true>, g + (fin.count > 0 ? fin.nf : 0), TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.S, c->ks.T,
+                       c->ks.RP, c->ks.n, c->ks.scal, c->ks.partials, c->ks.nb_max, fin);
+  else
+    hipLaunchKernelGGL(k_bcgs_xr<false>, g, TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.S, c->ks.T,
+                       c->ks.RP, c->ks.n, c->ks.scal, c->ks.partials, c->ks.nb_max, fin);
+  c->ks.nblocks = g;
+  return 0;
+}
+int bcgs_update_xrp(wai_ctx* c) {
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_bcgs_xrp<false>, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.V, c->ks.T, c->ks.n,
+                     c->ks.scal, nullptr, nullptr, 0);
+  return 0;
+}
+// the same launch deriving omega, (R,R), rho, beta from the all-reduced sums itself and posting the norm (several ranks)
+int bcgs_update_xrp_derive(wai_ctx* c) {
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_bcgs_xrp<true>, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.V, c->ks.T, c->ks.n,
+                     c->ks.scal, c->ks.started, c->ks.d_post, ++c->ks.seq);
+  return 0;
+}
+int gmres_mdot(wai_ctx* c, const double* w, int k) {
+  const int g = vgrid(c->ks.n);
+  for (int j0 = 0; j0 < k; j0 += 8) {
+    const int cnt = (k - j0) < 8 ? (k - j0) : 8;
+#define MD(CNT) hipLaunchKernelGGL(k_mdot<CNT>, g, TPB, 0, c->stream, w, c->ks.basis, (size_t)c->ks.nl, j0, c->ks.n, c->ks.partials, c->ks.nb_max)
+    c->ks.n_launch++;
+    switch (cnt) { case 1: MD(1); break; case 2: MD(2); break; case 3: MD(3); break; case 4: MD(4); break;
+                   case 5: MD(5); break; case 6: MD(6); break; case 7: MD(7); break; default: MD(8); break; }
+#undef MD
+    vec_finalize(c, g, S_H + j0, cnt, -1);   // k_finalize sums any number of slots (five at a time) in one launch
+  }
+  return 0;
+}
+int gmres_maxpy_norm(wai_ctx* c, double* w, int k) {
+  const int g = vgrid(c->ks.n);
+  hipLaunchKernelGGL(k_maxpy_norm, g, TPB, 0, c->stream, w, c->ks.basis, (size_t)c->ks.nl, k, c->ks.n,
+                     c->ks.scal, c->ks.partials, c->ks.nb_max);
+  return vec_finalize(c, g, S_W2, 1, -1);
+}
+int gmres_scale_to(wai_ctx* c, double* dst, const double* src, int slot_norm2, int n) {
+  hipLaunchKernelGGL(k_scale_to, vgrid(n), TPB, 0, c->stream, dst, src, c->ks.scal, slot_norm2, n);
+  return 0;
+}
+int gmres_update_x(wai_ctx* c, double* x, const double* ycoef_host, int k) {
+  double* dcoef = c->ks.scal + 64;  // coefficients travel through the tail of the scalar buffer
+  hipMemcpyAsync(dcoef, ycoef_host, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
+  hipLaunchKernelGGL(k_update_x, vgrid(c->ks.n), TPB, 0, c->stream, x, c->ks.basis, (size_t)c->ks.nl, k,
+                     c->ks.n, dcoef);
+  return 0;
+}
+int pack_halo(wai_ctx* c, const double* vec, int dof, hipStream_t stream) {
+  const int n = c->send_total;
+  if (n <= 0) return 0;
+  c->ks.n_launch++;
+  hipLaunchKernelGGL(k_pack, (n * dof + TPB - 1) / TPB, TPB, 0, stream ? stream : c->stream, vec, c->d_send_idx, n,
+                     dof, c->d_sendbuf);
+  return 0;
+}
+int pack_halo_axpy(wai_ctx* c, const double* a, const double* b, int dof, hipStream_t stream) {
+  const int n = c->send_total;
+  if (n <= 0) return 0;
+  c->ks.n_launch++;
+  with_flag(c->ks.alpha_pending, [&](auto derive) {
+    hipLaunchKernelGGL(k_pack_axpy<decltype(derive)::value>, (n * dof + TPB - 1) / TPB, TPB, 0, stream ? stream : c->stream, a, b,
+                       c->ks.scal, c->d_send_idx, n, dof, c->d_sendbuf);
+  });
+  c->ks.alpha_pending = false;
+  return 0;
+}
+int unpack_halo(wai_ctx* c, double* vec, int dof, hipStream_t stream) {
+  // halo cells are contiguous after the owned cells and the receive buffer is in halo order
+  const size_t n = (size_t)c->mesh.n_halo * dof;
+  if (n == 0) return 0;
+  c->ks.n_copy++;
+  return hipMemcpyAsync(vec + (size_t)c->mesh.n_owned * dof, c->d_recvbuf, n * sizeof(double),
+                        hipMemcpyDeviceToDevice, stream ? stream : c->stream) == hipSuccess ? 0 : -1;
+}
+
+}  // namespace wai

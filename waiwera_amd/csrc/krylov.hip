@@ -382,7 +382,7 @@ int ksp_bcgs(wai_ctx* c, const double* b, double* x, int* its, int* reason, doub
 // KSPGMRES [PETSc]: restarted, left preconditioning, classical Gram-Schmidt without refinement
 int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
   Krylov& k = c->ks;
-  partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, kernels_linalg.hip)
+  partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
   const int n = k.n, m = std::min(std::max(c->opts.gmres_restart, 1), k.basis_m);
   const size_t ld = (size_t)k.nl;
   const double rtol = c->opts.ksp_rtol, atol = c->opts.ksp_atol;
@@ -498,7 +498,7 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
 // vector or an error approximation.
 int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
   Krylov& k = c->ks;
-  partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, kernels_linalg.hip)
+  partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
   constexpr int AUG = 2;
   // restart = Krylov directions + AUG error approximations: at least one direction (wai_set_opts / wai_ctx_create
   // size the basis for restart >= AUG + 1 and refuse a restart beyond the basis cap)
@@ -634,7 +634,7 @@ int host_dots(wai_ctx* c, const double* a1, const double* b1, const double* a2, 
 int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
   constexpr int L = 2;
   Krylov& k = c->ks;
-  partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, kernels_linalg.hip)
+  partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
   const int n = k.n;
   const size_t nl = (size_t)k.nl;
   if (!k.bl) {

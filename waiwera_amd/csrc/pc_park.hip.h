@@ -1,0 +1,214 @@
+// The fused kernel for 2 x 2 blocks with the upper blocks parked in LDS, k_pc_park.
+#pragma once
+#include "reductions.hip.h"
+
+namespace wai {
+
+// ---- K6+K8 fused, upper blocks parked in LDS (bs = 2, pivot-scaled DILU, <= 3+3 couplings) -----
+// k_pc holds a row's three lower and three upper blocks in registers through both sweeps (~100
+// VGPRs: two workgroups per CU), although the upper blocks are only needed once the forward sweep
+// is over and the lower ones are dead by then.  Here the upper blocks go to LDS as the row is
+// loaded (compactly: a brick has ~2.6 in-brick upper couplings per row, 43 KB for 8x8x8) and come
+// back into the lower blocks' registers for the backward sweep.  ~75 VGPRs, 6 waves per SIMD:
+// three resident workgroups per CU (3 x 51 KB of the 160 KB LDS), so one more brick's loads are in
+// flight to cover the latency-bound sweeps of the others.
+// MEASURED (216^3, MI355X, same box): 0.604 ms against k_pc's 0.709 ms; 68 VGPRs, no spills.
+// MEASURED AND REMOVED (round 4): wave-staged sweeps.  With a brick's rows in dependency-level order a wave's 64 rows
+// span a contiguous range of levels and need no barrier among themselves (the LDS executes a wave's instructions in
+// order), so the workgroup barrier can shrink to the hand-over from one wave to the next -- 8 per sweep instead of 32.
+// Same bits, and SLOWER on every size: fused launch 0.6175 against 0.5904 ms at 216^3, 0.0960 / 0.0892 at 108^3,
+// 0.0839 / 0.0766 at 100^3 (same box, profiles/bench_r4_wavestage_ab.log): a level's cost is its LDS round trip and FMA
+// chain, not the barrier, and the per-level barriers let the two waves that share a level run it side by side.
+// C16 (round 5): the column indices come as brick-local 16-bit (segment, offset) pairs (IluSchedule::col16, sub_seg), a
+// row's eight together: ONE 16-byte load per row instead of seven 4-byte loads from seven planes (16 instead of 28 bytes,
+// and six vector-memory instructions fewer of a row's ~28); the eight segment bases of the brick are wave-uniform (scalar
+// loads) and the lane's pick among them a chain of selects.  Same columns, same order, same bits.
+// (First form, one 16-bit plane per slot: 2 bytes less per block but the same seven loads -- MEASURED no faster: fused
+// launch 0.0845 -> 0.0859 ms at 108^3, 0.584 -> 0.581 at 216^3, profiles/col16_planes_ab_r5.log.)
+// MEASURED AND NOT KEPT (round 6, profiles/persist_ab_r6_*.log; the variant was never committed -- this note is its record: the body
+// below inside `for (bpos = blockIdx.x; bpos < padded count; bpos += G)`, G = gridDim.x - finalisers, a barrier at the loop's end,
+// grid = 3 x CUs rounded to a multiple of 8): the launch as 768 PERSISTENT
+// workgroups (3 per CU), each walking the brick positions w, w + 768, ... of its XCD's eighth in a loop instead of giving its
+// slot back after one brick (the verdict's "no re-dispatch gap, bricks handed out by a cursor").  Same bits.  Two findings:
+// (i) the loop form alone costs registers -- 80 VGPRs and 20-36 bytes of scratch where the straight-line body has 73 and
+// none (loop-carried kernel arguments: 41-53 SGPR spills) -- 0.545 -> 0.627 ms first launch, 0.674 -> 0.769 composed at 216^3;
+// (ii) on that same code the persistent grid is SLOWER again than one workgroup per brick: 0.685 / 0.836 ms at 216^3, equal at
+// 108^3 and 100^3.  Re-dispatch is not a gap worth closing (a fresh workgroup is in its slot within the time a brick's
+// epilogue drains), and the dispatcher's hand-out -- whichever slot frees first -- decorrelates the bricks of a CU, which a
+// fixed stride never does: workgroups that started together stay in step, all loading, then all sweeping (the effect the
+// start-up cohorts were introduced against in round 4, now for the whole launch).
+// (Staging the brick's own operand segment in LDS, the in-brick columns read from there, was slower at C3, the 108^3
+// share and C2 -- two more barriers per brick replace the gathers' latency: profiles/stage_ab_r6_*.log.)
+template <bool SPMV, bool AX, bool C16>
+__global__ __launch_bounds__(512, 6) void k_pc_park(
+    int n, int W, int nsub, const int* __restrict__ sub_ptr, const int* __restrict__ sub_nlev,
+    const int* __restrict__ row_info, const int* __restrict__ row_uoff, const int* __restrict__ col,
+    const unsigned short* __restrict__ col16, const int* __restrict__ sub_seg,
+    const double* __restrict__ sval, const double* __restrict__ dinv, const double* __restrict__ in,
+    const double* __restrict__ in2, const double* __restrict__ scal,
+    double* __restrict__ z, const double* __restrict__ aux, double* partials, int nb_max, int dot,
+    const int* __restrict__ sub_list, Fin fin, Stagger stagger) {
+  constexpr int BS = 2, BB = 4, MLU = 3;
+  extern __shared__ __attribute__((aligned(16))) double lds[];  // [T*2] solution, [80] reduction scratch, then parked U blocks
+  // nsub subdomains to run: all of them, or (sub_list) the listed ones -- the bricks that touch no
+  // partition ghost while the halo exchange is in flight, the others after it
+  if (fin_block(fin, partials, nb_max)) return;
+  int s = xcd_remap(blockIdx.x, nsub);
+  if (s >= nsub) return;
+  if (sub_list) s = sub_list[s];
+  const int lo = sub_ptr[s], R = sub_ptr[s + 1] - lo;
+  const int nl = sub_nlev[s];
+  const int nlf = nl & 0xffff, nlb = nl >> 16;
+  const int tid = threadIdx.x, i = lo + tid;
+  const bool active = tid < R;
+  const double nalpha = AX ? -scal[S_ALPHA] : 0.0;   // input = in - alpha in2 (uniform: a scalar load)
+  stagger_start(stagger);
+  double* ys = lds;
+  double* upark = lds + (size_t)blockDim.x * BS + 80;
+  double Lf[MLU][BB];
+  int Lc[MLU], Uc[MLU], lf = -1, lb = -1, uo = 0, nU = 0;
+  double xin[BS] = {0.0, 0.0}, avp[BS] = {0.0, 0.0};
+#pragma unroll
+  for (int p = 0; p < MLU; p++) {
+    Lc[p] = tid; Uc[p] = tid;
+#pragma unroll
+    for (int e = 0; e < BB; e++) Lf[p][e] = 0.0;
+  }
+  int lfirst = 0, dslot = 0, ulast = 0;
+  int cgs[WMAX];
+  if (active) {
+    unpack_info(row_info[i], lfirst, dslot, ulast, lf, lb);
+    uo = row_uoff[i];
+    nU = ulast - dslot - 1;
+    // (MEASURED AND REMOVED, round 6: slot 0's block -- which needs nothing but the row number -- requested here, together with
+    // the descriptors and the index record, one dependent round trip less per brick: 77 VGPRs, no scratch, same bits, and
+    // 3 % SLOWER at 108^3 and 100^3 (first launch 0.0840 -> 0.0868, 0.0741 -> 0.0764 ms), no better at 216^3:
+    // profiles/hoist_ab_r6_*.log.  Like every earlier form that put more of a brick's loads in flight at once.)
+    // all column indices first: one round trip instead of one per slot (MEASURED at 216^3, same box:
+    // 0.6196 -> 0.6018 ms).  A branch-free 7-slot loop, which lets the compiler keep every slot's loads
+    // in flight, needs more than the 80 registers of 6 waves per SIMD: 188 bytes of scratch, 0.965 ms;
+    // fetching the next slot's block while the current one is used (80 registers, no scratch): 0.626 against 0.614
+    if constexpr (C16) {
+      const int* sg = sub_seg + (size_t)s * 8;     // wave-uniform
+      const int g0 = sg[0], g1 = sg[1], g2 = sg[2], g3 = sg[3], g4 = sg[4], g5 = sg[5], g6 = sg[6], g7 = sg[7];
+      typedef unsigned wai_u4v __attribute__((ext_vector_type(4)));
+      const wai_u4v pk = __builtin_nontemporal_load(reinterpret_cast<const wai_u4v*>(col16) + i);   // the row's eight 16-bit entries
+      const unsigned pw[4] = {pk.x, pk.y, pk.z, pk.w};
+      unsigned cu[WMAX];
+#pragma unroll
+      for (int q = 0; q < WMAX; q++) cu[q] = (pw[q >> 1] >> (16 * (q & 1))) & 0xffffu;
+#pragma unroll
+      for (int q = 0; q < WMAX; q++) {
+        const unsigned code = cu[q] >> 13;
+        int b = g0;
+        b = code == 1 ? g1 : b; b = code == 2 ? g2 : b; b = code == 3 ? g3 : b; b = code == 4 ? g4 : b;
+        b = code == 5 ? g5 : b; b = code == 6 ? g6 : b; b = code == 7 ? g7 : b;
+        cgs[q] = q < W ? b + (int)(cu[q] & 8191u) : i;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < WMAX; q++) {
+        cgs[q] = i;
+        if (q < W) cgs[q] = load_col(col, (size_t)q * n + i);
+      }
+    }
+  }
+  double acc[BS] = {0.0, 0.0};
+  if (active) {
+#pragma unroll
+    for (int q = 0; q < WMAX; q++) {
+      if (q < W) {
+        const int cg = cgs[q];
+        double blk[BB];
+        load_block<BS>(sval, n, q, i, blk);
+        if constexpr (SPMV) {
+          double xv[BS];
+          load_xs<BS, AX>(in, in2, nalpha, cg, xv);
+          acc[0] += blk[0] * xv[0] + blk[1] * xv[1];
+          acc[1] += blk[2] * xv[0] + blk[3] * xv[1];
+        }
+        const bool isl = (q >= lfirst) && (q < dslot), isu = (q > dslot) && (q < ulast);
+#pragma unroll
+        for (int p = 0; p < MLU; p++) {
+          const bool tl = isl && (q - lfirst == p), tu = isu && (q - dslot - 1 == p);
+          Lc[p] = tl ? cg - lo : Lc[p];
+          Uc[p] = tu ? cg - lo : Uc[p];
+#pragma unroll
+          for (int e = 0; e < BB; e++) Lf[p][e] = tl ? blk[e] : Lf[p][e];
+        }
+        if (isu) {
+          double* dst = upark + (size_t)(uo + (q - dslot - 1)) * BB;
+          *reinterpret_cast<double2*>(dst) = make_double2(blk[0], blk[1]);
+          *reinterpret_cast<double2*>(dst + 2) = make_double2(blk[2], blk[3]);
+        }
+      }
+    }
+    if constexpr (!SPMV) {  // plain application to an unscaled vector: scale it by the inverted pivot
+      double r[BS], dv[BB];
+      load_x<BS>(in, i, r);
+      load_pivot<BS>(dinv, n, i, dv);
+      acc[0] = dv[0] * r[0] + dv[1] * r[1];
+      acc[1] = dv[2] * r[0] + dv[3] * r[1];
+    }
+    if (dot == PC_DOT_XZ || dot == PC_DOT_MERGED) load_xs<BS, AX>(in, in2, nalpha, i, xin);
+    if (dot == PC_DOT_ZA || dot == PC_DOT_MERGED) load_x_stream<BS>(aux, i, avp);   // the dot product's partner: in flight through the sweeps
+  }
+  if (active) *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(acc[0], acc[1]);
+  __syncthreads();
+  auto gather3 = [&](const int (&cc)[MLU], const double (&ff)[MLU][BB], double* sum) {
+    double2 yk[MLU];
+#pragma unroll
+    for (int p = 0; p < MLU; p++) yk[p] = *reinterpret_cast<const double2*>(ys + cc[p] * 2);
+#pragma unroll
+    for (int r = 0; r < BS; r++) {
+      double part[MLU];
+#pragma unroll
+      for (int p = 0; p < MLU; p++) part[p] = ff[p][r * BS] * yk[p].x + ff[p][r * BS + 1] * yk[p].y;
+      sum[r] = (part[0] + part[1]) + part[2];
+    }
+  };
+  // (The sweeps at raised wave priority, s_setprio 3, measured slower: 0.6663 -> 0.6741 ms composed at 216^3, profiles/exp_ab_r6_*.log.)
+  for (int lev = 1; lev < nlf; lev++) {  // forward: y_i = t_i - sum A'_ik y_k
+    if (lf == lev) {
+      const double2 a = *reinterpret_cast<const double2*>(ys + tid * 2);
+      double sum[BS];
+      gather3(Lc, Lf, sum);
+      *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(a.x - sum[0], a.y - sum[1]);
+    }
+    __syncthreads();
+  }
+  // the lower blocks are dead: their registers take the parked upper blocks
+#pragma unroll
+  for (int p = 0; p < MLU; p++) {
+    const bool have = p < nU;
+    const double* src = upark + (size_t)(uo + (have ? p : 0)) * BB;
+    const double2 u0 = *reinterpret_cast<const double2*>(src), u1 = *reinterpret_cast<const double2*>(src + 2);
+    Lf[p][0] = have ? u0.x : 0.0; Lf[p][1] = have ? u0.y : 0.0;
+    Lf[p][2] = have ? u1.x : 0.0; Lf[p][3] = have ? u1.y : 0.0;
+  }
+  double out[BS] = {0.0, 0.0};
+  for (int lev = 0; lev < nlb; lev++) {  // backward: x_i = y_i - sum A'_ij x_j
+    if (lb == lev) {
+      const double2 a = *reinterpret_cast<const double2*>(ys + tid * 2);
+      double sum[BS];
+      gather3(Uc, Lf, sum);
+      out[0] = a.x - sum[0];
+      out[1] = a.y - sum[1];
+      *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(out[0], out[1]);
+    }
+    if (lev + 1 < nlb) __syncthreads();
+  }
+  if (active) store_z2(z, (size_t)i, out[0], out[1]);
+  if (dot != 0) {
+    double* red = lds + (size_t)blockDim.x * BS;
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    pc_row_dots<BS, true, false>(dot, v, out, active, [&](double (&x)[BS]) { x[0] = xin[0]; x[1] = xin[1]; },
+                                 [&](double (&a)[BS]) { a[0] = avp[0]; a[1] = avp[1]; });
+    // the reduction scratch is touched by nothing before this point; dropping the barrier was not felt (0.5704 / 0.6942
+    // against 0.5714 / 0.6924 ms at 216^3, profiles/nobar_ab_r6_c3.log), so it stays
+    __syncthreads();
+    pc_reduce_dots(dot, v, red, partials, nb_max, s);
+  }
+}
+
+}  // namespace wai
