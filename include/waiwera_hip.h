@@ -393,6 +393,23 @@ int wai_tracer_system(wai_ctx *ctx, int tracer, int method, double dt, double ra
 int wai_tracer_solve(wai_ctx *ctx, int method, double dt, double ratio, const double *alx_last,
                      const double *alx_last2, double *X, double *alx_new, int *its, int *reason);
 
+/* How wai_tracer_solve runs the auxiliary solve.  WAI_TRACER_PER_TRACER (the default): one scalar solve per tracer, as
+ * described above.  WAI_TRACER_COUPLED: all nt tracers in ONE left-preconditioned Krylov solve on the interleaved
+ * [cell][tracer] vector, as the reference does (one auxiliary matrix with nt degrees of freedom per cell,
+ * src/ode.F90:306-315; one KSPSolve per step, src/timestepper.F90:2345-2355): one assembly sweep, one ILU(0) pass, `its` the
+ * one solve's iteration count, `reason` its KSPConvergedReason, the convergence test on the 2-norm of the preconditioned
+ * residual of the whole vector against rtol * |M^-1 b| / atol of wai_set_aux_solver; zero initial guess.  The blocks are
+ * diagonal, so block ILU(0) is the nt scalar ILU(0)s.  Covered: WAI_PC_BJACOBI with ILU(0) and WAI_PC_NONE, GMRES and
+ * BiCGStab (what wai_set_aux_solver accepts).  WAI_PC_ASM, WAI_PC_LU and ilu_levels > 0 are refused (-2, named in wai_last_error), never run
+ * per tracer instead.  One tracer takes the per-tracer path in either mode. */
+enum { WAI_TRACER_PER_TRACER = 0, WAI_TRACER_COUPLED = 1 };
+int wai_set_tracer_solve_mode(wai_ctx *ctx, int mode);
+/* the system the coupled solve solves, after aux_pre_solve: val = nnzb x nt diagonals of its blocks on
+ * wai_jacobian_pattern's pattern ([block][tracer]), b = n_owned * nt interleaved [cell][tracer].  Entry by entry what nt
+ * calls of wai_tracer_system return.  No solve is involved: available under every preconditioner. */
+int wai_tracer_block_system(wai_ctx *ctx, int method, double dt, double ratio, const double *alx_last,
+                            const double *alx_last2, double *val, double *b);
+
 int wai_synchronize(wai_ctx *ctx);   /* wait for everything enqueued on the library's stream */
 const char *wai_pc_kernel_name(wai_ctx *ctx);   /* kernel / path of a preconditioned-operator application (reports) */
 

@@ -17,6 +17,9 @@ int wai_comm_stats(wai_ctx *ctx, long long *allreduces, long long *exchanges);
  * and no copy -- every reduction is finished by the last workgroups of its producer and the residual norm is
  * posted to pinned host memory */
 int wai_launch_stats(wai_ctx *ctx, long long *kernels, long long *copies);
+/* tracer assembly sweeps over the faces so far: a per-tracer auxiliary solve makes nt of them, a coupled one
+ * (wai_set_tracer_solve_mode) makes one */
+int wai_tracer_stats(wai_ctx *ctx, long long *assembly_sweeps);
 
 /* bench.py's A/B for the collectives' share of an iteration: on != 0 makes every all-reduce and neighbour exchange
  * of this context return without calling RCCL (results are then wrong; timing probes only).  Every rank must switch

@@ -182,6 +182,8 @@ void free_all(wai_ctx* c) {
   F(c->flu); F(c->flu_last_iter); F(c->flu_last_step); F(c->flu_pert); F(c->hstep);
   F(c->w_y); F(c->w_yold); F(c->w_delta); F(c->w_f); F(c->w_lhs); F(c->w_lhs2); F(c->w_hist); F(c->w_hist_prev);
   F(c->tr.bc); F(c->tr.inj); F(c->tr.val); F(c->w_a); F(c->w_b); F(c->w_c);
+  F(c->tr.valb); F(c->tr.fvalb); F(c->tr.rhsb); F(c->tr.kbasis);
+  for (auto& p : c->tr.kvec) F(p);
   F(c->d_flags); F(c->d_red);
   if (c->h_flags) (void)hipHostFree(c->h_flags);
   if (c->h_red) (void)hipHostFree(c->h_red);
@@ -1068,6 +1070,9 @@ int wai_set_tracers(wai_ctx* c, int n, const int* phase, const double* decay, co
   t.nt = n;
   auto F = [](double*& p) { if (p) (void)hipFree(p); p = nullptr; };
   F(t.bc); F(t.inj); F(t.val);
+  F(t.valb); F(t.fvalb); F(t.rhsb); F(t.kbasis);   // the coupled mode's buffers are sized by nt: rebuilt on first use
+  for (auto& p : t.kvec) F(p);
+  t.kbasis_m = 0;
   if (n == 0) return 0;
   const size_t nbc = (size_t)std::max(c->mesh.n_bc, 1) * n, nsrc = (size_t)std::max(c->src.n, 1) * n;
   if (dev_alloc(c, &t.bc, nbc) || dev_alloc(c, &t.inj, nsrc) ||
@@ -1109,6 +1114,13 @@ int wai_set_aux_solver(wai_ctx* c, int ksp_type, int gmres_restart, double rtol,
   if (rtol > 0.0) c->tr.rtol = rtol;
   if (atol > 0.0) c->tr.atol = atol;
   if (max_its > 0) c->tr.max_its = max_its;
+  return 0;
+}
+
+int wai_set_tracer_solve_mode(wai_ctx* c, int mode) {
+  if (!c) return -2;
+  if (mode != WAI_TRACER_PER_TRACER && mode != WAI_TRACER_COUPLED) { c->err = "unknown tracer solve mode"; return -2; }
+  c->tr.mode = mode;
   return 0;
 }
 
@@ -1156,9 +1168,99 @@ struct AuxScope {
   }
 };
 
+// The coupled tracer system: the drivers see ONE system of block size nt -- c->J's values are the nt diagonals per slot
+// (Bcsr::dg), the Krylov vectors are the tracers' own (nt * n_prim entries; the flow's have np), the halo exchange
+// carries nt doubles per cell.  The schedule (levels, bricks) is the flow Jacobian's: it depends on the pattern alone.
+struct CoupledScope {
+  wai_ctx* c;
+  AuxScope aux;
+  Krylov saved;
+  int dg; double* fdg;
+  explicit CoupledScope(wai_ctx* c_) : c(c_), aux(c_), saved(c_->ks), dg(c_->J.dg), fdg(c_->J.fdg) {
+    Tracers& t = c->tr;
+    const int nt = t.nt;
+    c->np = nt; c->J.bs = nt; c->J.dg = nt; c->J.val = t.valb; c->J.fdg = t.fvalb;
+    Krylov& k = c->ks;
+    k.n = c->mesh.n_owned * nt; k.nl = c->mesh.n_prim * nt;
+    double** kv[] = {&k.R, &k.RP, &k.P, &k.V, &k.S, &k.T, &k.tmp, &k.X};
+    for (int i = 0; i < 8; i++) *kv[i] = t.kvec[i];
+    k.basis = t.kbasis; k.basis_m = t.kbasis_m; k.bl = nullptr;   // (wai_set_aux_solver: bcgs or gmres, no BiCGStab(L))
+  }
+  ~CoupledScope() {
+    Krylov& k = c->ks;
+    saved.n_launch = k.n_launch; saved.n_copy = k.n_copy; saved.seq = k.seq;
+    c->ks = saved;
+    c->J.dg = dg; c->J.fdg = fdg;   // (np, bs, val, n, nl: AuxScope)
+  }
+};
+
+// the coupled system's own buffers (values, factor, right-hand side), on first use after wai_set_tracers
+static int coupled_system_buffers(wai_ctx* c) {
+  Tracers& t = c->tr;
+  const size_t nl = (size_t)c->mesh.n_prim * t.nt, nv = (size_t)c->J.W * t.nt * c->J.n;
+  if (!t.valb && dev_alloc(c, &t.valb, nv)) return -1;
+  if (!t.fvalb && dev_alloc(c, &t.fvalb, nv)) return -1;
+  if (!t.rhsb && dev_alloc(c, &t.rhsb, nl + 16)) return -1;
+  return 0;
+}
+
+// ... and what a coupled SOLVE needs beside them: the Krylov vectors of nt * n_prim entries, the GMRES basis, halo buffers
+// of nt values per cell.  What the mode does not cover is refused by name
+static int coupled_prepare(wai_ctx* c) {
+  Tracers& t = c->tr;
+  const char* what = nullptr;
+  if (c->opts.pc_type == WAI_PC_ASM) what = "the asm preconditioner";
+  else if (c->opts.pc_type == WAI_PC_LU) what = "the lu preconditioner";
+  else if (c->opts.ilu_levels > 0) what = "ILU(k) with k > 0";
+  else if (c->opts.pc_type != WAI_PC_BJACOBI && c->opts.pc_type != WAI_PC_NONE) what = "this preconditioner";
+  if (what) {
+    c->err = std::string("coupled tracer solve (WAI_TRACER_COUPLED) does not cover ") + what +
+             ": block Jacobi ILU(0) or none only; use WAI_TRACER_PER_TRACER";
+    return -2;
+  }
+  if (coupled_system_buffers(c)) return -1;
+  const size_t nl = (size_t)c->mesh.n_prim * t.nt;
+  for (auto& p : t.kvec) {
+    if (p) continue;
+    if (dev_alloc(c, &p, nl + 16)) return -1;
+    HIPCHK(c, hipMemset(p, 0, (nl + 16) * sizeof(double)));
+  }
+  if (t.ksp_type == WAI_KSP_GMRES && (!t.kbasis || t.kbasis_m < basis_vectors(t.restart))) {
+    if (t.kbasis) (void)hipFree(t.kbasis);
+    t.kbasis_m = basis_vectors(t.restart);
+    if (dev_alloc(c, &t.kbasis, (size_t)(t.kbasis_m + 4) * nl)) return -1;
+    HIPCHK(c, hipMemset(t.kbasis, 0, (size_t)(t.kbasis_m + 4) * nl * sizeof(double)));
+  }
+  if (c->comm && c->mesh.n_halo && ensure_halo_dof(c, t.nt)) return -1;
+  return 0;
+}
+
 }  // namespace wai
 
 extern "C" {
+
+int wai_tracer_block_system(wai_ctx* c, int method, double dt, double ratio, const double* alx_last,
+                            const double* alx_last2, double* val, double* b) {
+  if (!c || !val || !b) return -2;
+  Tracers& t = c->tr;
+  if (!t.nt) { c->err = "no tracers set"; return -1; }
+  if (method < WAI_METHOD_BEULER || method > WAI_METHOD_DIRECTSS) { c->err = "unknown time stepping method"; return -1; }
+  if (method != WAI_METHOD_DIRECTSS && !alx_last) return -2;
+  if (method == WAI_METHOD_BDF2 && !alx_last2) return -2;
+  if (coupled_system_buffers(c)) return -1;   // the system alone: no solver buffers, whatever the preconditioner
+  const size_t nx = (size_t)c->mesh.n_owned * t.nt;
+  VecArg a1{c}, a2{c};
+  if (a1.in(alx_last, nx, 0) || a2.in(alx_last2, nx, 1)) return -1;
+  if (launch_tracer_assemble_all(c, method, dt, ratio, a1.dev, a2.dev, t.rhsb)) return -1;
+  {
+    CoupledScope scope(c);
+    launch_dg_to_bcsr(c, c->J, t.fvalb);   // the factor buffer as scratch: nnzb * nt <= W * nt * n
+  }
+  HIPCHK(c, hipMemcpyAsync(val, t.fvalb, sizeof(double) * (size_t)c->J.nnzb * t.nt, hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b, t.rhsb, sizeof(double) * nx, hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
 
 int wai_tracer_system(wai_ctx* c, int tracer, int method, double dt, double ratio, const double* alx_last,
                       const double* alx_last2, double* val, double* b) {
@@ -1201,6 +1303,23 @@ int wai_tracer_solve(wai_ctx* c, int method, double dt, double ratio, const doub
   *its = 0;
   *reason = 100;
   int rc = 0;
+  if (t.mode == WAI_TRACER_COUPLED && t.nt > 1) {
+    // one assembly sweep, one factorisation, ONE Krylov solve on the [cell][tracer] vector (timestepper.F90:2345-2355):
+    // its iteration count, its reason, the combined preconditioned residual norm against rtol / atol
+    if (int e = coupled_prepare(c)) return e;
+    if (launch_tracer_assemble_all(c, method, dt, ratio, a1.dev, a2.dev, t.rhsb)) return -1;
+    {
+      CoupledScope scope(c);
+      double rn = 0.0;
+      vec_zero(c, xx.dev, c->ks.n);  // a failed factorisation returns before the solver zeroes it
+      rc = do_ksp(c, t.rhsb, xx.dev, its, reason, &rn) ? -1 : 0;
+    }
+    if (rc) return rc;
+    launch_tracer_alx(c, xx.dev, an.dev);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (xx.back() || an.back()) return -1;
+    return 0;
+  }
   if (t.ksp_type == WAI_KSP_GMRES && !c->ks.basis) {  // the flow solver may never have needed one
     if (dev_alloc(c, &c->ks.basis, (size_t)(c->ks.basis_m + 4) * c->ks.nl)) return -1;
     HIPCHK(c, hipMemset(c->ks.basis, 0, (size_t)(c->ks.basis_m + 4) * c->ks.nl * sizeof(double)));

@@ -204,6 +204,11 @@ struct Bcsr {
   int* col = nullptr;
   double* val = nullptr;
   int* rowptr = nullptr;  // device copy of the BCSR row pointer (layout conversion kernels)
+  // dg > 0: the coupled tracer system (kernels_tracer_block.hip) -- dg independent scalar matrices on this ONE set of
+  // column planes, i.e. diagonal dg x dg blocks stored as their diagonals: val[(slot * dg + t) * n + row], vectors
+  // interleaved [row][t].  fdg: its ILU(0) factor in the same layout (diagonal slot: the inverted pivot)
+  int dg = 0;
+  double* fdg = nullptr;
   std::vector<int> h_rowptr, h_colidx;
 };
 
@@ -331,6 +336,14 @@ struct Tracers {
   double* val = nullptr;   // scalar block-ELL values of the system being solved, W x n
   int ksp_type = 1, restart = 30, max_its = 10000;
   double rtol = 1.e-5, atol = 1.e-50;
+  // coupled mode (wai_set_tracer_solve_mode): all nt systems as one, allocated on first use
+  int mode = 0;            // WAI_TRACER_PER_TRACER | WAI_TRACER_COUPLED
+  double* valb = nullptr;  // [W][nt][n] values of the nt systems (Bcsr::dg layout)
+  double* fvalb = nullptr; // their ILU(0) factors, same layout
+  double* rhsb = nullptr;  // [n_prim * nt + 16] right-hand side, interleaved [cell][nt]
+  double* kvec[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // Krylov work vectors of nt * n_prim
+  double* kbasis = nullptr; int kbasis_m = 0;   // GMRES basis of such vectors
+  long long n_sweeps = 0;  // assembly sweeps over the faces so far (wai_tracer_stats)
 };
 
 // one tracer's system: which tracer, and the method's combination (timestepper.F90:458-581)
@@ -473,6 +486,9 @@ int launch_transitions(wai_ctx* c, const double* y_old, double* search, double* 
 // tracer system of tf.it on the flow Jacobian's pattern: values -> c->tr.val, rhs -> b
 int launch_tracer_assemble(wai_ctx* c, const TracerForm& tf, const double* alx_last,
                            const double* alx_last2, double* b);
+// all nt systems in one sweep over the faces: values -> c->tr.valb ([slot][tracer][row]), rhs -> b ([row][tracer])
+int launch_tracer_assemble_all(wai_ctx* c, int method, double dt, double ratio, const double* alx_last,
+                               const double* alx_last2, double* b);
 int launch_tracer_lhs(wai_ctx* c, double* Al);
 int launch_separator(wai_ctx* c, double pressure, double* out);   // out[3] on the device: hf, hg, err
 int launch_face_fluxes(wai_ctx* c, const int* face_cells, double* out);   // [face][np + nmob]
@@ -522,6 +538,13 @@ inline Fin make_fin_dots(wai_ctx* c, int dot_mode, int phase, bool post = false)
   return make_fin(c, pc_dot_slot0(dot_mode), pc_dot_nslots(dot_mode), phase, post);
 }
 int launch_ell_to_bcsr(wai_ctx* c, const double* ell, double* bcsr);
+// the coupled tracer system (Bcsr::dg; kernels_tracer_block.hip): what launch_spmv, launch_ilu_factor_on, launch_pc_on and
+// launch_big_solve hand such a matrix to, and its values as [block][tracer] on the BCSR pattern
+int launch_dg_spmv(wai_ctx* c, const Bcsr& M, const double* x, double* y);
+int launch_dg_factor(wai_ctx* c, const Bcsr& M, IluSchedule& s);
+int launch_dg_pc(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z, const int* list, int nrun);
+int launch_dg_big_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
+int launch_dg_to_bcsr(wai_ctx* c, const Bcsr& M, double* bcsr);
 int launch_bcsr_to_ell(wai_ctx* c, const double* bcsr, double* ell);
 // reductions: partial sums live in ks.partials[slot][block]; finalize sums nb partials of
 // nslots consecutive slots into ks.scal and (phase >= 0) derives the BiCGStab scalars

@@ -942,6 +942,141 @@ __global__ __launch_bounds__(TPB) void k_tracer_assemble(MeshView m, const doubl
   b[c] = absent ? 0.0 : rhs;
 }
 
+// Every tracer's system in ONE sweep over the faces (the coupled solve, kernels_tracer_block.hip): a face's geometry, the
+// two cells' states, each mobile phase's flux, upstream choice and diffusion factor are formed once and serve every tracer
+// of that phase; per tracer remain its diffusion coefficient, decay, history and aux_pre_solve's identity row.  The same
+// expressions in the same order as k_tracer_assemble, tracer by tracer: identical values.  Two cells share at most one
+// face (wai_ctx_create refuses duplicate connections), so a row's off-diagonal entries are stored where their face is met
+// (after the row's slots are given their empty value) instead of being collected in registers -- nt rows of up to 16 slots
+// would not fit them.  The empty value: k_tracer_assemble writes cA * 0.0 into a slot no face fills, which is -0.0 for the
+// transient methods (cA = -dt); the same product here keeps the two entry points bit-identical, sign of zero included; values: aval[(slot * nt + t) * n + cell],
+// right-hand side b[cell * nt + t].
+template <int KIND>
+__global__ __launch_bounds__(TPB) void k_tracer_assemble_all(MeshView m, const double* __restrict__ flu, size_t stride,
+                                                             Tracers tr, int method, double dt, double ratio, int n_prim,
+                                                             int W, const double* __restrict__ alx1,
+                                                             const double* __restrict__ alx2, double* __restrict__ aval,
+                                                             double* __restrict__ b) {
+  using E = EosT<KIND>;
+  constexpr int NT = MAX_TRACERS, NPH = 2;   // tracers live in the mobile phases: liquid, vapour
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= m.n_owned) return;
+  const int nt = tr.nt;
+  const size_t n = m.n_owned;
+  CellState<KIND> own;
+  RockState rown;
+  load_state<KIND>(flu, stride, c, own);
+  load_rock(m.rock, m.n_local, c, rown);
+  const double vol = m.vol[c];
+  const int dslot = m.diag_blk[c];
+  int used = 0;
+  for (int t = 0; t < nt; t++) used |= 1 << tr.phase[t];
+  const double r = ratio, r1 = r + 1.0;
+  const double cA = method == WAI_METHOD_DIRECTSS ? 1.0 : (method == WAI_METHOD_BDF2 ? -dt * r1 : -dt);
+  double cf_own[NPH];
+#pragma unroll
+  for (int p = 0; p < NPH; p++) cf_own[p] = (used >> p) & 1 ? tracer_coef<KIND>(own, rown, p) : 0.0;
+  bool absent[NT];
+  double diag[NT], br[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    diag[t] = 0.0; br[t] = 0.0;
+    absent[t] = t < nt ? !(((int)own.phases) & (1 << tr.phase[t])) : true;
+  }
+  for (int q = 0; q < W; q++)
+    for (int t = 0; t < nt; t++) aval[((size_t)q * nt + t) * n + c] = absent[t] ? 0.0 : cA * 0.0;   // (the sign k_tracer_assemble's empty slots carry)
+  for (int s = 0; s < m.max_deg; s++) {
+    const int fs = m.adj_face[(size_t)s * m.n_owned + c];
+    if (fs < 0) continue;
+    const int o = m.adj_other[(size_t)s * m.n_owned + c];
+    const int blk = m.adj_blk[(size_t)s * m.n_owned + c];
+    const int side = fs & 1;
+    FaceGeom g;
+    load_face(m, fs >> 1, g);
+    CellState<KIND> oth;
+    RockState roth;
+    load_state<KIND>(flu, stride, o, oth);
+    load_rock(m.rock, m.n_local, o, roth);
+    const double sign = side ? 1.0 : -1.0;
+    double fa[NPH], dfac[NPH];
+    bool up_is_own[NPH];
+#pragma unroll
+    for (int p = 0; p < NPH; p++) {
+      fa[p] = 0.0; dfac[p] = 0.0; up_is_own[p] = false;
+      if ((used >> p) & 1) {
+        const double pf = side == 0 ? face_phase_flux<KIND>(g, own, rown, oth, roth, p)
+                                    : face_phase_flux<KIND>(g, oth, roth, own, rown, p);
+        up_is_own[p] = (pf >= 0.0) == (side == 0);
+        fa[p] = sign * (pf * g.area) / vol;
+        const double cf_oth = tracer_coef<KIND>(oth, roth, p);
+        dfac[p] = side == 0 ? harmonic(g, cf_own[p], cf_oth) : harmonic(g, cf_oth, cf_own[p]);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      if (t < nt) {
+        const int p = tr.phase[t];
+        const double fap = p ? fa[1] : fa[0], dfp = p ? dfac[1] : dfac[0];
+        const bool up = p ? up_is_own[1] : up_is_own[0];
+        const double fd = g.area * dfp * tr.diffusion[t] / (g.d12 * vol);
+        double to_own = -fd, to_oth = fd;
+        if (up) to_own += fap; else to_oth += fap;
+        diag[t] += to_own;
+        if (blk >= 0) aval[((size_t)blk * nt + t) * n + c] = absent[t] ? 0.0 : cA * (0.0 + to_oth);
+        else br[t] += to_oth * tr.bc[(size_t)(o - n_prim) * nt + t];
+      }
+    }
+  }
+  // sources (tracer_source_iterator, flow_simulation.F90:1722-1772)
+  for (int si = m.cell_src[c]; si >= 0; si = m.src_next[si]) {
+    const double rate = source_rate<KIND>(own, m.src_ctl, si, m.src_rate[si], m.src_net);
+    const int comp = m.src_comp[si];
+    const int component = rate > 0.0 ? (comp <= 0 ? 1 : comp) : (comp <= 0 ? 0 : comp);
+    if (!(component < E::np)) continue;
+    if (rate < 0.0) {
+      const int ph = (int)own.phases;
+      double mobq[NPH] = {0.0, 0.0}, sum = 0.0;
+#pragma unroll
+      for (int q = 0; q < E::nph; q++)
+        if (ph & (1 << q)) {
+          const double mob = own.kr[q] * own.rho[q] / own.mu[q];
+          sum += mob;
+          if (q < NPH) mobq[q] = mob;
+        }
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+        if (t < nt) diag[t] += ((tr.phase[t] ? mobq[1] : mobq[0]) / sum) * rate / vol;
+    } else {
+#pragma unroll
+      for (int t = 0; t < NT; t++)
+        if (t < nt) br[t] += tr.inj[(size_t)si * nt + t] / vol;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    if (t < nt) {
+      const double al = tr.phase[t] ? cf_own[1] : cf_own[0];
+      // apply_tracer_decay (:1776-1831), tracer_decay (tracer.F90:48-61)
+      double d = diag[t];
+      d += -(tr.decay[t] * exp(-tr.activation[t] / (8.3144598 * (own.T + 273.15)))) * al;
+      // setup_linear: A = cA Ar + cL Al, b from the history
+      const size_t ix = (size_t)c * nt + t;
+      double rhs = -br[t];
+      d *= cA;
+      if (method == WAI_METHOD_BEULER) {
+        d += al;
+        rhs = alx1[ix] + dt * br[t];
+      } else if (method == WAI_METHOD_BDF2) {
+        d += al * (1.0 + 2.0 * r);
+        rhs = (alx1[ix] * (r1 * r1) + (-r * r) * alx2[ix]) + (dt * r1) * br[t];
+      }
+      // aux_pre_solve: phase absent -> identity row, zero right-hand side
+      aval[((size_t)dslot * nt + t) * n + c] = absent[t] ? 1.0 : d;
+      b[ix] = absent[t] ? 0.0 : rhs;
+    }
+  }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(TPB) void k_tracer_lhs(MeshView m, const double* __restrict__ flu, size_t stride,
                                                     Tracers tr, double* __restrict__ Al) {
@@ -1321,6 +1456,7 @@ int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
 int launch_tracer_assemble(wai_ctx* c, const TracerForm& tf, const double* alx_last,
                            const double* alx_last2, double* b) {
   const MeshView m = view(c);
+  c->tr.n_sweeps++;
   // rows indexed by ELL slot: up to W of them (wai_ctx_create refuses rows of more than MAXDEG_WIDE blocks)
   if (c->J.W > MAXDEG)
     WAI_BY_EOS_T(c, k_tracer_assemble, WAI_COMMA MAXDEG_WIDE, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
@@ -1328,6 +1464,15 @@ int launch_tracer_assemble(wai_ctx* c, const TracerForm& tf, const double* alx_l
   else
     WAI_BY_EOS(c, k_tracer_assemble, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
                c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->tr.val, b);
+  return 0;
+}
+
+int launch_tracer_assemble_all(wai_ctx* c, int method, double dt, double ratio, const double* alx_last,
+                               const double* alx_last2, double* b) {
+  const MeshView m = view(c);
+  c->tr.n_sweeps++;
+  WAI_BY_EOS(c, k_tracer_assemble_all, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, c->tr, method, dt, ratio,
+             c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.valb, b);
   return 0;
 }
 

@@ -572,6 +572,7 @@ static void ilu_factor_bs(wai_ctx* c, const Bcsr& J, IluSchedule& s) {
     hipLaunchKernelGGL(k_ilu_factor<BS>, grid, T, 0, c->stream, J.n, s.nsub, s.sub_ptr, s.sub_nlev, s.row_info, J.col, s.fval, s.dinv, c->d_flags);
 }
 int launch_ilu_factor_on(wai_ctx* c, const Bcsr& J, IluSchedule& s) {
+  if (J.dg) return launch_dg_factor(c, J, s);   // the coupled tracer system: its own factor buffer
   if (with_bs(J.bs, [&](auto bs) { ilu_factor_bs<decltype(bs)::value>(c, J, s); }) != 0) return -1;
   s.factored = true;
   return 0;
@@ -588,6 +589,7 @@ static void lvl_sweep(wai_ctx* c, const Bcsr& J, const IluSchedule& s, const int
   }
 }
 int launch_big_solve(wai_ctx* c, const Bcsr& J, const IluSchedule& s, double* z) {
+  if (J.dg) return launch_dg_big_solve(c, J, s, z);
   return with_bs(J.bs, [&](auto bs) {
     constexpr int BS = decltype(bs)::value;
     lvl_sweep<BS, true>(c, J, s, s.ord_f, s.lev_f_ptr, s.nlev_f, z);   // level-0 rows of the forward sweep have nothing to subtract, but the launch is harmless

@@ -26,6 +26,7 @@ void read_env(wai_ctx* c) {
 // which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc.
 // Kinds 1 .. 3 can form their input on the fly (in - alpha in2: launch_pc_on's in2)
 static int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s) {
+  if (J.dg) return -1;    // the coupled tracer system: k_dg_pc (kernels_tracer_block.hip)
   if (s.wide) return 4;   // rows of 9 .. 16 blocks: no other fused kernel reads their descriptor
   if (c->dbg) return 0;
   if (s.wave_kernel && J.bs >= 3) return 3;
@@ -148,6 +149,25 @@ int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, con
   if (in2 && (!spmv || !kind_composes(pc_kernel_kind(c, M, s)))) { c->err = "composed input asked of a kernel that cannot form it"; return -1; }
   const Fin* fin_later = nullptr;
   if (fin && dot_mode != 0 && c->env.fin_separate) { fin_later = fin; fin = nullptr; }
+  if (M.dg) {
+    // the coupled tracer system: the brick kernel reduces nothing; the dot mode's products of the result come from the vector
+    // kernels (their partial sums in ks.nb_pc blocks per slot) and are finished as the general path finishes them
+    c->ks.n_launch++;
+    if (launch_dg_pc(c, M, s, spmv, in, z, list, nrun)) return -1;
+    if (dot_mode == PC_DOT_NONE) return 0;
+    const int n = c->ks.n, s0 = pc_dot_slot0(dot_mode);
+    if (dot_mode == PC_DOT_ZA || dot_mode == PC_DOT_ZZ) vec_dots(c, z, dot_mode == PC_DOT_ZA ? aux : z, s0, nullptr, nullptr, 0, n);
+    else {
+      vec_dots(c, in, z, s0, z, z, s0 + 1, n);
+      if (dot_mode == PC_DOT_MERGED) { vec_dots(c, in, in, s0 + 2, in, aux, s0 + 3, n); vec_dots(c, z, aux, s0 + 4, nullptr, nullptr, 0, n); }
+    }
+    if (const Fin* f = fin ? fin : fin_later) {   // separate launches either way (WAI_FIN_SEPARATE changes nothing here)
+      if (dot_mode == PC_DOT_MERGED) { vec_finalize(c, c->ks.nb_pc, s0, 4, -1); vec_finalize(c, c->ks.nb_pc, s0 + 4, 1, f->phase); }
+      else vec_finalize(c, c->ks.nb_pc, s0, pc_dot_nslots(dot_mode), f->phase);
+      if (f->seq > 0) bcgs_post(c, f->seq);
+    }
+    return 0;
+  }
   c->ks.nb_pc = s.nsub;   // partial sums per slot this application leaves: one per brick (k_pc_wave: per workgroup, set there)
   if (with_bs(M.bs, [&](auto bs) { launch_pc_bs<decltype(bs)::value>(c, M, s, spmv, in, z, dot_mode, aux, list, nrun, fin, in2); }) != 0)
     return -1;

@@ -135,6 +135,7 @@ __global__ __launch_bounds__(TPB) void k_asm_scatter(int n_ext, int bs, const in
 int launch_spmv(wai_ctx* c, const double* x, double* y) {
   const Bcsr& J = c->J;
   c->ks.n_launch++;
+  if (J.dg) return launch_dg_spmv(c, J, x, y);   // the coupled tracer system
   const int nblk = (J.n + TPB - 1) / TPB;
   const int grid = ((nblk + 7) / 8) * 8;
   const int* rp = (size_t)J.nnzb * 10 < (size_t)J.n * J.W * 9 ? J.rowptr : nullptr;   // > 10 % padding

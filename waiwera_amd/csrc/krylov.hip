@@ -143,7 +143,9 @@ int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode, const double* aux, i
   }
   const bool halo = c->comm && c->mesh.n_halo;
   if (halo && c->np > c->max_dof_buf) { c->err = "halo dof too large"; return -1; }
-  if (halo && c->comm_stream && s.n_int > 0 && s.n_bnd > 0 && !c->prof_on) {
+  if (halo && c->comm_stream && s.n_int > 0 && s.n_bnd > 0 && !c->prof_on && (!c->J.dg || dot_mode == PC_DOT_NONE)) {
+    // (the coupled tracer system reduces its inner products over whole vectors behind the launch: with a dot mode -- BiCGStab --
+    // it takes the in-order exchange and one launch below; GMRES, the auxiliary default, asks for none and overlaps)
     // The partition-ghost values are needed only by the bricks on the rank's faces: pack on the
     // compute stream, send / receive / unpack on the communication stream while the interior bricks
     // run, then the face bricks.  (xGMI transfers and RCCL's launch latency hide behind ~90 % of

@@ -191,6 +191,11 @@ int wai_launch_stats(wai_ctx* c, long long* kernels, long long* copies) {
   if (copies) *copies = c->ks.n_copy;
   return 0;
 }
+int wai_tracer_stats(wai_ctx* c, long long* assembly_sweeps) {
+  if (!c) return -2;
+  if (assembly_sweeps) *assembly_sweeps = c->tr.n_sweeps;
+  return 0;
+}
 int wai_test_drop_partials(wai_ctx* c, int n) { return c ? test_drop_partials(c, n) : -2; }
 // one preconditioned-operator application as the drivers issue it (waiwera_hip_bench.h): the inputs into the Krylov work
 // vectors (halo room), the scalars seeded, the partial slots emptied as a driver empties them before its first producer,

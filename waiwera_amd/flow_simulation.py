@@ -57,6 +57,7 @@ class FlowSimulation:
         self.n_owned, self.n_prim, self.n_local = mesh.n_owned, mesh.n_prim, mesh.n_local
         self.num_dof = self.n_owned * self.num_primary_variables
         self.num_tracers, self.auxiliary = 0, False
+        self.tracer_solve_mode = "per_tracer"
         self.time = 0.0
         if mesh.n_bc:
             bp, br = _lib._f64(mesh.bc_primary), _lib._i32(mesh.bc_region)
@@ -424,6 +425,28 @@ class FlowSimulation:
         if injection is not None:
             self._chk(LIB.wai_set_tracer_injection(self.h, _lib.ptr(_lib._f64(np.asarray(injection, dtype=np.float64)))),
                       "set_tracer_injection")
+
+    def set_tracer_solve_mode(self, mode):
+        """"per_tracer" (default): one scalar Krylov solve per tracer; "coupled": all tracers in one solve on the
+        [cell][tracer] vector, as the reference's auxiliary KSPSolve (block Jacobi ILU(0) or no preconditioner; others
+        are refused by aux_solve)"""
+        self._chk(LIB.wai_set_tracer_solve_mode(self.h, _lib.TRACER_SOLVE[mode]), "set_tracer_solve_mode")
+        self.tracer_solve_mode = mode
+
+    def aux_block_system(self, method, dt, ratio, alx_last, alx_last2):
+        """(values (nnzb, nt): the diagonals of the coupled system's blocks on setup_jacobian()'s pattern, rhs
+        (n_owned * nt) interleaved [cell][tracer])"""
+        nnzb = LIB.wai_jacobian_nnzb(self.h)
+        val, b = np.zeros((nnzb, self.num_tracers)), np.zeros(self.n_owned * self.num_tracers)
+        self._chk(LIB.wai_tracer_block_system(self.h, _lib.METHOD_KIND[method], dt, ratio, _lib.ptr(alx_last),
+                                              _lib.ptr(alx_last2), val.ctypes.data, b.ctypes.data), "tracer_block_system")
+        return val, b
+
+    def tracer_assembly_sweeps(self):
+        """tracer assembly sweeps over the faces so far (nt per per-tracer solve, one per coupled solve)"""
+        a = C.c_longlong(0)
+        self._chk(LIB.wai_tracer_stats(self.h, C.byref(a)), "tracer_stats")
+        return a.value
 
     def set_aux_solver(self, ksp_type="gmres", restart=30, rtol=1e-5, atol=1e-50, max_its=10000):
         return self._chk(LIB.wai_set_aux_solver(self.h, {"bcgs": 0, "gmres": 1}[ksp_type], restart, rtol, atol,

@@ -471,6 +471,21 @@ module waiwera_hip_module
        real(c_double), intent(in) :: alx_last(*), alx_last2(*)
        real(c_double), intent(out) :: val(*), b(*)
      end function wai_tracer_system
+     ! WAI_TRACER_PER_TRACER (0, default) | WAI_TRACER_COUPLED (1): all tracers in one Krylov solve (timestepper.F90:2345-2355)
+     integer(c_int) function wai_set_tracer_solve_mode(ctx, mode) bind(c, name = "wai_set_tracer_solve_mode")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: mode
+     end function wai_set_tracer_solve_mode
+     integer(c_int) function wai_tracer_block_system(ctx, method, dt, ratio, alx_last, alx_last2, val, b) &
+          bind(c, name = "wai_tracer_block_system")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: method
+       real(c_double), value :: dt, ratio
+       real(c_double), intent(in) :: alx_last(*), alx_last2(*)
+       real(c_double), intent(out) :: val(*), b(*)
+     end function wai_tracer_block_system
      integer(c_int) function wai_synchronize(ctx) bind(c, name = "wai_synchronize")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -528,6 +543,7 @@ module waiwera_hip_module
        wai_comm_init, wai_comm_size, wai_halo_exchange, wai_jacobian_set_values, wai_spmv, wai_pc_setup, wai_pc_apply, &
        wai_max_scaled, wai_tracer_system, wai_synchronize, wai_network_evaluate
   public :: wai_set_tracers, wai_set_tracer_bc, wai_set_tracer_injection, wai_set_aux_solver
+  public :: wai_set_tracer_solve_mode, wai_tracer_block_system
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_default_eos, wai_default_opts, wai_set_bc, wai_set_sources, wai_update_sources, wai_set_source_controls, wai_get_source_rates, wai_separator_enthalpies, wai_set_regions, &

@@ -230,7 +230,7 @@ class Simulation:
     """One Waiwera input file -> mesh, flow simulation object and time stepper."""
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
-                 output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm"):
+                 output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering) and runs the same step sequence -- what
@@ -238,6 +238,11 @@ class Simulation:
         and their device-side controls; not (yet) MINC zones, source networks, tracers, rock table controls, output files
         (fields() returns the rank's cells, self.owned_gid their index in the input's numbering)."""
         self.rank, self.world = int(rank), int(world)
+        # tracer_solve: "per_tracer" (one scalar solve per tracer) or "coupled" (all tracers in one Krylov solve, as the
+        # reference; needs the bjacobi or no preconditioner).  Not a key of the input file: the reference has none
+        if tracer_solve not in ("per_tracer", "coupled"):
+            raise ValueError("tracer_solve 'per_tracer' or 'coupled'")
+        self.tracer_solve = tracer_solve
         if default_pc not in ("asm", "bjacobi"):
             raise ValueError("default_pc 'asm' (the reference's default) or 'bjacobi' (the library's fused path)")
         self.default_pc, self.pc_choice = default_pc, None
@@ -518,6 +523,7 @@ class Simulation:
             opts["ilu_levels"] = levels
         if opts:
             self.ode.set_opts(**opts)
+        self._pc_covers_coupled = opts.get("pc_type", "bjacobi") in ("bjacobi", "none") and not opts.get("ilu_levels")
         # tracers
         tr = inp.get("tracer")
         self.tracer_names = []
@@ -552,6 +558,11 @@ class Simulation:
                                  diffusion=[t.get("diffusion", 0.0) for t in tr],
                                  bc=bc if lm.n_bc else None, injection=inj)
             self.X = np.tile(np.asarray(tvals(init.get("tracer")), dtype=np.float64), lm.n_owned)
+            if self.tracer_solve == "coupled" and nt > 1 and not self._pc_covers_coupled:
+                # (one tracer takes the per-tracer path in either mode: nothing to refuse)
+                raise ValueError("tracer_solve='coupled' covers the bjacobi (ILU(0)) and none preconditioners; this run's is %r (%s)"
+                                 "%s: pass default_pc='bjacobi' or tracer_solve='per_tracer'"
+                                 % (self.pc_choice[0], self.pc_choice[1], " with ILU(k)" if opts.get("ilu_levels") else ""))
         ad = step.get("adapt", {}) or {}
         mx = step.get("maximum", {}) or {}
         self.ts = Timestepper(
@@ -563,7 +574,8 @@ class Simulation:
             max_num_tries=_get(step, "maximum.tries", 10), stop_time=_get(inp, "time.stop"),
             max_num_steps=mx.get("number") if mx.get("number") is not None else 100, aux_solution=self.X,
             checkpoints=_get(inp, "output.checkpoint.time"),
-            checkpoint_tolerance=_get(inp, "output.checkpoint.tolerance", 0.1))
+            checkpoint_tolerance=_get(inp, "output.checkpoint.tolerance", 0.1),
+            tracer_solve_mode=self.tracer_solve if self.tracer_solve != "per_tracer" else None)
         if _get(inp, "output.checkpoint.repeat") not in (None, False, 1):
             raise NotImplementedError("repeated output checkpoints")
 

@@ -62,7 +62,7 @@ class Timestepper:
                  adapt_method="iteration", adapt_min=5.0, adapt_max=8.0, reduction=0.2,
                  amplification=2.0, max_stepsize=0.0, max_num_tries=10, stop_time=None,
                  max_num_steps=100, stop_min_stepsize=-1.0, stop_max_stepsize=-1.0, aux_solution=None,
-                 checkpoints=None, checkpoint_tolerance=0.1):
+                 checkpoints=None, checkpoint_tolerance=0.1, tracer_solve_mode=None):
         self.ode = ode
         self.y = y              # numpy array or torch tensor, scaled primaries, in/out
         self.time = time
@@ -103,6 +103,9 @@ class Timestepper:
         self._alx = [None, None]
         self._last_stepsize = None
         self.aux_history = []   # (aux KSP reason, iterations) per accepted step
+        # "per_tracer" | "coupled" (one KSPSolve for all tracers, timestepper.F90:2345-2355); None: the ode's setting stays
+        if tracer_solve_mode is not None:
+            ode.set_tracer_solve_mode(tracer_solve_mode)
         if hasattr(ode, "set_timestep_method"):
             ode.set_timestep_method(method)
         elif method != "beuler":
