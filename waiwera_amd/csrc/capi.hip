@@ -67,12 +67,12 @@ int do_jacobian(wai_ctx* c, double dt, const double* y, const double* lhs_old) {
   if (fl[0]) return 1;
   Prof p(c, KC_JACOBIAN);
   if (launch_jacobian(c, dt, lhs_old)) return -1;
-  c->ilu.factored = false;
+  pc_invalidate(c, c->flow);
   return network_couplings(c, dt, const_cast<double*>(y), lhs_old);   // y is perturbed and restored in place
 }
 
 int do_norm2(wai_ctx* c, const double* v, double* out) {
-  vec_dot(c, v, v, c->ks.n, S_W2);
+  vec_dot(c, v, v, c->flow.n, S_W2);
   if (allreduce_scal(c, S_W2, 1)) return -1;
   if (read_scal(c, S_W2, 1)) return -1;
   *out = std::sqrt(c->ks.h_scal[S_W2]);
@@ -114,7 +114,7 @@ int snes_convergence(wai_ctx* c, int it, const double* f, const double* lhs_old,
 // one Newton iteration on device vectors y (nl), lhs_old (n), f (n)
 int do_newton_step(wai_ctx* c, double dt, int iter, double* y, const double* lhs_old, double* f,
                    int* ksp_its, int* reason, double* max_residual) {
-  const int n = c->ks.n;
+  const int n = c->flow.n;
   *ksp_its = 0;
   if (iter == 0 && do_norm2(c, f, &c->fnorm0)) return -1;
   // SNES_pre_iteration_update (flow_simulation.F90:2120): last_iteration_fluid = fluid.  Inside the device-resident Newton
@@ -130,10 +130,10 @@ int do_newton_step(wai_ctx* c, double dt, int iter, double* y, const double* lhs
   if (e > 0) { *reason = -3; return 0; }
   int kreason = 0;
   double rn = 0.0;
-  if (do_ksp(c, f, c->w_delta, ksp_its, &kreason, &rn)) return -1;
+  if (do_ksp(c, c->flow, f, c->w_delta, ksp_its, &kreason, &rn)) return -1;
   if (kreason < 0) { *reason = -3; return 0; }
   // SNES_linesearch, lambda = 1
-  vec_copy(c, c->w_yold, y, c->ks.nl);
+  vec_copy(c, c->w_yold, y, c->flow.nl);
   vec_waxpy(c, y, -1.0, c->w_delta, c->w_yold, n);
   {
     Prof p(c, KC_TRANSITIONS);
@@ -165,25 +165,62 @@ int restore_step(wai_ctx* c) {
   return 0;
 }
 
+// a set of Krylov work vectors for vectors of nl entries, zeroed (those it has already are kept)
+int alloc_krylov_vecs(wai_ctx* c, KrylovVecs& k, size_t nl) {
+  double** kv[] = {&k.R, &k.RP, &k.P, &k.V, &k.S, &k.T, &k.tmp, &k.X};
+  for (auto p : kv) {
+    if (*p) continue;
+    if (dev_alloc(c, p, nl + 16)) return -1;
+    HIPCHK(c, hipMemset(*p, 0, (nl + 16) * sizeof(double)));
+  }
+  return 0;
+}
+void free_krylov_vecs(KrylovVecs& k) {
+  for (double* p : {k.R, k.RP, k.P, k.V, k.S, k.T, k.tmp, k.X, k.basis, k.bl}) if (p) (void)hipFree(p);
+  k = KrylovVecs();
+}
+// a GMRES basis of at least m vectors for sys: m + 1 directions, + 2 error approximations + the update (lgmres)
+int ensure_basis(wai_ctx* c, LinSys& sys, int m) {
+  KrylovVecs& k = *sys.kv;
+  if (k.basis && k.basis_m >= m) return 0;
+  if (k.basis) (void)hipFree(k.basis);
+  k.basis_m = m;
+  const size_t len = (size_t)(m + 4) * sys.nl;
+  if (dev_alloc(c, &k.basis, len)) return -1;
+  HIPCHK(c, hipMemset(k.basis, 0, len * sizeof(double)));
+  return 0;
+}
+// a system's matrix: the mesh's pattern with its own block size and values
+static Bcsr matrix_on(const Pattern& p, int bs, double* val) {
+  Bcsr A;
+  A.n = p.n; A.ncols = p.ncols; A.nnzb = p.nnzb; A.W = p.W; A.col = p.col; A.rowptr = p.rowptr;
+  A.bs = bs; A.val = val;
+  return A;
+}
+static KspOpts ksp_of(const wai_solver_opts& o) {
+  KspOpts k;
+  k.type = o.ksp_type; k.restart = o.gmres_restart; k.max_its = o.ksp_max_its; k.rtol = o.ksp_rtol; k.atol = o.ksp_atol;
+  return k;
+}
+
 void free_all(wai_ctx* c) {
   auto F = [](void* p) { if (p) (void)hipFree(p); };
   DeviceMesh& m = c->mesh;
   F(m.rock); F(m.vol); F(m.fgeom); F(m.fdir); F(m.adj_face); F(m.adj_other); F(m.adj_blk); F(m.adj_tblk);
   F(m.diag_blk); F(m.cell_src); F(m.face_cells);
   F(c->src.cell); F(c->src.comp); F(c->src.next); F(c->src.rate); F(c->src.enth); F(c->src.ctl); F(c->src.net); c->net.free_device();
-  F(c->J.rowptr); F(c->J.col); F(c->J.val);
+  F(c->pat.rowptr); F(c->pat.col);
   free_schedule(c->ilu);
-  free_asm(c->as);
-  free_asm(c->as_aux);
+  for (LinSys* sys : {&c->flow, &c->aux, &c->coupled}) { F(sys->A.val); F(sys->A.fdg); free_asm(sys->as); }
+  free_krylov_vecs(c->kv);
+  free_krylov_vecs(c->kv_coupled);
   F(c->lu.inv); F(c->lu.inv_ptr);
   Krylov& k = c->ks;
-  F(k.R); F(k.RP); F(k.P); F(k.V); F(k.S); F(k.T); F(k.tmp); F(k.X); F(k.basis); F(k.bl); F(k.partials); F(k.partials2); F(k.scal); F(k.started);
+  F(k.partials); F(k.partials2); F(k.scal); F(k.started);
   if (k.h_scal) (void)hipHostFree(k.h_scal);
   F(c->flu); F(c->flu_last_iter); F(c->flu_last_step); F(c->flu_pert); F(c->hstep);
   F(c->w_y); F(c->w_yold); F(c->w_delta); F(c->w_f); F(c->w_lhs); F(c->w_lhs2); F(c->w_hist); F(c->w_hist_prev);
-  F(c->tr.bc); F(c->tr.inj); F(c->tr.val); F(c->w_a); F(c->w_b); F(c->w_c);
-  F(c->tr.valb); F(c->tr.fvalb); F(c->tr.rhsb); F(c->tr.kbasis);
-  for (auto& p : c->tr.kvec) F(p);
+  F(c->tr.bc); F(c->tr.inj); F(c->tr.rhsb); F(c->w_a); F(c->w_b); F(c->w_c);
   F(c->d_flags); F(c->d_red);
   if (c->h_flags) (void)hipHostFree(c->h_flags);
   if (c->h_red) (void)hipHostFree(c->h_red);
@@ -342,8 +379,8 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
       adj_face[(size_t)slot * N + cc] = f * 2 + s;
       adj_other[(size_t)slot * N + cc] = md->face_cells[2 * f + 1 - s];
     }
-  Bcsr& J = c->J;
-  J.n = N; J.ncols = m.n_prim; J.bs = np;
+  Pattern& J = c->pat;
+  J.n = N; J.ncols = m.n_prim;
   J.h_rowptr.assign(N + 1, 0);
   for (int i = 0; i < N; i++) {
     int cnt = 1;
@@ -403,10 +440,18 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
   }
   if (dev_upload(c, &m.adj_face, adj_face) || dev_upload(c, &m.adj_other, adj_other) ||
       dev_upload(c, &m.adj_blk, adj_blk) || dev_upload(c, &m.diag_blk, diag) ||
-      dev_upload(c, &J.rowptr, J.h_rowptr) || dev_upload(c, &J.col, ell_col) ||
-      dev_alloc(c, &J.val, ell_size(np, N, J.W)))
+      dev_upload(c, &J.rowptr, J.h_rowptr) || dev_upload(c, &J.col, ell_col))
     return -1;
-  HIPCHK(c, hipMemset(J.val, 0, sizeof(double) * ell_size(np, N, J.W)));
+  // the flow system: the Jacobian on that pattern, the network's blocks on top, the solver settings of `opts`
+  LinSys& flow = c->flow;
+  double* jval = nullptr;
+  if (dev_alloc(c, &jval, ell_size(np, N, J.W))) return -1;
+  HIPCHK(c, hipMemset(jval, 0, sizeof(double) * ell_size(np, N, J.W)));
+  flow.A = matrix_on(J, np, jval);
+  flow.net_blocks = true;
+  flow.ksp = ksp_of(c->opts);
+  flow.kv = &c->kv;
+  c->aux.ksp.type = c->coupled.ksp.type = WAI_KSP_GMRES;   // the auxiliary problem's default (timestepper.F90:2021-2022; wai_set_aux_solver)
   {
     std::vector<int> cs(N, -1);
     if (dev_upload(c, &m.cell_src, cs)) return -1;
@@ -437,19 +482,12 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
     if (dev_alloc(c, p, nl + 16)) return -1;
     HIPCHK(c, hipMemset(*p, 0, (nl + 16) * sizeof(double)));
   }
-  Krylov& k = c->ks;
-  k.n = (int)n; k.nl = (int)nl;
-  double** kv[] = {&k.R, &k.RP, &k.P, &k.V, &k.S, &k.T, &k.tmp, &k.X};
-  for (auto p : kv) {
-    if (dev_alloc(c, p, nl + 16)) return -1;
-    HIPCHK(c, hipMemset(*p, 0, (nl + 16) * sizeof(double)));
-  }
+  flow.n = (int)n; flow.nl = (int)nl;
+  if (alloc_krylov_vecs(c, c->kv, nl)) return -1;
   if (c->opts.gmres_restart > MAX_RESTART) { c->err = "gmres restart above 40 is not supported"; return -2; }
-  k.basis_m = basis_vectors(c->opts.gmres_restart);
-  if (c->opts.ksp_type == WAI_KSP_GMRES || c->opts.ksp_type == WAI_KSP_LGMRES) {
-    if (dev_alloc(c, &k.basis, (size_t)(k.basis_m + 4) * nl)) return -1;
-    HIPCHK(c, hipMemset(k.basis, 0, (size_t)(k.basis_m + 4) * nl * sizeof(double)));
-  }
+  c->kv.basis_m = basis_vectors(c->opts.gmres_restart);   // (a basis of this size on first need: here, wai_set_opts, wai_tracer_solve)
+  if ((flow.ksp.type == WAI_KSP_GMRES || flow.ksp.type == WAI_KSP_LGMRES) && ensure_basis(c, flow, c->kv.basis_m)) return -1;
+  Krylov& k = c->ks;
   k.nb_max = std::max(1024, c->ilu.nsub);
   if (dev_alloc(c, &k.partials, (size_t)NSLOTS * k.nb_max) || dev_alloc(c, &k.scal, (size_t)NSCAL) ||
       dev_alloc(c, &k.partials2, (size_t)NSLOTS * FIN_MAXF))
@@ -496,22 +534,13 @@ const char* wai_last_error(wai_ctx* c) { return c ? c->err.c_str() : "null conte
 
 int wai_set_opts(wai_ctx* c, const wai_solver_opts* o) {
   if (!c || !o) return -2;
-  const int old_type = c->opts.ksp_type;
   if (o->pc_type < WAI_PC_BJACOBI || o->pc_type > WAI_PC_LU) { c->err = "unknown preconditioner type"; return -2; }
   if (o->ilu_levels < 0 || o->ilu_levels > 8) { c->err = "ILU(k): levels 0..8"; return -2; }
-  if (o->pc_type != c->opts.pc_type || o->asm_overlap != c->opts.asm_overlap || o->ilu_levels != c->opts.ilu_levels) c->ilu.factored = false;
+  if (o->pc_type != c->opts.pc_type || o->asm_overlap != c->opts.asm_overlap || o->ilu_levels != c->opts.ilu_levels) pc_invalidate(c);
   if (o->gmres_restart > MAX_RESTART) { c->err = "gmres restart above 40 is not supported"; return -2; }
   c->opts = *o;
-  (void)old_type;
-  if (o->ksp_type == WAI_KSP_GMRES || o->ksp_type == WAI_KSP_LGMRES) {
-    const int want = basis_vectors(o->gmres_restart);
-    if (!c->ks.basis || c->ks.basis_m < want) {
-      if (c->ks.basis) (void)hipFree(c->ks.basis);
-      c->ks.basis_m = want;
-      if (dev_alloc(c, &c->ks.basis, (size_t)(want + 4) * c->ks.nl)) return -1;   // + 2 error approximations + the update (lgmres)
-      HIPCHK(c, hipMemset(c->ks.basis, 0, (size_t)(want + 4) * c->ks.nl * sizeof(double)));
-    }
-  }
+  c->flow.ksp = ksp_of(c->opts);
+  if ((o->ksp_type == WAI_KSP_GMRES || o->ksp_type == WAI_KSP_LGMRES) && ensure_basis(c, c->flow, basis_vectors(o->gmres_restart))) return -1;
   return 0;
 }
 
@@ -639,7 +668,7 @@ int wai_set_sources(wai_ctx* c, int n, const int* cell, const double* rate, cons
   c->net.h_enth0 = ve;
   c->net.h_cell.assign(vc.begin(), vc.begin() + n);
   c->net.coupling = coupling; c->net.cp_in_pc = cp_in_pc;
-  c->as.overlap = -1;   // an extended system built for another network's cells is stale
+  c->flow.as.overlap = -1;   // an extended system built for another network's cells is stale
   return 0;
 }
 
@@ -888,13 +917,13 @@ int wai_pre_iteration(wai_ctx* c) {
 
 // copy the owned part of a caller vector into an nl-sized work vector (halo room)
 static int to_work(wai_ctx* c, const double* y, double* work) {
-  const size_t n = c->ks.n;
+  const size_t n = c->flow.n;
   if (is_device_ptr(y)) HIPCHK(c, hipMemcpyAsync(work, y, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   else HIPCHK(c, hipMemcpyAsync(work, y, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 static int from_work(wai_ctx* c, const double* work, double* y) {
-  const size_t n = c->ks.n;
+  const size_t n = c->flow.n;
   if (is_device_ptr(y)) HIPCHK(c, hipMemcpyAsync(y, work, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   else HIPCHK(c, hipMemcpyAsync(y, work, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -912,7 +941,7 @@ int wai_lhs(wai_ctx* c, double t, const double* y, double* lhs) {
   (void)t; (void)y;
   if (!c || !lhs) return -2;
   VecArg o{c};
-  if (o.out_only(lhs, c->ks.n, 0)) return -1;
+  if (o.out_only(lhs, c->flow.n, 0)) return -1;
   {
     Prof p(c, KC_RESIDUAL);
     launch_residual(c, 0.0, nullptr, nullptr, o.dev, nullptr);
@@ -924,7 +953,7 @@ int wai_rhs(wai_ctx* c, double t, const double* y, double* rhs) {
   (void)t; (void)y;
   if (!c || !rhs) return -2;
   VecArg o{c};
-  if (o.out_only(rhs, c->ks.n, 0)) return -1;
+  if (o.out_only(rhs, c->flow.n, 0)) return -1;
   if (c->net.on && network_update(c)) return -1;
   {
     Prof p(c, KC_RESIDUAL);
@@ -939,7 +968,7 @@ int wai_set_residual_form(wai_ctx* c, int method, double ratio, const double* lh
   if (method == WAI_METHOD_BDF2) {
     if (!lhs_last2 || !(ratio > 0.0)) { c->err = "BDF2 needs a step size ratio > 0 and the lhs two steps back"; return -1; }
     if (lhs_last2 != c->w_lhs2) {
-      HIPCHK(c, hipMemcpyAsync(c->w_lhs2, lhs_last2, sizeof(double) * c->ks.n, hipMemcpyDefault, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->w_lhs2, lhs_last2, sizeof(double) * c->flow.n, hipMemcpyDefault, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
   }
@@ -963,7 +992,7 @@ int wai_residual(wai_ctx* c, double t, double dt, const double* y, const double*
   (void)t;
   if (!c || !y || !lhs_old || !f) return -2;
   VecArg lo{c}, fo{c};
-  if (to_work(c, y, c->w_y) || lo.in(lhs_old, c->ks.n, 1) || fo.out_only(f, c->ks.n, 2)) return -1;
+  if (to_work(c, y, c->w_y) || lo.in(lhs_old, c->flow.n, 1) || fo.out_only(f, c->flow.n, 2)) return -1;
   const int e = do_residual(c, dt, c->w_y, lo.dev, fo.dev);
   if (e) return e;
   return fo.back();
@@ -973,26 +1002,26 @@ int wai_jacobian(wai_ctx* c, double t, double dt, const double* y, const double*
   (void)t;
   if (!c || !y || !lhs_old) return -2;
   VecArg lo{c};
-  if (to_work(c, y, c->w_y) || lo.in(lhs_old, c->ks.n, 1)) return -1;
+  if (to_work(c, y, c->w_y) || lo.in(lhs_old, c->flow.n, 1)) return -1;
   if (c->comm && c->mesh.n_halo && halo_exchange(c, c->w_y, c->np)) return -1;
   return do_jacobian(c, dt, c->w_y, lo.dev);
 }
 
-int wai_jacobian_nnzb(wai_ctx* c) { return c ? c->J.nnzb : -2; }
+int wai_jacobian_nnzb(wai_ctx* c) { return c ? c->pat.nnzb : -2; }
 
 int wai_jacobian_pattern(wai_ctx* c, int* rowptr, int* colidx) {
   if (!c || !rowptr || !colidx) return -2;
-  std::memcpy(rowptr, c->J.h_rowptr.data(), sizeof(int) * (c->J.n + 1));
-  std::memcpy(colidx, c->J.h_colidx.data(), sizeof(int) * c->J.nnzb);
+  std::memcpy(rowptr, c->pat.h_rowptr.data(), sizeof(int) * (c->pat.n + 1));
+  std::memcpy(colidx, c->pat.h_colidx.data(), sizeof(int) * c->pat.nnzb);
   return 0;
 }
 
 int wai_jacobian_get_values(wai_ctx* c, double* val) {
   if (!c || !val) return -2;
-  const size_t n = (size_t)c->J.nnzb * c->np * c->np;
+  const size_t n = (size_t)c->pat.nnzb * c->np * c->np;
   double* tmp = nullptr;
   if (dev_alloc(c, &tmp, n)) return -1;
-  launch_ell_to_bcsr(c, c->J.val, tmp);
+  launch_ell_to_bcsr(c, c->flow.A, tmp);
   hipError_t e = hipMemcpyAsync(val, tmp, n * sizeof(double),
                                 is_device_ptr(val) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1003,15 +1032,15 @@ int wai_jacobian_get_values(wai_ctx* c, double* val) {
 
 int wai_jacobian_set_values(wai_ctx* c, const double* val) {
   if (!c || !val) return -2;
-  const size_t n = (size_t)c->J.nnzb * c->np * c->np;
+  const size_t n = (size_t)c->pat.nnzb * c->np * c->np;
   double* tmp = nullptr;
   if (dev_alloc(c, &tmp, n)) return -1;
   hipError_t e = hipMemcpyAsync(tmp, val, n * sizeof(double),
                                 is_device_ptr(val) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) { launch_bcsr_to_ell(c, tmp, c->J.val); e = hipStreamSynchronize(c->stream); }
+  if (e == hipSuccess) { launch_bcsr_to_ell(c, tmp, c->flow.A); e = hipStreamSynchronize(c->stream); }
   (void)hipFree(tmp);
   HIPCHK(c, e);
-  c->ilu.factored = false;
+  pc_invalidate(c, c->flow);
   c->net.cp_valid = false;   // values from outside: the network's blocks of the last wai_jacobian no longer belong
   return 0;
 }
@@ -1022,25 +1051,25 @@ int wai_spmv(wai_ctx* c, const double* x, double* y) {
   double* xd;
   if (is_device_ptr(x) && (!c->comm || c->mesh.n_halo == 0)) xd = const_cast<double*>(x);
   else { if (to_work(c, x, c->w_a)) return -1; xd = c->w_a; if (halo_exchange(c, xd, c->np)) return -1; }
-  if (yo.out_only(y, c->ks.n, 1)) return -1;
+  if (yo.out_only(y, c->flow.n, 1)) return -1;
   {
     Prof p(c, KC_SPMV);
-    if (apply_operator(c, xd, yo.dev)) return -1;
+    if (apply_operator(c, c->flow, xd, yo.dev)) return -1;
   }
   return yo.back();
 }
 
-int wai_pc_setup(wai_ctx* c) { return c ? do_pc_setup(c) : -2; }
+int wai_pc_setup(wai_ctx* c) { return c ? do_pc_setup(c, c->flow) : -2; }
 
 int wai_pc_apply(wai_ctx* c, const double* r, double* z) {
   if (!c || !r || !z) return -2;
   read_env(c);
-  if (!c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e; }
+  if (c->ilu.owner != &c->flow) { const int e = do_pc_setup(c, c->flow); if (e) return e; }
   VecArg ri{c}, zo{c};
-  if (ri.in(r, c->ks.n, 0) || zo.out_only(z, c->ks.n, 1)) return -1;
+  if (ri.in(r, c->flow.n, 0) || zo.out_only(z, c->flow.n, 1)) return -1;
   {
     Prof p(c, KC_PC_APPLY);
-    if (pc_solve(c, ri.dev, zo.dev, PC_DOT_NONE, nullptr, nullptr)) return -1;
+    if (pc_solve(c, c->flow, ri.dev, zo.dev, PC_DOT_NONE, nullptr, nullptr)) return -1;
   }
   return zo.back();
 }
@@ -1048,8 +1077,8 @@ int wai_pc_apply(wai_ctx* c, const double* r, double* z) {
 int wai_ksp_solve(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
   if (!c || !b || !x || !its || !reason || !rnorm) return -2;
   VecArg bi{c}, xo{c};
-  if (bi.in(b, c->ks.n, 0) || xo.out_only(x, c->ks.n, 1)) return -1;
-  if (do_ksp(c, bi.dev, xo.dev, its, reason, rnorm)) return -1;
+  if (bi.in(b, c->flow.n, 0) || xo.out_only(x, c->flow.n, 1)) return -1;
+  if (do_ksp(c, c->flow, bi.dev, xo.dev, its, reason, rnorm)) return -1;
   return xo.back();
 }
 
@@ -1069,15 +1098,24 @@ int wai_set_tracers(wai_ctx* c, int n, const int* phase, const double* decay, co
   }
   t.nt = n;
   auto F = [](double*& p) { if (p) (void)hipFree(p); p = nullptr; };
-  F(t.bc); F(t.inj); F(t.val);
-  F(t.valb); F(t.fvalb); F(t.rhsb); F(t.kbasis);   // the coupled mode's buffers are sized by nt: rebuilt on first use
-  for (auto& p : t.kvec) F(p);
-  t.kbasis_m = 0;
+  F(t.bc); F(t.inj); F(t.rhsb);
+  // the scalar system: block size 1 on the mesh's pattern, the flow's work vectors and basis (LinSys: the alias and the clamp)
+  LinSys& aux = c->aux;
+  F(aux.A.val);
+  aux.n = c->mesh.n_owned; aux.nl = c->mesh.n_prim; aux.kv = &c->kv;
+  // the coupled system's buffers are sized by nt: rebuilt on first use (coupled_system_buffers, coupled_prepare)
+  LinSys& cp = c->coupled;
+  F(cp.A.val); F(cp.A.fdg);
+  free_krylov_vecs(c->kv_coupled);
+  cp.n = c->mesh.n_owned * n; cp.nl = c->mesh.n_prim * n; cp.kv = &c->kv_coupled;
+  pc_invalidate(c, cp);
   if (n == 0) return 0;
   const size_t nbc = (size_t)std::max(c->mesh.n_bc, 1) * n, nsrc = (size_t)std::max(c->src.n, 1) * n;
-  if (dev_alloc(c, &t.bc, nbc) || dev_alloc(c, &t.inj, nsrc) ||
-      dev_alloc(c, &t.val, (size_t)c->J.W * c->J.n))
-    return -1;
+  double* val = nullptr;
+  if (dev_alloc(c, &t.bc, nbc) || dev_alloc(c, &t.inj, nsrc) || dev_alloc(c, &val, (size_t)c->pat.W * c->pat.n)) return -1;
+  aux.A = matrix_on(c->pat, 1, val);
+  cp.A = matrix_on(c->pat, n, nullptr);
+  cp.A.dg = n;
   HIPCHK(c, hipMemset(t.bc, 0, nbc * sizeof(double)));
   HIPCHK(c, hipMemset(t.inj, 0, nsrc * sizeof(double)));
   return 0;
@@ -1109,11 +1147,13 @@ int wai_set_aux_solver(wai_ctx* c, int ksp_type, int gmres_restart, double rtol,
   if (!c) return -2;
   if (ksp_type != WAI_KSP_BCGS && ksp_type != WAI_KSP_GMRES) { c->err = "unknown KSP type"; return -1; }
   if (gmres_restart > MAX_RESTART) { c->err = "gmres restart above 40 is not supported"; return -1; }
-  c->tr.ksp_type = ksp_type;
-  if (gmres_restart > 0) c->tr.restart = gmres_restart;
-  if (rtol > 0.0) c->tr.rtol = rtol;
-  if (atol > 0.0) c->tr.atol = atol;
-  if (max_its > 0) c->tr.max_its = max_its;
+  KspOpts& k = c->aux.ksp;
+  k.type = ksp_type;
+  if (gmres_restart > 0) k.restart = gmres_restart;
+  if (rtol > 0.0) k.rtol = rtol;
+  if (atol > 0.0) k.atol = atol;
+  if (max_its > 0) k.max_its = max_its;
+  c->coupled.ksp = k;   // one setting for the auxiliary problem, whichever way it is solved
   return 0;
 }
 
@@ -1138,76 +1178,21 @@ int wai_tracer_lhs(wai_ctx* c, double* Al) {
 
 namespace wai {
 
-// The Krylov drivers work on c->J / c->ilu / c->ks / c->np; for the scalar tracer systems those
-// are pointed at the auxiliary matrix (same sparsity, block size 1) for the scope's lifetime.
-struct AuxScope {
-  wai_ctx* c;
-  int np, n, nl, bs, ksp_type, restart, max_its;
-  double* val; double rtol, atol;
-  bool cp_valid;
-  explicit AuxScope(wai_ctx* c_) : c(c_) {
-    // the network's coupling blocks E belong to the flow Jacobian, and the extended ASM system is laid
-    // out for its block size: the scalar systems get their own (built on first use)
-    cp_valid = c->net.cp_valid; c->net.cp_valid = false;
-    std::swap(c->as, c->as_aux);
-    np = c->np; n = c->ks.n; nl = c->ks.nl; bs = c->J.bs; val = c->J.val;
-    ksp_type = c->opts.ksp_type; restart = c->opts.gmres_restart; max_its = c->opts.ksp_max_its;
-    rtol = c->opts.ksp_rtol; atol = c->opts.ksp_atol;
-    c->np = 1; c->ks.n = c->mesh.n_owned; c->ks.nl = c->mesh.n_prim; c->J.bs = 1; c->J.val = c->tr.val;
-    c->opts.ksp_type = c->tr.ksp_type; c->opts.gmres_restart = c->tr.restart;
-    c->opts.ksp_max_its = c->tr.max_its; c->opts.ksp_rtol = c->tr.rtol; c->opts.ksp_atol = c->tr.atol;
-    c->ilu.factored = false;
-  }
-  ~AuxScope() {
-    c->np = np; c->ks.n = n; c->ks.nl = nl; c->J.bs = bs; c->J.val = val;
-    c->opts.ksp_type = ksp_type; c->opts.gmres_restart = restart; c->opts.ksp_max_its = max_its;
-    c->opts.ksp_rtol = rtol; c->opts.ksp_atol = atol;
-    c->net.cp_valid = cp_valid;
-    std::swap(c->as, c->as_aux);
-    c->ilu.factored = false;  // the factor buffers now hold a tracer system's factor
-  }
-};
-
-// The coupled tracer system: the drivers see ONE system of block size nt -- c->J's values are the nt diagonals per slot
-// (Bcsr::dg), the Krylov vectors are the tracers' own (nt * n_prim entries; the flow's have np), the halo exchange
-// carries nt doubles per cell.  The schedule (levels, bricks) is the flow Jacobian's: it depends on the pattern alone.
-struct CoupledScope {
-  wai_ctx* c;
-  AuxScope aux;
-  Krylov saved;
-  int dg; double* fdg;
-  explicit CoupledScope(wai_ctx* c_) : c(c_), aux(c_), saved(c_->ks), dg(c_->J.dg), fdg(c_->J.fdg) {
-    Tracers& t = c->tr;
-    const int nt = t.nt;
-    c->np = nt; c->J.bs = nt; c->J.dg = nt; c->J.val = t.valb; c->J.fdg = t.fvalb;
-    Krylov& k = c->ks;
-    k.n = c->mesh.n_owned * nt; k.nl = c->mesh.n_prim * nt;
-    double** kv[] = {&k.R, &k.RP, &k.P, &k.V, &k.S, &k.T, &k.tmp, &k.X};
-    for (int i = 0; i < 8; i++) *kv[i] = t.kvec[i];
-    k.basis = t.kbasis; k.basis_m = t.kbasis_m; k.bl = nullptr;   // (wai_set_aux_solver: bcgs or gmres, no BiCGStab(L))
-  }
-  ~CoupledScope() {
-    Krylov& k = c->ks;
-    saved.n_launch = k.n_launch; saved.n_copy = k.n_copy; saved.seq = k.seq;
-    c->ks = saved;
-    c->J.dg = dg; c->J.fdg = fdg;   // (np, bs, val, n, nl: AuxScope)
-  }
-};
-
 // the coupled system's own buffers (values, factor, right-hand side), on first use after wai_set_tracers
 static int coupled_system_buffers(wai_ctx* c) {
   Tracers& t = c->tr;
-  const size_t nl = (size_t)c->mesh.n_prim * t.nt, nv = (size_t)c->J.W * t.nt * c->J.n;
-  if (!t.valb && dev_alloc(c, &t.valb, nv)) return -1;
-  if (!t.fvalb && dev_alloc(c, &t.fvalb, nv)) return -1;
-  if (!t.rhsb && dev_alloc(c, &t.rhsb, nl + 16)) return -1;
+  Bcsr& A = c->coupled.A;
+  const size_t nv = (size_t)A.W * t.nt * A.n;
+  if (!A.val && dev_alloc(c, &A.val, nv)) return -1;
+  if (!A.fdg && dev_alloc(c, &A.fdg, nv)) return -1;
+  if (!t.rhsb && dev_alloc(c, &t.rhsb, (size_t)c->coupled.nl + 16)) return -1;
   return 0;
 }
 
 // ... and what a coupled SOLVE needs beside them: the Krylov vectors of nt * n_prim entries, the GMRES basis, halo buffers
 // of nt values per cell.  What the mode does not cover is refused by name
 static int coupled_prepare(wai_ctx* c) {
-  Tracers& t = c->tr;
+  LinSys& sys = c->coupled;
   const char* what = nullptr;
   if (c->opts.pc_type == WAI_PC_ASM) what = "the asm preconditioner";
   else if (c->opts.pc_type == WAI_PC_LU) what = "the lu preconditioner";
@@ -1218,21 +1203,31 @@ static int coupled_prepare(wai_ctx* c) {
              ": block Jacobi ILU(0) or none only; use WAI_TRACER_PER_TRACER";
     return -2;
   }
-  if (coupled_system_buffers(c)) return -1;
-  const size_t nl = (size_t)c->mesh.n_prim * t.nt;
-  for (auto& p : t.kvec) {
-    if (p) continue;
-    if (dev_alloc(c, &p, nl + 16)) return -1;
-    HIPCHK(c, hipMemset(p, 0, (nl + 16) * sizeof(double)));
-  }
-  if (t.ksp_type == WAI_KSP_GMRES && (!t.kbasis || t.kbasis_m < basis_vectors(t.restart))) {
-    if (t.kbasis) (void)hipFree(t.kbasis);
-    t.kbasis_m = basis_vectors(t.restart);
-    if (dev_alloc(c, &t.kbasis, (size_t)(t.kbasis_m + 4) * nl)) return -1;
-    HIPCHK(c, hipMemset(t.kbasis, 0, (size_t)(t.kbasis_m + 4) * nl * sizeof(double)));
-  }
-  if (c->comm && c->mesh.n_halo && ensure_halo_dof(c, t.nt)) return -1;
+  if (coupled_system_buffers(c) || alloc_krylov_vecs(c, *sys.kv, (size_t)sys.nl)) return -1;
+  if (sys.ksp.type == WAI_KSP_GMRES && ensure_basis(c, sys, basis_vectors(sys.ksp.restart))) return -1;
+  if (c->comm && c->mesh.n_halo && ensure_halo_dof(c, c->tr.nt)) return -1;
   return 0;
+}
+
+// what wai_tracer_system (tracer: its index), wai_tracer_block_system and wai_tracer_solve (tracer: null; ratio: the solve
+// checks it with the BDF2 history) refuse alike
+static int tracer_args(wai_ctx* c, const int* tracer, int method, const double* alx_last, const double* alx_last2,
+                       const double* ratio = nullptr) {
+  if (tracer && (*tracer < 0 || *tracer >= c->tr.nt)) { c->err = "tracer index out of range"; return -1; }
+  if (!tracer && !c->tr.nt) { c->err = "no tracers set"; return -1; }
+  if (method < WAI_METHOD_BEULER || method > WAI_METHOD_DIRECTSS) { c->err = "unknown time stepping method"; return -1; }
+  if (method != WAI_METHOD_DIRECTSS && !alx_last) return -2;
+  if (method == WAI_METHOD_BDF2 && ratio && (!alx_last2 || !(*ratio > 0.0))) { c->err = "BDF2 needs a step size ratio > 0 and Al o X two steps back"; return -1; }
+  if (method == WAI_METHOD_BDF2 && !alx_last2) return -2;
+  return 0;
+}
+
+static TracerForm tracer_form(const Tracers& t, int it, int method, double dt, double ratio) {
+  TracerForm tf;
+  tf.method = method; tf.it = it; tf.nt = t.nt; tf.phase = t.phase[it];
+  tf.dt = dt; tf.ratio = ratio; tf.decay = t.decay[it]; tf.activation = t.activation[it];
+  tf.diffusion = t.diffusion[it];
+  return tf;
 }
 
 }  // namespace wai
@@ -1242,21 +1237,17 @@ extern "C" {
 int wai_tracer_block_system(wai_ctx* c, int method, double dt, double ratio, const double* alx_last,
                             const double* alx_last2, double* val, double* b) {
   if (!c || !val || !b) return -2;
+  if (int e = tracer_args(c, nullptr, method, alx_last, alx_last2)) return e;
   Tracers& t = c->tr;
-  if (!t.nt) { c->err = "no tracers set"; return -1; }
-  if (method < WAI_METHOD_BEULER || method > WAI_METHOD_DIRECTSS) { c->err = "unknown time stepping method"; return -1; }
-  if (method != WAI_METHOD_DIRECTSS && !alx_last) return -2;
-  if (method == WAI_METHOD_BDF2 && !alx_last2) return -2;
   if (coupled_system_buffers(c)) return -1;   // the system alone: no solver buffers, whatever the preconditioner
+  const Bcsr& A = c->coupled.A;
   const size_t nx = (size_t)c->mesh.n_owned * t.nt;
   VecArg a1{c}, a2{c};
   if (a1.in(alx_last, nx, 0) || a2.in(alx_last2, nx, 1)) return -1;
   if (launch_tracer_assemble_all(c, method, dt, ratio, a1.dev, a2.dev, t.rhsb)) return -1;
-  {
-    CoupledScope scope(c);
-    launch_dg_to_bcsr(c, c->J, t.fvalb);   // the factor buffer as scratch: nnzb * nt <= W * nt * n
-  }
-  HIPCHK(c, hipMemcpyAsync(val, t.fvalb, sizeof(double) * (size_t)c->J.nnzb * t.nt, hipMemcpyDefault, c->stream));
+  launch_dg_to_bcsr(c, A, A.fdg);   // the factor buffer as scratch: nnzb * nt <= W * nt * n
+  pc_invalidate(c);   // (as it always has: the next solve of any system sets up again)
+  HIPCHK(c, hipMemcpyAsync(val, A.fdg, sizeof(double) * (size_t)A.nnzb * t.nt, hipMemcpyDefault, c->stream));
   HIPCHK(c, hipMemcpyAsync(b, t.rhsb, sizeof(double) * nx, hipMemcpyDefault, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -1265,25 +1256,16 @@ int wai_tracer_block_system(wai_ctx* c, int method, double dt, double ratio, con
 int wai_tracer_system(wai_ctx* c, int tracer, int method, double dt, double ratio, const double* alx_last,
                       const double* alx_last2, double* val, double* b) {
   if (!c || !val || !b) return -2;
+  if (int e = tracer_args(c, &tracer, method, alx_last, alx_last2)) return e;
   Tracers& t = c->tr;
-  if (tracer < 0 || tracer >= t.nt) { c->err = "tracer index out of range"; return -1; }
-  if (method < WAI_METHOD_BEULER || method > WAI_METHOD_DIRECTSS) { c->err = "unknown time stepping method"; return -1; }
-  if (method != WAI_METHOD_DIRECTSS && !alx_last) return -2;
-  if (method == WAI_METHOD_BDF2 && !alx_last2) return -2;
   const size_t nx = (size_t)c->mesh.n_owned * t.nt;
   VecArg a1{c}, a2{c};
   if (a1.in(alx_last, nx, 0) || a2.in(alx_last2, nx, 1)) return -1;
-  TracerForm tf;
-  tf.method = method; tf.it = tracer; tf.nt = t.nt; tf.phase = t.phase[tracer];
-  tf.dt = dt; tf.ratio = ratio; tf.decay = t.decay[tracer]; tf.activation = t.activation[tracer];
-  tf.diffusion = t.diffusion[tracer];
-  if (launch_tracer_assemble(c, tf, a1.dev, a2.dev, c->w_a)) return -1;
+  if (launch_tracer_assemble(c, tracer_form(t, tracer, method, dt, ratio), a1.dev, a2.dev, c->w_a)) return -1;
   double* tmp = c->stage[2];  // nnzb scalars fit the staging buffer (>= 23 doubles per cell)
-  {
-    AuxScope scope(c);
-    launch_ell_to_bcsr(c, c->J.val, tmp);
-  }
-  HIPCHK(c, hipMemcpyAsync(val, tmp, sizeof(double) * c->J.nnzb, hipMemcpyDefault, c->stream));
+  launch_ell_to_bcsr(c, c->aux.A, tmp);
+  pc_invalidate(c);   // (as it always has: the next solve of any system sets up again)
+  HIPCHK(c, hipMemcpyAsync(val, tmp, sizeof(double) * c->pat.nnzb, hipMemcpyDefault, c->stream));
   HIPCHK(c, hipMemcpyAsync(b, c->w_a, sizeof(double) * c->mesh.n_owned, hipMemcpyDefault, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -1292,59 +1274,41 @@ int wai_tracer_system(wai_ctx* c, int tracer, int method, double dt, double rati
 int wai_tracer_solve(wai_ctx* c, int method, double dt, double ratio, const double* alx_last,
                      const double* alx_last2, double* X, double* alx_new, int* its, int* reason) {
   if (!c || !X || !alx_new || !its || !reason) return -2;
+  if (int e = tracer_args(c, nullptr, method, alx_last, alx_last2, &ratio)) return e;
   Tracers& t = c->tr;
-  if (!t.nt) { c->err = "no tracers set"; return -1; }
-  if (method < WAI_METHOD_BEULER || method > WAI_METHOD_DIRECTSS) { c->err = "unknown time stepping method"; return -1; }
-  if (method != WAI_METHOD_DIRECTSS && !alx_last) return -2;
-  if (method == WAI_METHOD_BDF2 && (!alx_last2 || !(ratio > 0.0))) { c->err = "BDF2 needs a step size ratio > 0 and Al o X two steps back"; return -1; }
   const size_t nx = (size_t)c->mesh.n_owned * t.nt;
   VecArg a1{c}, a2{c}, xx{c}, an{c};
   if (a1.in(alx_last, nx, 0) || a2.in(alx_last2, nx, 1) || xx.in(X, nx, 2) || an.out_only(alx_new, nx, 3)) return -1;
   *its = 0;
   *reason = 100;
-  int rc = 0;
   if (t.mode == WAI_TRACER_COUPLED && t.nt > 1) {
     // one assembly sweep, one factorisation, ONE Krylov solve on the [cell][tracer] vector (timestepper.F90:2345-2355):
     // its iteration count, its reason, the combined preconditioned residual norm against rtol / atol
+    LinSys& sys = c->coupled;
     if (int e = coupled_prepare(c)) return e;
     if (launch_tracer_assemble_all(c, method, dt, ratio, a1.dev, a2.dev, t.rhsb)) return -1;
-    {
-      CoupledScope scope(c);
-      double rn = 0.0;
-      vec_zero(c, xx.dev, c->ks.n);  // a failed factorisation returns before the solver zeroes it
-      rc = do_ksp(c, t.rhsb, xx.dev, its, reason, &rn) ? -1 : 0;
-    }
-    if (rc) return rc;
-    launch_tracer_alx(c, xx.dev, an.dev);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (xx.back() || an.back()) return -1;
-    return 0;
-  }
-  if (t.ksp_type == WAI_KSP_GMRES && !c->ks.basis) {  // the flow solver may never have needed one
-    if (dev_alloc(c, &c->ks.basis, (size_t)(c->ks.basis_m + 4) * c->ks.nl)) return -1;
-    HIPCHK(c, hipMemset(c->ks.basis, 0, (size_t)(c->ks.basis_m + 4) * c->ks.nl * sizeof(double)));
-  }
-  {
-    AuxScope scope(c);
+    pc_invalidate(c, sys);
+    double rn = 0.0;
+    vec_zero(c, xx.dev, sys.n);  // a failed factorisation returns before the solver zeroes it
+    if (do_ksp(c, sys, t.rhsb, xx.dev, its, reason, &rn)) return -1;
+  } else {
+    LinSys& sys = c->aux;
+    // the flow solver may never have needed a basis: the one it would have
+    if (sys.ksp.type == WAI_KSP_GMRES && !c->kv.basis && ensure_basis(c, c->flow, c->kv.basis_m)) return -1;
     double* b = c->w_a;
     double* x = c->w_c;
-    for (int it = 0; it < t.nt && !rc; it++) {
-      TracerForm tf;
-      tf.method = method; tf.it = it; tf.nt = t.nt; tf.phase = t.phase[it];
-      tf.dt = dt; tf.ratio = ratio; tf.decay = t.decay[it]; tf.activation = t.activation[it];
-      tf.diffusion = t.diffusion[it];
-      if (launch_tracer_assemble(c, tf, a1.dev, a2.dev, b)) { rc = -1; break; }
-      c->ilu.factored = false;
+    for (int it = 0; it < t.nt; it++) {
+      if (launch_tracer_assemble(c, tracer_form(t, it, method, dt, ratio), a1.dev, a2.dev, b)) return -1;
+      pc_invalidate(c, sys);   // new values: one factorisation per tracer
       int k = 0, r = 0;
       double rn = 0.0;
-      vec_zero(c, x, c->ks.n);  // a failed factorisation returns before the solver zeroes it
-      if (do_ksp(c, b, x, &k, &r, &rn)) { rc = -1; break; }
+      vec_zero(c, x, sys.n);  // a failed factorisation returns before the solver zeroes it
+      if (do_ksp(c, sys, b, x, &k, &r, &rn)) return -1;
       *its += k;
       if (r < *reason) *reason = r;
       launch_tracer_put(c, x, it, xx.dev);
     }
   }
-  if (rc) return rc;
   launch_tracer_alx(c, xx.dev, an.dev);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (xx.back() || an.back()) return -1;
@@ -1354,7 +1318,7 @@ int wai_tracer_solve(wai_ctx* c, int method, double dt, double ratio, const doub
 int wai_max_scaled(wai_ctx* c, const double* v, const double* scale, double tol, double* val, int* idx) {
   if (!c || !v || !scale || !val || !idx) return -2;
   VecArg a{c}, b{c};
-  if (a.in(v, c->ks.n, 0) || b.in(scale, c->ks.n, 1)) return -1;
+  if (a.in(v, c->flow.n, 0) || b.in(scale, c->flow.n, 1)) return -1;
   return do_max_scaled(c, a.dev, b.dev, tol, val, idx);
 }
 
@@ -1362,7 +1326,7 @@ int wai_post_linesearch(wai_ctx* c, const double* y_old, double* search, double*
                         int* changed_y) {
   if (!c || !y_old || !search || !y) return -2;
   VecArg a{c}, s{c}, yy{c};
-  if (a.in(y_old, c->ks.n, 0) || s.in(search, c->ks.n, 1) || yy.in(y, c->ks.n, 2)) return -1;
+  if (a.in(y_old, c->flow.n, 0) || s.in(search, c->flow.n, 1) || yy.in(y, c->flow.n, 2)) return -1;
   {
     Prof p(c, KC_TRANSITIONS);
     launch_transitions(c, a.dev, s.dev, yy.dev);
@@ -1380,7 +1344,7 @@ int wai_newton_step(wai_ctx* c, double t, double dt, int iter, double* y, const 
   (void)t;
   if (!c || !y || !lhs_old || !f || !ksp_its || !reason || !max_residual) return -2;
   VecArg lo{c}, ff{c};
-  if (to_work(c, y, c->w_y) || lo.in(lhs_old, c->ks.n, 1) || ff.in(f, c->ks.n, 2)) return -1;
+  if (to_work(c, y, c->w_y) || lo.in(lhs_old, c->flow.n, 1) || ff.in(f, c->flow.n, 2)) return -1;
   if (c->comm && c->mesh.n_halo && halo_exchange(c, c->w_y, c->np)) return -1;
   if (do_newton_step(c, dt, iter, c->w_y, lo.dev, ff.dev, ksp_its, reason, max_residual)) return -1;
   if (from_work(c, c->w_y, y)) return -1;
@@ -1390,7 +1354,7 @@ int wai_newton_step(wai_ctx* c, double t, double dt, int iter, double* y, const 
 int wai_timestep(wai_ctx* c, double t, double dt, double* y, int* newton_its, int* ksp_its, int* reason) {
   (void)t;
   if (!c || !y || !newton_its || !ksp_its || !reason) return -2;
-  const int n = c->ks.n;
+  const int n = c->flow.n;
   *newton_its = 0; *ksp_its = 0; *reason = 0;
   if (to_work(c, y, c->w_y)) return -1;
   if (snapshot_step(c)) return -1;

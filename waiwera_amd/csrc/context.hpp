@@ -199,6 +199,9 @@ struct Network {
 // rowptr[i] + s: the BCSR arrays (rowptr / colidx on the host) remain the exchange format of
 // the C ABI, the device layout is what lets one-thread-per-row kernels read and write fully
 // coalesced (64 consecutive doubles per wave instruction).
+// A Bcsr is a VIEW handed to the launchers: it owns nothing.  The three systems on the mesh's pattern (LinSys below)
+// share n, ncols, nnzb, W, col and rowptr (wai_ctx::pat) and differ in bs, val, dg and fdg; an extended ASM system's E
+// has a pattern of its own (AsmSystem).
 struct Bcsr {
   int n = 0, ncols = 0, nnzb = 0, bs = 0, W = 0;
   int* col = nullptr;
@@ -209,9 +212,17 @@ struct Bcsr {
   // interleaved [row][t].  fdg: its ILU(0) factor in the same layout (diagonal slot: the inverted pivot)
   int dg = 0;
   double* fdg = nullptr;
+};
+// The sparsity pattern of the mesh (the cell itself and its neighbours among the owned and ghost cells), single and shared:
+// built, owned and freed once (wai_ctx_create / free_all); every LinSys' matrix is a view on it
+struct Pattern {
+  int n = 0, ncols = 0, nnzb = 0, W = 0;
+  int* col = nullptr;     // block-ELL column planes [W][n]
+  int* rowptr = nullptr;  // device copy of h_rowptr
   std::vector<int> h_rowptr, h_colidx;
 };
 
+struct LinSys;
 // Block-Jacobi ILU(0): one workgroup per subdomain, one thread per block row.
 struct IluSchedule {
   int nsub = 0, max_rows = 0, max_lev = 0;
@@ -253,7 +264,6 @@ struct IluSchedule {
   int* sub_seg = nullptr;            // [nsub][8]
   bool level_sorted = false;  // every subdomain's rows are stored in dependency-level order (forward levels non-decreasing,
                               // backward levels non-increasing with the row index)
-  bool factored = false;
   // subdomains of more than 1024 rows ("one block per rank", sub_ptr = NULL, is the reference's
   // PCBJACOBI / PCASM default): rows of equal dependency level are independent across all
   // subdomains, so the factorisation and the two substitutions run as one launch per level over
@@ -264,6 +274,10 @@ struct IluSchedule {
   int* ord_b = nullptr;       // ... by backward level
   std::vector<int> lev_f_ptr, lev_b_ptr;   // host: row ranges of each level in ord_f / ord_b
   bool built = false;
+  // wai_ctx::ilu only: the system whose preconditioner is set up now (null: none) -- the factor buffers above are shared by
+  // the flow and the scalar tracer systems, and one record serves the extended systems' and the coupled system's own
+  // buffers too.  Set by do_pc_setup; pc_invalidate when a system's values or the preconditioner's kind change
+  const LinSys* owner = nullptr;
 };
 // threads of a brick kernel's workgroup: one per row of the largest subdomain, whole waves
 inline int pc_threads(const IluSchedule& s) { return ((s.max_rows + 63) / 64) * 64; }
@@ -322,8 +336,8 @@ struct ResForm {
   const double* last2 = nullptr;  // BDF2: lhs one step further back
 };
 
-// Passive tracers (src/tracer.F90:30-40) and the auxiliary linear problem's solver settings
-// (timestepper.F90:2021-2022, 2061-2064: gmres + bjacobi unless configured)
+// Passive tracers (src/tracer.F90:30-40).  Their two linear systems -- one scalar system at a time, or all nt coupled -- are
+// wai_ctx::aux and wai_ctx::coupled (LinSys below), which hold the values, the solver settings and the work vectors.
 constexpr int MAX_TRACERS = 8;
 constexpr int POST_OFF = 64;   // h_scal[POST_OFF ..+2]: {(R,R), 8 * sequence number + code, check word} posted by the device (post_scalars)
 constexpr unsigned long long POST_KEY = 0x5bd1e995a5a5c3c3ull;   // check = bits((R,R)) ^ bits(tag) ^ POST_KEY: zeroed memory never verifies
@@ -333,18 +347,15 @@ struct Tracers {
   double decay[MAX_TRACERS] = {0}, activation[MAX_TRACERS] = {0}, diffusion[MAX_TRACERS] = {0};
   double* bc = nullptr;    // [n_bc][nt] Dirichlet mass fractions
   double* inj = nullptr;   // [n_sources][nt] injection rates
-  double* val = nullptr;   // scalar block-ELL values of the system being solved, W x n
-  int ksp_type = 1, restart = 30, max_its = 10000;
-  double rtol = 1.e-5, atol = 1.e-50;
-  // coupled mode (wai_set_tracer_solve_mode): all nt systems as one, allocated on first use
-  int mode = 0;            // WAI_TRACER_PER_TRACER | WAI_TRACER_COUPLED
-  double* valb = nullptr;  // [W][nt][n] values of the nt systems (Bcsr::dg layout)
-  double* fvalb = nullptr; // their ILU(0) factors, same layout
-  double* rhsb = nullptr;  // [n_prim * nt + 16] right-hand side, interleaved [cell][nt]
-  double* kvec[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // Krylov work vectors of nt * n_prim
-  double* kbasis = nullptr; int kbasis_m = 0;   // GMRES basis of such vectors
+  double* rhsb = nullptr;  // coupled mode: [n_prim * nt + 16] right-hand side, interleaved [cell][nt] (allocated on first use)
+  int mode = 0;            // WAI_TRACER_PER_TRACER | WAI_TRACER_COUPLED (wai_set_tracer_solve_mode)
   long long n_sweeps = 0;  // assembly sweeps over the faces so far (wai_tracer_stats)
+  // k_tracer_assemble_all and k_tracer_lhs take this struct BY VALUE: its size fixes where their later arguments sit.  The
+  // solver state that used to follow (now in LinSys) leaves this tail, so that both kernels keep their argument layout --
+  // dropping it is a change of device code and belongs with one
+  unsigned char kernarg_tail[136] = {0};
 };
+static_assert(sizeof(Tracers) == 408, "Tracers is a kernel argument (k_tracer_assemble_all, k_tracer_lhs): its size is part of their argument layout");
 
 // one tracer's system: which tracer, and the method's combination (timestepper.F90:458-581)
 struct TracerForm {
@@ -370,16 +381,12 @@ struct Fin {
   double* post = nullptr;      // device address of the pinned host mirror (16 bytes, 16-byte aligned)
 };
 
+// The reduction workspace of the Krylov helpers: device scalars, partial sums, the posted scalars' mirror and the launch
+// counters.  Single and shared: one solve runs at a time on the library's stream, whichever system it solves.
 struct Krylov {
-  int n = 0, nl = 0;           // bs*n_owned, bs*n_prim
   double* d_post = nullptr;    // device address of h_scal + POST_OFF
   int seq = 0;                 // last sequence number handed out
   long long n_launch = 0, n_copy = 0;   // kernels launched / copies enqueued by the Krylov helpers (wai_launch_stats)
-  double *R = nullptr, *RP = nullptr, *P = nullptr, *V = nullptr, *S = nullptr, *T = nullptr,
-         *tmp = nullptr, *X = nullptr;
-  double* bl = nullptr;        // BiCGStab(L): r_0..r_L, u_0..u_L, r~ (allocated on first use)
-  double* basis = nullptr;     // GMRES: (m+1) vectors of nl
-  int basis_m = 0;
   double* partials = nullptr;  // [slots][nb_max]
   double* partials2 = nullptr; // [slots][FIN_MAXF]: slice sums of the finaliser workgroups (fin_block)
   unsigned* started = nullptr; // k_bcgs_xrp<DERIVE>: workgroups of the launch that have read their scalars (device counter, zero between launches)
@@ -389,6 +396,41 @@ struct Krylov {
   double* h_scal = nullptr;    // pinned host mirror
   int nblocks = 0;
   int nb_pc = 0;               // partial-sum blocks the last preconditioner application left per slot
+};
+
+// A set of Krylov work vectors
+struct KrylovVecs {
+  double *R = nullptr, *RP = nullptr, *P = nullptr, *V = nullptr, *S = nullptr, *T = nullptr,
+         *tmp = nullptr, *X = nullptr;   // nl + 16 doubles each (alloc_krylov_vecs)
+  double* bl = nullptr;        // BiCGStab(L): r_0..r_L, u_0..u_L, r~ (allocated on first use)
+  double* basis = nullptr;     // GMRES: (basis_m + 4) vectors of nl (ensure_basis)
+  int basis_m = 0;
+};
+
+struct KspOpts {
+  int type = WAI_KSP_BCGS, restart = 30, max_its = 10000;
+  double rtol = 1.e-5, atol = 1.e-50;
+};
+
+// One linear system: everything the Krylov drivers, the preconditioner set-up and the launchers below them need to know
+// about the system they work on, handed to them as an argument.  The context holds three, all on the mesh's pattern:
+//   flow     the flow Jacobian, block size np; built in wai_ctx_create
+//   aux      one scalar tracer system at a time, block size 1; built in wai_set_tracers.  Its kv ALIASES the flow's work
+//            vectors and GMRES basis (it uses the first n_prim entries of each vector, basis vectors n_prim apart; the two
+//            never solve at once).  So a per-tracer GMRES restart is clamped to the flow's basis size: the
+//            min(restart, basis_m) in ksp_gmres sees the flow's basis_m
+//   coupled  all nt tracer systems as one (Bcsr::dg), vectors of nt * n_prim; values, factor, vectors and basis its own
+//            (wai_ctx::kv_coupled), allocated on first use
+// Single and shared, NOT part of a system: the pattern (wai_ctx::pat), the ILU schedule with its factor buffers
+// (wai_ctx::ilu: it depends on the pattern alone), the reduction workspace (wai_ctx::ks), and pc_type, ilu_levels and
+// asm_overlap of wai_ctx::opts.
+struct LinSys {
+  Bcsr A;               // the values on the shared pattern; A.bs: unknowns per cell = block size = dof of the halo exchange
+  KspOpts ksp;
+  int n = 0, nl = 0;    // A.bs * n_owned, A.bs * n_prim
+  KrylovVecs* kv = nullptr;   // wai_ctx::kv (flow, aux) or wai_ctx::kv_coupled
+  AsmSystem as;         // its extended system (PCASM, ILU(k), network blocks in the factor), built on first use
+  bool net_blocks = false;   // the source network's coupling blocks E belong to its operator (the flow system only)
 };
 
 }  // namespace wai
@@ -403,7 +445,7 @@ struct LuBlocks {
   std::vector<size_t> h_inv_ptr;
   size_t total = 0;
 };
-int launch_lu_apply(wai_ctx* c, const double* r, double* z);
+int launch_lu_apply(wai_ctx* c, int bs, const double* r, double* z);
 }  // namespace wai
 
 struct wai_ctx {
@@ -419,10 +461,10 @@ struct wai_ctx {
   wai::Network net;
   std::vector<int> src_gidx;    // wai_set_source_global_index: global index of every local source (networks across ranks)
   int src_nglobal = 0;
-  wai::Bcsr J;
+  wai::Pattern pat;
+  wai::LinSys flow, aux, coupled;
+  wai::KrylovVecs kv, kv_coupled;
   wai::IluSchedule ilu;
-  wai::AsmSystem as;
-  wai::AsmSystem as_aux;   // the extended system of the scalar (tracer) problems, block size 1 (AuxScope swaps it in)
   wai::LuBlocks lu;
   wai::Krylov ks;
   wai::Tracers tr;
@@ -483,10 +525,10 @@ int launch_residual(wai_ctx* c, double dt, const double* lhs_old, double* f, dou
                     double* rhs_out, const int* only = nullptr, int n_only = 0);   // only: these rows alone (device list)
 int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old);
 int launch_transitions(wai_ctx* c, const double* y_old, double* search, double* y);
-// tracer system of tf.it on the flow Jacobian's pattern: values -> c->tr.val, rhs -> b
+// tracer system of tf.it on the mesh's pattern: values -> c->aux.A.val, rhs -> b
 int launch_tracer_assemble(wai_ctx* c, const TracerForm& tf, const double* alx_last,
                            const double* alx_last2, double* b);
-// all nt systems in one sweep over the faces: values -> c->tr.valb ([slot][tracer][row]), rhs -> b ([row][tracer])
+// all nt systems in one sweep over the faces: values -> c->coupled.A.val ([slot][tracer][row]), rhs -> b ([row][tracer])
 int launch_tracer_assemble_all(wai_ctx* c, int method, double dt, double ratio, const double* alx_last,
                                const double* alx_last2, double* b);
 int launch_tracer_lhs(wai_ctx* c, double* Al);
@@ -503,24 +545,25 @@ int launch_fluid_aos(wai_ctx* c, const double* flu_soa, double* out_aos);
 int launch_region_get(wai_ctx* c, double* out);  // regions as doubles, n_prim
 int launch_region_set(wai_ctx* c, const double* in, int first, int count);
 
-int launch_spmv(wai_ctx* c, const double* x, double* y);
-int launch_ilu_factor(wai_ctx* c);
-// the same on any (matrix, schedule) pair: the Jacobian with the brick schedule, or the extended
-// ASM system with its own
+int launch_spmv(wai_ctx* c, const Bcsr& M, const double* x, double* y);
+// ILU(0) of any (matrix, schedule) pair: a system's matrix with the brick schedule, or its extended ASM system with its own
 int launch_ilu_factor_on(wai_ctx* c, const Bcsr& M, IluSchedule& s);
 // in2 (optional, fused kernels that can: pc_axpy_capable): the input is in - alpha in2, alpha = the device scalar S_ALPHA
 int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z,
                  int dot_mode, const double* aux, const int* list = nullptr, int nrun = 0, const Fin* fin = nullptr,
                  const double* in2 = nullptr);
-bool pc_axpy_capable(const wai_ctx* c);
-bool pc_axpy_default(const wai_ctx* c);   // is the composed second launch the default for the kernel in force (k_pc_park with col16)
+// which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc,
+// -1 the coupled tracer system's k_dg_pc
+int pc_kernel_kind(const wai_ctx* c, const Bcsr& M, const IluSchedule& s);
+bool pc_axpy_capable(const wai_ctx* c, const Bcsr& M);
+bool pc_axpy_default(const wai_ctx* c, const Bcsr& M);   // is the composed second launch the default for the kernel in force (k_pc_park with col16)
 // subdomains of any size: level-by-level launches, in place on z (z = r on entry)
 int launch_big_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
-int launch_asm_gather_matrix(wai_ctx* c);                   // E.val <- J.val (and the ghost cells' rows; + the network's blocks)
-int launch_pack_rows(wai_ctx* c);                           // d_sendbuf <- matrix rows of the cells sent to neighbours
-int launch_unpack_rows(wai_ctx* c);                         // as.hval <- d_recvbuf
-int launch_asm_gather(wai_ctx* c, const double* r);        // as.r_ext <- r
-int launch_asm_scatter(wai_ctx* c, double* z);             // z[owned] <- as.r_ext
+int launch_asm_gather_matrix(wai_ctx* c, const Bcsr& M, const AsmSystem& a);   // a.E.val <- M.val (and the ghost cells' rows; + the network's blocks)
+int launch_pack_rows(wai_ctx* c, const Bcsr& M);                              // d_sendbuf <- matrix rows of the cells sent to neighbours
+int launch_unpack_rows(wai_ctx* c, const Bcsr& M, const AsmSystem& a);        // a.hval <- d_recvbuf
+int launch_asm_gather(wai_ctx* c, const AsmSystem& a, const double* r);       // a.r_ext <- r
+int launch_asm_scatter(wai_ctx* c, const AsmSystem& a, double* z);            // z[owned] <- a.r_ext
 // up to two dot products (a1,b1) -> slot1, (a2,b2) -> slot2 (a2 null: one); partial blocks in ks.nb_pc
 int vec_dots(wai_ctx* c, const double* a1, const double* b1, int slot1, const double* a2, const double* b2,
              int slot2, int n);
@@ -528,7 +571,7 @@ int vec_dots(wai_ctx* c, const double* a1, const double* b1, int slot1, const do
 // dot_mode: the inner products reduced on the way (PcDot above), aux the partner of modes 1 and 4
 // list / nrun: run only the listed subdomains (null: all)
 // fin (optional): finalise the dot products in the kernel's last workgroup instead of a k_finalize launch
-int launch_pc(wai_ctx* c, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
+int launch_pc(wai_ctx* c, const Bcsr& M, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
               const int* list = nullptr, int nrun = 0, const Fin* fin = nullptr, const double* in2 = nullptr);
 // finalisation descriptor for slots [slot0, slot0 + nslots) (the launcher fills in the workgroup counts);
 // post: mirror the scalars to the host with a fresh sequence number (left in ks.seq)
@@ -537,7 +580,7 @@ Fin make_fin(wai_ctx* c, int slot0, int nslots, int phase, bool post = false);
 inline Fin make_fin_dots(wai_ctx* c, int dot_mode, int phase, bool post = false) {
   return make_fin(c, pc_dot_slot0(dot_mode), pc_dot_nslots(dot_mode), phase, post);
 }
-int launch_ell_to_bcsr(wai_ctx* c, const double* ell, double* bcsr);
+int launch_ell_to_bcsr(wai_ctx* c, const Bcsr& M, double* bcsr);   // M.val on the BCSR pattern
 // the coupled tracer system (Bcsr::dg; kernels_tracer_block.hip): what launch_spmv, launch_ilu_factor_on, launch_pc_on and
 // launch_big_solve hand such a matrix to, and its values as [block][tracer] on the BCSR pattern
 int launch_dg_spmv(wai_ctx* c, const Bcsr& M, const double* x, double* y);
@@ -545,7 +588,7 @@ int launch_dg_factor(wai_ctx* c, const Bcsr& M, IluSchedule& s);
 int launch_dg_pc(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z, const int* list, int nrun);
 int launch_dg_big_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
 int launch_dg_to_bcsr(wai_ctx* c, const Bcsr& M, double* bcsr);
-int launch_bcsr_to_ell(wai_ctx* c, const double* bcsr, double* ell);
+int launch_bcsr_to_ell(wai_ctx* c, const double* bcsr, const Bcsr& M);   // ... and back into M.val
 // reductions: partial sums live in ks.partials[slot][block]; finalize sums nb partials of
 // nslots consecutive slots into ks.scal and (phase >= 0) derives the BiCGStab scalars
 int vec_finalize(wai_ctx* c, int nb, int slot0, int nslots, int phase);
@@ -555,21 +598,23 @@ int vec_copy(wai_ctx* c, double* dst, const double* src, size_t n);
 int vec_zero(wai_ctx* c, double* dst, size_t n);
 int vec_waxpy(wai_ctx* c, double* w, double alpha, const double* x, const double* y, int n);
 int bcgs_scalars(wai_ctx* c, int phase, bool post = false);
-int bcgs_update_xrp_derive(wai_ctx* c);
+int bcgs_update_xrp_derive(wai_ctx* c, const KrylovVecs& k, int n);
 int bcgs_post(wai_ctx* c, int seq);
 void read_env(wai_ctx* c);   // the launch switches above (kernels_fused.hip)
 int test_drop_partials(wai_ctx* c, int n);   // fault injection (tests): workgroup 0 loses its next n partial sums
-int bcgs_update_p(wai_ctx* c);
-int bcgs_update_s(wai_ctx* c);
+// the BiCGStab vector updates on the work vectors k, n entries each
+int bcgs_update_p(wai_ctx* c, const KrylovVecs& k, int n);
+int bcgs_update_s(wai_ctx* c, const KrylovVecs& k, int n);
 // dots: reduces (R,R), (R,RP) into S_DP2, S_RHONEW and (fin_phase >= -1) finalises them in its last workgroup
-int bcgs_update_xr(wai_ctx* c, bool dots = true, int fin_phase = -2, bool post = false);
+int bcgs_update_xr(wai_ctx* c, const KrylovVecs& k, int n, bool dots = true, int fin_phase = -2, bool post = false);
 // S = R - alpha V re-formed; X += alpha P + omega S; R = S - omega T; P = R + beta (P - omega V): one pass, no reduction
-int bcgs_update_xrp(wai_ctx* c);
+int bcgs_update_xrp(wai_ctx* c, const KrylovVecs& k, int n);
 int pack_halo_axpy(wai_ctx* c, const double* a, const double* b, int dof, hipStream_t stream = nullptr);
-int gmres_mdot(wai_ctx* c, const double* w, int k);          // scal[16+i] = (w, v_i), i<k
-int gmres_maxpy_norm(wai_ctx* c, double* w, int k);          // w -= sum h_i v_i ; scal[8] = |w|^2
+// GMRES on the basis vectors v_i = basis + i * ld, n entries each
+int gmres_mdot(wai_ctx* c, const double* basis, size_t ld, int n, const double* w, int k);          // scal[16+i] = (w, v_i), i<k
+int gmres_maxpy_norm(wai_ctx* c, const double* basis, size_t ld, int n, double* w, int k);          // w -= sum h_i v_i ; scal[8] = |w|^2
 int gmres_scale_to(wai_ctx* c, double* dst, const double* src, int slot_norm2, int n);
-int gmres_update_x(wai_ctx* c, double* x, const double* ycoef_host, int k);
+int gmres_update_x(wai_ctx* c, const double* basis, size_t ld, int n, double* x, const double* ycoef_host, int k);
 int pack_halo(wai_ctx* c, const double* vec, int dof, hipStream_t stream = nullptr);
 int unpack_halo(wai_ctx* c, double* vec, int dof, hipStream_t stream = nullptr);
 }  // namespace wai

@@ -99,17 +99,22 @@ struct Prof {
   }
 };
 
-// which preconditioner path is in force: the fused brick kernels (block Jacobi, every subdomain
+// the source network's blocks E are part of the system's operator in force: A + E (the flow Jacobian's only)
+inline bool net_in_operator(const wai_ctx* c, const LinSys& sys) { return sys.net_blocks && c->net.cp_valid; }
+// which preconditioner path is in force for a system: the fused brick kernels (block Jacobi, every subdomain
 // <= 1024 rows) or the general one (PCASM's extended system, subdomains of any size, PCNONE)
-// the source network's blocks are part of the Jacobian in force AND go into the factor's pattern (one rank)
-inline bool pc_with_net(const wai_ctx* c) { return c->net.cp_valid && c->net.cp_in_pc && !c->net.cp_span; }
-inline bool pc_fused(const wai_ctx* c) {
-  return c->opts.pc_type == WAI_PC_BJACOBI && !c->ilu.big && c->opts.ilu_levels <= 0 && !pc_with_net(c);
+// the source network's blocks are part of the operator in force AND go into the factor's pattern (one rank)
+inline bool pc_with_net(const wai_ctx* c, const LinSys& sys) { return net_in_operator(c, sys) && c->net.cp_in_pc && !c->net.cp_span; }
+inline bool pc_fused(const wai_ctx* c, const LinSys& sys) {
+  return c->opts.pc_type == WAI_PC_BJACOBI && !c->ilu.big && c->opts.ilu_levels <= 0 && !pc_with_net(c, sys);
 }
 // the extended-system path: PCASM's overlapped row sets and / or ILU(k)'s filled pattern and / or the network's blocks
-inline bool pc_extended(const wai_ctx* c) {
-  return c->opts.pc_type == WAI_PC_ASM || (c->opts.pc_type == WAI_PC_BJACOBI && (c->opts.ilu_levels > 0 || pc_with_net(c)));
+inline bool pc_extended(const wai_ctx* c, const LinSys& sys) {
+  return c->opts.pc_type == WAI_PC_ASM || (c->opts.pc_type == WAI_PC_BJACOBI && (c->opts.ilu_levels > 0 || pc_with_net(c, sys)));
 }
+// the preconditioner set up for `sys` no longer stands (its values changed); without a system: nobody's does
+inline void pc_invalidate(wai_ctx* c, const LinSys& sys) { if (c->ilu.owner == &sys) c->ilu.owner = nullptr; }
+inline void pc_invalidate(wai_ctx* c) { c->ilu.owner = nullptr; }
 
 // ---- pc_setup.hip ------------------------------------------------------------------------------------------------
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
@@ -117,33 +122,33 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
 void free_schedule(IluSchedule& s);
 void free_asm(AsmSystem& a);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell
-int do_pc_setup(wai_ctx* c);
+int do_pc_setup(wai_ctx* c, LinSys& sys);
 // ---- krylov.hip --------------------------------------------------------------------------------------------------
 int halo_exchange(wai_ctx* c, double* vec, int dof);
 // the two launches of the overlapped halo exchange on the compute stream: interior bricks, then face bricks behind `after`
 // (null: behind what the compute stream held when called)
-int launch_pc_split(wai_ctx* c, const double* x, double* z, int dot_mode, const double* aux, const Fin* fp, const double* x2,
+int launch_pc_split(wai_ctx* c, const Bcsr& M, const double* x, double* z, int dot_mode, const double* aux, const Fin* fp, const double* x2,
                     hipEvent_t after);
 int allreduce_scal(wai_ctx* c, int slot, int count);
 int read_scal(wai_ctx* c, int first, int count);
 // z = B^-1 r; dot_mode as launch_pc, with `x` the partner of mode 2.  fin_phase >= -1: the partial sums of the dot
 // products are summed into the device scalars (and the BiCGStab scalars of that phase derived); -2: left as partials
-int pc_solve(wai_ctx* c, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase = -2);
+int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase = -2);
 // z = B^-1 A x (x has halo room); x2: the operand is x - alpha x2 (fused kernels); post: the scalars to the host
-int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode = PC_DOT_NONE, const double* aux = nullptr, int fin_phase = -2,
+int pc_amul(wai_ctx* c, LinSys& sys, double* x, double* z, int dot_mode = PC_DOT_NONE, const double* aux = nullptr, int fin_phase = -2,
             const double* x2 = nullptr, bool post = false);
-int do_ksp(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm);
+int do_ksp(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm);
 int bcgs_mode(const wai_ctx* c);
-bool pc_axpy_ok(const wai_ctx* c);
+bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys);
 struct BcgsPlan { int mode; bool fused3, merged, axpy, multi; };
-BcgsPlan bcgs_plan(const wai_ctx* c);
-int bcgs_first_half(wai_ctx* c, const BcgsPlan& pl);
-int bcgs_second_half(wai_ctx* c, const BcgsPlan& pl);
+BcgsPlan bcgs_plan(const wai_ctx* c, const LinSys& sys);
+int bcgs_first_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
+int bcgs_second_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
 // ---- network.hip -------------------------------------------------------------------------------------------------
 void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n);   // separator.F90:139-166, 212-260
 int network_update(wai_ctx* c);
 int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old);
-int apply_operator(wai_ctx* c, const double* x, double* t);   // t = (A + E) x, E = the source network's blocks
+int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t);   // t = A x, + E x where the source network's blocks belong to sys
 // ---- capi.hip ----------------------------------------------------------------------------------------------------
 int fetch_flags(wai_ctx* c, int out[4]);
 int do_pre_eval(wai_ctx* c, double* y);

@@ -1404,7 +1404,7 @@ int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
       constexpr int T = ParkT<K>::threads;                                                                \
       const int g = (((int)((m.n_owned + T - 1) / T) + 7) / 8) * 8;                                        \
       hipLaunchKernelGGL(k_jacobian_sym<K>, g, T, EosT<K>::np * (ParkT<K>::npark + EosT<K>::np) * 8 * T, c->stream, \
-                         m, c->flu, stride, c->flu_pert, c->hstep, c->mesh.n_prim, res_form_of(c, dt, lhs_old), c->J.val); \
+                         m, c->flu, stride, c->flu_pert, c->hstep, c->mesh.n_prim, res_form_of(c, dt, lhs_old), c->flow.A.val); \
     } while (0)
     if (c->kind == EOS_W) JS(EOS_W);
     else if (c->kind == EOS_WE) JS(EOS_WE);
@@ -1432,11 +1432,11 @@ int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
       if (ParkT<K>::use)                                                                                  \
         hipLaunchKernelGGL(k_jacobian_park<K>, g, T, ParkT<K>::lds_bytes(m.max_deg), c->stream,                       \
                            m, c->flu, stride, c->flu_pert, c->hstep, c->mesh.n_prim, res_form_of(c, dt, lhs_old), \
-                           c->J.val);                                                                     \
+                           c->flow.A.val);                                                                     \
       else                                                                                                \
         hipLaunchKernelGGL(k_jacobian<K>, grid8_for(m.n_owned), TPB, 0, c->stream,                        \
                            m, c->flu, stride, c->flu_pert, c->hstep, c->mesh.n_prim, res_form_of(c, dt, lhs_old), \
-                           c->J.val);                                                                     \
+                           c->flow.A.val);                                                                     \
     } while (0)
     if (c->kind == EOS_W) JP(EOS_W);
     else if (c->kind == EOS_WE) JP(EOS_WE);
@@ -1449,7 +1449,7 @@ int launch_jacobian(wai_ctx* c, double dt, const double* lhs_old) {
     return 0;
   }
   WAI_BY_EOS(c, k_jacobian, grid8_for(m.n_owned), m, c->flu, stride, c->flu_pert, c->hstep, c->mesh.n_prim,
-             res_form_of(c, dt, lhs_old), c->J.val);
+             res_form_of(c, dt, lhs_old), c->flow.A.val);
   return 0;
 }
 
@@ -1458,12 +1458,12 @@ int launch_tracer_assemble(wai_ctx* c, const TracerForm& tf, const double* alx_l
   const MeshView m = view(c);
   c->tr.n_sweeps++;
   // rows indexed by ELL slot: up to W of them (wai_ctx_create refuses rows of more than MAXDEG_WIDE blocks)
-  if (c->J.W > MAXDEG)
+  if (c->pat.W > MAXDEG)
     WAI_BY_EOS_T(c, k_tracer_assemble, WAI_COMMA MAXDEG_WIDE, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
-                 c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->tr.val, b);
+                 c->mesh.n_prim, c->pat.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->aux.A.val, b);
   else
     WAI_BY_EOS(c, k_tracer_assemble, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, tf,
-               c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->tr.val, b);
+               c->mesh.n_prim, c->pat.W, alx_last, alx_last2, c->tr.bc, c->tr.inj, c->aux.A.val, b);
   return 0;
 }
 
@@ -1472,7 +1472,7 @@ int launch_tracer_assemble_all(wai_ctx* c, int method, double dt, double ratio, 
   const MeshView m = view(c);
   c->tr.n_sweeps++;
   WAI_BY_EOS(c, k_tracer_assemble_all, grid_for(m.n_owned), m, c->flu, (size_t)c->mesh.n_local, c->tr, method, dt, ratio,
-             c->mesh.n_prim, c->J.W, alx_last, alx_last2, c->tr.valb, b);
+             c->mesh.n_prim, c->pat.W, alx_last, alx_last2, c->coupled.A.val, b);
   return 0;
 }
 

@@ -515,8 +515,8 @@ __global__ __launch_bounds__(256) void k_lu_apply(int nsub, int bs, const int* _
     if (lane == 0) z[lo + i] = t;
   }
 }
-int launch_lu_apply(wai_ctx* c, const double* r, double* z) {
-  hipLaunchKernelGGL(k_lu_apply, c->ilu.nsub, 256, 0, c->stream, c->ilu.nsub, c->J.bs, c->ilu.sub_ptr, c->lu.inv_ptr,
+int launch_lu_apply(wai_ctx* c, int bs, const double* r, double* z) {
+  hipLaunchKernelGGL(k_lu_apply, c->ilu.nsub, 256, 0, c->stream, c->ilu.nsub, bs, c->ilu.sub_ptr, c->lu.inv_ptr,
                      c->lu.inv, r, z);
   return 0;
 }
@@ -573,11 +573,8 @@ static void ilu_factor_bs(wai_ctx* c, const Bcsr& J, IluSchedule& s) {
 }
 int launch_ilu_factor_on(wai_ctx* c, const Bcsr& J, IluSchedule& s) {
   if (J.dg) return launch_dg_factor(c, J, s);   // the coupled tracer system: its own factor buffer
-  if (with_bs(J.bs, [&](auto bs) { ilu_factor_bs<decltype(bs)::value>(c, J, s); }) != 0) return -1;
-  s.factored = true;
-  return 0;
+  return with_bs(J.bs, [&](auto bs) { ilu_factor_bs<decltype(bs)::value>(c, J, s); });
 }
-int launch_ilu_factor(wai_ctx* c) { return launch_ilu_factor_on(c, c->J, c->ilu); }
 
 // the rows of each level of one sweep, a launch per level (FWD: forward)
 template <int BS, bool FWD>

@@ -23,9 +23,9 @@ void read_env(wai_ctx* c) {
   c->env.scalar_kernels = getenv("WAI_BCGS_SCALAR_KERNELS") != nullptr;   // several ranks: the one-thread kernels behind the all-reduces (rounds 3-4)
 }
 
-// which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc.
-// Kinds 1 .. 3 can form their input on the fly (in - alpha in2: launch_pc_on's in2)
-static int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s) {
+// which fused kernel serves (matrix, schedule; context.hpp).  Kinds 1 .. 3 can form their input on the fly (in - alpha in2:
+// launch_pc_on's in2)
+int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s) {
   if (J.dg) return -1;    // the coupled tracer system: k_dg_pc (kernels_tracer_block.hip)
   if (s.wide) return 4;   // rows of 9 .. 16 blocks: no other fused kernel reads their descriptor
   if (c->dbg) return 0;
@@ -35,10 +35,10 @@ static int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s)
   return 0;
 }
 static bool kind_composes(int kind) { return kind >= 1 && kind <= 3; }
-bool pc_axpy_capable(const wai_ctx* c) { return !c->ilu.big && kind_composes(pc_kernel_kind(c, c->J, c->ilu)); }
-bool pc_axpy_default(const wai_ctx* c) {
+bool pc_axpy_capable(const wai_ctx* c, const Bcsr& M) { return !c->ilu.big && kind_composes(pc_kernel_kind(c, M, c->ilu)); }
+bool pc_axpy_default(const wai_ctx* c, const Bcsr& M) {
   if (c->ilu.big) return false;
-  const int kind = pc_kernel_kind(c, c->J, c->ilu);
+  const int kind = pc_kernel_kind(c, M, c->ilu);
   return (kind == 1 && c->ilu.col16 && !c->env.no_col16) || kind == 3;   // k_pc_park on col16, k_pc_wave: measured faster end to end
 }
 
@@ -155,7 +155,7 @@ int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, con
     c->ks.n_launch++;
     if (launch_dg_pc(c, M, s, spmv, in, z, list, nrun)) return -1;
     if (dot_mode == PC_DOT_NONE) return 0;
-    const int n = c->ks.n, s0 = pc_dot_slot0(dot_mode);
+    const int n = M.dg * M.n, s0 = pc_dot_slot0(dot_mode);
     if (dot_mode == PC_DOT_ZA || dot_mode == PC_DOT_ZZ) vec_dots(c, z, dot_mode == PC_DOT_ZA ? aux : z, s0, nullptr, nullptr, 0, n);
     else {
       vec_dots(c, in, z, s0, z, z, s0 + 1, n);
@@ -177,9 +177,9 @@ int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, con
   }
   return 0;
 }
-int launch_pc(wai_ctx* c, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
+int launch_pc(wai_ctx* c, const Bcsr& M, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
               const int* list, int nrun, const Fin* fin, const double* in2) {
-  return launch_pc_on(c, c->J, c->ilu, spmv, in, z, dot_mode, aux, list, nrun, fin, in2);
+  return launch_pc_on(c, M, c->ilu, spmv, in, z, dot_mode, aux, list, nrun, fin, in2);
 }
 Fin make_fin(wai_ctx* c, int slot0, int nslots, int phase, bool post) {
   Fin f;   // count / nb: filled in by the launcher
@@ -243,57 +243,57 @@ int bcgs_post(wai_ctx* c, int seq) {   // the device scalars as they stand, unde
   return 0;
 }
 
-int bcgs_update_p(wai_ctx* c) {
+int bcgs_update_p(wai_ctx* c, const KrylovVecs& k, int n) {
   c->ks.n_launch++;
-  hipLaunchKernelGGL(k_bcgs_p, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.P, c->ks.R, c->ks.V, c->ks.n, c->ks.scal);
+  hipLaunchKernelGGL(k_bcgs_p, vgrid(n), TPB, 0, c->stream, k.P, k.R, k.V, n, c->ks.scal);
   return 0;
 }
-int bcgs_update_s(wai_ctx* c) {
+int bcgs_update_s(wai_ctx* c, const KrylovVecs& k, int n) {
   c->ks.n_launch++;
-  hipLaunchKernelGGL(k_bcgs_s, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.S, c->ks.R, c->ks.V, c->ks.n, c->ks.scal);
+  hipLaunchKernelGGL(k_bcgs_s, vgrid(n), TPB, 0, c->stream, k.S, k.R, k.V, n, c->ks.scal);
   return 0;
 }
-int bcgs_update_xr(wai_ctx* c, bool dots, int fin_phase, bool post) {
-  const int g = vgrid(c->ks.n);
+int bcgs_update_xr(wai_ctx* c, const KrylovVecs& k, int n, bool dots, int fin_phase, bool post) {
+  const int g = vgrid(n);
   Fin fin;
   if (dots && fin_phase >= -1) { fin = make_fin(c, S_DP2, 2, fin_phase, post); fin.count = g; fin.nb = g; fin.nf = fin_slices(g); }
   c->ks.n_launch++;
   if (dots && fin.count > 0 && c->env.fin_separate) {
     Fin none;
-    hipLaunchKernelGGL(k_bcgs_xr<true>, g, TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.S, c->ks.T,
-                       c->ks.RP, c->ks.n, c->ks.scal, c->ks.partials, c->ks.nb_max, none);
+    hipLaunchKernelGGL(k_bcgs_xr<true>, g, TPB, 0, c->stream, k.X, k.R, k.P, k.S, k.T,
+                       k.RP, n, c->ks.scal, c->ks.partials, c->ks.nb_max, none);
     c->ks.nblocks = g;
     vec_finalize(c, g, S_DP2, 2, fin_phase);
     if (fin.seq > 0) bcgs_post(c, fin.seq);
     return 0;
   }
   if (dots)
-    hipLaunchKernelGGL(k_bcgs_xr<true>, g + (fin.count > 0 ? fin.nf : 0), TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.S, c->ks.T,
-                       c->ks.RP, c->ks.n, c->ks.scal, c->ks.partials, c->ks.nb_max, fin);
+    hipLaunchKernelGGL(k_bcgs_xr<true>, g + (fin.count > 0 ? fin.nf : 0), TPB, 0, c->stream, k.X, k.R, k.P, k.S, k.T,
+                       k.RP, n, c->ks.scal, c->ks.partials, c->ks.nb_max, fin);
   else
-    hipLaunchKernelGGL(k_bcgs_xr<false>, g, TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.S, c->ks.T,
-                       c->ks.RP, c->ks.n, c->ks.scal, c->ks.partials, c->ks.nb_max, fin);
+    hipLaunchKernelGGL(k_bcgs_xr<false>, g, TPB, 0, c->stream, k.X, k.R, k.P, k.S, k.T,
+                       k.RP, n, c->ks.scal, c->ks.partials, c->ks.nb_max, fin);
   c->ks.nblocks = g;
   return 0;
 }
-int bcgs_update_xrp(wai_ctx* c) {
+int bcgs_update_xrp(wai_ctx* c, const KrylovVecs& k, int n) {
   c->ks.n_launch++;
-  hipLaunchKernelGGL(k_bcgs_xrp<false>, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.V, c->ks.T, c->ks.n,
+  hipLaunchKernelGGL(k_bcgs_xrp<false>, vgrid(n), TPB, 0, c->stream, k.X, k.R, k.P, k.V, k.T, n,
                      c->ks.scal, nullptr, nullptr, 0);
   return 0;
 }
 // the same launch deriving omega, (R,R), rho, beta from the all-reduced sums itself and posting the norm (several ranks)
-int bcgs_update_xrp_derive(wai_ctx* c) {
+int bcgs_update_xrp_derive(wai_ctx* c, const KrylovVecs& k, int n) {
   c->ks.n_launch++;
-  hipLaunchKernelGGL(k_bcgs_xrp<true>, vgrid(c->ks.n), TPB, 0, c->stream, c->ks.X, c->ks.R, c->ks.P, c->ks.V, c->ks.T, c->ks.n,
+  hipLaunchKernelGGL(k_bcgs_xrp<true>, vgrid(n), TPB, 0, c->stream, k.X, k.R, k.P, k.V, k.T, n,
                      c->ks.scal, c->ks.started, c->ks.d_post, ++c->ks.seq);
   return 0;
 }
-int gmres_mdot(wai_ctx* c, const double* w, int k) {
-  const int g = vgrid(c->ks.n);
+int gmres_mdot(wai_ctx* c, const double* basis, size_t ld, int n, const double* w, int k) {
+  const int g = vgrid(n);
   for (int j0 = 0; j0 < k; j0 += 8) {
     const int cnt = (k - j0) < 8 ? (k - j0) : 8;
-#define MD(CNT) hipLaunchKernelGGL(k_mdot<CNT>, g, TPB, 0, c->stream, w, c->ks.basis, (size_t)c->ks.nl, j0, c->ks.n, c->ks.partials, c->ks.nb_max)
+#define MD(CNT) hipLaunchKernelGGL(k_mdot<CNT>, g, TPB, 0, c->stream, w, basis, ld, j0, n, c->ks.partials, c->ks.nb_max)
     c->ks.n_launch++;
     switch (cnt) { case 1: MD(1); break; case 2: MD(2); break; case 3: MD(3); break; case 4: MD(4); break;
                    case 5: MD(5); break; case 6: MD(6); break; case 7: MD(7); break; default: MD(8); break; }
@@ -302,9 +302,9 @@ int gmres_mdot(wai_ctx* c, const double* w, int k) {
   }
   return 0;
 }
-int gmres_maxpy_norm(wai_ctx* c, double* w, int k) {
-  const int g = vgrid(c->ks.n);
-  hipLaunchKernelGGL(k_maxpy_norm, g, TPB, 0, c->stream, w, c->ks.basis, (size_t)c->ks.nl, k, c->ks.n,
+int gmres_maxpy_norm(wai_ctx* c, const double* basis, size_t ld, int n, double* w, int k) {
+  const int g = vgrid(n);
+  hipLaunchKernelGGL(k_maxpy_norm, g, TPB, 0, c->stream, w, basis, ld, k, n,
                      c->ks.scal, c->ks.partials, c->ks.nb_max);
   return vec_finalize(c, g, S_W2, 1, -1);
 }
@@ -312,11 +312,10 @@ int gmres_scale_to(wai_ctx* c, double* dst, const double* src, int slot_norm2, i
   hipLaunchKernelGGL(k_scale_to, vgrid(n), TPB, 0, c->stream, dst, src, c->ks.scal, slot_norm2, n);
   return 0;
 }
-int gmres_update_x(wai_ctx* c, double* x, const double* ycoef_host, int k) {
+int gmres_update_x(wai_ctx* c, const double* basis, size_t ld, int n, double* x, const double* ycoef_host, int k) {
   double* dcoef = c->ks.scal + 64;  // coefficients travel through the tail of the scalar buffer
   hipMemcpyAsync(dcoef, ycoef_host, sizeof(double) * k, hipMemcpyHostToDevice, c->stream);
-  hipLaunchKernelGGL(k_update_x, vgrid(c->ks.n), TPB, 0, c->stream, x, c->ks.basis, (size_t)c->ks.nl, k,
-                     c->ks.n, dcoef);
+  hipLaunchKernelGGL(k_update_x, vgrid(n), TPB, 0, c->stream, x, basis, ld, k, n, dcoef);
   return 0;
 }
 int pack_halo(wai_ctx* c, const double* vec, int dof, hipStream_t stream) {

@@ -132,8 +132,7 @@ __global__ __launch_bounds__(TPB) void k_asm_scatter(int n_ext, int bs, const in
   for (int k = 0; k < bs; k++) z[(size_t)i * bs + k] = z_ext[(size_t)q * bs + k];
 }
 
-int launch_spmv(wai_ctx* c, const double* x, double* y) {
-  const Bcsr& J = c->J;
+int launch_spmv(wai_ctx* c, const Bcsr& J, const double* x, double* y) {
   c->ks.n_launch++;
   if (J.dg) return launch_dg_spmv(c, J, x, y);   // the coupled tracer system
   const int nblk = (J.n + TPB - 1) / TPB;
@@ -152,11 +151,10 @@ int launch_spmv(wai_ctx* c, const double* x, double* y) {
   });
 }
 
-int launch_asm_gather_matrix(wai_ctx* c) {
-  const AsmSystem& a = c->as;
+int launch_asm_gather_matrix(wai_ctx* c, const Bcsr& J, const AsmSystem& a) {
   const size_t tot = (size_t)a.E.W * a.n_ext;
-  hipLaunchKernelGGL(k_asm_gather_matrix, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, c->J.n, a.n_ext, a.E.W,
-                     a.E.bs, c->mesh.n_halo, a.gmap, c->J.val, a.hval, a.E.val);
+  hipLaunchKernelGGL(k_asm_gather_matrix, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, J.n, a.n_ext, a.E.W,
+                     a.E.bs, c->mesh.n_halo, a.gmap, J.val, a.hval, a.E.val);
   if (a.with_net && a.n_net > 0 && c->net.cp_valid && c->net.d_cp_val) {   // + the source network's blocks of this Jacobian
     const int nt = a.n_net * a.E.bs * a.E.bs;
     hipLaunchKernelGGL(k_asm_add_couplings, (nt + TPB - 1) / TPB, TPB, 0, c->stream, a.n_net, a.n_ext, a.E.bs, a.net_pos,
@@ -164,41 +162,35 @@ int launch_asm_gather_matrix(wai_ctx* c) {
   }
   return 0;
 }
-int launch_pack_rows(wai_ctx* c) {
-  const Bcsr& J = c->J;
+int launch_pack_rows(wai_ctx* c, const Bcsr& J) {
   const size_t tot = (size_t)c->send_total * J.W * J.bs * J.bs;
   if (tot) hipLaunchKernelGGL(k_pack_rows, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, J.n, J.W, J.bs, c->send_total,
                               c->d_send_idx, J.val, c->d_sendbuf);
   return 0;
 }
-int launch_unpack_rows(wai_ctx* c) {
-  const Bcsr& J = c->J;
+int launch_unpack_rows(wai_ctx* c, const Bcsr& J, const AsmSystem& a) {
   const size_t tot = (size_t)c->mesh.n_halo * J.W * J.bs * J.bs;
   if (tot) hipLaunchKernelGGL(k_unpack_rows, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, c->mesh.n_halo, J.W, J.bs,
-                              c->d_recvbuf, c->as.hval);
+                              c->d_recvbuf, a.hval);
   return 0;
 }
-int launch_asm_gather(wai_ctx* c, const double* r) {
-  const AsmSystem& a = c->as;
+int launch_asm_gather(wai_ctx* c, const AsmSystem& a, const double* r) {
   hipLaunchKernelGGL(k_asm_gather, (a.n_ext + TPB - 1) / TPB, TPB, 0, c->stream, a.n_ext, a.E.bs, a.ext_row, r, a.r_ext);
   return 0;
 }
-int launch_asm_scatter(wai_ctx* c, double* z) {
-  const AsmSystem& a = c->as;
+int launch_asm_scatter(wai_ctx* c, const AsmSystem& a, double* z) {
   hipLaunchKernelGGL(k_asm_scatter, (a.n_ext + TPB - 1) / TPB, TPB, 0, c->stream, a.n_ext, a.E.bs, a.ext_row, a.r_ext, z);
   return 0;
 }
 
-int launch_ell_to_bcsr(wai_ctx* c, const double* ell, double* bcsr) {
-  const Bcsr& J = c->J;
+int launch_ell_to_bcsr(wai_ctx* c, const Bcsr& J, double* bcsr) {
   const size_t tot = (size_t)J.n * J.W;
-  hipLaunchKernelGGL(k_ell_to_bcsr, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, J.n, J.W, J.bs, J.rowptr, ell, bcsr);
+  hipLaunchKernelGGL(k_ell_to_bcsr, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, J.n, J.W, J.bs, J.rowptr, J.val, bcsr);
   return 0;
 }
-int launch_bcsr_to_ell(wai_ctx* c, const double* bcsr, double* ell) {
-  const Bcsr& J = c->J;
+int launch_bcsr_to_ell(wai_ctx* c, const double* bcsr, const Bcsr& J) {
   const size_t tot = (size_t)J.n * J.W;
-  hipLaunchKernelGGL(k_bcsr_to_ell, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, J.n, J.W, J.bs, J.rowptr, bcsr, ell);
+  hipLaunchKernelGGL(k_bcsr_to_ell, (int)((tot + TPB - 1) / TPB), TPB, 0, c->stream, J.n, J.W, J.bs, J.rowptr, bcsr, J.val);
   return 0;
 }
 

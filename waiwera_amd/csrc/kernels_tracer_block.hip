@@ -400,7 +400,6 @@ int launch_dg_factor(wai_ctx* c, const Bcsr& M, IluSchedule& s) {
     else
       hipLaunchKernelGGL(k_dg_factor<0>, grid, T, 0, c->stream, M.n, M.dg, s.nsub, s.sub_ptr, s.sub_nlev, s.row_info, s.row_infow, M.col, M.fdg, c->d_flags);
   }
-  s.factored = true;
   return 0;
 }
 

@@ -21,12 +21,12 @@ int halo_exchange(wai_ctx* c, double* vec, int dof) {
 // Interior bricks, then face bricks, both on the compute stream.  (The face bricks on a stream of their own, waiting for
 // the unpack only, measured slower -- the two launches do not overlap enough to pay for the two cross-queue event
 // hand-overs: profiles/facestream_ab_r5.log.)
-int launch_pc_split(wai_ctx* c, const double* x, double* z, int dot_mode, const double* aux, const Fin* fp, const double* x2,
+int launch_pc_split(wai_ctx* c, const Bcsr& M, const double* x, double* z, int dot_mode, const double* aux, const Fin* fp, const double* x2,
                     hipEvent_t after) {
   const IluSchedule& s = c->ilu;
-  if (launch_pc(c, true, x, z, dot_mode, aux, s.sub_int, s.n_int, nullptr, x2)) return -1;   // its partials wait for ...
+  if (launch_pc(c, M, true, x, z, dot_mode, aux, s.sub_int, s.n_int, nullptr, x2)) return -1;   // its partials wait for ...
   if (after) HIPCHK(c, hipStreamWaitEvent(c->stream, after, 0));
-  return launch_pc(c, true, x, z, dot_mode, aux, s.sub_bnd, s.n_bnd, fp, x2);                // ... the face bricks' last workgroup
+  return launch_pc(c, M, true, x, z, dot_mode, aux, s.sub_bnd, s.n_bnd, fp, x2);                // ... the face bricks' last workgroup
 }
 
 int allreduce_scal(wai_ctx* c, int slot, int count) {
@@ -56,8 +56,8 @@ int read_scal_end(wai_ctx* c) {
 }
 
 // the dot mode's products of a preconditioner result (context.hpp, PcDot), reduced by separate launches: general path
-int pc_dots(wai_ctx* c, int dot_mode, const double* x, const double* z, const double* aux) {
-  const int n = c->ks.n, s = pc_dot_slot0(dot_mode);
+int pc_dots(wai_ctx* c, int n, int dot_mode, const double* x, const double* z, const double* aux) {
+  const int s = pc_dot_slot0(dot_mode);
   switch (dot_mode) {
     case PC_DOT_ZA: return vec_dots(c, z, aux, s, nullptr, nullptr, 0, n);
     case PC_DOT_XZ: return vec_dots(c, x, z, s, z, z, s + 1, n);
@@ -82,41 +82,41 @@ int pc_finalize(wai_ctx* c, int dot_mode, int phase) {
 // z = B^-1 r; dot_mode as launch_pc, with `x` the partner of mode 2.  fin_phase >= -1: the partial sums of
 // the dot products are summed into the device scalars (and the BiCGStab scalars of that phase derived) --
 // in the fused kernel's last workgroup, or by a k_finalize launch on the general path; -2: left as partials
-int pc_solve(wai_ctx* c, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase) {
-  if (pc_fused(c)) {
+int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase) {
+  if (pc_fused(c, sys)) {
     // the fused kernels take the partner of modes 2 and 4 from their own input vector (the x of
     // z = B^-1 A x); here the input is r = (A + E) x, so those inner products are reduced separately
     if (dot_mode == PC_DOT_XZ || dot_mode == PC_DOT_MERGED) {
-      if (launch_pc(c, false, r, z, PC_DOT_NONE, nullptr)) return -1;
-      if (pc_dots(c, dot_mode, x, z, aux)) return -1;
+      if (launch_pc(c, sys.A, false, r, z, PC_DOT_NONE, nullptr)) return -1;
+      if (pc_dots(c, sys.n, dot_mode, x, z, aux)) return -1;
       return fin_phase >= -1 ? pc_finalize(c, dot_mode, fin_phase) : 0;
     }
     if (fin_phase >= -1 && dot_mode) {
       const Fin fin = make_fin_dots(c, dot_mode, fin_phase);
-      return launch_pc(c, false, r, z, dot_mode, aux, nullptr, 0, &fin);
+      return launch_pc(c, sys.A, false, r, z, dot_mode, aux, nullptr, 0, &fin);
     }
-    return launch_pc(c, false, r, z, dot_mode, aux);
+    return launch_pc(c, sys.A, false, r, z, dot_mode, aux);
   }
-  const size_t n = (size_t)c->ks.n;
+  const size_t n = (size_t)sys.n;
   if (c->opts.pc_type == WAI_PC_NONE) {
     if (z != r) vec_copy(c, z, r, n);
   } else if (c->opts.pc_type == WAI_PC_LU) {
-    if (launch_lu_apply(c, r, z)) return -1;
-  } else if (pc_extended(c)) {
-    AsmSystem& a = c->as;
+    if (launch_lu_apply(c, sys.A.bs, r, z)) return -1;
+  } else if (pc_extended(c, sys)) {
+    AsmSystem& a = sys.as;
     if (a.cross) {   // the residual's ghost entries: one more halo exchange per application
       vec_copy(c, a.r_full, r, n);
-      if (halo_exchange(c, a.r_full, c->np)) return -1;
-      launch_asm_gather(c, a.r_full);
-    } else launch_asm_gather(c, r);
+      if (halo_exchange(c, a.r_full, sys.A.bs)) return -1;
+      launch_asm_gather(c, a, a.r_full);
+    } else launch_asm_gather(c, a, r);
     if (a.sched.big) { if (launch_big_solve(c, a.E, a.sched, a.r_ext)) return -1; }
     else if (launch_pc_on(c, a.E, a.sched, false, a.r_ext, a.r_ext, PC_DOT_NONE, nullptr)) return -1;
-    launch_asm_scatter(c, z);
+    launch_asm_scatter(c, a, z);
   } else {   // block Jacobi with subdomains of more than 1024 rows
     if (z != r) vec_copy(c, z, r, n);
-    if (launch_big_solve(c, c->J, c->ilu, z)) return -1;
+    if (launch_big_solve(c, sys.A, c->ilu, z)) return -1;
   }
-  if (pc_dots(c, dot_mode, x, z, aux)) return -1;
+  if (pc_dots(c, sys.n, dot_mode, x, z, aux)) return -1;
   return fin_phase >= -1 ? pc_finalize(c, dot_mode, fin_phase) : 0;
 }
 
@@ -124,14 +124,15 @@ int pc_solve(wai_ctx* c, const double* r, double* z, int dot_mode, const double*
 // x2 (optional; fused kernels only, pc_axpy_ok): the operand is x - alpha x2 with alpha the device scalar S_ALPHA, formed
 // inside the kernel (BiCGStab's S = R - alpha V); both vectors have halo room, the operand's ghost values are packed as
 // one vector on the sending side and arrive in x's ghost entries, x2's stay zero.
-int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode, const double* aux, int fin_phase, const double* x2, bool post) {
+int pc_amul(wai_ctx* c, LinSys& sys, double* x, double* z, int dot_mode, const double* aux, int fin_phase, const double* x2, bool post) {
   const IluSchedule& s = c->ilu;
-  if (!pc_fused(c) || c->net.cp_valid) {   // unfused: t = A x (+ the network's blocks), then the preconditioner
+  const int bs = sys.A.bs;
+  if (!pc_fused(c, sys) || net_in_operator(c, sys)) {   // unfused: t = A x (+ the network's blocks), then the preconditioner
     if (x2) { c->err = "pc_amul: composed operand on the unfused path"; return -1; }
-    if (halo_exchange(c, x, c->np)) return -1;
-    { Prof p(c, KC_SPMV); if (apply_operator(c, x, c->ks.tmp)) return -1; }
+    if (halo_exchange(c, x, bs)) return -1;
+    { Prof p(c, KC_SPMV); if (apply_operator(c, sys, x, sys.kv->tmp)) return -1; }
     Prof p(c, KC_PC_APPLY);
-    if (int e = pc_solve(c, c->ks.tmp, z, dot_mode, x, aux, fin_phase)) return e;
+    if (int e = pc_solve(c, sys, sys.kv->tmp, z, dot_mode, x, aux, fin_phase)) return e;
     if (post) bcgs_scalars(c, -1, true);   // the scalars k_finalize derived, posted to the host
     return 0;
   }
@@ -142,36 +143,36 @@ int pc_amul(wai_ctx* c, double* x, double* z, int dot_mode, const double* aux, i
     fp = &fin;
   }
   const bool halo = c->comm && c->mesh.n_halo;
-  if (halo && c->np > c->max_dof_buf) { c->err = "halo dof too large"; return -1; }
-  if (halo && c->comm_stream && s.n_int > 0 && s.n_bnd > 0 && !c->prof_on && (!c->J.dg || dot_mode == PC_DOT_NONE)) {
+  if (halo && bs > c->max_dof_buf) { c->err = "halo dof too large"; return -1; }
+  if (halo && c->comm_stream && s.n_int > 0 && s.n_bnd > 0 && !c->prof_on && (!sys.A.dg || dot_mode == PC_DOT_NONE)) {
     // (the coupled tracer system reduces its inner products over whole vectors behind the launch: with a dot mode -- BiCGStab --
     // it takes the in-order exchange and one launch below; GMRES, the auxiliary default, asks for none and overlaps)
     // The partition-ghost values are needed only by the bricks on the rank's faces: pack on the
     // compute stream, send / receive / unpack on the communication stream while the interior bricks
     // run, then the face bricks.  (xGMI transfers and RCCL's launch latency hide behind ~90 % of
     // the kernel at 108^3 cells per rank.)
-    if (x2) pack_halo_axpy(c, x, x2, c->np); else pack_halo(c, x, c->np);
+    if (x2) pack_halo_axpy(c, x, x2, bs); else pack_halo(c, x, bs);
     HIPCHK(c, hipEventRecord(c->ev_pack, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_pack, 0));
-    if (comm_exchange(c->comm, c->n_nbr, c->nbr_rank.data(), c->send_ptr.data(), c->recv_ptr.data(), c->np,
+    if (comm_exchange(c->comm, c->n_nbr, c->nbr_rank.data(), c->send_ptr.data(), c->recv_ptr.data(), bs,
                       c->d_sendbuf, c->d_recvbuf, c->comm_stream, c->err))
       return -1;
-    if (unpack_halo(c, x, c->np, c->comm_stream)) return -1;
+    if (unpack_halo(c, x, bs, c->comm_stream)) return -1;
     HIPCHK(c, hipEventRecord(c->ev_halo, c->comm_stream));
     // (fault injection, wai_test_drop_stream_wait: the face bricks ordered behind the pack instead of behind the unpack)
-    return launch_pc_split(c, x, z, dot_mode, aux, fp, x2, (c->test_drop_wait & 1) ? c->ev_pack : c->ev_halo);
+    return launch_pc_split(c, sys.A, x, z, dot_mode, aux, fp, x2, (c->test_drop_wait & 1) ? c->ev_pack : c->ev_halo);
   }
   if (halo) {
     if (x2) {
-      pack_halo_axpy(c, x, x2, c->np);
-      if (comm_exchange(c->comm, c->n_nbr, c->nbr_rank.data(), c->send_ptr.data(), c->recv_ptr.data(), c->np, c->d_sendbuf,
+      pack_halo_axpy(c, x, x2, bs);
+      if (comm_exchange(c->comm, c->n_nbr, c->nbr_rank.data(), c->send_ptr.data(), c->recv_ptr.data(), bs, c->d_sendbuf,
                         c->d_recvbuf, c->stream, c->err))
         return -1;
-      if (unpack_halo(c, x, c->np)) return -1;
-    } else if (halo_exchange(c, x, c->np)) return -1;
+      if (unpack_halo(c, x, bs)) return -1;
+    } else if (halo_exchange(c, x, bs)) return -1;
   }
   Prof p(c, KC_PC_APPLY);
-  return launch_pc(c, true, x, z, dot_mode, aux, nullptr, 0, fp, x2);
+  return launch_pc(c, sys.A, true, x, z, dot_mode, aux, nullptr, 0, fp, x2);
 }
 
 // wait for the scalars a kernel posted to the host mirror with sequence number `seq` (Fin / k_bcgs_scalars):
@@ -239,17 +240,17 @@ int bcgs_mode(const wai_ctx* c) {
 // share 0.2192 -> 0.2127, C2 0.1946 -> 0.1897 -- and for the one-wave-per-brick kernel of 3 x 3 blocks on the SELL-64 layout
 // (profiles/compose_full_c4c5_ab_r5.log): C4 1.303 -> 1.265, C5 0.486 -> 0.467.  WAI_BCGS_COMPOSE=0 / 1 forces it off / on
 // (k_pc_rows -- 4 x 4 blocks, MINC inside 3-D bricks -- not measured: on request).
-bool pc_axpy_ok(const wai_ctx* c) {
-  if (!(pc_fused(c) && !c->net.cp_valid && pc_axpy_capable(c))) return false;
+bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys) {
+  if (!(pc_fused(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
   if (const char* e = getenv("WAI_BCGS_COMPOSE")) return e[0] == '1';
-  return pc_axpy_default(c);
+  return pc_axpy_default(c, sys.A);
 }
 
-BcgsPlan bcgs_plan(const wai_ctx* c) {
+BcgsPlan bcgs_plan(const wai_ctx* c, const LinSys& sys) {
   BcgsPlan p;
   p.mode = bcgs_mode(c);
   p.fused3 = p.mode == 2; p.merged = p.mode >= 1;
-  p.axpy = p.fused3 && pc_axpy_ok(c);
+  p.axpy = p.fused3 && pc_axpy_ok(c, sys);
   p.multi = c->comm && c->comm->nranks > 1;
   return p;
 }
@@ -257,10 +258,10 @@ BcgsPlan bcgs_plan(const wai_ctx* c) {
 // scalars only -- not X, R -- so ksp_bcgs enqueues the NEXT iteration's first half *before* the host waits for this
 // iteration's residual norm: the device never idles through the read-back, and if the norm says "converged" the
 // speculative half is simply discarded.
-int bcgs_first_half(wai_ctx* c, const BcgsPlan& pl) {
-  Krylov& k = c->ks;
-  if (!pl.fused3) { Prof p(c, KC_VECTOR); bcgs_update_p(c); }
-  if (int e = pc_amul(c, k.P, k.V, PC_DOT_ZA, k.RP, pl.multi ? -1 : 2)) return e;
+int bcgs_first_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl) {
+  KrylovVecs& k = *sys.kv;
+  if (!pl.fused3) { Prof p(c, KC_VECTOR); bcgs_update_p(c, k, sys.n); }
+  if (int e = pc_amul(c, sys, k.P, k.V, PC_DOT_ZA, k.RP, pl.multi ? -1 : 2)) return e;
   Prof p(c, KC_VECTOR);
   if (pl.multi) {
     if (int e = allreduce_scal(c, S_D1, 1)) return e;
@@ -269,7 +270,7 @@ int bcgs_first_half(wai_ctx* c, const BcgsPlan& pl) {
     if (pl.axpy && c->send_total > 0 && c->mesh.n_halo > 0 && !c->env.scalar_kernels) c->ks.alpha_pending = true;
     else bcgs_scalars(c, 2);
   }
-  if (!pl.axpy) bcgs_update_s(c);
+  if (!pl.axpy) bcgs_update_s(c, k, sys.n);
   return 0;
 }
 // Second half: T = B^-1 A S with its inner products, omega (and with merged reductions (R,R), rho, beta), the scalars
@@ -278,29 +279,29 @@ int bcgs_first_half(wai_ctx* c, const BcgsPlan& pl) {
 // omega and (S,S), (S,RP), (T,RP), from which (R,R) and (R,RP) of R = S - omega T follow -- so an iteration costs two
 // all-reduces ((V,RP); these five) instead of three, and omega, rho and beta are known before X and R are touched: the
 // host sees the norm one launch earlier, and (fused) the updates of X, R and the next P are one pass.
-int bcgs_second_half(wai_ctx* c, const BcgsPlan& pl) {
-  Krylov& k = c->ks;
+int bcgs_second_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl) {
+  KrylovVecs& k = *sys.kv;
   if (pl.fused3) {
-    if (int e = pc_amul(c, pl.axpy ? k.R : k.S, k.T, PC_DOT_MERGED, k.RP, pl.multi ? -1 : 6, pl.axpy ? k.V : nullptr, !pl.multi)) return e;
+    if (int e = pc_amul(c, sys, pl.axpy ? k.R : k.S, k.T, PC_DOT_MERGED, k.RP, pl.multi ? -1 : 6, pl.axpy ? k.V : nullptr, !pl.multi)) return e;
     Prof p(c, KC_VECTOR);
     if (pl.multi) {
       // omega, (R,R), rho, beta and the post: derived by the X / R / P update itself (k_bcgs_xrp<DERIVE>), no scalar kernel
       if (int e = allreduce_scal(c, S_D1, 5)) return e;
-      if (c->env.scalar_kernels) { bcgs_scalars(c, 6, true); bcgs_update_xrp(c); }
-      else bcgs_update_xrp_derive(c);
+      if (c->env.scalar_kernels) { bcgs_scalars(c, 6, true); bcgs_update_xrp(c, k, sys.n); }
+      else bcgs_update_xrp_derive(c, k, sys.n);
       return 0;
     }
-    bcgs_update_xrp(c);
+    bcgs_update_xrp(c, k, sys.n);
     return 0;
   }
-  if (int e = pc_amul(c, k.S, k.T, pl.merged ? PC_DOT_MERGED : PC_DOT_XZ, pl.merged ? k.RP : nullptr, pl.merged ? -1 : 3)) return e;
+  if (int e = pc_amul(c, sys, k.S, k.T, pl.merged ? PC_DOT_MERGED : PC_DOT_XZ, pl.merged ? k.RP : nullptr, pl.merged ? -1 : 3)) return e;
   Prof p(c, KC_VECTOR);
   if (pl.merged) {
     if (pl.multi) { if (int e = allreduce_scal(c, S_D1, 5)) return e; }
     bcgs_scalars(c, 6, true);   // omega, (R,R), (R,RP), rotation; posted: the host sees the norm before X, R are updated
-    bcgs_update_xr(c, false);
+    bcgs_update_xr(c, k, sys.n, false);
   } else {
-    bcgs_update_xr(c, true, 4, true);
+    bcgs_update_xr(c, k, sys.n, true, 4, true);
   }
   return 0;
 }
@@ -313,22 +314,22 @@ int bcgs_second_half(wai_ctx* c, const BcgsPlan& pl) {
 // fused -- four: fused A*P + ILU solve + (V,RP) + alpha; S = R - alpha V; fused A*S + ILU solve + (S,T),(T,T),(S,S),(S,RP),
 // (T,RP) + omega, (R,R), rho, beta, posted; X / R / P update in one pass.  Composed (the default where pc_axpy_ok says so):
 // three, S formed inside the second fused launch.
-int ksp_bcgs(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
-  Krylov& k = c->ks;
-  const int n = k.n;
-  const double rtol = c->opts.ksp_rtol, atol = c->opts.ksp_atol;
-  const int maxits = c->opts.ksp_max_its;
-  const BcgsPlan pl = bcgs_plan(c);
+int ksp_bcgs(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm) {
+  KrylovVecs& k = *sys.kv;
+  const int n = sys.n;
+  const double rtol = sys.ksp.rtol, atol = sys.ksp.atol;
+  const int maxits = sys.ksp.max_its;
+  const BcgsPlan pl = bcgs_plan(c, sys);
   const bool multi = pl.multi;
   vec_zero(c, x, n);
-  vec_zero(c, k.P, k.nl);
-  vec_zero(c, k.V, pl.fused3 ? k.nl : n);   // fused: V's ghost entries stay zero (the composed operand's ghosts arrive in R's)
-  k.alpha_pending = false;
+  vec_zero(c, k.P, sys.nl);
+  vec_zero(c, k.V, pl.fused3 ? sys.nl : n);   // fused: V's ghost entries stay zero (the composed operand's ghosts arrive in R's)
+  c->ks.alpha_pending = false;
   partials_clear(c, S_D1, 5);   // S_D1 .. S_W2: whatever an aborted solve or a probe left behind
-  vec_zero(c, k.scal + S_BREAK, 1);
+  vec_zero(c, c->ks.scal + S_BREAK, 1);
   {
     Prof p(c, KC_PC_APPLY);
-    if (pc_solve(c, b, k.R, PC_DOT_ZZ, nullptr, nullptr, multi ? -1 : 0)) return -1;  // R = B^-1 b, (R,R), first rho / beta
+    if (pc_solve(c, sys, b, k.R, PC_DOT_ZZ, nullptr, nullptr, multi ? -1 : 0)) return -1;  // R = B^-1 b, (R,R), first rho / beta
   }
   {
     Prof p(c, KC_VECTOR);
@@ -337,11 +338,11 @@ int ksp_bcgs(wai_ctx* c, const double* b, double* x, int* its, int* reason, doub
     if (pl.fused3) vec_copy(c, k.P, k.R, n);   // the first P = R + beta (0 - omega 0): the later ones come out of k_bcgs_xrp
   }
   if (read_scal(c, S_DP2, S_BREAK - S_DP2 + 1)) return -1;
-  double dp = std::sqrt(k.h_scal[S_DP2]);
+  double dp = std::sqrt(c->ks.h_scal[S_DP2]);
   const double dp0 = dp, ttol = std::max(rtol * dp, atol);
   *its = 0;
   *reason = 0;
-  if (k.h_scal[S_BREAK] == 4.0) { *reason = -9; c->err = "a reduction's partial sum never arrived (finaliser wait ran out)"; }
+  if (c->ks.h_scal[S_BREAK] == 4.0) { *reason = -9; c->err = "a reduction's partial sum never arrived (finaliser wait ran out)"; }
   else if (std::isnan(dp)) *reason = -9;
   else if (dp <= ttol) *reason = (dp <= atol) ? 3 : 2;
   double* Xsave = k.X;
@@ -354,18 +355,18 @@ int ksp_bcgs(wai_ctx* c, const double* b, double* x, int* its, int* reason, doub
 #endif
   bool have_first_half = false;
   for (int i = 0; i < maxits && !*reason && !rc; i++) {
-    if (!have_first_half && (rc = bcgs_first_half(c, pl))) break;
+    if (!have_first_half && (rc = bcgs_first_half(c, sys, pl))) break;
     have_first_half = false;
-    if ((rc = bcgs_second_half(c, pl))) break;
-    const int seq = k.seq;
+    if ((rc = bcgs_second_half(c, sys, pl))) break;
+    const int seq = c->ks.seq;
     if (speculate && i + 1 < maxits) {
-      if ((rc = bcgs_first_half(c, pl))) break;
+      if ((rc = bcgs_first_half(c, sys, pl))) break;
       have_first_half = true;
     }
     if ((rc = wait_post(c, seq))) break;
-    dp = std::sqrt(k.h_scal[S_DP2]);
+    dp = std::sqrt(c->ks.h_scal[S_DP2]);
     *its = i + 1;
-    const double brk = k.h_scal[S_BREAK];
+    const double brk = c->ks.h_scal[S_BREAK];
     if (brk == 4.0) { *reason = -9; c->err = "a reduction's partial sum never arrived (finaliser wait ran out)"; }
     else if (brk == 1.0) *reason = -5;                        // (R,RP) or (V,RP) vanished
     else if (brk == 2.0) *reason = (dp == 0.0) ? 3 : -5;      // (T,T) = 0: solved exactly, or breakdown
@@ -382,13 +383,13 @@ int ksp_bcgs(wai_ctx* c, const double* b, double* x, int* its, int* reason, doub
 }
 
 // KSPGMRES [PETSc]: restarted, left preconditioning, classical Gram-Schmidt without refinement
-int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
-  Krylov& k = c->ks;
+int ksp_gmres(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm) {
+  KrylovVecs& k = *sys.kv;
   partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
-  const int n = k.n, m = std::min(std::max(c->opts.gmres_restart, 1), k.basis_m);
-  const size_t ld = (size_t)k.nl;
-  const double rtol = c->opts.ksp_rtol, atol = c->opts.ksp_atol;
-  const int maxits = c->opts.ksp_max_its;
+  const int n = sys.n, m = std::min(std::max(sys.ksp.restart, 1), k.basis_m);
+  const size_t ld = (size_t)sys.nl;
+  const double rtol = sys.ksp.rtol, atol = sys.ksp.atol;
+  const int maxits = sys.ksp.max_its;
   std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), yv(m);
   vec_zero(c, x, n);
   int it = 0;
@@ -398,14 +399,14 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
     double* v0 = k.basis;
     if (it == 0) {
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, b, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
+      if (pc_solve(c, sys, b, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     } else {
       vec_copy(c, k.P, x, n);
-      if (halo_exchange(c, k.P, c->np)) return -1;
-      { Prof p(c, KC_SPMV); if (apply_operator(c, k.P, k.tmp)) return -1; }
+      if (halo_exchange(c, k.P, sys.A.bs)) return -1;
+      { Prof p(c, KC_SPMV); if (apply_operator(c, sys, k.P, k.tmp)) return -1; }
       vec_waxpy(c, k.tmp, -1.0, k.tmp, b, n);
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, k.tmp, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
+      if (pc_solve(c, sys, k.tmp, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     }
     {
       Prof p(c, KC_VECTOR);
@@ -413,7 +414,7 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
       if (allreduce_scal(c, S_W2, 1)) return -1;
     }
     if (read_scal(c, S_W2, 1)) return -1;
-    res = std::sqrt(k.h_scal[S_W2]);
+    res = std::sqrt(c->ks.h_scal[S_W2]);
     if (it == 0) {
       res0 = res;
       ttol = std::max(rtol * res, atol);
@@ -435,13 +436,13 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
       double* vj = k.basis + ld * j;
       double* vn = k.basis + ld * (j + 1);
       double* w = k.T;
-      if (!have_amul && pc_amul(c, vj, w)) return -1;
+      if (!have_amul && pc_amul(c, sys, vj, w)) return -1;
       have_amul = false;
       {
         Prof p(c, KC_VECTOR);
-        gmres_mdot(c, w, j + 1);
+        gmres_mdot(c, k.basis, ld, n, w, j + 1);
         if (allreduce_scal(c, S_H, j + 1)) return -1;
-        gmres_maxpy_norm(c, w, j + 1);
+        gmres_maxpy_norm(c, k.basis, ld, n, w, j + 1);
         if (allreduce_scal(c, S_W2, 1)) return -1;
         gmres_scale_to(c, vn, w, S_W2, n);
       }
@@ -450,13 +451,13 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
 #else
       if (read_scal_begin(c, S_W2, S_H + j + 1 - S_W2)) return -1;  // |w|^2 and h_0..h_j
       if (j + 1 < m && it + 1 < maxits && !c->prof_on) {
-        if (pc_amul(c, vn, w)) return -1;      // (w's last reader, the scaling into v_{j+1}, is ahead of it on the stream)
+        if (pc_amul(c, sys, vn, w)) return -1;      // (w's last reader, the scaling into v_{j+1}, is ahead of it on the stream)
         have_amul = true;
       }
       if (read_scal_end(c)) return -1;
 #endif
-      for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = k.h_scal[S_H + i];
-      const double hn = std::sqrt(k.h_scal[S_W2]);
+      for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = c->ks.h_scal[S_H + i];
+      const double hn = std::sqrt(c->ks.h_scal[S_W2]);
       H[(size_t)(j + 1) * m + j] = hn;
       for (int i = 0; i < j; i++) {
         const double a = H[(size_t)i * m + j], bq = H[(size_t)(i + 1) * m + j];
@@ -484,7 +485,7 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
     }
     {
       Prof p(c, KC_VECTOR);
-      gmres_update_x(c, x, yv.data(), kk);
+      gmres_update_x(c, k.basis, ld, n, x, yv.data(), kk);
       HIPCHK(c, hipStreamSynchronize(c->stream));  // yv is reused by the next cycle
     }
   }
@@ -498,19 +499,19 @@ int ksp_gmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
 // directions + 2 error approximations, classical Gram-Schmidt, left preconditioning.  "linear.type":
 // "lgmres", src/timestepper.F90:1729-1730.  Same kernels as ksp_gmres; the Arnoldi step multiplies a basis
 // vector or an error approximation.
-int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
-  Krylov& k = c->ks;
+int ksp_lgmres(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm) {
+  KrylovVecs& k = *sys.kv;
   partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
   constexpr int AUG = 2;
   // restart = Krylov directions + AUG error approximations: at least one direction (wai_set_opts / wai_ctx_create
   // size the basis for restart >= AUG + 1 and refuse a restart beyond the basis cap)
-  const int n = k.n, mt = std::max(std::min(std::max(c->opts.gmres_restart, AUG + 1), k.basis_m), AUG + 1), mk = mt - AUG, m = mt;
-  double* Z = k.basis + (size_t)(mt + 1) * k.nl;          // Z[0] most recent
-  double* dx = k.basis + (size_t)(mt + 1 + AUG) * k.nl;
+  const int n = sys.n, mt = std::max(std::min(std::max(sys.ksp.restart, AUG + 1), k.basis_m), AUG + 1), mk = mt - AUG, m = mt;
+  double* Z = k.basis + (size_t)(mt + 1) * sys.nl;          // Z[0] most recent
+  double* dx = k.basis + (size_t)(mt + 1 + AUG) * sys.nl;
   int naug = 0;
-  const size_t ld = (size_t)k.nl;
-  const double rtol = c->opts.ksp_rtol, atol = c->opts.ksp_atol;
-  const int maxits = c->opts.ksp_max_its;
+  const size_t ld = (size_t)sys.nl;
+  const double rtol = sys.ksp.rtol, atol = sys.ksp.atol;
+  const int maxits = sys.ksp.max_its;
   std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), yv(m);
   vec_zero(c, x, n);
   int it = 0;
@@ -520,14 +521,14 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
     double* v0 = k.basis;
     if (it == 0) {
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, b, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
+      if (pc_solve(c, sys, b, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     } else {
       vec_copy(c, k.P, x, n);
-      if (halo_exchange(c, k.P, c->np)) return -1;
-      { Prof p(c, KC_SPMV); if (apply_operator(c, k.P, k.tmp)) return -1; }
+      if (halo_exchange(c, k.P, sys.A.bs)) return -1;
+      { Prof p(c, KC_SPMV); if (apply_operator(c, sys, k.P, k.tmp)) return -1; }
       vec_waxpy(c, k.tmp, -1.0, k.tmp, b, n);
       Prof p(c, KC_PC_APPLY);
-      if (pc_solve(c, k.tmp, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
+      if (pc_solve(c, sys, k.tmp, v0, PC_DOT_NONE, nullptr, nullptr)) return -1;
     }
     {
       Prof p(c, KC_VECTOR);
@@ -535,7 +536,7 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
       if (allreduce_scal(c, S_W2, 1)) return -1;
     }
     if (read_scal(c, S_W2, 1)) return -1;
-    res = std::sqrt(k.h_scal[S_W2]);
+    res = std::sqrt(c->ks.h_scal[S_W2]);
     if (it == 0) {
       res0 = res;
       ttol = std::max(rtol * res, atol);
@@ -552,18 +553,18 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
       double* vj = j < mk ? k.basis + ld * j : Z + ld * (j - mk);   // Krylov direction, then error approximations
       double* vn = k.basis + ld * (j + 1);
       double* w = k.T;
-      if (pc_amul(c, vj, w)) return -1;
+      if (pc_amul(c, sys, vj, w)) return -1;
       {
         Prof p(c, KC_VECTOR);
-        gmres_mdot(c, w, j + 1);
+        gmres_mdot(c, k.basis, ld, n, w, j + 1);
         if (allreduce_scal(c, S_H, j + 1)) return -1;
-        gmres_maxpy_norm(c, w, j + 1);
+        gmres_maxpy_norm(c, k.basis, ld, n, w, j + 1);
         if (allreduce_scal(c, S_W2, 1)) return -1;
         gmres_scale_to(c, vn, w, S_W2, n);
       }
       if (read_scal(c, S_W2, S_H + j + 1 - S_W2)) return -1;  // |w|^2 and h_0..h_j
-      for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = k.h_scal[S_H + i];
-      const double hn = std::sqrt(k.h_scal[S_W2]);
+      for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = c->ks.h_scal[S_H + i];
+      const double hn = std::sqrt(c->ks.h_scal[S_W2]);
       H[(size_t)(j + 1) * m + j] = hn;
       for (int i = 0; i < j; i++) {
         const double a = H[(size_t)i * m + j], bq = H[(size_t)(i + 1) * m + j];
@@ -592,7 +593,7 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
     {
       Prof p(c, KC_VECTOR);
       vec_zero(c, dx, n);
-      gmres_update_x(c, dx, yv.data(), std::min(kk, mk));
+      gmres_update_x(c, k.basis, ld, n, dx, yv.data(), std::min(kk, mk));
       HIPCHK(c, hipStreamSynchronize(c->stream));  // yv is reused by the next cycle
       for (int i = mk; i < kk; i++) vec_waxpy(c, dx, yv[i], Z + ld * (i - mk), dx, n);
       vec_waxpy(c, x, 1.0, dx, x, n);
@@ -600,7 +601,7 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
       if (allreduce_scal(c, S_W2, 1)) return -1;
     }
     if (read_scal(c, S_W2, 1)) return -1;
-    if (k.h_scal[S_W2] > 0.0) {   // the new error approximation goes to the front
+    if (c->ks.h_scal[S_W2] > 0.0) {   // the new error approximation goes to the front
       for (int a = AUG - 1; a > 0; a--) vec_copy(c, Z + ld * a, Z + ld * (a - 1), n);
       gmres_scale_to(c, Z, dx, S_W2, n);
       if (naug < AUG) naug++;
@@ -613,17 +614,16 @@ int ksp_lgmres(wai_ctx* c, const double* b, double* x, int* its, int* reason, do
 
 // up to two inner products brought to the host: (a1,b1) -> out[0], (a2,b2) -> out[1] (a2 null: one);
 // one all-reduce on several ranks
-int host_dots(wai_ctx* c, const double* a1, const double* b1, const double* a2, const double* b2, double* out) {
-  Krylov& k = c->ks;
+int host_dots(wai_ctx* c, const LinSys& sys, const double* a1, const double* b1, const double* a2, const double* b2, double* out) {
   {
     Prof p(c, KC_VECTOR);
-    vec_dots(c, a1, b1, S_D1, a2, b2, S_D2, k.n);
-    vec_finalize(c, k.nb_pc, S_D1, a2 ? 2 : 1, -1);
+    vec_dots(c, a1, b1, S_D1, a2, b2, S_D2, sys.n);
+    vec_finalize(c, c->ks.nb_pc, S_D1, a2 ? 2 : 1, -1);
     if (allreduce_scal(c, S_D1, a2 ? 2 : 1)) return -1;
   }
   if (read_scal(c, S_D1, 2)) return -1;
-  out[0] = k.h_scal[S_D1];
-  if (a2) out[1] = k.h_scal[S_D2];
+  out[0] = c->ks.h_scal[S_D1];
+  if (a2) out[1] = c->ks.h_scal[S_D2];
   return 0;
 }
 
@@ -633,12 +633,12 @@ int host_dots(wai_ctx* c, const double* a1, const double* b1, const double* a2, 
 // fused kernels; the vector updates and inner products use the generic vector kernels with the
 // scalars formed on the host (the documented use of this solver is the occasional ill-conditioned
 // system, not the headline path).
-int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
+int ksp_bcgsl(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm) {
   constexpr int L = 2;
-  Krylov& k = c->ks;
+  KrylovVecs& k = *sys.kv;
   partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
-  const int n = k.n;
-  const size_t nl = (size_t)k.nl;
+  const int n = sys.n;
+  const size_t nl = (size_t)sys.nl;
   if (!k.bl) {
     if (dev_alloc(c, &k.bl, (2 * (L + 1) + 1) * (nl + 16))) return -1;
     HIPCHK(c, hipMemsetAsync(k.bl, 0, (2 * (L + 1) + 1) * (nl + 16) * sizeof(double), c->stream));
@@ -646,14 +646,14 @@ int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
   double *r[L + 1], *u[L + 1];
   for (int j = 0; j <= L; j++) { r[j] = k.bl + (size_t)j * (nl + 16); u[j] = k.bl + (size_t)(L + 1 + j) * (nl + 16); }
   double* rt = k.bl + (size_t)(2 * (L + 1)) * (nl + 16);
-  const double rtol = c->opts.ksp_rtol, atol = c->opts.ksp_atol;
-  const int maxits = c->opts.ksp_max_its;
+  const double rtol = sys.ksp.rtol, atol = sys.ksp.atol;
+  const int maxits = sys.ksp.max_its;
   vec_zero(c, x, n);
   for (int j = 0; j <= L; j++) vec_zero(c, u[j], nl);
-  { Prof p(c, KC_PC_APPLY); if (pc_solve(c, b, r[0], PC_DOT_NONE, nullptr, nullptr)) return -1; }
+  { Prof p(c, KC_PC_APPLY); if (pc_solve(c, sys, b, r[0], PC_DOT_NONE, nullptr, nullptr)) return -1; }
   vec_copy(c, rt, r[0], n);
   double d[2];
-  if (host_dots(c, r[0], r[0], nullptr, nullptr, d)) return -1;
+  if (host_dots(c, sys, r[0], r[0], nullptr, nullptr, d)) return -1;
   double dp = std::sqrt(d[0]);
   const double dp0 = dp, ttol = std::max(rtol * dp, atol);
   *its = 0; *reason = 0;
@@ -663,27 +663,27 @@ int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
   while (!*reason && *its < maxits) {
     rho0 = -omega * rho0;
     for (int j = 0; j < L && !*reason; j++) {
-      if (host_dots(c, r[j], rt, nullptr, nullptr, d)) return -1;
+      if (host_dots(c, sys, r[j], rt, nullptr, nullptr, d)) return -1;
       const double rho1 = d[0];
       if (rho0 == 0.0) { *reason = -5; break; }
       const double beta = alpha * (rho1 / rho0);
       rho0 = rho1;
       for (int i = 0; i <= j; i++) vec_waxpy(c, u[i], -beta, u[i], r[i], n);     // u_i = r_i - beta u_i
-      if (pc_amul(c, u[j], u[j + 1])) return -1;
-      if (host_dots(c, u[j + 1], rt, nullptr, nullptr, d)) return -1;
+      if (pc_amul(c, sys, u[j], u[j + 1])) return -1;
+      if (host_dots(c, sys, u[j + 1], rt, nullptr, nullptr, d)) return -1;
       if (d[0] == 0.0) { *reason = -5; break; }
       alpha = rho0 / d[0];
       for (int i = 0; i <= j; i++) vec_waxpy(c, r[i], -alpha, u[i + 1], r[i], n);  // r_i -= alpha u_{i+1}
-      if (pc_amul(c, r[j], r[j + 1])) return -1;
+      if (pc_amul(c, sys, r[j], r[j + 1])) return -1;
       vec_waxpy(c, x, alpha, u[0], x, n);
     }
     if (*reason) break;
     double Z[L][L], z[L], g[L], t2[2];
-    if (host_dots(c, r[1], r[1], r[1], r[2], t2)) return -1;
+    if (host_dots(c, sys, r[1], r[1], r[1], r[2], t2)) return -1;
     Z[0][0] = t2[0]; Z[0][1] = Z[1][0] = t2[1];
-    if (host_dots(c, r[2], r[2], r[1], r[0], t2)) return -1;
+    if (host_dots(c, sys, r[2], r[2], r[1], r[0], t2)) return -1;
     Z[1][1] = t2[0]; z[0] = t2[1];
-    if (host_dots(c, r[2], r[0], nullptr, nullptr, t2)) return -1;
+    if (host_dots(c, sys, r[2], r[0], nullptr, nullptr, t2)) return -1;
     z[1] = t2[0];
     const double det = Z[0][0] * Z[1][1] - Z[0][1] * Z[1][0];
     if (det == 0.0) { *reason = -5; break; }
@@ -696,7 +696,7 @@ int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
     for (int j = 0; j < L; j++) vec_waxpy(c, r[0], -g[j], r[j + 1], r[0], n);
     omega = g[L - 1];
     *its += L;
-    if (host_dots(c, r[0], r[0], nullptr, nullptr, d)) return -1;
+    if (host_dots(c, sys, r[0], r[0], nullptr, nullptr, d)) return -1;
     dp = std::sqrt(d[0]);
     if (std::isnan(dp)) *reason = -9;
     else if (dp <= ttol) *reason = (dp <= atol) ? 3 : 2;
@@ -708,17 +708,17 @@ int ksp_bcgsl(wai_ctx* c, const double* b, double* x, int* its, int* reason, dou
   return 0;
 }
 
-int do_ksp(wai_ctx* c, const double* b, double* x, int* its, int* reason, double* rnorm) {
+int do_ksp(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm) {
   read_env(c);
-  if (!c->ilu.factored) {
-    const int e = do_pc_setup(c);
+  if (c->ilu.owner != &sys) {
+    const int e = do_pc_setup(c, sys);
     if (e < 0) return -1;
     if (e > 0) { *reason = -11; *its = 0; *rnorm = 0.0; return 0; }
   }
-  if (c->opts.ksp_type == WAI_KSP_GMRES) return ksp_gmres(c, b, x, its, reason, rnorm);
-  if (c->opts.ksp_type == WAI_KSP_BCGSL) return ksp_bcgsl(c, b, x, its, reason, rnorm);
-  if (c->opts.ksp_type == WAI_KSP_LGMRES) return ksp_lgmres(c, b, x, its, reason, rnorm);
-  return ksp_bcgs(c, b, x, its, reason, rnorm);
+  if (sys.ksp.type == WAI_KSP_GMRES) return ksp_gmres(c, sys, b, x, its, reason, rnorm);
+  if (sys.ksp.type == WAI_KSP_BCGSL) return ksp_bcgsl(c, sys, b, x, its, reason, rnorm);
+  if (sys.ksp.type == WAI_KSP_LGMRES) return ksp_lgmres(c, sys, b, x, its, reason, rnorm);
+  return ksp_bcgs(c, sys, b, x, its, reason, rnorm);
 }
 
 }  // namespace wai

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_stream_read(const stream_d2* __restrict
   if (t == 1.2345678e300) *sink = t;   // never: keeps the loads
 }
 // can pc_amul form its operand x - alpha x2 inside the launch?  (pc_axpy_ok without the switch and the default)
-bool pc_operand_composable(const wai_ctx* c) { return pc_fused(c) && !c->net.cp_valid && pc_axpy_capable(c); }
+bool pc_operand_composable(const wai_ctx* c) { return pc_fused(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A); }
 }  // namespace
 
 extern "C" {
@@ -39,46 +39,47 @@ extern "C" {
 // 1 = ILU(0) apply z = B^-1 r, 2 = fused z = B^-1 (A x) with the (z, aux) reduction finished in the kernel,
 // 3/4 = probes of 1/2 with the substitution sweeps skipped (load/compute phase split), 5 = the five launches
 // of a whole BiCGStab iteration (overwrites the Krylov work vectors), 6 = its vector updates alone,
-// 9 / 10 = the fused kernel on the interior / face bricks only, 23 = z = B^-1 (A x) by the launch-per-level path on the
+// 9 / 10 = the fused kernel on the interior / face bricks only (all on the flow system), 23 = z = B^-1 (A x) by the launch-per-level path on the
 // factor in force (k_spmv + k_lvl_solve per level: the path k_pc_wide replaces, on the same system).
 int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   if (!c || !ms_per_launch || reps <= 0) return -2;
   read_env(c);
-  if ((which == 20 || which == 21) && !c->ks.basis) { c->err = "wai_bench_kernel 20 / 21: no Krylov basis (ksp_type gmres)"; return -2; }
-  if (which > 0 && !c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e < 0 ? -1 : e; }
-  if (which == 23 && (!pc_fused(c) || !c->ilu.ord_f)) { c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh)"; return -2; }
-  Krylov& k = c->ks;
+  LinSys& sys = c->flow;
+  KrylovVecs& k = *sys.kv;
+  if ((which == 20 || which == 21) && !k.basis) { c->err = "wai_bench_kernel 20 / 21: no Krylov basis (ksp_type gmres)"; return -2; }
+  if (which > 0 && c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
+  if (which == 23 && (!pc_fused(c, sys) || !c->ilu.ord_f)) { c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh)"; return -2; }
   const size_t copy_n = (size_t)c->np * c->df * c->mesh.n_prim / 2;   // modes 18 / 19 (the scratch is rewritten by every Jacobian)
   auto run = [&]() {
     switch (which) {
-      case 0: launch_spmv(c, k.P, k.tmp); break;
-      case 1: case 3: pc_solve(c, k.P, k.V, PC_DOT_NONE, nullptr, nullptr); break;
+      case 0: launch_spmv(c, sys.A, k.P, k.tmp); break;
+      case 1: case 3: pc_solve(c, sys, k.P, k.V, PC_DOT_NONE, nullptr, nullptr); break;
       case 23:   // the launch-per-level path on the schedule in force (wide schedules: the factor k_pc_wide applies), for comparison
-        launch_spmv(c, k.P, k.V);
-        launch_big_solve(c, c->J, c->ilu, k.V);
+        launch_spmv(c, sys.A, k.P, k.V);
+        launch_big_solve(c, sys.A, c->ilu, k.V);
         break;
-      case 9: if (c->ilu.n_int > 0) launch_pc(c, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_int, c->ilu.n_int); break;   // interior bricks only
-      case 10: if (c->ilu.n_bnd > 0) launch_pc(c, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_bnd, c->ilu.n_bnd); break;  // face bricks only
+      case 9: if (c->ilu.n_int > 0) launch_pc(c, sys.A, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_int, c->ilu.n_int); break;   // interior bricks only
+      case 10: if (c->ilu.n_bnd > 0) launch_pc(c, sys.A, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_bnd, c->ilu.n_bnd); break;  // face bricks only
       case 16:  // interior + face bricks as the overlapped halo exchange launches them (no halo here): the split's cost against case 2
         if (c->ilu.n_int > 0 && c->ilu.n_bnd > 0) {
           const Fin fin = make_fin_dots(c, PC_DOT_ZA, 2);
-          launch_pc_split(c, k.P, k.V, PC_DOT_ZA, k.RP, &fin, nullptr, nullptr);
+          launch_pc_split(c, sys.A, k.P, k.V, PC_DOT_ZA, k.RP, &fin, nullptr, nullptr);
         }
         break;
       case 5: {  // the launches (and, on several ranks, collectives) of one BiCGStab iteration back to back, no host in
                  // the loop: the iteration's floor
-        const BcgsPlan pl = bcgs_plan(c);
-        bcgs_first_half(c, pl); bcgs_second_half(c, pl);
+        const BcgsPlan pl = bcgs_plan(c, sys);
+        bcgs_first_half(c, sys, pl); bcgs_second_half(c, sys, pl);
         break;
       }
       case 6:   // its vector updates alone
-        if (bcgs_mode(c) == 2) { if (!pc_axpy_ok(c)) bcgs_update_s(c); bcgs_update_xrp(c); }
-        else { bcgs_update_p(c); bcgs_update_s(c); bcgs_update_xr(c, true, 4, false); }
+        if (bcgs_mode(c) == 2) { if (!pc_axpy_ok(c, sys)) bcgs_update_s(c, k, sys.n); bcgs_update_xrp(c, k, sys.n); }
+        else { bcgs_update_p(c, k, sys.n); bcgs_update_s(c, k, sys.n); bcgs_update_xr(c, k, sys.n, true, 4, false); }
         break;
       case 17: {  // the second fused launch of the iteration exactly as bcgs_second_half issues it on one rank: operand S (or
                   // R - alpha V formed in the launch), five inner products, omega / (R,R) / rho / beta + the post in the finaliser
-        const BcgsPlan pl = bcgs_plan(c);
-        pc_amul(c, pl.axpy ? k.R : k.S, k.T, PC_DOT_MERGED, k.RP, 6, pl.axpy ? k.V : nullptr, true);
+        const BcgsPlan pl = bcgs_plan(c, sys);
+        pc_amul(c, sys, pl.axpy ? k.R : k.S, k.T, PC_DOT_MERGED, k.RP, 6, pl.axpy ? k.V : nullptr, true);
         break;
       }
       case 18:   // what a copy achieves on this box: hipMemcpy device to device, half of the perturbed-fluid scratch onto the other
@@ -94,29 +95,29 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
         break;
       case 20: {  // GMRES: the classical Gram-Schmidt inner products (w, v_0 .. v_j) of a whole restart cycle, j = 0 .. m - 1,
                   // as ksp_gmres issues them (k_mdot passes + their finalisations); ms_per_launch = per Krylov iteration
-        const int m = std::min(std::max(c->opts.gmres_restart, 1), k.basis_m);
-        for (int j = 0; j < m; j++) gmres_mdot(c, k.T, j + 1);
+        const int m = std::min(std::max(sys.ksp.restart, 1), k.basis_m);
+        for (int j = 0; j < m; j++) gmres_mdot(c, k.basis, (size_t)sys.nl, sys.n, k.T, j + 1);
         break;
       }
       case 21: {  // GMRES: w -= sum h_j v_j + |w|^2 of a whole restart cycle (k_maxpy_norm + finalisation), per iteration
-        const int m = std::min(std::max(c->opts.gmres_restart, 1), k.basis_m);
-        for (int j = 0; j < m; j++) gmres_maxpy_norm(c, k.T, j + 1);
+        const int m = std::min(std::max(sys.ksp.restart, 1), k.basis_m);
+        for (int j = 0; j < m; j++) gmres_maxpy_norm(c, k.basis, (size_t)sys.nl, sys.n, k.T, j + 1);
         break;
       }
       case 7:   // the second fused launch of the "fused" iteration: z = B^-1 A (R - alpha V) with the five inner products
-        pc_amul(c, k.R, k.T, PC_DOT_MERGED, k.RP, -1, pc_axpy_ok(c) ? k.V : nullptr, false);
+        pc_amul(c, sys, k.R, k.T, PC_DOT_MERGED, k.RP, -1, pc_axpy_ok(c, sys) ? k.V : nullptr, false);
         break;
       // the fused launch by reduction mode: 11 none; 12 (z,aux) left as partials; 13 (x,z),(z,z) + omega in the launch;
       // 14 the five merged products left as partials; 15 the five + omega, (R,R), rho, beta in the launch
-      case 11: pc_amul(c, k.P, k.V, PC_DOT_NONE, nullptr, -2); break;
-      case 12: pc_amul(c, k.P, k.V, PC_DOT_ZA, k.RP, -2); break;
-      case 13: pc_amul(c, k.P, k.V, PC_DOT_XZ, nullptr, 3); break;
-      case 14: pc_amul(c, k.P, k.V, PC_DOT_MERGED, k.RP, -2); break;
-      case 15: pc_amul(c, k.P, k.V, PC_DOT_MERGED, k.RP, 6); break;
-      default: pc_amul(c, k.P, k.V, PC_DOT_ZA, k.RP, 2); break;   // what a BiCGStab half-iteration runs (no halo on one rank)
+      case 11: pc_amul(c, sys, k.P, k.V, PC_DOT_NONE, nullptr, -2); break;
+      case 12: pc_amul(c, sys, k.P, k.V, PC_DOT_ZA, k.RP, -2); break;
+      case 13: pc_amul(c, sys, k.P, k.V, PC_DOT_XZ, nullptr, 3); break;
+      case 14: pc_amul(c, sys, k.P, k.V, PC_DOT_MERGED, k.RP, -2); break;
+      case 15: pc_amul(c, sys, k.P, k.V, PC_DOT_MERGED, k.RP, 6); break;
+      default: pc_amul(c, sys, k.P, k.V, PC_DOT_ZA, k.RP, 2); break;   // what a BiCGStab half-iteration runs (no halo on one rank)
     }
   };
-  c->dbg = (which == 3 || which == 4) && pc_fused(c) && !(c->J.bs == 2 && c->ilu.park) ? 1 : 0;
+  c->dbg = (which == 3 || which == 4) && pc_fused(c, sys) && !(sys.A.bs == 2 && c->ilu.park) ? 1 : 0;
   partials_clear(c, S_D1, 5);
   // Warm-up by TIME, not by count: the probes run behind host-side work (the bench's checks, a Jacobian), and the first
   // launches after such a pause run below the clocks the real iteration sees -- MEASURED (round 6, one box, same process
@@ -149,7 +150,7 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   float ms = 0.f;
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
   *ms_per_launch = ms / reps;
-  if (which == 20 || which == 21) *ms_per_launch /= (float)std::min(std::max(c->opts.gmres_restart, 1), k.basis_m);
+  if (which == 20 || which == 21) *ms_per_launch /= (float)std::min(std::max(sys.ksp.restart, 1), k.basis_m);
   return 0;
 }
 
@@ -157,24 +158,27 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
 const char* wai_pc_kernel_name(wai_ctx* c) {
   if (!c) return "";
   const IluSchedule& s = c->ilu;
+  const LinSys& sys = c->flow;
+  const int bs = sys.A.bs;
   if (c->opts.pc_type == WAI_PC_NONE) return "k_spmv (no preconditioner)";
   if (c->opts.pc_type == WAI_PC_LU) return "k_spmv + k_lu_apply (dense block inverses)";
-  if (pc_extended(c)) {
-    static thread_local char b3[96];
-    snprintf(b3, sizeof(b3), "k_spmv + %s on the extended system (%s, ILU(%d))",
-             c->as.sched.big ? "k_lvl_solve per level" : (c->as.sched.wide ? "k_pc_wide" : "k_pc"),
+  static thread_local char buf[96];
+  if (pc_extended(c, sys)) {
+    snprintf(buf, sizeof(buf), "k_spmv + %s on the extended system (%s, ILU(%d))",
+             sys.as.sched.big ? "k_lvl_solve per level" : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),
              c->opts.pc_type == WAI_PC_ASM ? "ASM" : "block Jacobi", std::max(c->opts.ilu_levels, 0));
-    return b3;
+    return buf;
   }
   if (s.big) return "k_spmv + k_lvl_solve per level";
-  if (s.wide) { static thread_local char bw[64]; snprintf(bw, sizeof(bw), "k_pc_wide<%d,spmv>", c->J.bs); return bw; }
-  if (s.wave_kernel) { static thread_local char b4[64]; snprintf(b4, sizeof(b4), "k_pc_wave<%d,spmv>", c->J.bs); return b4; }
-  if (s.rows_kernel) { static thread_local char b2[64]; snprintf(b2, sizeof(b2), "k_pc_rows<%d,spmv,%d+%d>", c->J.bs, s.max_nlu <= 3 ? 3 : 4, s.max_nlu <= 3 ? 3 : 4); return b2; }
-  if (c->J.bs == 2 && s.park && s.diag_only && s.scaled && s.fast3 && s.max_rows <= 512)
-    return s.col16 && !getenv("WAI_NO_COL16") ? "k_pc_park<spmv,col16>" : "k_pc_park<spmv>";
-  static thread_local char buf[96];
-  snprintf(buf, sizeof(buf), "k_pc<%d,spmv,%s,%s>", c->J.bs, s.diag_only ? (s.scaled ? "dilu-scaled" : "dilu") : "ilu",
-           s.fast3 ? "compact3" : "generic");
+  switch (pc_kernel_kind(c, sys.A, s)) {   // the launcher's own rule (kernels_fused.hip)
+    case 4: snprintf(buf, sizeof(buf), "k_pc_wide<%d,spmv>", bs); break;
+    case 3: snprintf(buf, sizeof(buf), "k_pc_wave<%d,spmv>", bs); break;
+    case 2: snprintf(buf, sizeof(buf), "k_pc_rows<%d,spmv,%d+%d>", bs, s.max_nlu <= 3 ? 3 : 4, s.max_nlu <= 3 ? 3 : 4); break;
+    case 1: return s.col16 && !getenv("WAI_NO_COL16") ? "k_pc_park<spmv,col16>" : "k_pc_park<spmv>";
+    default:
+      snprintf(buf, sizeof(buf), "k_pc<%d,spmv,%s,%s>", bs, s.diag_only ? (s.scaled ? "dilu-scaled" : "dilu") : "ilu",
+               s.fast3 ? "compact3" : "generic");
+  }
   return buf;
 }
 int wai_comm_size(wai_ctx* c) { return c ? comm_count(c->comm) : -2; }
@@ -182,7 +186,7 @@ int wai_comm_size(wai_ctx* c) { return c ? comm_count(c->comm) : -2; }
 int wai_bcgs_composed(wai_ctx* c) {
   if (!c) return -2;
   read_env(c);
-  const BcgsPlan pl = bcgs_plan(c);
+  const BcgsPlan pl = bcgs_plan(c, c->flow);
   return pl.axpy ? 1 : 0;
 }
 int wai_launch_stats(wai_ctx* c, long long* kernels, long long* copies) {
@@ -205,21 +209,22 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   if (!c || !x || !z || !scal_in || !scal_out || dot_mode < PC_DOT_NONE || dot_mode > PC_DOT_MERGED || fin_phase < -2) return -2;
   if ((dot_mode == PC_DOT_ZA || dot_mode == PC_DOT_MERGED) && !aux) { c->err = "wai_test_pc_operator: dot modes 1 and 4 need aux"; return -2; }
   read_env(c);
-  if (!c->ilu.factored) { const int e = do_pc_setup(c); if (e) return e < 0 ? -1 : e; }
+  LinSys& sys = c->flow;
+  if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
   if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
-  if (split && (!spmv || !pc_fused(c) || c->net.cp_valid || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
+  if (split && (!spmv || !pc_fused(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
     c->err = "wai_test_pc_operator: no interior / face brick lists to split the launch over";
     return -1;
   }
-  Krylov& k = c->ks;
-  const size_t n = (size_t)k.n;
+  KrylovVecs& k = *sys.kv;
+  const size_t n = (size_t)sys.n;
   double s[16];
   for (int i = 0; i < 16; i++) s[i] = scal_in[i];
   s[S_ALPHA] = alpha;
   HIPCHK(c, hipMemcpyAsync(k.R, x, n * sizeof(double), hipMemcpyDefault, c->stream));
   if (x2) HIPCHK(c, hipMemcpyAsync(k.V, x2, n * sizeof(double), hipMemcpyDefault, c->stream));
   if (aux) HIPCHK(c, hipMemcpyAsync(k.RP, aux, n * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipMemcpyAsync(k.scal, s, sizeof(s), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->ks.scal, s, sizeof(s), hipMemcpyHostToDevice, c->stream));
   partials_clear(c, S_D1, 5);
   const double* a = aux ? k.RP : nullptr;
   const double* v = x2 ? k.V : nullptr;
@@ -231,17 +236,17 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
       fin = make_fin_dots(c, dot_mode, fin_phase);
       fp = &fin;
     }
-    e = launch_pc_split(c, k.R, k.T, dot_mode, a, fp, v, nullptr);
+    e = launch_pc_split(c, sys.A, k.R, k.T, dot_mode, a, fp, v, nullptr);
   } else if (spmv) {
-    e = pc_amul(c, k.R, k.T, dot_mode, a, fin_phase, v, false);
+    e = pc_amul(c, sys, k.R, k.T, dot_mode, a, fin_phase, v, false);
   } else {
-    e = pc_solve(c, k.R, k.T, dot_mode, k.R, a, fin_phase);
+    e = pc_solve(c, sys, k.R, k.T, dot_mode, k.R, a, fin_phase);
   }
   if (e) return e;
   if (fin_phase == -2 && dot_mode)   // the partial sums left behind, summed by k_finalize as the general path sums them
-    vec_finalize(c, k.nb_pc, pc_dot_slot0(dot_mode), pc_dot_nslots(dot_mode), -1);
+    vec_finalize(c, c->ks.nb_pc, pc_dot_slot0(dot_mode), pc_dot_nslots(dot_mode), -1);
   HIPCHK(c, hipMemcpyAsync(z, k.T, n * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipMemcpyAsync(s, k.scal, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(s, c->ks.scal, sizeof(s), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < 16; i++) scal_out[i] = s[i];
   return 0;

@@ -367,11 +367,11 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
 
 // t = (A + E) x: the block-ELL SpMV and, when the network couples cells, its blocks on top.  A network on several
 // ranks: x at the network's cells is gathered first (one all-reduce of m * bs doubles per application)
-int apply_operator(wai_ctx* c, const double* x, double* t) {
-  launch_spmv(c, x, t);
+int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t) {
+  launch_spmv(c, sys.A, x, t);
   const Network& nw = c->net;
-  if (!nw.cp_valid) return 0;
-  const int ml = (int)nw.cp_cells.size(), bs = c->np;
+  if (!net_in_operator(c, sys)) return 0;
+  const int ml = (int)nw.cp_cells.size(), bs = sys.A.bs;
   if (!nw.cp_span) {
     hipLaunchKernelGGL(k_coupling_apply, (ml * bs + 63) / 64, 64, 0, c->stream, ml, ml, bs, nw.d_cp_cells, nw.d_cp_val, x,
                        (const double*)nullptr, t);
@@ -578,7 +578,7 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
   nw.on = true;
   if (!span) network_cells(nw, n);
   else network_cells_span(nw, ng, span_id, c->comm->rank);
-  c->as.overlap = -1;   // the factor's pattern carries the network's cell pairs: built again at the next set-up
+  c->flow.as.overlap = -1;   // the factor's pattern carries the network's cell pairs: built again at the next set-up
   return 0;
 }
 
@@ -594,15 +594,15 @@ int wai_set_source_global_index(wai_ctx* c, int n_global, const int* global_inde
 
 int wai_set_network_couplings(wai_ctx* c, int on) {
   if (!c) return -2;
-  const bool was = pc_with_net(c);
+  const bool was = pc_with_net(c, c->flow);
   c->net.coupling = on != 0;
   c->net.cp_in_pc = on != 1;      // 1: in the operator only (rounds 2-3); 2 (and any other non-zero value): in the factor's pattern too
   if (!on) c->net.cp_valid = false;
   // pc_fused() / pc_extended() follow pc_with_net(): a set-up made for the other path (the extended system factored and
   // c->ilu not, or the other way round) must not be applied -- the next solve sets up again, the extended pattern included
-  if (pc_with_net(c) != was) {
-    c->ilu.factored = false;
-    c->as.overlap = -1;
+  if (pc_with_net(c, c->flow) != was) {
+    pc_invalidate(c);
+    c->flow.as.overlap = -1;
   }
   return 0;
 }

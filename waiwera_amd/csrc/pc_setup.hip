@@ -99,10 +99,10 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
   }
   // the brick kernels hold a row's <= 8 blocks in registers and pack slot numbers in 4 bits: wider rows (ILU(k)
   // fill) and subdomains of more than 1024 rows take the launch-per-level path, whose descriptor has 8-bit slots.
-  // A mesh whose own rows are wider (cells with 9 .. 16 faces: c->J.W > 8) has k_pc_wide for its subdomains of <= 1024
+  // A mesh whose own rows are wider (cells with 9 .. 16 faces: c->pat.W > 8) has k_pc_wide for its subdomains of <= 1024
   // rows of <= 16 blocks: its own Jacobian's and the ILU(0) extended systems of PCASM built on it (`allow_wide`; ILU(k)
   // fill stays on the launch-per-level path).  A mesh of at most 8 blocks per row keeps the schedule it always had.
-  s.wide = allow_wide && c->J.W > 8 && W > 8 && W <= 16 && s.max_rows <= 1024;
+  s.wide = allow_wide && c->pat.W > 8 && W > 8 && W <= 16 && s.max_rows <= 1024;
   s.big = s.max_rows > 1024 || (W > 8 && !s.wide);
   if (!s.big && s.max_lev > 1023) { c->err = "more than 1023 dependency levels in a subdomain"; return -2; }
   for (int i = 0; i < N; i++)
@@ -301,7 +301,6 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
     }
   }
   s.built = true;
-  s.factored = false;
   return 0;
 }
 
@@ -376,18 +375,18 @@ int ensure_halo_dof(wai_ctx* c, int dof) {   // halo buffers wide enough for `do
 // second exchange carries, for every cell a rank sends, the identities of its row's columns.  The receiver keeps
 // the columns it knows (its owned and ghost cells -- what the overlapped row sets can contain) in ascending local
 // order, with the sender's slot each came from.
-int ghost_rows(wai_ctx* c, std::vector<int>& grp, std::vector<int>& gci, std::vector<int>& gslot) {
-  const Bcsr& J = c->J;
+int ghost_rows(wai_ctx* c, const LinSys& sys, std::vector<int>& grp, std::vector<int>& gci, std::vector<int>& gslot) {
+  const Pattern& J = c->pat;
   const int N = J.n, H = c->mesh.n_halo, W = J.W;
   std::vector<double> ids((size_t)N + H, -1.0);
   const double base = (double)c->comm->rank * 4294967296.0;
   for (int i = 0; i < N; i++) ids[i] = base + i;
-  double* scratch = c->ks.tmp;   // a Krylov work vector (n_prim * bs + 16 doubles): idle while the preconditioner is set up
+  double* scratch = sys.kv->tmp;   // a Krylov work vector (at least n_prim + 16 doubles): idle while the preconditioner is set up
   HIPCHK(c, hipMemcpyAsync(scratch, ids.data(), sizeof(double) * (N + H), hipMemcpyHostToDevice, c->stream));
   if (halo_exchange(c, scratch, 1)) return -1;
   HIPCHK(c, hipMemcpyAsync(ids.data(), scratch, sizeof(double) * (N + H), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (ensure_halo_dof(c, W * J.bs * J.bs)) return -1;
+  if (ensure_halo_dof(c, W * sys.A.bs * sys.A.bs)) return -1;
   std::vector<int> sidx((size_t)c->send_total);
   HIPCHK(c, hipMemcpy(sidx.data(), c->d_send_idx, sizeof(int) * sidx.size(), hipMemcpyDeviceToHost));
   std::vector<double> sb((size_t)c->send_total * W, -1.0), rb((size_t)H * W, -1.0);
@@ -422,11 +421,11 @@ int ghost_rows(wai_ctx* c, std::vector<int>& grp, std::vector<int>& gci, std::ve
   return 0;
 }
 
-int build_asm(wai_ctx* c, int overlap, int levels, bool with_net) {
-  AsmSystem& a = c->as;
+int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net) {
+  AsmSystem& a = sys.as;
   free_asm(a);
-  const Bcsr& J = c->J;
-  const int N = J.n, np = J.bs;
+  const Pattern& J = c->pat;
+  const int N = J.n, np = sys.A.bs;
   // Overlap across rank boundaries (the reference's PCASM subdomains are the ranks and MatIncreaseOverlap
   // pulls in the neighbours' rows): the overlapped sets may contain partition-ghost cells, whose matrix rows come
   // from their owners.  One ghost layer exists, so overlap 1 -- the reference's default -- is exact; a deeper overlap would
@@ -438,7 +437,7 @@ int build_asm(wai_ctx* c, int overlap, int levels, bool with_net) {
   }
   const int H = cross ? c->mesh.n_halo : 0, NX = N + H;
   std::vector<int> grp, gci, gslot;
-  if (cross && ghost_rows(c, grp, gci, gslot)) return -1;
+  if (cross && ghost_rows(c, sys, grp, gci, gslot)) return -1;
   // row i of the local matrix: owned rows are the Jacobian's, ghost rows the received ones
   auto row_begin = [&](int i) { return i < N ? J.h_rowptr[i] : grp[i - N]; };
   auto row_end = [&](int i) { return i < N ? J.h_rowptr[i + 1] : grp[i - N + 1]; };
@@ -540,7 +539,6 @@ int build_asm(wai_ctx* c, int overlap, int levels, bool with_net) {
   a.sched = fresh;
   a.n_ext = n_ext;
   a.E.n = n_ext; a.E.ncols = n_ext; a.E.bs = np; a.E.W = W; a.E.nnzb = (int)ecol.size();
-  a.E.h_rowptr = erp; a.E.h_colidx = ecol;
   if (dev_upload(c, &a.E.col, ell_col) || dev_upload(c, &a.gmap, gmap) || dev_upload(c, &a.ext_row, erow) ||
       dev_alloc(c, &a.E.val, ell_size(np, n_ext, W)) || dev_alloc(c, &a.r_ext, (size_t)np * n_ext + 16))
     return -1;
@@ -573,9 +571,9 @@ int build_asm(wai_ctx* c, int overlap, int levels, bool with_net) {
 
 // PCLU: dense inverse of every preconditioner block (one block per rank with sub_ptr = NULL), by
 // Gauss-Jordan elimination with partial pivoting on the host.  Meant for small systems.
-int lu_setup(wai_ctx* c) {
-  const Bcsr& J = c->J;
-  const int bs = J.bs, bb = bs * bs, nsub = c->ilu.nsub;
+int lu_setup(wai_ctx* c, const LinSys& sys) {
+  const Pattern& J = c->pat;
+  const int bs = sys.A.bs, bb = bs * bs, nsub = c->ilu.nsub;
   std::vector<int> sub((size_t)nsub + 1);
   HIPCHK(c, hipMemcpy(sub.data(), c->ilu.sub_ptr, sizeof(int) * sub.size(), hipMemcpyDeviceToHost));
   LuBlocks& L = c->lu;
@@ -594,7 +592,7 @@ int lu_setup(wai_ctx* c) {
   {
     double* tmp = nullptr;
     if (dev_alloc(c, &tmp, val.size())) return -1;
-    launch_ell_to_bcsr(c, J.val, tmp);
+    launch_ell_to_bcsr(c, sys.A, tmp);
     HIPCHK(c, hipMemcpyAsync(val.data(), tmp, val.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     (void)hipFree(tmp);
@@ -632,35 +630,39 @@ int lu_setup(wai_ctx* c) {
   return 0;
 }
 
-int do_pc_setup(wai_ctx* c) {
+// Sets the preconditioner up for `sys` and records it as the owner of the (shared) factor: 0 done, 1 a pivot failed
+// (recoverable; the record stands as it did for the flags read back last), < 0 error
+int do_pc_setup(wai_ctx* c, LinSys& sys) {
   read_env(c);
-  if (c->opts.pc_type == WAI_PC_NONE) { c->ilu.factored = true; return 0; }
+  if (c->opts.pc_type == WAI_PC_NONE) { c->ilu.owner = &sys; return 0; }
   if (c->opts.pc_type == WAI_PC_LU) {
     Prof p(c, KC_PC_SETUP);
-    const int e = lu_setup(c);
-    if (e == 0) c->ilu.factored = true;
+    const int e = lu_setup(c, sys);
+    if (e == 0) c->ilu.owner = &sys;
     return e;
   }
   {
     Prof p(c, KC_PC_SETUP);
-    if (pc_extended(c)) {
+    const Bcsr& A = sys.A;
+    if (pc_extended(c, sys)) {
+      AsmSystem& as = sys.as;
       const int ov = c->opts.pc_type == WAI_PC_ASM ? (c->opts.asm_overlap > 0 ? c->opts.asm_overlap : 1) : 0;
       const int lv = std::max(c->opts.ilu_levels, 0);
-      const bool wn = pc_with_net(c);
-      if (c->as.overlap != ov || c->as.levels != lv || c->as.E.bs != c->J.bs || c->as.with_net != wn) { if (int e = build_asm(c, ov, lv, wn)) return e < 0 ? -1 : e; }
-      if (c->as.cross) {   // the ghost cells' matrix rows, from their owners
-        const int dof = c->J.W * c->J.bs * c->J.bs;
+      const bool wn = pc_with_net(c, sys);
+      if (as.overlap != ov || as.levels != lv || as.E.bs != A.bs || as.with_net != wn) { if (int e = build_asm(c, sys, ov, lv, wn)) return e < 0 ? -1 : e; }
+      if (as.cross) {   // the ghost cells' matrix rows, from their owners
+        const int dof = A.W * A.bs * A.bs;
         if (ensure_halo_dof(c, dof)) return -1;
-        launch_pack_rows(c);
+        launch_pack_rows(c, A);
         if (comm_exchange(c->comm, c->n_nbr, c->nbr_rank.data(), c->send_ptr.data(), c->recv_ptr.data(), dof, c->d_sendbuf,
                           c->d_recvbuf, c->stream, c->err))
           return -1;
-        launch_unpack_rows(c);
+        launch_unpack_rows(c, A, as);
       }
-      launch_asm_gather_matrix(c);
-      if (launch_ilu_factor_on(c, c->as.E, c->as.sched)) return -1;
-      c->ilu.factored = true;
-    } else if (launch_ilu_factor(c)) return -1;
+      launch_asm_gather_matrix(c, A, as);
+      if (launch_ilu_factor_on(c, as.E, as.sched)) return -1;
+    } else if (launch_ilu_factor_on(c, A, c->ilu)) return -1;
+    c->ilu.owner = &sys;
   }
   int fl[4];
   if (fetch_flags(c, fl)) return -1;
