@@ -410,6 +410,16 @@ int wai_set_tracer_solve_mode(wai_ctx *ctx, int mode);
 int wai_tracer_block_system(wai_ctx *ctx, int method, double dt, double ratio, const double *alx_last,
                             const double *alx_last2, double *val, double *b);
 
+/* Sub-preconditioner of WAI_PC_BJACOBI and WAI_PC_ASM (linear.preconditioner.sub.preconditioner.type, src/timestepper.F90:1704-1718,
+ * 1789-1834).  WAI_SUB_ILU (the default): ILU(ilu_levels).  WAI_SUB_LU: the exact LU factorisation of every subdomain block -- under
+ * WAI_PC_ASM of every overlapped block, the reference's Schwarz method with exact local solves -- factored and applied on the
+ * device as ILU with every level of fill kept; ilu_levels is ignored.  Under WAI_PC_NONE and WAI_PC_LU the setting is ignored.
+ * A block whose complete fill gives a factor row of more than 255 blocks is refused by the set-up (-2, wai_last_error names
+ * the width found and the cap), never factored incompletely; a zero pivot is reported like ILU's (the solve's reason is
+ * PC_FAILED).  The coupled tracer solve (WAI_TRACER_COUPLED) refuses WAI_SUB_LU.  Unknown value: -2. */
+enum { WAI_SUB_ILU = 0, WAI_SUB_LU = 1 };
+int wai_set_sub_pc(wai_ctx *ctx, int sub);
+
 int wai_synchronize(wai_ctx *ctx);   /* wait for everything enqueued on the library's stream */
 const char *wai_pc_kernel_name(wai_ctx *ctx);   /* kernel / path of a preconditioned-operator application (reports) */
 

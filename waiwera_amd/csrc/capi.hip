@@ -1164,6 +1164,14 @@ int wai_set_tracer_solve_mode(wai_ctx* c, int mode) {
   return 0;
 }
 
+int wai_set_sub_pc(wai_ctx* c, int sub) {
+  if (!c) return -2;
+  if (sub != WAI_SUB_ILU && sub != WAI_SUB_LU) { c->err = "unknown sub-preconditioner (WAI_SUB_ILU or WAI_SUB_LU)"; return -2; }
+  if (sub != c->sub_pc) pc_invalidate(c);   // (the cached extended systems are rebuilt by the next set-up: do_pc_setup)
+  c->sub_pc = sub;
+  return 0;
+}
+
 int wai_tracer_lhs(wai_ctx* c, double* Al) {
   if (!c || !Al) return -2;
   if (!c->tr.nt) { c->err = "no tracers set"; return -1; }
@@ -1194,7 +1202,8 @@ static int coupled_system_buffers(wai_ctx* c) {
 static int coupled_prepare(wai_ctx* c) {
   LinSys& sys = c->coupled;
   const char* what = nullptr;
-  if (c->opts.pc_type == WAI_PC_ASM) what = "the asm preconditioner";
+  if (pc_sub_lu(c)) what = "the lu sub-preconditioner (WAI_SUB_LU)";
+  else if (c->opts.pc_type == WAI_PC_ASM) what = "the asm preconditioner";
   else if (c->opts.pc_type == WAI_PC_LU) what = "the lu preconditioner";
   else if (c->opts.ilu_levels > 0) what = "ILU(k) with k > 0";
   else if (c->opts.pc_type != WAI_PC_BJACOBI && c->opts.pc_type != WAI_PC_NONE) what = "this preconditioner";

@@ -269,6 +269,10 @@ struct IluSchedule {
   // subdomains, so the factorisation and the two substitutions run as one launch per level over
   // the rows of that level (stored factor, unfused)
   bool big = false;
+  // sub-preconditioner lu (wai_set_sub_pc): the pattern carries the complete fill of every block -- one row per dependency
+  // level -- and k_sublu_factor / k_sublu_solve (pc_lu.hip.h) serve it: one workgroup per block, rows in order.  Such a
+  // schedule is `big` as well (8-bit slot descriptors) but has no level sets
+  bool sublu = false;
   int nlev_f = 0, nlev_b = 0;
   int* ord_f = nullptr;       // rows sorted by forward level, ...
   int* ord_b = nullptr;       // ... by backward level
@@ -307,6 +311,7 @@ void with_flag(bool flag, F&& f) {
 struct AsmSystem {
   int overlap = -1;           // what E was built for (-1: not built; 0: no overlap, fill only)
   int levels = 0;             // ILU(k) fill levels E's pattern carries
+  bool sublu = false;         // ... or the complete fill of sub-preconditioner lu (levels is 0 then)
   int n_ext = 0;
   Bcsr E;                     // block-ELL over the n_ext rows, columns in ext numbering
   IluSchedule sched;
@@ -456,6 +461,7 @@ struct wai_ctx {
   int kind = 0, np = 0, df = 0;
   wai::EosParams ep{};
   wai_solver_opts opts{};
+  int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
   wai::DeviceMesh mesh;
   wai::Sources src;
   wai::Network net;
@@ -559,6 +565,9 @@ bool pc_axpy_capable(const wai_ctx* c, const Bcsr& M);
 bool pc_axpy_default(const wai_ctx* c, const Bcsr& M);   // is the composed second launch the default for the kernel in force (k_pc_park with col16)
 // subdomains of any size: level-by-level launches, in place on z (z = r on entry)
 int launch_big_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
+// sub-preconditioner lu (IluSchedule::sublu): both substitutions of every block in one launch, in place on z
+int launch_sublu_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
+bool sublu_vector_in_lds(const IluSchedule& s, int bs);   // does k_sublu_solve hold a block's part of the vector in LDS
 int launch_asm_gather_matrix(wai_ctx* c, const Bcsr& M, const AsmSystem& a);   // a.E.val <- M.val (and the ghost cells' rows; + the network's blocks)
 int launch_pack_rows(wai_ctx* c, const Bcsr& M);                              // d_sendbuf <- matrix rows of the cells sent to neighbours
 int launch_unpack_rows(wai_ctx* c, const Bcsr& M, const AsmSystem& a);        // a.hval <- d_recvbuf

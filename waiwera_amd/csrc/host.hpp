@@ -105,12 +105,17 @@ inline bool net_in_operator(const wai_ctx* c, const LinSys& sys) { return sys.ne
 // <= 1024 rows) or the general one (PCASM's extended system, subdomains of any size, PCNONE)
 // the source network's blocks are part of the operator in force AND go into the factor's pattern (one rank)
 inline bool pc_with_net(const wai_ctx* c, const LinSys& sys) { return net_in_operator(c, sys) && c->net.cp_in_pc && !c->net.cp_span; }
+// sub-preconditioner lu is in force (wai_set_sub_pc; it acts under bjacobi and asm alone, and ilu_levels is ignored then)
+inline bool pc_sub_lu(const wai_ctx* c) {
+  return c->sub_pc == WAI_SUB_LU && (c->opts.pc_type == WAI_PC_BJACOBI || c->opts.pc_type == WAI_PC_ASM);
+}
 inline bool pc_fused(const wai_ctx* c, const LinSys& sys) {
-  return c->opts.pc_type == WAI_PC_BJACOBI && !c->ilu.big && c->opts.ilu_levels <= 0 && !pc_with_net(c, sys);
+  return c->opts.pc_type == WAI_PC_BJACOBI && !c->ilu.big && c->opts.ilu_levels <= 0 && !pc_with_net(c, sys) && !pc_sub_lu(c);
 }
 // the extended-system path: PCASM's overlapped row sets and / or ILU(k)'s filled pattern and / or the network's blocks
 inline bool pc_extended(const wai_ctx* c, const LinSys& sys) {
-  return c->opts.pc_type == WAI_PC_ASM || (c->opts.pc_type == WAI_PC_BJACOBI && (c->opts.ilu_levels > 0 || pc_with_net(c, sys)));
+  return c->opts.pc_type == WAI_PC_ASM ||
+         (c->opts.pc_type == WAI_PC_BJACOBI && (c->opts.ilu_levels > 0 || pc_with_net(c, sys) || pc_sub_lu(c)));
 }
 // the preconditioner set up for `sys` no longer stands (its values changed); without a system: nobody's does
 inline void pc_invalidate(wai_ctx* c, const LinSys& sys) { if (c->ilu.owner == &sys) c->ilu.owner = nullptr; }
@@ -118,7 +123,7 @@ inline void pc_invalidate(wai_ctx* c) { c->ilu.owner = nullptr; }
 
 // ---- pc_setup.hip ------------------------------------------------------------------------------------------------
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true);
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true, bool sublu = false);
 void free_schedule(IluSchedule& s);
 void free_asm(AsmSystem& a);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell

@@ -1,6 +1,7 @@
 // K7/K8 outside the fused launches: the ILU(0) / DILU factorisation kernels of the brick schedules, the level-per-launch
 // factorisation and substitutions for subdomains of any size, the dense LU apply, and their launchers.
 #include "linalg_device.hip.h"
+#include "pc_lu.hip.h"
 
 namespace wai {
 
@@ -523,6 +524,14 @@ int launch_lu_apply(wai_ctx* c, int bs, const double* r, double* z) {
 
 template <int BS>
 static void ilu_factor_bs(wai_ctx* c, const Bcsr& J, IluSchedule& s) {
+  if (s.sublu) {
+    // sub-preconditioner lu: the complete factor of every block, one workgroup per block (pc_lu.hip.h)
+    hipMemcpyAsync(s.fval, J.val, sizeof(double) * ell_size(J.bs, J.n, J.W), hipMemcpyDeviceToDevice, c->stream);
+    const size_t lds = (size_t)J.W * (BS * BS * sizeof(double) + sizeof(int));
+    hipLaunchKernelGGL(k_sublu_factor<BS>, s.nsub, SUBLU_FACTOR_THREADS, lds, c->stream, J.n, s.nsub, J.W, s.sub_ptr, s.row_info, J.col,
+                       s.fval, s.dinv, c->d_flags);
+    return;
+  }
   if (s.big) {
     // one launch per forward level; the factor starts as a copy of the matrix
     hipMemcpyAsync(s.fval, J.val, sizeof(double) * ell_size(J.bs, J.n, J.W), hipMemcpyDeviceToDevice, c->stream);
@@ -585,6 +594,21 @@ static void lvl_sweep(wai_ctx* c, const Bcsr& J, const IluSchedule& s, const int
     hipLaunchKernelGGL((k_lvl_solve<BS, FWD>), g, TPB, 0, c->stream, J.n, cnt, ord + a, s.row_info, J.col, s.fval, s.dinv, z);
   }
 }
+// sub-preconditioner lu: both substitutions of every block in one launch, in place on z.  The block's part of the vector
+// rides in LDS where the largest block's fits the 64 KB a workgroup gets without asking for more
+bool sublu_vector_in_lds(const IluSchedule& s, int bs) { return (size_t)s.max_rows * bs * sizeof(double) <= 64 * 1024; }
+int launch_sublu_solve(wai_ctx* c, const Bcsr& J, const IluSchedule& s, double* z) {
+  if (J.dg || !s.sublu) { c->err = "launch_sublu_solve: not a sub-preconditioner lu schedule"; return -1; }
+  return with_bs(J.bs, [&](auto bs) {
+    constexpr int BS = decltype(bs)::value;
+    const size_t lds = sublu_vector_in_lds(s, BS) ? (size_t)s.max_rows * BS * sizeof(double) : 0;
+    with_flag(lds > 0, [&](auto in_lds) {
+      hipLaunchKernelGGL((k_sublu_solve<BS, decltype(in_lds)::value>), s.nsub, 64 * SUBLU_SOLVE_WAVES, lds, c->stream, J.n, s.nsub, s.sub_ptr,
+                         s.row_info, J.col, s.fval, s.dinv, z);
+    });
+  });
+}
+
 int launch_big_solve(wai_ctx* c, const Bcsr& J, const IluSchedule& s, double* z) {
   if (J.dg) return launch_dg_big_solve(c, J, s, z);
   return with_bs(J.bs, [&](auto bs) {

@@ -109,7 +109,8 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
       if (halo_exchange(c, a.r_full, sys.A.bs)) return -1;
       launch_asm_gather(c, a, a.r_full);
     } else launch_asm_gather(c, a, r);
-    if (a.sched.big) { if (launch_big_solve(c, a.E, a.sched, a.r_ext)) return -1; }
+    if (a.sched.sublu) { if (launch_sublu_solve(c, a.E, a.sched, a.r_ext)) return -1; }   // exact local solves, one launch
+    else if (a.sched.big) { if (launch_big_solve(c, a.E, a.sched, a.r_ext)) return -1; }
     else if (launch_pc_on(c, a.E, a.sched, false, a.r_ext, a.r_ext, PC_DOT_NONE, nullptr)) return -1;
     launch_asm_scatter(c, a, z);
   } else {   // block Jacobi with subdomains of more than 1024 rows

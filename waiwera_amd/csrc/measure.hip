@@ -163,6 +163,11 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
   if (c->opts.pc_type == WAI_PC_NONE) return "k_spmv (no preconditioner)";
   if (c->opts.pc_type == WAI_PC_LU) return "k_spmv + k_lu_apply (dense block inverses)";
   static thread_local char buf[96];
+  if (pc_sub_lu(c)) {
+    snprintf(buf, sizeof(buf), "k_spmv + k_sublu_solve on the extended system (%s, sub-preconditioner lu)",
+             c->opts.pc_type == WAI_PC_ASM ? "ASM" : "block Jacobi");
+    return buf;
+  }
   if (pc_extended(c, sys)) {
     snprintf(buf, sizeof(buf), "k_spmv + %s on the extended system (%s, ILU(%d))",
              sys.as.sched.big ? "k_lvl_solve per level" : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),

@@ -14,7 +14,7 @@ namespace wai {
 // compact / parked kernel conditions -- or, for subdomains of more than 1024 rows, the level sets
 // of the launch-per-level path.  `ghosts`: rows may have columns >= n (partition ghosts).
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide) {
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide, bool sublu) {
   s.nsub = (int)sub.size() - 1;
   if (sub.front() != 0 || sub.back() != N) { c->err = "sub_ptr must cover [0, n_owned]"; return -2; }
   std::vector<int> diag(N);
@@ -102,8 +102,11 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
   // A mesh whose own rows are wider (cells with 9 .. 16 faces: c->pat.W > 8) has k_pc_wide for its subdomains of <= 1024
   // rows of <= 16 blocks: its own Jacobian's and the ILU(0) extended systems of PCASM built on it (`allow_wide`; ILU(k)
   // fill stays on the launch-per-level path).  A mesh of at most 8 blocks per row keeps the schedule it always had.
-  s.wide = allow_wide && c->pat.W > 8 && W > 8 && W <= 16 && s.max_rows <= 1024;
-  s.big = s.max_rows > 1024 || (W > 8 && !s.wide);
+  // Sub-preconditioner lu (complete fill: one row per level) has kernels of its own, k_sublu_factor / k_sublu_solve, on
+  // the 8-bit descriptor and without level sets.
+  s.sublu = sublu;
+  s.wide = !sublu && allow_wide && c->pat.W > 8 && W > 8 && W <= 16 && s.max_rows <= 1024;
+  s.big = sublu || s.max_rows > 1024 || (W > 8 && !s.wide);
   if (!s.big && s.max_lev > 1023) { c->err = "more than 1023 dependency levels in a subdomain"; return -2; }
   for (int i = 0; i < N; i++)
     info[i] = (s.big || s.wide) ? (lfirst[i] | (diag[i] << 8) | (ulast[i] << 16))
@@ -170,7 +173,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       if (dev_upload(c, &s.sub_int, li) || dev_upload(c, &s.sub_bnd, lb)) return -1;
     }
   }
-  if (s.big || s.wide) {
+  if ((s.big || s.wide) && !sublu) {
     // level sets over all subdomains: rows of one level are independent wherever they live (wide schedules: for the
     // measurement of the launch-per-level path on the same factor, wai_bench_kernel 23)
     s.nlev_f = nlf_all; s.nlev_b = nlb_all;
@@ -323,10 +326,13 @@ void free_asm(AsmSystem& a) {
 // <= levels ("sub_preconditioner": {"factor": {"levels": k}}, src/timestepper.F90:1716-1718, 1827).  ILU(k)'s
 // numeric phase is ILU(0) on the filled pattern with explicit zeros, which is how it runs here.
 // src: per entry the index it is filled from (kept for original entries, -1 for fill).
-void iluk_fill(const std::vector<int>& ptr, int levels, std::vector<int>& rp, std::vector<int>& col, std::vector<int>& src) {
+// levels = ILU_COMPLETE_FILL keeps every level: the pattern of the blocks' exact LU factors (sub-preconditioner lu).
+// Returns 0, or the width of the first row found with more than max_width entries (the patterns are left as they were).
+constexpr int ILU_COMPLETE_FILL = 1 << 28;
+int iluk_fill(const std::vector<int>& ptr, int levels, int max_width, std::vector<int>& rp, std::vector<int>& col, std::vector<int>& src) {
   const int n = (int)rp.size() - 1;
   std::vector<int> orp(n + 1, 0), ocol, osrc, olev, odiag(n, 0);
-  ocol.reserve(col.size() * (size_t)(1 + 2 * levels)); osrc.reserve(ocol.capacity()); olev.reserve(ocol.capacity());
+  ocol.reserve(col.size() * (size_t)(1 + 2 * std::min(levels, 8))); osrc.reserve(ocol.capacity()); olev.reserve(ocol.capacity());
   std::vector<int> wc, wl, ws;
   for (size_t b = 0; b + 1 < ptr.size(); b++)
     for (int i = ptr[b]; i < ptr[b + 1]; i++) {
@@ -342,6 +348,7 @@ void iluk_fill(const std::vector<int>& ptr, int levels, std::vector<int>& rp, st
           if (pos < wc.size() && wc[pos] == j) { wl[pos] = std::min(wl[pos], lv); continue; }
           wc.insert(wc.begin() + pos, j); wl.insert(wl.begin() + pos, lv); ws.insert(ws.begin() + pos, -1);
         }
+        if ((int)wc.size() > max_width) return (int)wc.size();
       }
       orp[i] = (int)ocol.size();
       odiag[i] = -1;
@@ -353,6 +360,7 @@ void iluk_fill(const std::vector<int>& ptr, int levels, std::vector<int>& rp, st
       if (odiag[i] < 0) odiag[i] = orp[i + 1] - 1;
     }
   rp.swap(orp); col.swap(ocol); src.swap(osrc);
+  return 0;
 }
 
 // PCASM: the overlapped row set of every subdomain (MatIncreaseOverlap over the matrix graph, owned
@@ -421,7 +429,8 @@ int ghost_rows(wai_ctx* c, const LinSys& sys, std::vector<int>& grp, std::vector
   return 0;
 }
 
-int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net) {
+// sublu: complete fill instead (sub-preconditioner lu; levels is 0 then)
+int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
   AsmSystem& a = sys.as;
   free_asm(a);
   const Pattern& J = c->pat;
@@ -519,9 +528,18 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net) {
     }
     erp.swap(nrp); ecol.swap(ncol); esrc.swap(nsrc);
   }
-  if (levels > 0) iluk_fill(ext_ptr, levels, erp, ecol, esrc);
+  constexpr int MAX_FACTOR_ROW = 255;   // slots of a factor row (8-bit row descriptors)
+  if (sublu) {
+    // the exact LU of a block is ILU with every level kept.  A block whose complete fill does not fit a factor row is
+    // refused -- it never falls back to an incomplete factor
+    if (const int w = iluk_fill(ext_ptr, ILU_COMPLETE_FILL, MAX_FACTOR_ROW, erp, ecol, esrc)) {
+      c->err = "sub-preconditioner lu: the complete fill of a block gives a factor row of " + std::to_string(w) +
+               " blocks or more, the cap is " + std::to_string(MAX_FACTOR_ROW) + " (smaller subdomains, or sub-preconditioner ilu)";
+      return -2;
+    }
+  } else if (levels > 0) iluk_fill(ext_ptr, levels, 1 << 30, erp, ecol, esrc);
   for (int q = 0; q < n_ext; q++) W = std::max(W, erp[q + 1] - erp[q]);
-  if (W > 255) { c->err = "ILU(k): more than 255 blocks in a factor row"; return -2; }
+  if (W > MAX_FACTOR_ROW) { c->err = "ILU(k): more than 255 blocks in a factor row"; return -2; }
   std::vector<int> ell_col((size_t)W * n_ext), gmap((size_t)W * n_ext, -1), erow(n_ext);
   for (int sd = 0; sd < nsub; sd++)
     for (int q = ext_ptr[sd]; q < ext_ptr[sd + 1]; q++) {
@@ -542,7 +560,7 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net) {
   if (dev_upload(c, &a.E.col, ell_col) || dev_upload(c, &a.gmap, gmap) || dev_upload(c, &a.ext_row, erow) ||
       dev_alloc(c, &a.E.val, ell_size(np, n_ext, W)) || dev_alloc(c, &a.r_ext, (size_t)np * n_ext + 16))
     return -1;
-  if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0)) return e;
+  if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0, sublu)) return e;
   a.with_net = with_net;
   a.n_net = 0;
   if (mnet > 0) {   // where the blocks of the network's E land in the extended planes
@@ -566,6 +584,7 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net) {
   a.cross = cross;
   a.overlap = overlap;
   a.levels = levels;
+  a.sublu = sublu;
   return 0;
 }
 
@@ -647,9 +666,13 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
     if (pc_extended(c, sys)) {
       AsmSystem& as = sys.as;
       const int ov = c->opts.pc_type == WAI_PC_ASM ? (c->opts.asm_overlap > 0 ? c->opts.asm_overlap : 1) : 0;
-      const int lv = std::max(c->opts.ilu_levels, 0);
+      const bool sl = pc_sub_lu(c);
+      const int lv = sl ? 0 : std::max(c->opts.ilu_levels, 0);   // (ilu_levels is ignored under sub-preconditioner lu)
       const bool wn = pc_with_net(c, sys);
-      if (as.overlap != ov || as.levels != lv || as.E.bs != A.bs || as.with_net != wn) { if (int e = build_asm(c, sys, ov, lv, wn)) return e < 0 ? -1 : e; }
+      if (as.overlap != ov || as.levels != lv || as.sublu != sl || as.E.bs != A.bs || as.with_net != wn) {
+        // (a refusal of sub-preconditioner lu is the caller's to read: -2 with its text)
+        if (int e = build_asm(c, sys, ov, lv, wn, sl)) return sl && e == -2 ? -2 : (e < 0 ? -1 : e);
+      }
       if (as.cross) {   // the ghost cells' matrix rows, from their owners
         const int dof = A.W * A.bs * A.bs;
         if (ensure_halo_dof(c, dof)) return -1;

@@ -58,6 +58,7 @@ class FlowSimulation:
         self.num_dof = self.n_owned * self.num_primary_variables
         self.num_tracers, self.auxiliary = 0, False
         self.tracer_solve_mode = "per_tracer"
+        self.sub_pc = "ilu"
         self.time = 0.0
         if mesh.n_bc:
             bp, br = _lib._f64(mesh.bc_primary), _lib._i32(mesh.bc_region)
@@ -432,6 +433,12 @@ class FlowSimulation:
         are refused by aux_solve)"""
         self._chk(LIB.wai_set_tracer_solve_mode(self.h, _lib.TRACER_SOLVE[mode]), "set_tracer_solve_mode")
         self.tracer_solve_mode = mode
+
+    def set_sub_pc(self, sub):
+        """sub-preconditioner of pc_type bjacobi / asm: "ilu" (default, ILU(ilu_levels)) or "lu", the exact LU of every
+        (overlapped) block, factored and applied on the device; ignored under pc_type none and lu"""
+        self._chk(LIB.wai_set_sub_pc(self.h, _lib.SUB_PC[sub]), "set_sub_pc")
+        self.sub_pc = sub
 
     def aux_block_system(self, method, dt, ratio, alx_last, alx_last2):
         """(values (nnzb, nt): the diagonals of the coupled system's blocks on setup_jacobian()'s pattern, rhs

@@ -486,6 +486,12 @@ module waiwera_hip_module
        real(c_double), intent(in) :: alx_last(*), alx_last2(*)
        real(c_double), intent(out) :: val(*), b(*)
      end function wai_tracer_block_system
+     ! sub-preconditioner of bjacobi / asm: WAI_SUB_ILU (0, default) | WAI_SUB_LU (1): exact LU of every block, on the device
+     integer(c_int) function wai_set_sub_pc(ctx, sub) bind(c, name = "wai_set_sub_pc")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: sub
+     end function wai_set_sub_pc
      integer(c_int) function wai_synchronize(ctx) bind(c, name = "wai_synchronize")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -505,6 +511,7 @@ module waiwera_hip_module
   end interface
 
   integer, parameter, public :: WAI_METHOD_BEULER = 0, WAI_METHOD_BDF2 = 1, WAI_METHOD_DIRECTSS = 2
+  integer, parameter, public :: WAI_SUB_ILU = 0, WAI_SUB_LU = 1
 
   type, public :: hip_flow_simulation_type
      !! Concrete ode_type whose hot loops run on the GPU.
@@ -527,6 +534,7 @@ module waiwera_hip_module
      procedure, public :: setup_jacobian => hip_sim_setup_jacobian
      procedure, public :: set_residual_form => hip_sim_set_residual_form
      procedure, public :: set_timestep_method => hip_sim_set_timestep_method
+     procedure, public :: set_sub_pc => hip_sim_set_sub_pc
      procedure, public :: aux_lhs => hip_sim_aux_lhs
      procedure, public :: aux_solve => hip_sim_aux_solve
      procedure, public :: residual => hip_sim_residual
@@ -543,7 +551,7 @@ module waiwera_hip_module
        wai_comm_init, wai_comm_size, wai_halo_exchange, wai_jacobian_set_values, wai_spmv, wai_pc_setup, wai_pc_apply, &
        wai_max_scaled, wai_tracer_system, wai_synchronize, wai_network_evaluate
   public :: wai_set_tracers, wai_set_tracer_bc, wai_set_tracer_injection, wai_set_aux_solver
-  public :: wai_set_tracer_solve_mode, wai_tracer_block_system
+  public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_default_eos, wai_default_opts, wai_set_bc, wai_set_sources, wai_update_sources, wai_set_source_controls, wai_get_source_rates, wai_separator_enthalpies, wai_set_regions, &
@@ -773,6 +781,15 @@ contains
     integer, intent(out) :: err
     err = wai_set_timestep_method(self%ctx, int(method, c_int))
   end subroutine hip_sim_set_timestep_method
+
+  subroutine hip_sim_set_sub_pc(self, sub, err)
+    !! Sub-preconditioner of bjacobi / asm (PCSetType of the sub-KSPs' PC, src/timestepper.F90:1789-1834):
+    !! WAI_SUB_ILU | WAI_SUB_LU (exact block solves on the device).
+    class(hip_flow_simulation_type), intent(in out) :: self
+    integer, intent(in) :: sub
+    integer, intent(out) :: err
+    err = wai_set_sub_pc(self%ctx, int(sub, c_int))
+  end subroutine hip_sim_set_sub_pc
 
   subroutine hip_sim_aux_lhs(self, t, interval, Al, err)
     !! ode_type aux_lhs (src/ode.F90, flow_simulation_tracer_cell_balances

@@ -27,6 +27,7 @@ pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
 
 THERMO = {"iapws": 0, "ifc67": 1}   # "thermodynamics" (src/thermodynamics_setup.F90)
 TRACER_SOLVE = {"per_tracer": 0, "coupled": 1}   # wai_set_tracer_solve_mode
+SUB_PC = {"ilu": 0, "lu": 1}   # wai_set_sub_pc: sub-preconditioner of bjacobi / asm
 METHOD_KIND = {"beuler": 0, "bdf2": 1, "directss": 2}  # src/timestepper.F90:2262-2275
 
 
@@ -181,6 +182,7 @@ def _load():
         "wai_tracer_system": (i32, [vp, i32, i32, d, d, vp, vp, vp, vp]),
         "wai_tracer_solve": (i32, [vp, i32, d, d, vp, vp, vp, vp, pi, pi]),
         "wai_set_tracer_solve_mode": (i32, [vp, i32]),
+        "wai_set_sub_pc": (i32, [vp, i32]),
         "wai_tracer_block_system": (i32, [vp, i32, d, d, vp, vp, vp, vp]),
         "wai_tracer_stats": (i32, [vp, C.POINTER(C.c_longlong)]),
         "wai_timer_start": (i32, [vp]),

@@ -27,6 +27,9 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--tracer-solve", choices=("per_tracer", "coupled"), default="per_tracer",
                     help="tracers: one Krylov solve each (default) or all in one solve, as the reference (bjacobi / none preconditioner)")
+    ap.add_argument("--sub-lu", choices=("host", "device"), default="host",
+                    help="sub-preconditioner lu under bjacobi / asm: dense block inverses from the host without overlap (default) "
+                         "or the exact LU of the (overlapped) blocks on the device")
     a = ap.parse_args(argv)
     import os
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -42,7 +45,7 @@ def main(argv=None):
         # one rank per GPU; WAI_BENCH_LOOPBACK=1 (tests on a one-GPU box, with a stand-in for librccl): every rank on --device
         if os.environ.get("WAI_BENCH_LOOPBACK") != "1":
             a.device = int(os.environ.get("LOCAL_RANK", a.device))
-    sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, **kw)
+    sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

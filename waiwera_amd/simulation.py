@@ -28,7 +28,16 @@ src/timestepper.F90:1960-2275; src/tracer.F90:63-140; utils/input_schema.json):
               rate and enthalpy)
 
 Anything else that changes results (deliverability thresholds, ...) raises
-NotImplementedError instead of being ignored.  Output: `Simulation.run` returns the final cell
+NotImplementedError instead of being ignored.
+
+Sub-preconditioner "lu" ("preconditioner": {"sub": {"preconditioner": {"type": "lu"}}}) under bjacobi or asm has two
+mappings.  The default (sub_lu="host") takes the library's pc_type "lu": dense block inverses formed on the host, block
+Jacobi -- under "asm" this DROPS the overlap, a deviation from the reference -- and at most 8192 unknowns per block.
+sub_lu="device" (python -m waiwera_amd.run --sub-lu device) keeps the outer preconditioner and sets the library's
+sub-preconditioner lu (wai_set_sub_pc): bjacobi + exact block solves, or asm (overlap 1, PETSc's default: the input format has no key for it) +
+exact local solves, which is the reference's meaning; factored and applied on the device.  pc_choice records the mapping taken.
+
+Output: `Simulation.run` returns the final cell
 fields under the reference's HDF5 dataset names (fluid_pressure, ...) and writes "output.filename"
 in the reference's HDF5 layout (waiwera_amd/hdf5io.py, HDF5 C library through ctypes); `save`
 writes a .npz archive.
@@ -230,7 +239,8 @@ class Simulation:
     """One Waiwera input file -> mesh, flow simulation object and time stepper."""
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
-                 output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer"):
+                 output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
+                 sub_lu="host"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering) and runs the same step sequence -- what
@@ -246,6 +256,11 @@ class Simulation:
         if default_pc not in ("asm", "bjacobi"):
             raise ValueError("default_pc 'asm' (the reference's default) or 'bjacobi' (the library's fused path)")
         self.default_pc, self.pc_choice = default_pc, None
+        # sub_lu: how sub-preconditioner "lu" under bjacobi / asm is mapped (module docstring): "host" dense block inverses
+        # without overlap (the default: no earlier result moves), "device" the library's sub-preconditioner lu
+        if sub_lu not in ("host", "device"):
+            raise ValueError("sub_lu 'host' (dense block inverses, no overlap) or 'device' (exact LU of the blocks on the device)")
+        self.sub_lu = sub_lu
         # output files go to output_dir (default: $WAIWERA_OUTPUT_DIR, else beside the input file)
         self.output_dir = output_dir or os.environ.get("WAIWERA_OUTPUT_DIR") or base_dir
         self.output_error = None
@@ -512,8 +527,14 @@ class Simulation:
         opts["pc_type"] = {"ilu": "bjacobi"}.get(pct, pct)
         sub = _get(lin, "preconditioner.sub.preconditioner", {}) or {}
         subt = (sub.get("type") or "ilu").lower()
-        if subt == "lu" and pct in ("bjacobi", "asm"):
+        sub_device = False
+        if subt == "lu" and pct in ("bjacobi", "asm") and self.sub_lu == "device":
+            # exact solves of the (overlapped) blocks on the device: the outer preconditioner stays what the input names
+            sub_device = True
+            self.pc_choice += ("sub lu: exact block solves on the device (wai_set_sub_pc)",)
+        elif subt == "lu" and pct in ("bjacobi", "asm"):
             opts["pc_type"] = "lu"       # exact block solves (block Jacobi; no overlap)
+            self.pc_choice += ("sub lu: dense block inverses from the host, block Jacobi%s" % (" (the overlap is dropped)" if pct == "asm" else ""),)
         elif subt != "ilu":
             raise NotImplementedError("sub-preconditioner %r" % (sub,))
         else:
@@ -523,7 +544,9 @@ class Simulation:
             opts["ilu_levels"] = levels
         if opts:
             self.ode.set_opts(**opts)
-        self._pc_covers_coupled = opts.get("pc_type", "bjacobi") in ("bjacobi", "none") and not opts.get("ilu_levels")
+        if sub_device:
+            self.ode.set_sub_pc("lu")
+        self._pc_covers_coupled = opts.get("pc_type", "bjacobi") in ("bjacobi", "none") and not opts.get("ilu_levels") and not sub_device
         # tracers
         tr = inp.get("tracer")
         self.tracer_names = []
