@@ -114,6 +114,13 @@ def test_assembly_kernels_and_oracle_round_alike():
     then does not depend on how a kernel orders its loops, and the device follows the oracle's Krylov
     counts."""
     from waiwera_amd import build as B
-    assert "-ffp-contract=off" in B.PER_FILE.get("kernels_assembly.hip", [])
+    assert B.ASSEMBLY_UNITS
+    for unit in B.ASSEMBLY_UNITS:
+        assert unit in B.SOURCES, unit
+        assert "-ffp-contract=off" in B.PER_FILE.get(unit, []), unit
+    # ... and the list is complete: whatever includes the assembly sweeps' shared header is an assembly unit
+    for name in sorted(os.listdir(B.CSRC)):
+        if name.endswith(".hip") and "assembly_device.hip.h" in open(os.path.join(B.CSRC, name)).read():
+            assert name in B.ASSEMBLY_UNITS, name
     mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
     assert "-ffp-contract=off" in mk

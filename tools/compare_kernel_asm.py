@@ -20,11 +20,12 @@ import subprocess
 import sys
 
 LABEL = re.compile(r"\.L([A-Za-z]+)\d+_(\d+)")
+GETPC = re.compile(r"\.Lpost_getpc\d+")   # numbered through the file, in the order the functions are emitted
 
 
 def norm(line):
     line = line.split(";", 1)[0].strip()
-    return LABEL.sub(r".L\1_\2", line)
+    return GETPC.sub(".Lpost_getpc", LABEL.sub(r".L\1_\2", line))
 
 
 def kernels(path):

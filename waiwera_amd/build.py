@@ -10,7 +10,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwaiwera_hip.so")
-SOURCES = ["capi.hip", "krylov.hip", "pc_setup.hip", "network.hip", "measure.hip", "kernels_assembly.hip", "kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_tracer_block.hip", "comm.cpp"]
+# the cell/face assembly sweeps: every unit that includes assembly_device.hip.h (tests/test_abi.py holds the list complete)
+ASSEMBLY_UNITS = ["kernels_eos.hip", "kernels_residual.hip", "kernels_jacobian.hip", "kernels_tracer.hip"]
+SOURCES = ["capi.hip", "krylov.hip", "pc_setup.hip", "network.hip", "measure.hip"] + ASSEMBLY_UNITS + \
+    ["kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_tracer_block.hip", "comm.cpp"]
 import glob  # noqa: E402
 # every header any source could include: a stale object after a header edit is worse than a rebuild
 HEADERS = sorted(os.path.basename(h) for pat in ("*.h", "*.hpp") for h in glob.glob(os.path.join(CSRC, pat))) + \
@@ -25,7 +28,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # give bit-identical blocks for every EOS (with contraction 0.5 % of the eos we entries differed by 1 ulp
 # of the residual, 2.5e-8 of the entry: enough to send a failing time step of the bench window down another
 # Newton path).  WAI_ASM_CONTRACT=1 builds with the compiler's default contraction.
-PER_FILE = {} if os.environ.get("WAI_ASM_CONTRACT") == "1" else {"kernels_assembly.hip": ["-ffp-contract=off"]}
+PER_FILE = {} if os.environ.get("WAI_ASM_CONTRACT") == "1" else {u: ["-ffp-contract=off"] for u in ASSEMBLY_UNITS}
 
 
 def _stale(target, deps):

@@ -291,13 +291,9 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
   HIPCHK(c, hipEventCreate(&c->pev0)); HIPCHK(c, hipEventCreate(&c->pev1));
   if (od) c->opts = *od; else wai_default_opts(&c->opts);
   c->kind = ed->kind;
-  if (c->kind == WAI_EOS_W) { c->np = 1; c->df = 15; }
-  else if (c->kind == WAI_EOS_WE) { c->np = 2; c->df = 23; }
-  else if (c->kind == WAI_EOS_WCE) { c->np = 3; c->df = 26; }
-  else if (c->kind == WAI_EOS_WSE) { c->np = 3; c->df = 35; }
-  else if (c->kind == WAI_EOS_WAE) { c->np = 3; c->df = 26; }
-  else if (c->kind == WAI_EOS_WSCE || c->kind == WAI_EOS_WSAE) { c->np = 4; c->df = 39; }
-  else { c->err = "unsupported eos kind"; return -2; }
+  EosTraits et;
+  if (eos_traits(c->kind, et)) { c->err = "unsupported eos kind"; return -2; }
+  c->np = et.np; c->df = et.df; c->nmob = et.nmob; c->salt = et.salt;
   std::memset(&c->ep, 0, sizeof(c->ep));
   c->ep.temperature = ed->temperature;
   const double ps = ed->pressure_scale > 0 ? ed->pressure_scale : 1.e6;
@@ -308,7 +304,7 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
   // eos.primary.scale.partial_pressure: absent/<= 0 = adaptive Pg/P (eos_wge.F90:95-104)
   const double gs = ed->partial_pressure_scale > 0 ? ed->partial_pressure_scale : 0.0;
   c->ep.scale[1][2] = gs; c->ep.scale[2][2] = gs; c->ep.scale[4][2] = gs;
-  if (c->kind == WAI_EOS_WSE || c->kind == WAI_EOS_WSCE || c->kind == WAI_EOS_WSAE) {
+  if (c->salt) {
     // eos_wse.F90:155-165, eos_wsge.F90:118-140: regions 5, 6, 8 scale like 1, 2, 4; salt variable
     // unscaled; gas partial pressure (4th) adaptive Pg / P unless a scale is given
     for (int r : {1, 2, 4}) {
@@ -619,7 +615,7 @@ int wai_set_bc(wai_ctx* c, const double* primary, const int* region) {
   std::vector<double> reg(nb), ys((size_t)(first + nb) * np, 0.0);
   for (int b = 0; b < nb; b++) {
     const int rg = region[b];
-    const int rmax = (c->kind == WAI_EOS_WSE || c->kind == WAI_EOS_WSCE || c->kind == WAI_EOS_WSAE) ? 8 : 4;
+    const int rmax = c->salt ? 8 : 4;
     if (rg < 1 || rg > rmax || rg == 3 || rg == 7) { c->err = "bad bc region"; return -2; }
     reg[b] = (double)rg;
     for (int k = 0; k < np; k++) {
@@ -787,8 +783,7 @@ int wai_get_source_rates(wai_ctx* c, double* rate, double* enthalpy) {
 // phase fluxes per unit area, positive from cell 1 to cell 2, on the fluid state in force
 int wai_get_fluxes(wai_ctx* c, double* out) {
   if (!c || !out) return -2;
-  const int nmob = (c->kind == WAI_EOS_W) ? 1 : 2;
-  const size_t n = (size_t)c->mesh.n_faces * (c->np + nmob);
+  const size_t n = (size_t)c->mesh.n_faces * (c->np + c->nmob);
   if (!n) return 0;
   double* tmp = nullptr;
   HIPCHK(c, hipMalloc(&tmp, n * sizeof(double)));
@@ -798,7 +793,7 @@ int wai_get_fluxes(wai_ctx* c, double* out) {
   (void)hipFree(tmp);
   return 0;
 }
-int wai_num_flux_dof(wai_ctx* c) { return c ? c->np + ((c->kind == WAI_EOS_W) ? 1 : 2) : -2; }
+int wai_num_flux_dof(wai_ctx* c) { return c ? c->np + c->nmob : -2; }
 
 // separated water / steam flows of every source (source_network_node_type: water_rate, water_enthalpy,
 // steam_rate, steam_enthalpy; separator.F90:212-260) for the rates and enthalpies in force; zero for
@@ -1087,10 +1082,9 @@ int wai_set_tracers(wai_ctx* c, int n, const int* phase, const double* decay, co
                     const double* diffusion) {
   if (!c || n < 0 || (n > 0 && !phase)) return -2;
   if (n > wai::MAX_TRACERS) { c->err = "too many tracers (at most 8)"; return -1; }
-  const int nmob = c->kind == WAI_EOS_W ? 1 : 2;
   Tracers& t = c->tr;
   for (int i = 0; i < n; i++) {
-    if (phase[i] < 0 || phase[i] >= nmob) { c->err = "tracer phase index out of range"; return -1; }
+    if (phase[i] < 0 || phase[i] >= c->nmob) { c->err = "tracer phase index out of range"; return -1; }
     t.phase[i] = phase[i];
     t.decay[i] = decay ? decay[i] : 0.0;
     t.activation[i] = activation ? activation[i] : 0.0;

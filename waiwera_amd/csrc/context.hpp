@@ -303,6 +303,29 @@ void with_flag(bool flag, F&& f) {
   if (flag) f(std::true_type{});
   else f(std::false_type{});
 }
+// The run-time equation of state likewise: f(std::integral_constant<int, EOS_...>{}) for the seven kinds (else -1, f not
+// called; wai_ctx_create refuses such a kind).  Inside f: `constexpr int K = decltype(k)::value;`
+template <class F>
+int with_eos(int kind, F&& f) {
+  switch (kind) {
+    case EOS_W: f(std::integral_constant<int, EOS_W>{}); return 0;
+    case EOS_WE: f(std::integral_constant<int, EOS_WE>{}); return 0;
+    case EOS_WCE: f(std::integral_constant<int, EOS_WCE>{}); return 0;
+    case EOS_WSE: f(std::integral_constant<int, EOS_WSE>{}); return 0;
+    case EOS_WAE: f(std::integral_constant<int, EOS_WAE>{}); return 0;
+    case EOS_WSCE: f(std::integral_constant<int, EOS_WSCE>{}); return 0;
+    case EOS_WSAE: f(std::integral_constant<int, EOS_WSAE>{}); return 0;
+    default: return -1;
+  }
+}
+// what the host asks of an EOS, from EosT<K> / is_salt<K>; -1 for an unknown kind (t untouched)
+struct EosTraits { int np, df, nmob; bool salt; };
+inline int eos_traits(int kind, EosTraits& t) {
+  return with_eos(kind, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    t = EosTraits{EosT<K>::np, EosT<K>::df, EosT<K>::nmob, is_salt<K>};
+  });
+}
 
 // PCASM (restricted additive Schwarz) system: every subdomain's overlapped row set is stored as
 // its own block of an extended matrix E (couplings leaving the set dropped), so the block-Jacobi
@@ -458,7 +481,8 @@ struct wai_ctx {
   int n_cu = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   size_t lds_per_block = 64 * 1024;   // LDS a workgroup may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KB on gfx950)
   hipStream_t stream = nullptr;
-  int kind = 0, np = 0, df = 0;
+  int kind = 0, np = 0, df = 0, nmob = 0;   // the EOS, and its EosTraits (wai_ctx_create)
+  bool salt = false;
   wai::EosParams ep{};
   wai_solver_opts opts{};
   int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
@@ -524,7 +548,7 @@ struct wai_ctx {
   int dbg = 0;                  // timing probes (wai_bench_kernel)
 };
 
-// ---- kernel launchers (kernels_assembly.hip / kernels_matrix.hip, kernels_factor.hip, kernels_fused.hip) --------------------------
+// ---- kernel launchers (kernels_eos.hip, kernels_residual.hip, kernels_jacobian.hip, kernels_tracer.hip / kernels_matrix.hip, kernels_factor.hip, kernels_fused.hip) ----
 namespace wai {
 int launch_eos(wai_ctx* c, const double* y, int first, int count, bool perturbed);
 int launch_residual(wai_ctx* c, double dt, const double* lhs_old, double* f, double* lhs_out,

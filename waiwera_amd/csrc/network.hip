@@ -320,7 +320,7 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
     for (int k = 0; k < bs; k++) {
       double h = 0.0;
       if (mine) {
-        double dx = yc[k];   // MatFDColoring "ds" increment, as fd_step (kernels_assembly.hip)
+        double dx = yc[k];   // MatFDColoring "ds" increment, as fd_step of the assembly sweeps
         if (std::fabs(dx) < c->opts.fd_umin) dx = dx >= 0.0 ? c->opts.fd_umin : -c->opts.fd_umin;
         h = dx * c->opts.fd_eps;
       }
