@@ -32,6 +32,9 @@ int wai_test_drop_partials(wai_ctx *ctx, int n);
  * is enqueued WITHOUT waiting for the event behind the unpack on the communication stream.  Over a stream-asynchronous
  * transport a multi-rank solve must then go wrong (tests/test_hip_multirank.py); 0 restores the product's ordering */
 int wai_test_drop_stream_wait(wai_ctx *ctx, int which);
+/* device allocations the library holds in this process now, over all contexts and its temporaries, and their bytes: what
+ * a context allocated is returned when it is destroyed, and setting something again does not grow it (tests/test_hip_memory.py) */
+int wai_test_device_memory(long long *allocations, long long *bytes);
 /* one preconditioned-operator application exactly as the Krylov drivers issue it, for the tests (vectors: bs * n_owned doubles,
  * host or device; scal_in / scal_out: the 16 device scalars S_RHO .. S_BREAK before / after).
  * spmv 1: z = B^-1 A (x - alpha x2) through the drivers' pc_amul (x2 may be NULL; non-NULL only where wai_pc_axpy_capable);

@@ -72,6 +72,7 @@ struct MeshView {
   const double* src_net;   // null: no source network (source_network_rate)
   int n_owned, n_local, n_faces, max_deg;
 };
+static_assert(std::is_trivially_copyable<MeshView>::value, "a kernel argument holds views, never an owner");
 
 __device__ __forceinline__ void load_face(const MeshView& m, int f, FaceGeom& g) {
   const size_t nf = m.n_faces;

@@ -167,28 +167,17 @@ int restore_step(wai_ctx* c) {
 
 // a set of Krylov work vectors for vectors of nl entries, zeroed (those it has already are kept)
 int alloc_krylov_vecs(wai_ctx* c, KrylovVecs& k, size_t nl) {
-  double** kv[] = {&k.R, &k.RP, &k.P, &k.V, &k.S, &k.T, &k.tmp, &k.X};
-  for (auto p : kv) {
-    if (*p) continue;
-    if (dev_alloc(c, p, nl + 16)) return -1;
-    HIPCHK(c, hipMemset(*p, 0, (nl + 16) * sizeof(double)));
-  }
+  for (auto p : {&k.R, &k.RP, &k.P, &k.V, &k.S, &k.T, &k.tmp, &k.X_own})
+    if (!*p && p->alloc_zeroed(c, nl + 16)) return -1;
+  k.X = k.X_own;
   return 0;
-}
-void free_krylov_vecs(KrylovVecs& k) {
-  for (double* p : {k.R, k.RP, k.P, k.V, k.S, k.T, k.tmp, k.X, k.basis, k.bl}) if (p) (void)hipFree(p);
-  k = KrylovVecs();
 }
 // a GMRES basis of at least m vectors for sys: m + 1 directions, + 2 error approximations + the update (lgmres)
 int ensure_basis(wai_ctx* c, LinSys& sys, int m) {
   KrylovVecs& k = *sys.kv;
   if (k.basis && k.basis_m >= m) return 0;
-  if (k.basis) (void)hipFree(k.basis);
   k.basis_m = m;
-  const size_t len = (size_t)(m + 4) * sys.nl;
-  if (dev_alloc(c, &k.basis, len)) return -1;
-  HIPCHK(c, hipMemset(k.basis, 0, len * sizeof(double)));
-  return 0;
+  return k.basis.alloc_zeroed(c, (size_t)(m + 4) * sys.nl);
 }
 // a system's matrix: the mesh's pattern with its own block size and values
 static Bcsr matrix_on(const Pattern& p, int bs, double* val) {
@@ -203,39 +192,13 @@ static KspOpts ksp_of(const wai_solver_opts& o) {
   return k;
 }
 
-void free_all(wai_ctx* c) {
-  auto F = [](void* p) { if (p) (void)hipFree(p); };
-  DeviceMesh& m = c->mesh;
-  F(m.rock); F(m.vol); F(m.fgeom); F(m.fdir); F(m.adj_face); F(m.adj_other); F(m.adj_blk); F(m.adj_tblk);
-  F(m.diag_blk); F(m.cell_src); F(m.face_cells);
-  F(c->src.cell); F(c->src.comp); F(c->src.next); F(c->src.rate); F(c->src.enth); F(c->src.ctl); F(c->src.net); c->net.free_device();
-  F(c->pat.rowptr); F(c->pat.col);
-  free_schedule(c->ilu);
-  for (LinSys* sys : {&c->flow, &c->aux, &c->coupled}) { F(sys->A.val); F(sys->A.fdg); free_asm(sys->as); }
-  free_krylov_vecs(c->kv);
-  free_krylov_vecs(c->kv_coupled);
-  F(c->lu.inv); F(c->lu.inv_ptr);
-  Krylov& k = c->ks;
-  F(k.partials); F(k.partials2); F(k.scal); F(k.started);
-  if (k.h_scal) (void)hipHostFree(k.h_scal);
-  F(c->flu); F(c->flu_last_iter); F(c->flu_last_step); F(c->flu_pert); F(c->hstep);
-  F(c->w_y); F(c->w_yold); F(c->w_delta); F(c->w_f); F(c->w_lhs); F(c->w_lhs2); F(c->w_hist); F(c->w_hist_prev);
-  F(c->tr.bc); F(c->tr.inj); F(c->tr.rhsb); F(c->w_a); F(c->w_b); F(c->w_c);
-  F(c->d_flags); F(c->d_red);
-  if (c->h_flags) (void)hipHostFree(c->h_flags);
-  if (c->h_red) (void)hipHostFree(c->h_red);
-  for (auto& p : c->stage) F(p);
-  F(c->d_send_idx); F(c->d_sendbuf); F(c->d_recvbuf);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->ev_scal) (void)hipEventDestroy(c->ev_scal);
-  if (c->ev_pack) (void)hipEventDestroy(c->ev_pack);
-  if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);
-  if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-  if (c->pev0) (void)hipEventDestroy(c->pev0);
-  if (c->pev1) (void)hipEventDestroy(c->pev1);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  comm_destroy(c->comm);
+// events and streams, then the communicator: after the context's device buffers (context.hpp)
+Handles::~Handles() {
+  for (hipEvent_t e : {ev0, ev1, ev_scal, ev_pack, ev_halo}) if (e) (void)hipEventDestroy(e);
+  if (comm_stream) (void)hipStreamDestroy(comm_stream);
+  for (hipEvent_t e : {pev0, pev1}) if (e) (void)hipEventDestroy(e);
+  if (stream) (void)hipStreamDestroy(stream);
+  comm_destroy(comm);
 }
 
 }  // namespace wai
@@ -346,9 +309,7 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
       fdir[f] = (int)std::lround(g[11]);
       if (fdir[f] < 1 || fdir[f] > 3) { c->err = "bad permeability direction"; return -2; }
     }
-    if (dev_upload(c, &m.rock, rock) || dev_upload(c, &m.vol, vol) || dev_upload(c, &m.fgeom, fg) ||
-        dev_upload(c, &m.fdir, fdir))
-      return -1;
+    if (m.rock.upload(c, rock) || m.vol.upload(c, vol) || m.fgeom.upload(c, fg) || m.fdir.upload(c, fdir)) return -1;
   }
   // cell -> face adjacency (ascending face index per cell) and BCSR pattern
   std::vector<int> deg(N, 0);
@@ -428,29 +389,26 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
         const int* p = std::lower_bound(row, row + cnt, i);
         if (p < row + cnt && *p == i) adj_tblk[(size_t)s * N + i] = (int)(p - row);
       }
-    if (dev_upload(c, &m.adj_tblk, adj_tblk)) return -1;
+    if (m.adj_tblk.upload(c, adj_tblk)) return -1;
   }
   {
     std::vector<int> fc(md->face_cells, md->face_cells + (size_t)2 * NF);
-    if (dev_upload(c, &m.face_cells, fc)) return -1;
+    if (m.face_cells.upload(c, fc)) return -1;
   }
-  if (dev_upload(c, &m.adj_face, adj_face) || dev_upload(c, &m.adj_other, adj_other) ||
-      dev_upload(c, &m.adj_blk, adj_blk) || dev_upload(c, &m.diag_blk, diag) ||
-      dev_upload(c, &J.rowptr, J.h_rowptr) || dev_upload(c, &J.col, ell_col))
+  if (m.adj_face.upload(c, adj_face) || m.adj_other.upload(c, adj_other) || m.adj_blk.upload(c, adj_blk) ||
+      m.diag_blk.upload(c, diag) || J.rowptr.upload(c, J.h_rowptr) || J.col.upload(c, ell_col))
     return -1;
   // the flow system: the Jacobian on that pattern, the network's blocks on top, the solver settings of `opts`
   LinSys& flow = c->flow;
-  double* jval = nullptr;
-  if (dev_alloc(c, &jval, ell_size(np, N, J.W))) return -1;
-  HIPCHK(c, hipMemset(jval, 0, sizeof(double) * ell_size(np, N, J.W)));
-  flow.A = matrix_on(J, np, jval);
+  if (flow.val.alloc_zeroed(c, ell_size(np, N, J.W))) return -1;
+  flow.A = matrix_on(J, np, flow.val);
   flow.net_blocks = true;
   flow.ksp = ksp_of(c->opts);
   flow.kv = &c->kv;
   c->aux.ksp.type = c->coupled.ksp.type = WAI_KSP_GMRES;   // the auxiliary problem's default (timestepper.F90:2021-2022; wai_set_aux_solver)
   {
     std::vector<int> cs(N, -1);
-    if (dev_upload(c, &m.cell_src, cs)) return -1;
+    if (m.cell_src.upload(c, cs)) return -1;
   }
   // block-Jacobi subdomains + dependency levels of the ILU(0) factors (symbolic phase, once)
   {
@@ -462,22 +420,17 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
   // state and work vectors
   const size_t nl = (size_t)np * m.n_prim, n = (size_t)np * N;
   const size_t fsz = (size_t)c->df * NL;
-  if (dev_alloc(c, &c->flu, fsz) || dev_alloc(c, &c->flu_last_iter, fsz) ||
-      dev_alloc(c, &c->flu_last_step, fsz) || dev_alloc(c, &c->flu_pert, (size_t)np * c->df * m.n_prim) ||
-      dev_alloc(c, &c->hstep, nl))
+  if (c->flu.alloc_zeroed(c, fsz) || c->flu_last_iter.alloc(c, fsz) || c->flu_last_step.alloc(c, fsz) ||
+      c->flu_pert.alloc(c, (size_t)np * c->df * m.n_prim) || c->hstep.alloc(c, nl))
     return -1;
-  HIPCHK(c, hipMemset(c->flu, 0, fsz * sizeof(double)));
   {
     std::vector<double> ones(NL, 1.0);  // default region 1 (eos_we.F90:91)
     HIPCHK(c, hipMemcpy(c->flu + (size_t)F_REGION * NL, ones.data(), NL * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->flu + (size_t)F_OLD_REGION * NL, ones.data(), NL * sizeof(double), hipMemcpyHostToDevice));
   }
-  double** wv[] = {&c->w_y, &c->w_yold, &c->w_delta, &c->w_f, &c->w_lhs, &c->w_a, &c->w_b, &c->w_c,
-                   &c->w_lhs2, &c->w_hist, &c->w_hist_prev};
-  for (auto p : wv) {
-    if (dev_alloc(c, p, nl + 16)) return -1;
-    HIPCHK(c, hipMemset(*p, 0, (nl + 16) * sizeof(double)));
-  }
+  for (auto p : {&c->w_y, &c->w_yold, &c->w_delta, &c->w_f, &c->w_lhs, &c->w_a, &c->w_b, &c->w_c, &c->w_lhs2, &c->w_hist,
+                 &c->w_hist_prev})
+    if (p->alloc_zeroed(c, nl + 16)) return -1;
   flow.n = (int)n; flow.nl = (int)nl;
   if (alloc_krylov_vecs(c, c->kv, nl)) return -1;
   if (c->opts.gmres_restart > MAX_RESTART) { c->err = "gmres restart above 40 is not supported"; return -2; }
@@ -485,34 +438,27 @@ int wai_ctx_create(const wai_mesh_desc* md, const wai_eos_desc* ed, const wai_so
   if ((flow.ksp.type == WAI_KSP_GMRES || flow.ksp.type == WAI_KSP_LGMRES) && ensure_basis(c, flow, c->kv.basis_m)) return -1;
   Krylov& k = c->ks;
   k.nb_max = std::max(1024, c->ilu.nsub);
-  if (dev_alloc(c, &k.partials, (size_t)NSLOTS * k.nb_max) || dev_alloc(c, &k.scal, (size_t)NSCAL) ||
-      dev_alloc(c, &k.partials2, (size_t)NSLOTS * FIN_MAXF))
+  if (k.partials.alloc(c, (size_t)NSLOTS * k.nb_max) || k.scal.alloc_zeroed(c, NSCAL) || k.partials2.alloc(c, (size_t)NSLOTS * FIN_MAXF) ||
+      k.started.alloc_zeroed(c, 16))
     return -1;
-  if (!k.started) {
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&k.started), 64));
-    HIPCHK(c, hipMemset(k.started, 0, 64));
-  }
   partials_clear(c, 0, NSLOTS);   // every reduction slot starts empty (fin_block reads arrival off the data)
-  HIPCHK(c, hipMemset(k.scal, 0, NSCAL * sizeof(double)));
   // pinned, coherent, device-mapped: the kernels that finish a BiCGStab iteration write the scalars the host
   // tests straight into h_scal[POST_OFF ..] (wait_post)
-  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&k.h_scal), NSCAL * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+  if (k.h_scal.alloc(c, NSCAL, hipHostMallocCoherent | hipHostMallocMapped)) return -1;
   std::memset(k.h_scal, 0, NSCAL * sizeof(double));
   {
     void* dp = nullptr;
     HIPCHK(c, hipHostGetDevicePointer(&dp, k.h_scal, 0));
     k.d_post = reinterpret_cast<double*>(dp) + POST_OFF;
   }
-  if (dev_alloc(c, &c->d_flags, (size_t)4) || dev_alloc(c, &c->d_red, (size_t)4096)) return -1;
-  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_flags), 4 * sizeof(int)));
-  HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_red), 64 * sizeof(double)));
+  if (c->d_flags.alloc(c, 4) || c->d_red.alloc(c, 4096) || c->h_flags.alloc(c, 4) || c->h_red.alloc(c, 64)) return -1;
   {
     const int reset[4] = {0, 0x7fffffff, 0, 0};
     HIPCHK(c, hipMemcpy(c->d_flags, reset, sizeof(reset), hipMemcpyHostToDevice));
   }
   c->stage_len = std::max(nl, fsz) + 16;
   for (auto& p : c->stage)
-    if (dev_alloc(c, &p, c->stage_len)) return -1;
+    if (p.alloc(c, c->stage_len)) return -1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -521,7 +467,6 @@ int wai_ctx_destroy(wai_ctx* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  free_all(c);
   delete c;
   return 0;
 }
@@ -626,13 +571,11 @@ int wai_set_bc(wai_ctx* c, const double* primary, const int* region) {
   }
   HIPCHK(c, hipMemcpy(c->flu + (size_t)F_REGION * NL + first, reg.data(), nb * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->flu + (size_t)F_OLD_REGION * NL + first, reg.data(), nb * sizeof(double), hipMemcpyHostToDevice));
-  double* tmp = nullptr;
-  if (dev_upload(c, &tmp, ys)) return -1;
+  DevBuf<double> tmp;
+  if (tmp.upload(c, ys)) return -1;
   launch_eos(c, tmp, first, nb, false);
   int fl[4];
-  const int e = fetch_flags(c, fl);
-  (void)hipFree(tmp);
-  if (e) return -1;
+  if (fetch_flags(c, fl)) return -1;
   c->bc_set = true;
   return fl[0] ? 1 : 0;
 }
@@ -641,8 +584,6 @@ int wai_set_sources(wai_ctx* c, int n, const int* cell, const double* rate, cons
                     const int* component) {
   if (!c || n < 0) return -2;
   Sources& s = c->src;
-  auto F = [](void* p) { if (p) (void)hipFree(p); };
-  F(s.cell); F(s.comp); F(s.next); F(s.rate); F(s.enth); F(s.ctl); F(s.net); c->net.free_device();
   s = Sources();
   s.n = n;
   const int N = c->mesh.n_owned;
@@ -656,9 +597,7 @@ int wai_set_sources(wai_ctx* c, int n, const int* cell, const double* rate, cons
     vc[i] = cell[i]; vk[i] = component ? component[i] : 0; vr[i] = rate[i]; ve[i] = enthalpy ? enthalpy[i] : 0.0;
   }
   HIPCHK(c, hipMemcpy(c->mesh.cell_src, head.data(), N * sizeof(int), hipMemcpyHostToDevice));
-  if (dev_upload(c, &s.cell, vc) || dev_upload(c, &s.comp, vk) || dev_upload(c, &s.next, next) ||
-      dev_upload(c, &s.rate, vr) || dev_upload(c, &s.enth, ve))
-    return -1;
+  if (s.cell.upload(c, vc) || s.comp.upload(c, vk) || s.next.upload(c, next) || s.rate.upload(c, vr) || s.enth.upload(c, ve)) return -1;
   const bool coupling = c->net.coupling, cp_in_pc = c->net.cp_in_pc;
   c->net = Network();   // a network refers to sources by index: set it again after the sources
   c->net.h_enth0 = ve;
@@ -713,8 +652,7 @@ int wai_set_source_controls(wai_ctx* c, const wai_source_control* controls) {
   if (!c) return -2;
   Sources& s = c->src;
   if (!controls || !s.n) {
-    if (s.ctl) (void)hipFree(s.ctl);
-    s.ctl = nullptr;
+    s.ctl.reset();
     return 0;
   }
   for (int i = 0; i < s.n; i++) {
@@ -740,7 +678,7 @@ int wai_set_source_controls(wai_ctx* c, const wai_source_control* controls) {
         recs[i].threshold_pi = (!old.empty() && old[i].threshold > 0.0 && old[i].threshold_pi >= 0.0) ? old[i].threshold_pi : recs[i].coef;
   }
   controls = reinterpret_cast<const wai_source_control*>(recs.data());
-  if (!s.ctl) HIPCHK(c, hipMalloc(&s.ctl, sizeof(SrcCtl) * (size_t)s.n));
+  if (!s.ctl && s.ctl.alloc(c, (size_t)s.n)) return -1;
   if (c->net.gidx.empty()) c->net.h_ctl.assign(reinterpret_cast<const SrcCtl*>(controls), reinterpret_cast<const SrcCtl*>(controls) + s.n);
   else   // a network across ranks numbers its control records globally: this rank's own entries
     for (int i = 0; i < s.n; i++) c->net.h_ctl[c->net.gidx[i]] = reinterpret_cast<const SrcCtl*>(controls)[i];
@@ -751,13 +689,12 @@ int wai_set_source_controls(wai_ctx* c, const wai_source_control* controls) {
 
 int wai_separator_enthalpies(wai_ctx* c, double pressure, double* hf, double* hg) {
   if (!c || !hf || !hg) return -2;
-  double* tmp = nullptr;
+  DevBuf<double> tmp;
   double host[3];
-  HIPCHK(c, hipMalloc(&tmp, 3 * sizeof(double)));
+  if (tmp.alloc(c, 3)) return -1;
   launch_separator(c, pressure, tmp);
   HIPCHK(c, hipMemcpyAsync(host, tmp, sizeof host, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(tmp);
   if (host[2] != 0.0) { c->err = "separator pressure outside the saturation line"; return -1; }
   *hf = host[0];
   *hg = host[1];
@@ -769,13 +706,12 @@ int wai_get_source_rates(wai_ctx* c, double* rate, double* enthalpy) {
   const size_t n = (size_t)c->src.n;
   if (!n) return 0;
   if (c->net.on && network_update(c)) return -1;   // on the fluid state in force, like the residual's pass
-  double* tmp = nullptr;
-  HIPCHK(c, hipMalloc(&tmp, 2 * n * sizeof(double)));
+  DevBuf<double> tmp;
+  if (tmp.alloc(c, 2 * n)) return -1;
   launch_source_rates(c, tmp);
   HIPCHK(c, hipMemcpyAsync(rate, tmp, n * sizeof(double), hipMemcpyDefault, c->stream));
   if (enthalpy) HIPCHK(c, hipMemcpyAsync(enthalpy, tmp + n, n * sizeof(double), hipMemcpyDefault, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(tmp);
   return 0;
 }
 
@@ -785,12 +721,11 @@ int wai_get_fluxes(wai_ctx* c, double* out) {
   if (!c || !out) return -2;
   const size_t n = (size_t)c->mesh.n_faces * (c->np + c->nmob);
   if (!n) return 0;
-  double* tmp = nullptr;
-  HIPCHK(c, hipMalloc(&tmp, n * sizeof(double)));
+  DevBuf<double> tmp;
+  if (tmp.alloc(c, n)) return -1;
   launch_face_fluxes(c, c->mesh.face_cells, tmp);
   HIPCHK(c, hipMemcpyAsync(out, tmp, n * sizeof(double), hipMemcpyDefault, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(tmp);
   return 0;
 }
 int wai_num_flux_dof(wai_ctx* c) { return c ? c->np + c->nmob : -2; }
@@ -842,12 +777,9 @@ int wai_set_halo(wai_ctx* c, int n_nbr, const int* nbr_rank, const int* send_ptr
   if (n_nbr && recv_ptr[n_nbr] != c->mesh.n_halo) { c->err = "recv_ptr does not cover the halo cells"; return -2; }
   std::vector<int> idx(send_idx, send_idx + c->send_total);
   for (int v : idx) if (v < 0 || v >= c->mesh.n_owned) { c->err = "send_idx not an owned cell"; return -2; }
-  if (c->d_send_idx) (void)hipFree(c->d_send_idx);
-  if (c->d_sendbuf) (void)hipFree(c->d_sendbuf);
-  if (c->d_recvbuf) (void)hipFree(c->d_recvbuf);
   c->max_dof_buf = std::max(c->np, 1);
-  if (dev_upload(c, &c->d_send_idx, idx) || dev_alloc(c, &c->d_sendbuf, (size_t)c->send_total * c->max_dof_buf) ||
-      dev_alloc(c, &c->d_recvbuf, (size_t)c->mesh.n_halo * c->max_dof_buf))
+  if (c->d_send_idx.upload(c, idx) || c->d_sendbuf.alloc(c, (size_t)c->send_total * c->max_dof_buf) ||
+      c->d_recvbuf.alloc(c, (size_t)c->mesh.n_halo * c->max_dof_buf))
     return -1;
   return 0;
 }
@@ -1014,27 +946,22 @@ int wai_jacobian_pattern(wai_ctx* c, int* rowptr, int* colidx) {
 int wai_jacobian_get_values(wai_ctx* c, double* val) {
   if (!c || !val) return -2;
   const size_t n = (size_t)c->pat.nnzb * c->np * c->np;
-  double* tmp = nullptr;
-  if (dev_alloc(c, &tmp, n)) return -1;
+  DevBuf<double> tmp;
+  if (tmp.alloc(c, n)) return -1;
   launch_ell_to_bcsr(c, c->flow.A, tmp);
-  hipError_t e = hipMemcpyAsync(val, tmp, n * sizeof(double),
-                                is_device_ptr(val) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  HIPCHK(c, e);
+  HIPCHK(c, hipMemcpyAsync(val, tmp, n * sizeof(double), is_device_ptr(val) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int wai_jacobian_set_values(wai_ctx* c, const double* val) {
   if (!c || !val) return -2;
   const size_t n = (size_t)c->pat.nnzb * c->np * c->np;
-  double* tmp = nullptr;
-  if (dev_alloc(c, &tmp, n)) return -1;
-  hipError_t e = hipMemcpyAsync(tmp, val, n * sizeof(double),
-                                is_device_ptr(val) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) { launch_bcsr_to_ell(c, tmp, c->flow.A); e = hipStreamSynchronize(c->stream); }
-  (void)hipFree(tmp);
-  HIPCHK(c, e);
+  DevBuf<double> tmp;
+  if (tmp.alloc(c, n)) return -1;
+  HIPCHK(c, hipMemcpyAsync(tmp, val, n * sizeof(double), is_device_ptr(val) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  launch_bcsr_to_ell(c, tmp, c->flow.A);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   pc_invalidate(c, c->flow);
   c->net.cp_valid = false;   // values from outside: the network's blocks of the last wai_jacobian no longer belong
   return 0;
@@ -1091,27 +1018,25 @@ int wai_set_tracers(wai_ctx* c, int n, const int* phase, const double* decay, co
     t.diffusion[i] = diffusion ? diffusion[i] : 0.0;
   }
   t.nt = n;
-  auto F = [](double*& p) { if (p) (void)hipFree(p); p = nullptr; };
-  F(t.bc); F(t.inj); F(t.rhsb);
+  c->tr_bc.reset(); c->tr_inj.reset(); c->tr_rhsb.reset();
+  t.bc = t.inj = t.rhsb = nullptr;
   // the scalar system: block size 1 on the mesh's pattern, the flow's work vectors and basis (LinSys: the alias and the clamp)
   LinSys& aux = c->aux;
-  F(aux.A.val);
+  aux.val.reset(); aux.A.val = nullptr;
   aux.n = c->mesh.n_owned; aux.nl = c->mesh.n_prim; aux.kv = &c->kv;
   // the coupled system's buffers are sized by nt: rebuilt on first use (coupled_system_buffers, coupled_prepare)
   LinSys& cp = c->coupled;
-  F(cp.A.val); F(cp.A.fdg);
-  free_krylov_vecs(c->kv_coupled);
+  cp.val.reset(); cp.fdg.reset(); cp.A.val = cp.A.fdg = nullptr;
+  c->kv_coupled = KrylovVecs();
   cp.n = c->mesh.n_owned * n; cp.nl = c->mesh.n_prim * n; cp.kv = &c->kv_coupled;
   pc_invalidate(c, cp);
   if (n == 0) return 0;
   const size_t nbc = (size_t)std::max(c->mesh.n_bc, 1) * n, nsrc = (size_t)std::max(c->src.n, 1) * n;
-  double* val = nullptr;
-  if (dev_alloc(c, &t.bc, nbc) || dev_alloc(c, &t.inj, nsrc) || dev_alloc(c, &val, (size_t)c->pat.W * c->pat.n)) return -1;
-  aux.A = matrix_on(c->pat, 1, val);
+  if (c->tr_bc.alloc_zeroed(c, nbc) || c->tr_inj.alloc_zeroed(c, nsrc) || aux.val.alloc(c, (size_t)c->pat.W * c->pat.n)) return -1;
+  t.bc = c->tr_bc; t.inj = c->tr_inj;
+  aux.A = matrix_on(c->pat, 1, aux.val);
   cp.A = matrix_on(c->pat, n, nullptr);
   cp.A.dg = n;
-  HIPCHK(c, hipMemset(t.bc, 0, nbc * sizeof(double)));
-  HIPCHK(c, hipMemset(t.inj, 0, nsrc * sizeof(double)));
   return 0;
 }
 
@@ -1127,11 +1052,9 @@ int wai_set_tracer_injection(wai_ctx* c, const double* rate) {
   if (!c || !rate) return -2;
   if (!c->tr.nt) { c->err = "no tracers set"; return -1; }
   // sized by the sources in force now: wai_set_sources first
-  if (c->tr.inj) (void)hipFree(c->tr.inj);
   c->tr.inj = nullptr;
-  const size_t nsrc = (size_t)std::max(c->src.n, 1) * c->tr.nt;
-  if (dev_alloc(c, &c->tr.inj, nsrc)) return -1;
-  HIPCHK(c, hipMemset(c->tr.inj, 0, nsrc * sizeof(double)));
+  if (c->tr_inj.alloc_zeroed(c, (size_t)std::max(c->src.n, 1) * c->tr.nt)) return -1;
+  c->tr.inj = c->tr_inj;
   if (c->src.n)
     HIPCHK(c, hipMemcpy(c->tr.inj, rate, sizeof(double) * (size_t)c->src.n * c->tr.nt, hipMemcpyDefault));
   return 0;
@@ -1185,9 +1108,11 @@ static int coupled_system_buffers(wai_ctx* c) {
   Tracers& t = c->tr;
   Bcsr& A = c->coupled.A;
   const size_t nv = (size_t)A.W * t.nt * A.n;
-  if (!A.val && dev_alloc(c, &A.val, nv)) return -1;
-  if (!A.fdg && dev_alloc(c, &A.fdg, nv)) return -1;
-  if (!t.rhsb && dev_alloc(c, &t.rhsb, (size_t)c->coupled.nl + 16)) return -1;
+  LinSys& cp = c->coupled;
+  if (!cp.val && cp.val.alloc(c, nv)) return -1;
+  if (!cp.fdg && cp.fdg.alloc(c, nv)) return -1;
+  if (!c->tr_rhsb && c->tr_rhsb.alloc(c, (size_t)cp.nl + 16)) return -1;
+  A.val = cp.val; A.fdg = cp.fdg; t.rhsb = c->tr_rhsb;
   return 0;
 }
 

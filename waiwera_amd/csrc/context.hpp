@@ -6,6 +6,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/waiwera_hip.h"
+#include "devbuf.hpp"
 #include "physics.hip.h"
 
 namespace wai {
@@ -89,26 +90,26 @@ struct Comm;  // RCCL state (comm.cpp)
 
 struct DeviceMesh {
   int n_owned = 0, n_halo = 0, n_bc = 0, n_prim = 0, n_local = 0, n_faces = 0, max_deg = 0;
-  double* rock = nullptr;    // SoA 8 x n_local
-  double* vol = nullptr;     // n_local
-  double* fgeom = nullptr;   // SoA 5 x n_faces: area, d1, d2, d12, g.n
-  int* fdir = nullptr;       // permeability direction 1..3
+  DevBuf<double> rock;       // SoA 8 x n_local
+  DevBuf<double> vol;        // n_local
+  DevBuf<double> fgeom;      // SoA 5 x n_faces: area, d1, d2, d12, g.n
+  DevBuf<int> fdir;          // permeability direction 1..3
   // ELL cell->face adjacency of owned cells, slot-major: [slot * n_owned + cell]
-  int* adj_face = nullptr;   // face*2 + side (side 0: cell is cell 1 of the face), -1 = empty
-  int* adj_other = nullptr;  // local index of the cell across the face
-  int* adj_blk = nullptr;    // matrix slot of (cell, other) in the cell's block row, -1 for a bc cell
-  int* adj_tblk = nullptr;   // matrix slot of (other, cell) in the OTHER cell's block row, -1 where the other cell is no owned row (k_jacobian_sym)
-  int* diag_blk = nullptr;   // matrix slot of (cell, cell)
-  int* cell_src = nullptr;   // first source in the cell or -1
-  int* face_cells = nullptr; // [2 n_faces] (cell 1, cell 2) of every face: flux output only
+  DevBuf<int> adj_face;   // face*2 + side (side 0: cell is cell 1 of the face), -1 = empty
+  DevBuf<int> adj_other;  // local index of the cell across the face
+  DevBuf<int> adj_blk;    // matrix slot of (cell, other) in the cell's block row, -1 for a bc cell
+  DevBuf<int> adj_tblk;   // matrix slot of (other, cell) in the OTHER cell's block row, -1 where the other cell is no owned row (k_jacobian_sym)
+  DevBuf<int> diag_blk;   // matrix slot of (cell, cell)
+  DevBuf<int> cell_src;   // first source in the cell or -1
+  DevBuf<int> face_cells; // [2 n_faces] (cell 1, cell 2) of every face: flux output only
 };
 
 struct Sources {
   int n = 0;
-  int* cell = nullptr; int* comp = nullptr; int* next = nullptr;
-  double* rate = nullptr; double* enth = nullptr;
-  SrcCtl* ctl = nullptr;   // state-dependent controls (wai_set_source_controls), null: none
-  double* net = nullptr;   // [2 n] what the source network does to each source (source_network_rate), null: no network
+  DevBuf<int> cell, comp, next;
+  DevBuf<double> rate, enth;
+  DevBuf<SrcCtl> ctl;      // state-dependent controls (wai_set_source_controls), null: none
+  DevBuf<double> net;      // [2 n] what the source network does to each source (source_network_rate), null: no network
 };
 
 // Source network: groups and reinjectors (src/source_network_group.F90, source_network_reinjector.F90),
@@ -151,14 +152,14 @@ struct Network {
   std::vector<double> h_enth0, h_raw, out_rate, out_enth;
   std::vector<char> is_out;                        // sources a reinjector feeds (last pass)
   std::vector<SrcCtl> h_ctl;                       // host copy of the control records (separators)
-  double* d_raw = nullptr;                         // device scratch: raw rates and enthalpies, 2 n
+  DevBuf<double> d_raw;                            // device scratch: raw rates and enthalpies, 2 n
   // A network whose sources live on several ranks (source_network_group.F90:494-515, 579-596: gathers over the
   // group's communicator): every rank holds the whole description, numbered by GLOBAL source index; the sources' own
   // rates are all-gathered (an all-reduce of a vector each rank fills at its own entries) before the pass, which
   // every rank then evaluates identically.  gidx: global index of each local source; empty: one rank, identity
   std::vector<int> gidx;
   int n_global = 0;
-  double* d_all = nullptr;                         // [2 n_global] all-reduce buffer
+  DevBuf<double> d_all;                            // [2 n_global] all-reduce buffer
   std::vector<double> h_loc, l_net, l_enth;        // local staging: raw rates (2 n_local), factors (2 n_local), enthalpies
   // Jacobian couplings through the network (flow_simulation_modify_jacobian, src/flow_simulation.F90:3023-3084,
   // dependencies of src/source_network.F90:359-498): blocks E[i][j] = d R(cell i) / d y(cell j) *through the
@@ -176,20 +177,9 @@ struct Network {
   bool cp_span = false;
   int cp_m = 0, cp_j0 = 0;
   std::vector<int> cp_owner;                       // [m] owner rank of every column cell
-  int* d_cp_cells = nullptr;
-  double *d_cp_val = nullptr, *d_cp_f = nullptr, *d_cp_g = nullptr;
-  double* d_cp_x = nullptr;                        // [m * bs + 2] x at the column cells, gathered over the ranks
-  void free_device() {
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_all) (void)hipFree(d_all);
-    d_all = nullptr;
-    if (d_cp_cells) (void)hipFree(d_cp_cells);
-    if (d_cp_val) (void)hipFree(d_cp_val);
-    if (d_cp_f) (void)hipFree(d_cp_f);
-    if (d_cp_g) (void)hipFree(d_cp_g);
-    if (d_cp_x) (void)hipFree(d_cp_x);
-    d_raw = d_cp_val = d_cp_f = d_cp_g = d_cp_x = nullptr; d_cp_cells = nullptr;
-  }
+  DevBuf<int> d_cp_cells;
+  DevBuf<double> d_cp_val, d_cp_f, d_cp_g;
+  DevBuf<double> d_cp_x;                           // [m * bs + 2] x at the column cells, gathered over the ranks
 };
 
 // Block matrix in HBM: block-ELL, slot-major struct-of-arrays ("SELL" with one slice):
@@ -201,7 +191,8 @@ struct Network {
 // coalesced (64 consecutive doubles per wave instruction).
 // A Bcsr is a VIEW handed to the launchers: it owns nothing.  The three systems on the mesh's pattern (LinSys below)
 // share n, ncols, nnzb, W, col and rowptr (wai_ctx::pat) and differ in bs, val, dg and fdg; an extended ASM system's E
-// has a pattern of its own (AsmSystem).
+// has a pattern of its own (AsmSystem).  The owners stand beside the views: Pattern's col and rowptr, LinSys' val and fdg,
+// AsmSystem's E_col and E_val.
 struct Bcsr {
   int n = 0, ncols = 0, nnzb = 0, bs = 0, W = 0;
   int* col = nullptr;
@@ -214,11 +205,11 @@ struct Bcsr {
   double* fdg = nullptr;
 };
 // The sparsity pattern of the mesh (the cell itself and its neighbours among the owned and ghost cells), single and shared:
-// built, owned and freed once (wai_ctx_create / free_all); every LinSys' matrix is a view on it
+// built once (wai_ctx_create) and owned here; every LinSys' matrix is a view on it
 struct Pattern {
   int n = 0, ncols = 0, nnzb = 0, W = 0;
-  int* col = nullptr;     // block-ELL column planes [W][n]
-  int* rowptr = nullptr;  // device copy of h_rowptr
+  DevBuf<int> col;        // block-ELL column planes [W][n]
+  DevBuf<int> rowptr;     // device copy of h_rowptr
   std::vector<int> h_rowptr, h_colidx;
 };
 
@@ -226,42 +217,42 @@ struct LinSys;
 // Block-Jacobi ILU(0): one workgroup per subdomain, one thread per block row.
 struct IluSchedule {
   int nsub = 0, max_rows = 0, max_lev = 0;
-  int* sub_ptr = nullptr;   // nsub+1 row ranges
-  int* sub_nlev = nullptr;  // per subdomain: forward levels | backward levels << 16
-  int* sub_split = nullptr; // per subdomain: leading rows longer than half the block-ELL width (k_pc_rows: MINC bricks), or null
-  int* row_info = nullptr;  // per row: lfirst | dslot<<4 | ulast<<8 | lev_f<<12 | lev_b<<22 (big, wide: lfirst | dslot<<8 | ulast<<16)
+  DevBuf<int> sub_ptr;      // nsub+1 row ranges
+  DevBuf<int> sub_nlev;     // per subdomain: forward levels | backward levels << 16
+  DevBuf<int> sub_split;    // per subdomain: leading rows longer than half the block-ELL width (k_pc_rows: MINC bricks), or null
+  DevBuf<int> row_info;     // per row: lfirst | dslot<<4 | ulast<<8 | lev_f<<12 | lev_b<<22 (big, wide: lfirst | dslot<<8 | ulast<<16)
   // rows of 9 .. 16 blocks in subdomains of <= 1024 rows (cells with up to 16 faces): k_ilu_factor_wide and k_pc_wide read
   // the 64-bit descriptor, lfirst | dslot<<5 | ulast<<10 in the low word, lev_f | lev_b<<10 in the high one
   bool wide = false;
-  unsigned long long* row_infow = nullptr;
-  double* fval = nullptr;   // factor in the matrix' block-ELL layout; the diagonal slot holds
+  DevBuf<unsigned long long> row_infow;
+  DevBuf<double> fval;      // factor in the matrix' block-ELL layout; the diagonal slot holds
                             // the inverted pivot block
-  double* dinv = nullptr;   // inverted pivot blocks, SoA [bb][n]
+  DevBuf<double> dinv;      // inverted pivot blocks, SoA [bb][n]
   bool diag_only = false;   // ILU(0) touches no off-diagonal block in any subdomain (== DILU)
   bool scaled = true;       // diag_only: rows pre-scaled by the inverted pivots
   bool park = true;         // k_pc_park: upper blocks parked in LDS
-  int* row_uoff = nullptr;  // first parked upper block of a row inside its subdomain
-  int* row_tslot = nullptr; // per row: slot of A_ki in row k for each of its (<= 4) in-subdomain lower couplings k, 4 bits each (15: none)
+  DevBuf<int> row_uoff;     // first parked upper block of a row inside its subdomain
+  DevBuf<int> row_tslot;    // per row: slot of A_ki in row k for each of its (<= 4) in-subdomain lower couplings k, 4 bits each (15: none)
   int max_nl = 0;           // most in-subdomain lower couplings of any row
   bool park2 = false;
-  int* sub_int = nullptr;   // subdomains none of whose rows has a partition-ghost column ...
-  int* sub_bnd = nullptr;   // ... and the others (device lists; null on a single rank)
+  DevBuf<int> sub_int;      // subdomains none of whose rows has a partition-ghost column ...
+  DevBuf<int> sub_bnd;      // ... and the others (device lists; null on a single rank)
   int n_int = 0, n_bnd = 0;
-  int* sub_order = nullptr; // launch order of all subdomains when they differ in cost (ragged bricks): inside each XCD's
+  DevBuf<int> sub_order;    // launch order of all subdomains when they differ in cost (ragged bricks): inside each XCD's
                             // contiguous eighth the long ones first, so the short ones make the tail; null: uniform
   int max_ublocks = 0;      // most in-subdomain upper blocks of any subdomain
   bool fast3 = false;         // <= 3 lower and <= 3 upper in-subdomain couplings per row, offsets < 4
   int max_nlu = 0;            // most lower or upper in-subdomain couplings of any row
   bool rows_kernel = false;   // k_pc_rows (one thread per scalar row) applies and is selected
   bool wave_kernel = false;   // k_pc_wave (one wave per brick of <= 64 block rows) applies and is selected
-  int* row_uoffw = nullptr;   // first parked upper block of a row inside its subdomain, all (<= 4) uppers counted
+  DevBuf<int> row_uoffw;      // first parked upper block of a row inside its subdomain, all (<= 4) uppers counted
   int max_ublocks_w = 0;
   // Brick-local 16-bit column indices for k_pc_park (2 x 2 blocks): entry = segment << 13 | offset, column = the brick's
   // sub_seg[segment] + offset.  Segment 0 starts at the brick's own first row; the others cover what its rows reach in
   // other bricks and among the ghost columns, windows of 8192 columns each (a 16 x 16 x 2 brick of a structured mesh:
   // its six neighbour bricks).  Null when some brick would need more than 8 segments: the int32 planes serve then.
-  unsigned short* col16 = nullptr;   // [n][8]: the (<= 8) slots of a row together, 16 bytes -- one load per row instead of one per slot
-  int* sub_seg = nullptr;            // [nsub][8]
+  DevBuf<unsigned short> col16;      // [n][8]: the (<= 8) slots of a row together, 16 bytes -- one load per row instead of one per slot
+  DevBuf<int> sub_seg;               // [nsub][8]
   bool level_sorted = false;  // every subdomain's rows are stored in dependency-level order (forward levels non-decreasing,
                               // backward levels non-increasing with the row index)
   // subdomains of more than 1024 rows ("one block per rank", sub_ptr = NULL, is the reference's
@@ -274,8 +265,8 @@ struct IluSchedule {
   // schedule is `big` as well (8-bit slot descriptors) but has no level sets
   bool sublu = false;
   int nlev_f = 0, nlev_b = 0;
-  int* ord_f = nullptr;       // rows sorted by forward level, ...
-  int* ord_b = nullptr;       // ... by backward level
+  DevBuf<int> ord_f;          // rows sorted by forward level, ...
+  DevBuf<int> ord_b;          // ... by backward level
   std::vector<int> lev_f_ptr, lev_b_ptr;   // host: row ranges of each level in ord_f / ord_b
   bool built = false;
   // wai_ctx::ilu only: the system whose preconditioner is set up now (null: none) -- the factor buffers above are shared by
@@ -336,11 +327,13 @@ struct AsmSystem {
   int levels = 0;             // ILU(k) fill levels E's pattern carries
   bool sublu = false;         // ... or the complete fill of sub-preconditioner lu (levels is 0 then)
   int n_ext = 0;
-  Bcsr E;                     // block-ELL over the n_ext rows, columns in ext numbering
+  Bcsr E;                     // block-ELL over the n_ext rows, columns in ext numbering: a view of ...
+  DevBuf<int> E_col;          // ... its column planes and
+  DevBuf<double> E_val;       // ... its values, owned here
   IluSchedule sched;
-  int* ext_row = nullptr;     // [n_ext] row of the global system, bit 31 set: owned by this block
-  int* gmap = nullptr;        // [W * n_ext] plane position (slot * n + row) of the source block in J, -1: none
-  double* r_ext = nullptr;    // [bs * n_ext] gathered right-hand side / solution
+  DevBuf<int> ext_row;        // [n_ext] row of the global system, bit 31 set: owned by this block
+  DevBuf<int> gmap;           // [W * n_ext] plane position (slot * n + row) of the source block in J, -1: none
+  DevBuf<double> r_ext;       // [bs * n_ext] gathered right-hand side / solution
   // overlap across rank boundaries: the matrix rows of the partition-ghost cells, received from
   // their owners at every set-up (block-ELL over the n_halo cells, the sender's slot order), and the residual
   // with its ghost entries filled by one more halo exchange per application
@@ -349,11 +342,11 @@ struct AsmSystem {
   // block of the network's E goes (plane position t * n_ext + q; pair = row * m + column in the coupling array)
   bool with_net = false;
   int n_net = 0;
-  int* net_pos = nullptr;
-  int* net_pair = nullptr;
+  DevBuf<int> net_pos;
+  DevBuf<int> net_pair;
   bool cross = false;
-  double* hval = nullptr;     // [W * bs * bs * n_halo]
-  double* r_full = nullptr;   // [bs * n_prim]
+  DevBuf<double> hval;        // [W * bs * bs * n_halo]
+  DevBuf<double> r_full;      // [bs * n_prim]
 };
 
 // Residual form of the time stepping method (src/timestepper.F90:345-452), by value to kernels
@@ -373,6 +366,7 @@ struct Tracers {
   int nt = 0;
   int phase[MAX_TRACERS] = {0};
   double decay[MAX_TRACERS] = {0}, activation[MAX_TRACERS] = {0}, diffusion[MAX_TRACERS] = {0};
+  // views: the struct is a kernel argument, so the owners live beside it in the context (wai_ctx::tr_bc, tr_inj, tr_rhsb)
   double* bc = nullptr;    // [n_bc][nt] Dirichlet mass fractions
   double* inj = nullptr;   // [n_sources][nt] injection rates
   double* rhsb = nullptr;  // coupled mode: [n_prim * nt + 16] right-hand side, interleaved [cell][nt] (allocated on first use)
@@ -384,12 +378,15 @@ struct Tracers {
   unsigned char kernarg_tail[136] = {0};
 };
 static_assert(sizeof(Tracers) == 408, "Tracers is a kernel argument (k_tracer_assemble_all, k_tracer_lhs): its size is part of their argument layout");
+static_assert(std::is_trivially_copyable<Tracers>::value, "a kernel argument holds views, never an owner");
 
 // one tracer's system: which tracer, and the method's combination (timestepper.F90:458-581)
 struct TracerForm {
   int method, it, nt, phase;
   double dt, ratio, decay, activation, diffusion;
 };
+static_assert(std::is_trivially_copyable<TracerForm>::value && std::is_trivially_copyable<ResForm>::value &&
+              std::is_trivially_copyable<EosParams>::value, "a kernel argument holds views, never an owner");
 
 // Finalisation of a producer kernel's partial sums inside its own launch (fin_block, reductions.hip.h): one
 // extra workgroup waits for the partials of `nslots` consecutive reduction slots, sums them into the device
@@ -408,30 +405,31 @@ struct Fin {
   double* scal = nullptr;
   double* post = nullptr;      // device address of the pinned host mirror (16 bytes, 16-byte aligned)
 };
+static_assert(std::is_trivially_copyable<Fin>::value, "a kernel argument holds views, never an owner");
 
 // The reduction workspace of the Krylov helpers: device scalars, partial sums, the posted scalars' mirror and the launch
 // counters.  Single and shared: one solve runs at a time on the library's stream, whichever system it solves.
 struct Krylov {
-  double* d_post = nullptr;    // device address of h_scal + POST_OFF
+  double* d_post = nullptr;    // device address of h_scal + POST_OFF (a view)
   int seq = 0;                 // last sequence number handed out
   long long n_launch = 0, n_copy = 0;   // kernels launched / copies enqueued by the Krylov helpers (wai_launch_stats)
-  double* partials = nullptr;  // [slots][nb_max]
-  double* partials2 = nullptr; // [slots][FIN_MAXF]: slice sums of the finaliser workgroups (fin_block)
-  unsigned* started = nullptr; // k_bcgs_xrp<DERIVE>: workgroups of the launch that have read their scalars (device counter, zero between launches)
+  DevBuf<double> partials;     // [slots][nb_max]
+  DevBuf<double> partials2;    // [slots][FIN_MAXF]: slice sums of the finaliser workgroups (fin_block)
+  DevBuf<unsigned> started;    // k_bcgs_xrp<DERIVE>: workgroups of the launch that have read their scalars (device counter, zero between launches)
   bool alpha_pending = false;  // several ranks: alpha = rho / (V,rP) is to be derived by the next pack_halo_axpy launch (no scalar kernel)
   int nb_max = 0;
-  double* scal = nullptr;      // device scalars
-  double* h_scal = nullptr;    // pinned host mirror
+  DevBuf<double> scal;         // device scalars
+  PinnedBuf<double> h_scal;    // pinned host mirror
   int nblocks = 0;
   int nb_pc = 0;               // partial-sum blocks the last preconditioner application left per slot
 };
 
 // A set of Krylov work vectors
 struct KrylovVecs {
-  double *R = nullptr, *RP = nullptr, *P = nullptr, *V = nullptr, *S = nullptr, *T = nullptr,
-         *tmp = nullptr, *X = nullptr;   // nl + 16 doubles each (alloc_krylov_vecs)
-  double* bl = nullptr;        // BiCGStab(L): r_0..r_L, u_0..u_L, r~ (allocated on first use)
-  double* basis = nullptr;     // GMRES: (basis_m + 4) vectors of nl (ensure_basis)
+  DevBuf<double> R, RP, P, V, S, T, tmp, X_own;   // nl + 16 doubles each (alloc_krylov_vecs)
+  double* X = nullptr;         // BiCGStab's iterate, a view: the caller's x during a solve (ksp_bcgs), X_own otherwise
+  DevBuf<double> bl;           // BiCGStab(L): r_0..r_L, u_0..u_L, r~ (allocated on first use)
+  DevBuf<double> basis;        // GMRES: (basis_m + 4) vectors of nl (ensure_basis)
   int basis_m = 0;
 };
 
@@ -454,9 +452,10 @@ struct KspOpts {
 // asm_overlap of wai_ctx::opts.
 struct LinSys {
   Bcsr A;               // the values on the shared pattern; A.bs: unknowns per cell = block size = dof of the halo exchange
+  DevBuf<double> val, fdg;   // what A.val and A.fdg point to, owned here
   KspOpts ksp;
   int n = 0, nl = 0;    // A.bs * n_owned, A.bs * n_prim
-  KrylovVecs* kv = nullptr;   // wai_ctx::kv (flow, aux) or wai_ctx::kv_coupled
+  KrylovVecs* kv = nullptr;   // wai_ctx::kv (flow, aux) or wai_ctx::kv_coupled (a view)
   AsmSystem as;         // its extended system (PCASM, ILU(k), network blocks in the factor), built on first use
   bool net_blocks = false;   // the source network's coupling blocks E belong to its operator (the flow system only)
 };
@@ -468,19 +467,35 @@ namespace wai {
 // purposes"): exact solves of the preconditioner blocks.  Each block's dense inverse, formed on the
 // host with partial pivoting at every set-up, applied on the device as one dense product per block.
 struct LuBlocks {
-  double* inv = nullptr;      // concatenated dense inverses, block b at inv_ptr[b], row-major m_b x m_b
-  size_t* inv_ptr = nullptr;  // device, nsub + 1
+  DevBuf<double> inv;         // concatenated dense inverses, block b at inv_ptr[b], row-major m_b x m_b
+  DevBuf<size_t> inv_ptr;     // device, nsub + 1
   std::vector<size_t> h_inv_ptr;
   size_t total = 0;
 };
 int launch_lu_apply(wai_ctx* c, int bs, const double* r, double* z);
+
+// The streams, the events and the communicator of a context.  A base of wai_ctx, so that its destructor runs after the
+// members' -- every device buffer is released first, then the events and streams, then the communicator (capi.hip)
+struct Handles {
+  hipStream_t stream = nullptr;
+  Comm* comm = nullptr;
+  hipEvent_t ev_scal = nullptr;   // marks the scalar read-back of a Krylov iteration (ksp_bcgs)
+  // halo exchange overlapped with the preconditioned operator on the bricks that touch no ghost
+  hipStream_t comm_stream = nullptr;
+  hipEvent_t ev_pack = nullptr, ev_halo = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, pev0 = nullptr, pev1 = nullptr;   // measurement
+  Handles() = default;
+  Handles(const Handles&) = delete;
+  ~Handles();
+};
 }  // namespace wai
 
-struct wai_ctx {
+// Every DevBuf below, and in the structs below, is released when the context is deleted (wai_ctx_destroy): a new buffer is
+// a new field and nothing else
+struct wai_ctx : wai::Handles {
   int device = 0;
   int n_cu = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   size_t lds_per_block = 64 * 1024;   // LDS a workgroup may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KB on gfx950)
-  hipStream_t stream = nullptr;
   int kind = 0, np = 0, df = 0, nmob = 0;   // the EOS, and its EosTraits (wai_ctx_create)
   bool salt = false;
   wai::EosParams ep{};
@@ -498,23 +513,18 @@ struct wai_ctx {
   wai::LuBlocks lu;
   wai::Krylov ks;
   wai::Tracers tr;
+  wai::DevBuf<double> tr_bc, tr_inj, tr_rhsb;   // what tr.bc, tr.inj and tr.rhsb point to (Tracers is a kernel argument: views only)
   // fluid state, SoA df x n_local each; perturbed states np x df x n_prim
-  double *flu = nullptr, *flu_last_iter = nullptr, *flu_last_step = nullptr, *flu_pert = nullptr;
-  double* hstep = nullptr;      // FD steps np x n_prim (interleaved like y)
+  wai::DevBuf<double> flu, flu_last_iter, flu_last_step, flu_pert;
+  wai::DevBuf<double> hstep;    // FD steps np x n_prim (interleaved like y)
   // work vectors (interleaved [cell][bs], nl entries)
-  double *w_y = nullptr, *w_yold = nullptr, *w_delta = nullptr, *w_f = nullptr, *w_lhs = nullptr,
-         *w_a = nullptr, *w_b = nullptr, *w_c = nullptr;
-  int* d_flags = nullptr;       // [0] err, [1] first bad cell, [2] changed_y, [3] changed_search
-  int* h_flags = nullptr;       // pinned
-  double* d_red = nullptr;      // reduction scratch
-  double* h_red = nullptr;      // pinned
-  double* stage[4] = {nullptr, nullptr, nullptr, nullptr};  // host-vector staging
+  wai::DevBuf<double> w_y, w_yold, w_delta, w_f, w_lhs, w_a, w_b, w_c;
+  wai::DevBuf<int> d_flags;     // [0] err, [1] first bad cell, [2] changed_y, [3] changed_search
+  wai::PinnedBuf<int> h_flags;
+  wai::DevBuf<double> d_red;    // reduction scratch
+  wai::PinnedBuf<double> h_red;
+  wai::DevBuf<double> stage[4]; // host-vector staging
   size_t stage_len = 0;
-  wai::Comm* comm = nullptr;
-  hipEvent_t ev_scal = nullptr;   // marks the scalar read-back of a Krylov iteration (ksp_bcgs)
-  // halo exchange overlapped with the preconditioned operator on the bricks that touch no ghost
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_pack = nullptr, ev_halo = nullptr;
   // run-time switches of the fused launches, read from the environment once per solve / set-up / probe (read_env),
   // not per launch: WAI_FIN_SEPARATE, WAI_NO_COL16 (k_pc_park on the int32 column planes), WAI_BCGS_SCALAR_KERNELS
   struct EnvSw { bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; } env;
@@ -522,27 +532,25 @@ struct wai_ctx {
   // halo
   int n_nbr = 0;
   std::vector<int> nbr_rank, send_ptr, recv_ptr;
-  int* d_send_idx = nullptr; double* d_sendbuf = nullptr; double* d_recvbuf = nullptr;
+  wai::DevBuf<int> d_send_idx; wai::DevBuf<double> d_sendbuf, d_recvbuf;
   int send_total = 0, max_dof_buf = 0;
   // Newton bookkeeping
   double fnorm0 = 0.0;
   // time stepping method: residual form in force, and wai_timestep's own BDF2 history
   int method = 0;               // residual form (wai_set_residual_form)
   double ratio = 0.0;
-  double* w_lhs2 = nullptr;     // lhs two steps back, as handed to wai_set_residual_form
+  wai::DevBuf<double> w_lhs2;   // lhs two steps back, as handed to wai_set_residual_form
   int scheme = 0, taken = 0;    // wai_set_timestep_method, accepted wai_timestep calls since
   double dt_last = 0.0;
-  double* w_hist = nullptr;     // lhs at the start of the last accepted wai_timestep
-  double* w_hist_prev = nullptr;  // ... and of the one before, to undo an acceptance
+  wai::DevBuf<double> w_hist;   // lhs at the start of the last accepted wai_timestep
+  wai::DevBuf<double> w_hist_prev;  // ... and of the one before, to undo an acceptance
   double dt_last_prev = 0.0;
   bool can_reject = false;      // the last wai_timestep converged and has not been rejected
   // measurement
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool prof_on = false;
   bool last_iter_partial = false;   // flu_last_iter holds only the transition sweep's planes (do_newton_step)
   double prof_ms[wai::KC_COUNT] = {0};
   long long prof_n[wai::KC_COUNT] = {0};
-  hipEvent_t pev0 = nullptr, pev1 = nullptr;
   std::string err;
   bool bc_set = false;
   int dbg = 0;                  // timing probes (wai_bench_kernel)

@@ -13,15 +13,6 @@
 #include "context.hpp"
 #include "../../include/waiwera_hip_bench.h"
 
-#define HIPCHK(c, call)                                                                 \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);                     \
-      return -1;                                                                        \
-    }                                                                                   \
-  } while (0)
-
 namespace wai {
 
 constexpr int NSLOTS = 64;
@@ -31,20 +22,6 @@ constexpr int NSCAL = 128;
 // at most MAX_RESTART (the Hessenberg column travels through the scalar / partial-sum slots S_H ..)
 constexpr int MAX_RESTART = 40;
 inline int basis_vectors(int restart) { return std::max(3, std::min(restart > 0 ? restart : 30, MAX_RESTART)); }
-
-template <typename T>
-int dev_alloc(wai_ctx* c, T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) n = 1;
-  HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  return 0;
-}
-template <typename T>
-int dev_upload(wai_ctx* c, T** p, const std::vector<T>& v) {
-  if (dev_alloc(c, p, v.size())) return -1;
-  if (!v.empty()) HIPCHK(c, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
 
 inline bool is_device_ptr(const void* p) {
   hipPointerAttribute_t a;
@@ -124,8 +101,6 @@ inline void pc_invalidate(wai_ctx* c) { c->ilu.owner = nullptr; }
 // ---- pc_setup.hip ------------------------------------------------------------------------------------------------
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
                    const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true, bool sublu = false);
-void free_schedule(IluSchedule& s);
-void free_asm(AsmSystem& a);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell
 int do_pc_setup(wai_ctx* c, LinSys& sys);
 // ---- krylov.hip --------------------------------------------------------------------------------------------------

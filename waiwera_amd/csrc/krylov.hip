@@ -346,7 +346,6 @@ int ksp_bcgs(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int*
   if (c->ks.h_scal[S_BREAK] == 4.0) { *reason = -9; c->err = "a reduction's partial sum never arrived (finaliser wait ran out)"; }
   else if (std::isnan(dp)) *reason = -9;
   else if (dp <= ttol) *reason = (dp <= atol) ? 3 : 2;
-  double* Xsave = k.X;
   k.X = x;  // X aliases the caller's x during the iteration
   int rc = 0;
 #ifdef WAI_BCGS_NO_SPECULATION
@@ -376,7 +375,7 @@ int ksp_bcgs(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int*
     else if (brk == 3.0) *reason = -5;                        // next rho = 0 without convergence
     else if (dp >= 1.e4 * dp0) *reason = -4;
   }
-  k.X = Xsave;
+  k.X = k.X_own;
   if (rc) return -1;
   if (!*reason) *reason = -3;
   *rnorm = dp;
@@ -641,7 +640,7 @@ int ksp_bcgsl(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int
   const int n = sys.n;
   const size_t nl = (size_t)sys.nl;
   if (!k.bl) {
-    if (dev_alloc(c, &k.bl, (2 * (L + 1) + 1) * (nl + 16))) return -1;
+    if (k.bl.alloc(c, (2 * (L + 1) + 1) * (nl + 16))) return -1;
     HIPCHK(c, hipMemsetAsync(k.bl, 0, (2 * (L + 1) + 1) * (nl + 16) * sizeof(double), c->stream));
   }
   double *r[L + 1], *u[L + 1];

@@ -86,11 +86,11 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
         hipMemcpyAsync(c->flu_pert + copy_n, c->flu_pert, copy_n * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
         break;
       case 19:   // the same bytes through a streaming copy kernel (16-byte non-temporal loads and stores)
-        hipLaunchKernelGGL(k_stream_copy, 8192, 256, 0, c->stream, reinterpret_cast<const stream_d2*>(c->flu_pert),
+        hipLaunchKernelGGL(k_stream_copy, 8192, 256, 0, c->stream, reinterpret_cast<const stream_d2*>(c->flu_pert.get()),
                            reinterpret_cast<stream_d2*>(c->flu_pert + (copy_n & ~(size_t)1)), copy_n / 2);
         break;
       case 22:   // read-only stream over the whole scratch (2 x copy_n doubles)
-        hipLaunchKernelGGL(k_stream_read, 8192, 256, 0, c->stream, reinterpret_cast<const stream_d2*>(c->flu_pert), copy_n & ~(size_t)1,
+        hipLaunchKernelGGL(k_stream_read, 8192, 256, 0, c->stream, reinterpret_cast<const stream_d2*>(c->flu_pert.get()), copy_n & ~(size_t)1,
                            c->ks.scal + 60);
         break;
       case 20: {  // GMRES: the classical Gram-Schmidt inner products (w, v_0 .. v_j) of a whole restart cycle, j = 0 .. m - 1,
@@ -206,6 +206,11 @@ int wai_tracer_stats(wai_ctx* c, long long* assembly_sweeps) {
   return 0;
 }
 int wai_test_drop_partials(wai_ctx* c, int n) { return c ? test_drop_partials(c, n) : -2; }
+int wai_test_device_memory(long long* allocations, long long* bytes) {
+  if (!allocations || !bytes) return -2;
+  *allocations = dev_live_allocs; *bytes = dev_live_bytes;
+  return 0;
+}
 // one preconditioned-operator application as the drivers issue it (waiwera_hip_bench.h): the inputs into the Krylov work
 // vectors (halo room), the scalars seeded, the partial slots emptied as a driver empties them before its first producer,
 // then pc_amul / pc_solve / launch_pc_split unchanged

@@ -284,9 +284,9 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
   if (!nw.d_cp_val) {
     std::vector<int> cells = nw.cp_cells;
     if (cells.empty()) cells.push_back(0);
-    if (dev_upload(c, &nw.d_cp_cells, cells) || dev_alloc(c, &nw.d_cp_val, (size_t)std::max(ml, 1) * m * bs * bs) ||
-        dev_alloc(c, &nw.d_cp_f, (size_t)c->mesh.n_local * bs) || dev_alloc(c, &nw.d_cp_g, (size_t)2 * std::max(mb, 1)) ||
-        dev_alloc(c, &nw.d_cp_x, (size_t)m * bs + 2))
+    if (nw.d_cp_cells.upload(c, cells) || nw.d_cp_val.alloc(c, (size_t)std::max(ml, 1) * m * bs * bs) ||
+        nw.d_cp_f.alloc(c, (size_t)c->mesh.n_local * bs) || nw.d_cp_g.alloc(c, (size_t)2 * std::max(mb, 1)) ||
+        nw.d_cp_x.alloc(c, (size_t)m * bs + 2))
       return -1;
   }
   nw.h_cp_val.assign((size_t)ml * m * bs * bs, 0.0);
@@ -520,8 +520,7 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
   const int n = c->src.n;
   auto ctl = nw.h_ctl; auto e0 = nw.h_enth0; auto cells = nw.h_cell;
   const bool coupling = nw.coupling;
-  nw.free_device();
-  if (c->src.net) { (void)hipFree(c->src.net); c->src.net = nullptr; }
+  c->src.net.reset();
   nw = Network();
   nw.h_ctl = ctl; nw.h_enth0 = e0; nw.h_cell = cells; nw.coupling = coupling;
   if (n_groups <= 0 && n_reinj <= 0) return 0;
@@ -547,13 +546,10 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
       all[(size_t)NG * g + 8] = i < (int)e0.size() ? e0[i] : 0.0;
       all[(size_t)NG * g + 9] = (double)c->comm->rank * 4294967296.0 + (double)(i < (int)cells.size() ? cells[i] : 0);
     }
-    double* tmp = nullptr;
-    if (dev_upload(c, &tmp, all)) return -1;
-    int rc = comm_allreduce(c->comm, tmp, all.size(), 0, c->stream, c->err);
-    if (!rc && hipMemcpyAsync(all.data(), tmp, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = -1;
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = -1;
-    (void)hipFree(tmp);
-    if (rc) return -1;
+    DevBuf<double> tmp;
+    if (tmp.upload(c, all) || comm_allreduce(c->comm, tmp, all.size(), 0, c->stream, c->err)) return -1;
+    HIPCHK(c, hipMemcpyAsync(all.data(), tmp, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     nw.h_ctl.assign((size_t)ng, SrcCtl{});
     nw.h_enth0.assign((size_t)ng, 0.0);
     span_id.assign((size_t)ng, 0.0);
@@ -568,8 +564,8 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
                             grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow, out_kind,
                             out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, c->err))
     return e;
-  if (dev_alloc(c, &nw.d_raw, 2 * (size_t)std::max(n, 1)) || dev_alloc(c, &c->src.net, 2 * (size_t)std::max(n, 1))) return -1;
-  if (span && dev_alloc(c, &nw.d_all, 2 * (size_t)ng)) return -1;
+  if (nw.d_raw.alloc(c, 2 * (size_t)std::max(n, 1)) || c->src.net.alloc(c, 2 * (size_t)std::max(n, 1))) return -1;
+  if (span && nw.d_all.alloc(c, 2 * (size_t)ng)) return -1;
   HIPCHK(c, hipMemset(c->src.net, 0, sizeof(double) * 2 * std::max(n, 1)));
   nw.h_loc.assign(2 * (size_t)n, 0.0);
   nw.l_net.assign(2 * (size_t)n, 0.0);

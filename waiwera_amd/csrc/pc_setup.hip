@@ -116,11 +116,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
     for (int i = 0; i < N; i++)
       infow[i] = (unsigned long long)(lfirst[i] | (diag[i] << 5) | (ulast[i] << 10)) |
                  ((unsigned long long)(levf[i] | (levb[i] << 10)) << 32);
-    if (hipMalloc(reinterpret_cast<void**>(&s.row_infow), infow.size() * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemcpy(s.row_infow, infow.data(), infow.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
-      c->err = "hipMalloc of the wide row descriptors failed";
-      return -1;
-    }
+    if (s.row_infow.upload(c, infow)) return -1;
   }
   // Launch order.  Workgroup b of a fused launch runs on XCD b % 8 and takes position (b & 7) * per + (b >> 3) of the
   // list it is given, so each XCD works through one contiguous eighth in order.  Where bricks differ in cost (the
@@ -143,7 +139,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       std::vector<int> order(s.nsub);
       std::iota(order.begin(), order.end(), 0);
       lpt_order(order);
-      if (dev_upload(c, &s.sub_order, order)) return -1;
+      if (s.sub_order.upload(c, order)) return -1;
     }
   }
   if (ghosts) {   // subdomains without / with partition-ghost columns (for the overlapped halo exchange)
@@ -170,7 +166,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
     s.n_bnd = (int)lb.size();
     lpt_order(li); lpt_order(lb);
     if (s.n_int > 0 && s.n_bnd > 0) {
-      if (dev_upload(c, &s.sub_int, li) || dev_upload(c, &s.sub_bnd, lb)) return -1;
+      if (s.sub_int.upload(c, li) || s.sub_bnd.upload(c, lb)) return -1;
     }
   }
   if ((s.big || s.wide) && !sublu) {
@@ -184,11 +180,11 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
     for (int l = 0; l < nlb_all; l++) s.lev_b_ptr[l + 1] += s.lev_b_ptr[l];
     std::vector<int> pf(s.lev_f_ptr.begin(), s.lev_f_ptr.end() - 1), pb(s.lev_b_ptr.begin(), s.lev_b_ptr.end() - 1);
     for (int i = 0; i < N; i++) { of[pf[levf[i]]++] = i; ob[pb[levb[i]]++] = i; }
-    if (dev_upload(c, &s.ord_f, of) || dev_upload(c, &s.ord_b, ob)) return -1;
+    if (s.ord_f.upload(c, of) || s.ord_b.upload(c, ob)) return -1;
   }
-  if (dev_upload(c, &s.sub_ptr, sub) || dev_upload(c, &s.sub_nlev, nlev) || dev_upload(c, &s.row_info, info) ||
-      dev_upload(c, &s.row_uoff, uoff) || dev_upload(c, &s.row_uoffw, uoffw) || dev_upload(c, &s.row_tslot, tslot) ||
-      dev_alloc(c, &s.fval, ell_size(np, N, W)) || dev_alloc(c, &s.dinv, (size_t)np * np * ell_rows(np, N)))
+  if (s.sub_ptr.upload(c, sub) || s.sub_nlev.upload(c, nlev) || s.row_info.upload(c, info) || s.row_uoff.upload(c, uoff) ||
+      s.row_uoffw.upload(c, uoffw) || s.row_tslot.upload(c, tslot) || s.fval.alloc(c, ell_size(np, N, W)) ||
+      s.dinv.alloc(c, (size_t)np * np * ell_rows(np, N)))
     return -1;
   // Kernel-selection switches.  Build time, for the fallback build that drives the GPU tests through the generic kernels
   // (tools/ci_fallback_kernels.sh): WAI_ILU_GENERAL, WAI_PC_ROWS, WAI_PC_WAVE.  Run time, for the tests that compare paths
@@ -252,7 +248,7 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       for (int i = lo; i < hi && !mixed; i++) mixed = (i < r1) != ((rowptr[i + 1] - rowptr[i]) * 2 > W);
       split[sd] |= (mixed || !sorted ? 15 : short_cnt) << 16;
     }
-    if (any && dev_upload(c, &s.sub_split, split)) return -1;
+    if (any && s.sub_split.upload(c, split)) return -1;
   }
   if (np == 2 && W <= 8 && !s.big && s.park && s.diag_only && s.scaled && s.fast3 && s.max_rows <= 512) {
     // k_pc_park will serve: its column indices as 16-bit (segment, offset) pairs -- 14 of a row's 304 bytes less per launch
@@ -294,30 +290,10 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
         }
       }
     }
-    if (ok) {
-      if (hipMalloc(reinterpret_cast<void**>(&s.col16), c16.size() * sizeof(unsigned short)) != hipSuccess ||
-          hipMemcpy(s.col16, c16.data(), c16.size() * sizeof(unsigned short), hipMemcpyHostToDevice) != hipSuccess) {
-        c->err = "hipMalloc of the 16-bit column indices failed";
-        return -1;
-      }
-      if (dev_upload(c, &s.sub_seg, seg)) return -1;
-    }
+    if (ok && (s.col16.upload(c, c16) || s.sub_seg.upload(c, seg))) return -1;
   }
   s.built = true;
   return 0;
-}
-
-void free_schedule(IluSchedule& s) {
-  hipFree(s.col16); hipFree(s.sub_seg); hipFree(s.row_infow);
-  hipFree(s.sub_ptr); hipFree(s.sub_nlev); hipFree(s.sub_split); hipFree(s.row_info); hipFree(s.fval); hipFree(s.dinv);
-  hipFree(s.row_uoff); hipFree(s.row_uoffw); hipFree(s.row_tslot); hipFree(s.sub_order); hipFree(s.sub_int); hipFree(s.sub_bnd); hipFree(s.ord_f); hipFree(s.ord_b);
-  s = IluSchedule();
-}
-void free_asm(AsmSystem& a) {
-  hipFree(a.net_pos); hipFree(a.net_pair);
-  free_schedule(a.sched);
-  hipFree(a.E.col); hipFree(a.E.val); hipFree(a.ext_row); hipFree(a.gmap); hipFree(a.r_ext); hipFree(a.hval); hipFree(a.r_full);
-  a = AsmSystem();
 }
 
 // ILU(k) symbolic phase on the blocks of a block matrix (host CSR, ascending columns, all columns inside the
@@ -370,12 +346,8 @@ int iluk_fill(const std::vector<int>& ptr, int levels, int max_width, std::vecto
 // levels > 0: ILU(k) fill inside every block; overlap 0 with levels > 0 is block Jacobi + ILU(k) on the same path
 int ensure_halo_dof(wai_ctx* c, int dof) {   // halo buffers wide enough for `dof` doubles per cell
   if (dof <= c->max_dof_buf) return 0;
-  if (c->d_sendbuf) (void)hipFree(c->d_sendbuf);
-  if (c->d_recvbuf) (void)hipFree(c->d_recvbuf);
-  c->d_sendbuf = c->d_recvbuf = nullptr;
   c->max_dof_buf = dof;
-  if (dev_alloc(c, &c->d_sendbuf, (size_t)c->send_total * dof) || dev_alloc(c, &c->d_recvbuf, (size_t)c->mesh.n_halo * dof)) return -1;
-  return 0;
+  return c->d_sendbuf.alloc(c, (size_t)c->send_total * dof) || c->d_recvbuf.alloc(c, (size_t)c->mesh.n_halo * dof) ? -1 : 0;
 }
 
 // The structure of the partition-ghost cells' matrix rows, from their owners (collective).  Every cell gets the
@@ -432,7 +404,7 @@ int ghost_rows(wai_ctx* c, const LinSys& sys, std::vector<int>& grp, std::vector
 // sublu: complete fill instead (sub-preconditioner lu; levels is 0 then)
 int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
   AsmSystem& a = sys.as;
-  free_asm(a);
+  a = AsmSystem();
   const Pattern& J = c->pat;
   const int N = J.n, np = sys.A.bs;
   // Overlap across rank boundaries (the reference's PCASM subdomains are the ranks and MatIncreaseOverlap
@@ -553,13 +525,12 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, b
       }
     }
   // (re)build
-  IluSchedule fresh;
-  a.sched = fresh;
   a.n_ext = n_ext;
   a.E.n = n_ext; a.E.ncols = n_ext; a.E.bs = np; a.E.W = W; a.E.nnzb = (int)ecol.size();
-  if (dev_upload(c, &a.E.col, ell_col) || dev_upload(c, &a.gmap, gmap) || dev_upload(c, &a.ext_row, erow) ||
-      dev_alloc(c, &a.E.val, ell_size(np, n_ext, W)) || dev_alloc(c, &a.r_ext, (size_t)np * n_ext + 16))
+  if (a.E_col.upload(c, ell_col) || a.gmap.upload(c, gmap) || a.ext_row.upload(c, erow) ||
+      a.E_val.alloc(c, ell_size(np, n_ext, W)) || a.r_ext.alloc(c, (size_t)np * n_ext + 16))
     return -1;
+  a.E.col = a.E_col; a.E.val = a.E_val;
   if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0, sublu)) return e;
   a.with_net = with_net;
   a.n_net = 0;
@@ -575,11 +546,10 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, b
       }
     }
     a.n_net = (int)pos.size();
-    if (a.n_net && (dev_upload(c, &a.net_pos, pos) || dev_upload(c, &a.net_pair, pair))) return -1;
+    if (a.n_net && (a.net_pos.upload(c, pos) || a.net_pair.upload(c, pair))) return -1;
   }
   if (cross) {
-    if (dev_alloc(c, &a.hval, ell_size(np, H, J.W)) || dev_alloc(c, &a.r_full, (size_t)np * NX + 16)) return -1;
-    HIPCHK(c, hipMemset(a.r_full, 0, sizeof(double) * ((size_t)np * NX + 16)));
+    if (a.hval.alloc(c, ell_size(np, H, J.W)) || a.r_full.alloc_zeroed(c, (size_t)np * NX + 16)) return -1;
   }
   a.cross = cross;
   a.overlap = overlap;
@@ -605,16 +575,15 @@ int lu_setup(wai_ctx* c, const LinSys& sys) {
     }
     L.total = L.h_inv_ptr[nsub];
     if (L.total > ((size_t)1 << 29)) { c->err = "preconditioner lu: more than 4 GB of dense block inverses"; return -2; }
-    if (dev_alloc(c, &L.inv, L.total) || dev_upload(c, &L.inv_ptr, L.h_inv_ptr)) return -1;
+    if (L.inv.alloc(c, L.total) || L.inv_ptr.upload(c, L.h_inv_ptr)) return -1;
   }
   std::vector<double> val((size_t)J.nnzb * bb), inv(L.total), A;
   {
-    double* tmp = nullptr;
-    if (dev_alloc(c, &tmp, val.size())) return -1;
+    DevBuf<double> tmp;
+    if (tmp.alloc(c, val.size())) return -1;
     launch_ell_to_bcsr(c, sys.A, tmp);
     HIPCHK(c, hipMemcpyAsync(val.data(), tmp, val.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(tmp);
   }
   for (int s = 0; s < nsub; s++) {
     const int lo = sub[s], hi = sub[s + 1], m = (hi - lo) * bs;

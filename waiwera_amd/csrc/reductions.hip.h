@@ -302,6 +302,7 @@ __device__ __forceinline__ bool fin_block(const Fin& f, const double* partials, 
 // 0.1687-0.1695 -> 0.1661-0.1666).  (Round 3 tried the same on the all-loads-at-once experiment k_pc_rows3 and saw no
 // change: there a brick's loads ARE one burst.)
 struct Stagger { int ticks = 0, ncu = 256, per_cu = 3; };
+static_assert(std::is_trivially_copyable<Stagger>::value, "a kernel argument holds views, never an owner");
 __device__ __forceinline__ void stagger_start(const Stagger& st) {
   if (st.ticks > 0 && (int)blockIdx.x < st.ncu * st.per_cu) {
     const unsigned long long t0 = wall_clock64(), wait = (unsigned long long)((int)blockIdx.x / st.ncu) * (unsigned long long)st.ticks;

@@ -148,6 +148,7 @@ def _load():
         "wai_bench_mute_comm": (i32, [vp, i32]),
         "wai_test_drop_partials": (i32, [vp, i32]),
         "wai_test_drop_stream_wait": (i32, [vp, i32]),
+        "wai_test_device_memory": (i32, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "wai_test_pc_operator": (i32, [vp, i32, vp, vp, d, i32, vp, i32, i32, pd, vp, pd]),
         "wai_pc_axpy_capable": (i32, [vp]),
         "wai_halo_size": (i32, [vp, i32, C.POINTER(C.c_longlong), C.POINTER(i32)]),
@@ -259,6 +260,14 @@ def eos_desc(kind="we", temperature=20.0, relperm=("linear", [0.0, 1.0, 0.0, 1.0
         for k, v in enumerate(permeability_modifier[1]):
             e.perm_par[k] = v
     return e
+
+
+def device_memory():
+    """(device allocations the library holds in this process now, their bytes) -- wai_test_device_memory"""
+    n, b = C.c_longlong(0), C.c_longlong(0)
+    if LIB.wai_test_device_memory(C.byref(n), C.byref(b)) != 0:
+        raise WaiError("wai_test_device_memory failed")
+    return n.value, b.value
 
 
 def comm_unique_id():
