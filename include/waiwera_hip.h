@@ -376,7 +376,11 @@ int wai_set_tracers(wai_ctx *ctx, int n, const int *phase, const double *decay,
                     const double *activation, const double *diffusion);
 int wai_set_tracer_bc(wai_ctx *ctx, const double *x_bc);         /* [n_bc][n] Dirichlet values */
 int wai_set_tracer_injection(wai_ctx *ctx, const double *rate);  /* [n_sources][n] kg/s, after wai_set_sources */
-/* auxiliary KSP (defaults gmres(30), rtol 1e-5, atol 1e-50, 10000 its: timestepper.F90:2021-2022) */
+/* auxiliary KSP (time.step.solver.auxiliary; defaults gmres(30), rtol 1e-5, atol 1e-50, 10000 its: timestepper.F90:2021-2022,
+ * which are the reference's).  Every WAI_KSP_* type serves the per-tracer solves (scalar systems on the flow solver's
+ * drivers); the coupled mode runs gmres and bcgs and refuses bcgsl and lgmres by name at the solve (-2).
+ * The auxiliary PRECONDITIONER is wai_set_aux_pc's, below: its default -- the flow solver's -- is NOT the reference's,
+ * which is bjacobi (default_auxiliary_pc_type_str, :2021-2022); wai_set_aux_pc(ctx, WAI_PC_BJACOBI, 1, 0, WAI_SUB_ILU) gives that. */
 int wai_set_aux_solver(wai_ctx *ctx, int ksp_type, int gmres_restart, double rtol, double atol,
                        int max_its);
 /* aux_lhs: Al = porosity * saturation * density of the tracer's phase, [cell][tracer] */
@@ -400,8 +404,11 @@ int wai_tracer_solve(wai_ctx *ctx, int method, double dt, double ratio, const do
  * one solve's iteration count, `reason` its KSPConvergedReason, the convergence test on the 2-norm of the preconditioned
  * residual of the whole vector against rtol * |M^-1 b| / atol of wai_set_aux_solver; zero initial guess.  The blocks are
  * diagonal, so block ILU(0) is the nt scalar ILU(0)s.  Covered: WAI_PC_BJACOBI with ILU(0) and WAI_PC_NONE, GMRES and
- * BiCGStab (what wai_set_aux_solver accepts).  WAI_PC_ASM, WAI_PC_LU and ilu_levels > 0 are refused (-2, named in wai_last_error), never run
- * per tracer instead.  One tracer takes the per-tracer path in either mode. */
+ * BiCGStab.  WAI_PC_ASM, WAI_PC_LU, ilu_levels > 0, WAI_SUB_LU, bcgsl and lgmres are refused (-2, named in wai_last_error), never run
+ * per tracer instead.  The preconditioner tested is the AUXILIARY one: wai_set_aux_pc's, or the flow solver's where it
+ * follows (the default).  So the reference's defaults -- flow asm, auxiliary bjacobi -- are covered once wai_set_aux_pc names
+ * bjacobi; with the auxiliary preconditioner left to follow a flow asm, the mode is refused.
+ * One tracer takes the per-tracer path in either mode. */
 enum { WAI_TRACER_PER_TRACER = 0, WAI_TRACER_COUPLED = 1 };
 int wai_set_tracer_solve_mode(wai_ctx *ctx, int mode);
 /* the system the coupled solve solves, after aux_pre_solve: val = nnzb x nt diagonals of its blocks on
@@ -416,9 +423,25 @@ int wai_tracer_block_system(wai_ctx *ctx, int method, double dt, double ratio, c
  * device as ILU with every level of fill kept; ilu_levels is ignored.  Under WAI_PC_NONE and WAI_PC_LU the setting is ignored.
  * A block whose complete fill gives a factor row of more than 255 blocks is refused by the set-up (-2, wai_last_error names
  * the width found and the cap), never factored incompletely; a zero pivot is reported like ILU's (the solve's reason is
- * PC_FAILED).  The coupled tracer solve (WAI_TRACER_COUPLED) refuses WAI_SUB_LU.  Unknown value: -2. */
+ * PC_FAILED).  The coupled tracer solve (WAI_TRACER_COUPLED) refuses WAI_SUB_LU.  Unknown value: -2.
+ * The setting is the flow solver's; the tracer solves take it too unless wai_set_aux_pc gave them a preconditioner of their
+ * own, which carries its own sub-preconditioner (the reference reads one per solver object; its default is ilu for both). */
 enum { WAI_SUB_ILU = 0, WAI_SUB_LU = 1 };
 int wai_set_sub_pc(wai_ctx *ctx, int sub);
+
+/* The auxiliary (tracer) solver's own preconditioner: time.step.solver.auxiliary.preconditioner.{type, sub.preconditioner.{type,
+ * factor.levels}} (timestepper_configure_auxiliary_linear_solver, src/timestepper.F90:2057-2065; the same keys as the flow
+ * solver's).  pc_type: a WAI_PC_* value, or WAI_AUX_PC_FOLLOW (the default): the tracer solves use the flow solver's
+ * preconditioner, ilu_levels and sub-preconditioner (wai_solver_opts, wai_set_sub_pc), whatever they are set to later.  That
+ * default is NOT the reference's, whose auxiliary solver defaults to bjacobi whatever the flow solver uses (:2021-2022):
+ * wai_set_aux_pc(ctx, WAI_PC_BJACOBI, 1, 0, WAI_SUB_ILU) is the reference's default.  Any value but WAI_AUX_PC_FOLLOW gives both
+ * ways of solving the tracers (per tracer and coupled) these four settings in place of the flow solver's; asm_overlap, ilu_levels
+ * (0..8) and sub_pc (WAI_SUB_*) mean what they mean there.  The subdomains (wai_mesh_desc::sub_ptr) are shared.  The flow
+ * solver's set-up is left alone; the tracer systems' is made again by the next tracer solve.  Unknown value: -2 with a text.
+ * wai_get_aux_pc returns what was set, WAI_AUX_PC_FOLLOW included (out-arguments may be NULL). */
+enum { WAI_AUX_PC_FOLLOW = -1 };
+int wai_set_aux_pc(wai_ctx *ctx, int pc_type, int asm_overlap, int ilu_levels, int sub_pc);
+int wai_get_aux_pc(wai_ctx *ctx, int *pc_type, int *asm_overlap, int *ilu_levels, int *sub_pc);
 
 int wai_synchronize(wai_ctx *ctx);   /* wait for everything enqueued on the library's stream */
 const char *wai_pc_kernel_name(wai_ctx *ctx);   /* kernel / path of a preconditioned-operator application (reports) */

@@ -179,6 +179,11 @@ int ensure_basis(wai_ctx* c, LinSys& sys, int m) {
   k.basis_m = m;
   return k.basis.alloc_zeroed(c, (size_t)(m + 4) * sys.nl);
 }
+// BiCGStab(L)'s vectors r_0..r_L, u_0..u_L, r~ (L = 2) for vectors of nl entries, zeroed (kept where they exist)
+int ensure_bcgsl_vecs(wai_ctx* c, KrylovVecs& k, size_t nl) {
+  if (k.bl) return 0;
+  return k.bl.alloc_zeroed(c, BCGSL_VECS * (nl + 16));
+}
 // a system's matrix: the mesh's pattern with its own block size and values
 static Bcsr matrix_on(const Pattern& p, int bs, double* val) {
   Bcsr A;
@@ -1062,7 +1067,7 @@ int wai_set_tracer_injection(wai_ctx* c, const double* rate) {
 
 int wai_set_aux_solver(wai_ctx* c, int ksp_type, int gmres_restart, double rtol, double atol, int max_its) {
   if (!c) return -2;
-  if (ksp_type != WAI_KSP_BCGS && ksp_type != WAI_KSP_GMRES) { c->err = "unknown KSP type"; return -1; }
+  if (ksp_type < WAI_KSP_BCGS || ksp_type > WAI_KSP_LGMRES) { c->err = "unknown KSP type"; return -1; }
   if (gmres_restart > MAX_RESTART) { c->err = "gmres restart above 40 is not supported"; return -1; }
   KspOpts& k = c->aux.ksp;
   k.type = ksp_type;
@@ -1086,6 +1091,35 @@ int wai_set_sub_pc(wai_ctx* c, int sub) {
   if (sub != WAI_SUB_ILU && sub != WAI_SUB_LU) { c->err = "unknown sub-preconditioner (WAI_SUB_ILU or WAI_SUB_LU)"; return -2; }
   if (sub != c->sub_pc) pc_invalidate(c);   // (the cached extended systems are rebuilt by the next set-up: do_pc_setup)
   c->sub_pc = sub;
+  return 0;
+}
+
+// The auxiliary systems' own preconditioner (both of them: per tracer and coupled, as wai_set_aux_solver's settings), or
+// WAI_AUX_PC_FOLLOW: the flow solver's.  Their set-up alone is invalidated; the extended systems they cached are rebuilt
+// by the next set-up where the settings differ (do_pc_setup)
+int wai_set_aux_pc(wai_ctx* c, int pc_type, int asm_overlap, int ilu_levels, int sub_pc) {
+  if (!c) return -2;
+  if (pc_type != WAI_AUX_PC_FOLLOW && (pc_type < WAI_PC_BJACOBI || pc_type > WAI_PC_LU)) {
+    c->err = "unknown auxiliary preconditioner type (a WAI_PC_* value or WAI_AUX_PC_FOLLOW)";
+    return -2;
+  }
+  if (ilu_levels < 0 || ilu_levels > 8) { c->err = "auxiliary preconditioner: ILU(k) levels 0..8"; return -2; }
+  if (sub_pc != WAI_SUB_ILU && sub_pc != WAI_SUB_LU) { c->err = "unknown auxiliary sub-preconditioner (WAI_SUB_ILU or WAI_SUB_LU)"; return -2; }
+  PcOpts p;
+  p.type = pc_type; p.asm_overlap = asm_overlap; p.ilu_levels = ilu_levels; p.sub = sub_pc;
+  c->aux.pc = c->coupled.pc = p;
+  pc_invalidate(c, c->aux);
+  pc_invalidate(c, c->coupled);
+  return 0;
+}
+
+int wai_get_aux_pc(wai_ctx* c, int* pc_type, int* asm_overlap, int* ilu_levels, int* sub_pc) {
+  if (!c) return -2;
+  const PcOpts& p = c->aux.pc;
+  if (pc_type) *pc_type = p.type;
+  if (asm_overlap) *asm_overlap = p.asm_overlap;
+  if (ilu_levels) *ilu_levels = p.ilu_levels;
+  if (sub_pc) *sub_pc = p.sub;
   return 0;
 }
 
@@ -1121,14 +1155,20 @@ static int coupled_system_buffers(wai_ctx* c) {
 static int coupled_prepare(wai_ctx* c) {
   LinSys& sys = c->coupled;
   const char* what = nullptr;
-  if (pc_sub_lu(c)) what = "the lu sub-preconditioner (WAI_SUB_LU)";
-  else if (c->opts.pc_type == WAI_PC_ASM) what = "the asm preconditioner";
-  else if (c->opts.pc_type == WAI_PC_LU) what = "the lu preconditioner";
-  else if (c->opts.ilu_levels > 0) what = "ILU(k) with k > 0";
-  else if (c->opts.pc_type != WAI_PC_BJACOBI && c->opts.pc_type != WAI_PC_NONE) what = "this preconditioner";
+  const PcOpts pc = pc_of(c, sys);   // the auxiliary systems' own preconditioner, or the flow solver's where they follow
+  if (pc_sub_lu(pc)) what = "the lu sub-preconditioner (WAI_SUB_LU)";
+  else if (pc.type == WAI_PC_ASM) what = "the asm preconditioner";
+  else if (pc.type == WAI_PC_LU) what = "the lu preconditioner";
+  else if (pc.ilu_levels > 0) what = "ILU(k) with k > 0";
+  else if (pc.type != WAI_PC_BJACOBI && pc.type != WAI_PC_NONE) what = "this preconditioner";
   if (what) {
     c->err = std::string("coupled tracer solve (WAI_TRACER_COUPLED) does not cover ") + what +
              ": block Jacobi ILU(0) or none only; use WAI_TRACER_PER_TRACER";
+    return -2;
+  }
+  if (sys.ksp.type == WAI_KSP_LGMRES || sys.ksp.type == WAI_KSP_BCGSL) {
+    c->err = std::string("coupled tracer solve (WAI_TRACER_COUPLED) does not cover the ") +
+             (sys.ksp.type == WAI_KSP_LGMRES ? "lgmres" : "bcgsl") + " solver: gmres or bcgs only; use WAI_TRACER_PER_TRACER";
     return -2;
   }
   if (coupled_system_buffers(c) || alloc_krylov_vecs(c, *sys.kv, (size_t)sys.nl)) return -1;
@@ -1222,7 +1262,9 @@ int wai_tracer_solve(wai_ctx* c, int method, double dt, double ratio, const doub
   } else {
     LinSys& sys = c->aux;
     // the flow solver may never have needed a basis: the one it would have
-    if (sys.ksp.type == WAI_KSP_GMRES && !c->kv.basis && ensure_basis(c, c->flow, c->kv.basis_m)) return -1;
+    if ((sys.ksp.type == WAI_KSP_GMRES || sys.ksp.type == WAI_KSP_LGMRES) && !c->kv.basis && ensure_basis(c, c->flow, c->kv.basis_m)) return -1;
+    // ... nor BiCGStab(L)'s vectors: they are shared like the rest, so sized for the flow's vectors, not for a tracer's
+    if (sys.ksp.type == WAI_KSP_BCGSL && ensure_bcgsl_vecs(c, c->kv, (size_t)c->flow.nl)) return -1;
     double* b = c->w_a;
     double* x = c->w_c;
     for (int it = 0; it < t.nt; it++) {

@@ -437,6 +437,12 @@ struct KspOpts {
   int type = WAI_KSP_BCGS, restart = 30, max_its = 10000;
   double rtol = 1.e-5, atol = 1.e-50;
 };
+// A system's preconditioner: kind, PCASM overlap, ILU(k) levels, sub-preconditioner.  type = WAI_AUX_PC_FOLLOW: the system has
+// none of its own and takes the flow solver's (wai_ctx::opts and wai_ctx::sub_pc) -- read through pc_of (host.hpp), never
+// directly
+struct PcOpts {
+  int type = WAI_AUX_PC_FOLLOW, asm_overlap = 1, ilu_levels = 0, sub = WAI_SUB_ILU;
+};
 
 // One linear system: everything the Krylov drivers, the preconditioner set-up and the launchers below them need to know
 // about the system they work on, handed to them as an argument.  The context holds three, all on the mesh's pattern:
@@ -447,13 +453,16 @@ struct KspOpts {
 //            min(restart, basis_m) in ksp_gmres sees the flow's basis_m
 //   coupled  all nt tracer systems as one (Bcsr::dg), vectors of nt * n_prim; values, factor, vectors and basis its own
 //            (wai_ctx::kv_coupled), allocated on first use
-// Single and shared, NOT part of a system: the pattern (wai_ctx::pat), the ILU schedule with its factor buffers
-// (wai_ctx::ilu: it depends on the pattern alone), the reduction workspace (wai_ctx::ks), and pc_type, ilu_levels and
-// asm_overlap of wai_ctx::opts.
+// Each system has its preconditioner's settings too (pc; pc_of in host.hpp): the flow's follow wai_ctx::opts and
+// wai_ctx::sub_pc, and so do the two tracer systems' until wai_set_aux_pc gives them their own.
+// Single and shared, NOT part of a system: the pattern (wai_ctx::pat), the subdomain list and the ILU schedule on it with
+// its factor buffers (wai_ctx::ilu: it depends on the pattern alone; one system's factor at a time, IluSchedule::owner), the
+// dense block inverses of preconditioner lu (wai_ctx::lu, likewise) and the reduction workspace (wai_ctx::ks).
 struct LinSys {
   Bcsr A;               // the values on the shared pattern; A.bs: unknowns per cell = block size = dof of the halo exchange
   DevBuf<double> val, fdg;   // what A.val and A.fdg point to, owned here
   KspOpts ksp;
+  PcOpts pc;            // its preconditioner, or "the flow solver's" (the flow system's always is)
   int n = 0, nl = 0;    // A.bs * n_owned, A.bs * n_prim
   KrylovVecs* kv = nullptr;   // wai_ctx::kv (flow, aux) or wai_ctx::kv_coupled (a view)
   AsmSystem as;         // its extended system (PCASM, ILU(k), network blocks in the factor), built on first use
@@ -471,6 +480,7 @@ struct LuBlocks {
   DevBuf<size_t> inv_ptr;     // device, nsub + 1
   std::vector<size_t> h_inv_ptr;
   size_t total = 0;
+  int bs = 0;                 // block size the offsets were laid out for (the flow's and the tracers' differ)
 };
 int launch_lu_apply(wai_ctx* c, int bs, const double* r, double* z);
 

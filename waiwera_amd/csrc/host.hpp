@@ -21,6 +21,7 @@ constexpr int NSCAL = 128;
 // GMRES / LGMRES basis: restart vectors, at least 3 (LGMRES: one Krylov direction + 2 error approximations),
 // at most MAX_RESTART (the Hessenberg column travels through the scalar / partial-sum slots S_H ..)
 constexpr int MAX_RESTART = 40;
+constexpr int BCGSL_VECS = 7;   // BiCGStab(2): r_0..r_2, u_0..u_2, r~ (KrylovVecs::bl)
 inline int basis_vectors(int restart) { return std::max(3, std::min(restart > 0 ? restart : 30, MAX_RESTART)); }
 
 inline bool is_device_ptr(const void* p) {
@@ -82,17 +83,23 @@ inline bool net_in_operator(const wai_ctx* c, const LinSys& sys) { return sys.ne
 // <= 1024 rows) or the general one (PCASM's extended system, subdomains of any size, PCNONE)
 // the source network's blocks are part of the operator in force AND go into the factor's pattern (one rank)
 inline bool pc_with_net(const wai_ctx* c, const LinSys& sys) { return net_in_operator(c, sys) && c->net.cp_in_pc && !c->net.cp_span; }
-// sub-preconditioner lu is in force (wai_set_sub_pc; it acts under bjacobi and asm alone, and ilu_levels is ignored then)
-inline bool pc_sub_lu(const wai_ctx* c) {
-  return c->sub_pc == WAI_SUB_LU && (c->opts.pc_type == WAI_PC_BJACOBI || c->opts.pc_type == WAI_PC_ASM);
+// the preconditioner settings in force for a system: its own (wai_set_aux_pc) or, when it follows, the flow solver's
+inline PcOpts pc_of(const wai_ctx* c, const LinSys& sys) {
+  if (sys.pc.type != WAI_AUX_PC_FOLLOW) return sys.pc;
+  PcOpts p;
+  p.type = c->opts.pc_type; p.asm_overlap = c->opts.asm_overlap; p.ilu_levels = c->opts.ilu_levels; p.sub = c->sub_pc;
+  return p;
 }
+// sub-preconditioner lu is in force (wai_set_sub_pc; it acts under bjacobi and asm alone, and ilu_levels is ignored then)
+inline bool pc_sub_lu(const PcOpts& p) { return p.sub == WAI_SUB_LU && (p.type == WAI_PC_BJACOBI || p.type == WAI_PC_ASM); }
 inline bool pc_fused(const wai_ctx* c, const LinSys& sys) {
-  return c->opts.pc_type == WAI_PC_BJACOBI && !c->ilu.big && c->opts.ilu_levels <= 0 && !pc_with_net(c, sys) && !pc_sub_lu(c);
+  const PcOpts p = pc_of(c, sys);
+  return p.type == WAI_PC_BJACOBI && !c->ilu.big && p.ilu_levels <= 0 && !pc_with_net(c, sys) && !pc_sub_lu(p);
 }
 // the extended-system path: PCASM's overlapped row sets and / or ILU(k)'s filled pattern and / or the network's blocks
 inline bool pc_extended(const wai_ctx* c, const LinSys& sys) {
-  return c->opts.pc_type == WAI_PC_ASM ||
-         (c->opts.pc_type == WAI_PC_BJACOBI && (c->opts.ilu_levels > 0 || pc_with_net(c, sys) || pc_sub_lu(c)));
+  const PcOpts p = pc_of(c, sys);
+  return p.type == WAI_PC_ASM || (p.type == WAI_PC_BJACOBI && (p.ilu_levels > 0 || pc_with_net(c, sys) || pc_sub_lu(p)));
 }
 // the preconditioner set up for `sys` no longer stands (its values changed); without a system: nobody's does
 inline void pc_invalidate(wai_ctx* c, const LinSys& sys) { if (c->ilu.owner == &sys) c->ilu.owner = nullptr; }
@@ -130,6 +137,7 @@ int network_update(wai_ctx* c);
 int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old);
 int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t);   // t = A x, + E x where the source network's blocks belong to sys
 // ---- capi.hip ----------------------------------------------------------------------------------------------------
+int ensure_bcgsl_vecs(wai_ctx* c, KrylovVecs& k, size_t nl);
 int fetch_flags(wai_ctx* c, int out[4]);
 int do_pre_eval(wai_ctx* c, double* y);
 int do_residual(wai_ctx* c, double dt, double* y, const double* lhs_old, double* f);

@@ -98,9 +98,10 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
     return launch_pc(c, sys.A, false, r, z, dot_mode, aux);
   }
   const size_t n = (size_t)sys.n;
-  if (c->opts.pc_type == WAI_PC_NONE) {
+  const int pc_type = pc_of(c, sys).type;
+  if (pc_type == WAI_PC_NONE) {
     if (z != r) vec_copy(c, z, r, n);
-  } else if (c->opts.pc_type == WAI_PC_LU) {
+  } else if (pc_type == WAI_PC_LU) {
     if (launch_lu_apply(c, sys.A.bs, r, z)) return -1;
   } else if (pc_extended(c, sys)) {
     AsmSystem& a = sys.as;
@@ -639,10 +640,8 @@ int ksp_bcgsl(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int
   partials_clear(c, 0, NSLOTS);   // every reduction slot empty before the first producer (fin_block invariant, reductions.hip.h)
   const int n = sys.n;
   const size_t nl = (size_t)sys.nl;
-  if (!k.bl) {
-    if (k.bl.alloc(c, (2 * (L + 1) + 1) * (nl + 16))) return -1;
-    HIPCHK(c, hipMemsetAsync(k.bl, 0, (2 * (L + 1) + 1) * (nl + 16) * sizeof(double), c->stream));
-  }
+  static_assert(BCGSL_VECS == 2 * (L + 1) + 1, "r_0..r_L, u_0..u_L, r~");
+  if (ensure_bcgsl_vecs(c, k, nl)) return -1;   // (a tracer solve has made them at the flow's size already: capi.hip)
   double *r[L + 1], *u[L + 1];
   for (int j = 0; j <= L; j++) { r[j] = k.bl + (size_t)j * (nl + 16); u[j] = k.bl + (size_t)(L + 1 + j) * (nl + 16); }
   double* rt = k.bl + (size_t)(2 * (L + 1)) * (nl + 16);

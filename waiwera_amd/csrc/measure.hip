@@ -160,18 +160,19 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
   const IluSchedule& s = c->ilu;
   const LinSys& sys = c->flow;
   const int bs = sys.A.bs;
-  if (c->opts.pc_type == WAI_PC_NONE) return "k_spmv (no preconditioner)";
-  if (c->opts.pc_type == WAI_PC_LU) return "k_spmv + k_lu_apply (dense block inverses)";
+  const PcOpts pc = pc_of(c, sys);
+  if (pc.type == WAI_PC_NONE) return "k_spmv (no preconditioner)";
+  if (pc.type == WAI_PC_LU) return "k_spmv + k_lu_apply (dense block inverses)";
   static thread_local char buf[96];
-  if (pc_sub_lu(c)) {
+  if (pc_sub_lu(pc)) {
     snprintf(buf, sizeof(buf), "k_spmv + k_sublu_solve on the extended system (%s, sub-preconditioner lu)",
-             c->opts.pc_type == WAI_PC_ASM ? "ASM" : "block Jacobi");
+             pc.type == WAI_PC_ASM ? "ASM" : "block Jacobi");
     return buf;
   }
   if (pc_extended(c, sys)) {
     snprintf(buf, sizeof(buf), "k_spmv + %s on the extended system (%s, ILU(%d))",
              sys.as.sched.big ? "k_lvl_solve per level" : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),
-             c->opts.pc_type == WAI_PC_ASM ? "ASM" : "block Jacobi", std::max(c->opts.ilu_levels, 0));
+             pc.type == WAI_PC_ASM ? "ASM" : "block Jacobi", std::max(pc.ilu_levels, 0));
     return buf;
   }
   if (s.big) return "k_spmv + k_lvl_solve per level";

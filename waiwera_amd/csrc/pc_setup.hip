@@ -566,7 +566,8 @@ int lu_setup(wai_ctx* c, const LinSys& sys) {
   std::vector<int> sub((size_t)nsub + 1);
   HIPCHK(c, hipMemcpy(sub.data(), c->ilu.sub_ptr, sizeof(int) * sub.size(), hipMemcpyDeviceToHost));
   LuBlocks& L = c->lu;
-  if (L.h_inv_ptr.empty()) {
+  if (L.h_inv_ptr.empty() || L.bs != bs) {   // (laid out per block size: the flow's blocks and a tracer's scalars differ)
+    L.bs = 0;
     L.h_inv_ptr.assign((size_t)nsub + 1, 0);
     for (int s = 0; s < nsub; s++) {
       const size_t m = (size_t)(sub[s + 1] - sub[s]) * bs;
@@ -576,6 +577,7 @@ int lu_setup(wai_ctx* c, const LinSys& sys) {
     L.total = L.h_inv_ptr[nsub];
     if (L.total > ((size_t)1 << 29)) { c->err = "preconditioner lu: more than 4 GB of dense block inverses"; return -2; }
     if (L.inv.alloc(c, L.total) || L.inv_ptr.upload(c, L.h_inv_ptr)) return -1;
+    L.bs = bs;
   }
   std::vector<double> val((size_t)J.nnzb * bb), inv(L.total), A;
   {
@@ -622,8 +624,9 @@ int lu_setup(wai_ctx* c, const LinSys& sys) {
 // (recoverable; the record stands as it did for the flags read back last), < 0 error
 int do_pc_setup(wai_ctx* c, LinSys& sys) {
   read_env(c);
-  if (c->opts.pc_type == WAI_PC_NONE) { c->ilu.owner = &sys; return 0; }
-  if (c->opts.pc_type == WAI_PC_LU) {
+  const PcOpts pc = pc_of(c, sys);   // the system's own choice, or the flow solver's
+  if (pc.type == WAI_PC_NONE) { c->ilu.owner = &sys; return 0; }
+  if (pc.type == WAI_PC_LU) {
     Prof p(c, KC_PC_SETUP);
     const int e = lu_setup(c, sys);
     if (e == 0) c->ilu.owner = &sys;
@@ -634,9 +637,9 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
     const Bcsr& A = sys.A;
     if (pc_extended(c, sys)) {
       AsmSystem& as = sys.as;
-      const int ov = c->opts.pc_type == WAI_PC_ASM ? (c->opts.asm_overlap > 0 ? c->opts.asm_overlap : 1) : 0;
-      const bool sl = pc_sub_lu(c);
-      const int lv = sl ? 0 : std::max(c->opts.ilu_levels, 0);   // (ilu_levels is ignored under sub-preconditioner lu)
+      const int ov = pc.type == WAI_PC_ASM ? (pc.asm_overlap > 0 ? pc.asm_overlap : 1) : 0;
+      const bool sl = pc_sub_lu(pc);
+      const int lv = sl ? 0 : std::max(pc.ilu_levels, 0);   // (ilu_levels is ignored under sub-preconditioner lu)
       const bool wn = pc_with_net(c, sys);
       if (as.overlap != ov || as.levels != lv || as.sublu != sl || as.E.bs != A.bs || as.with_net != wn) {
         // (a refusal of sub-preconditioner lu is the caller's to read: -2 with its text)

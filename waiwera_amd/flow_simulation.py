@@ -456,8 +456,24 @@ class FlowSimulation:
         return a.value
 
     def set_aux_solver(self, ksp_type="gmres", restart=30, rtol=1e-5, atol=1e-50, max_its=10000):
-        return self._chk(LIB.wai_set_aux_solver(self.h, {"bcgs": 0, "gmres": 1}[ksp_type], restart, rtol, atol,
+        """the auxiliary (tracer) KSP: "gmres" (default), "bcgs", "lgmres" or "bcgsl" (the last two per tracer only: the
+        coupled solve refuses them)"""
+        return self._chk(LIB.wai_set_aux_solver(self.h, _lib.KSP[ksp_type], restart, rtol, atol,
                                                 max_its), "set_aux_solver")
+
+    def set_aux_pc(self, pc_type="follow", asm_overlap=1, ilu_levels=0, sub_pc="ilu"):
+        """the tracer solves' own preconditioner (wai_set_aux_pc): "bjacobi" (the reference's auxiliary default), "asm",
+        "none", "lu", or "follow" (default): the flow solver's pc_type, ilu_levels and sub-preconditioner"""
+        self._chk(LIB.wai_set_aux_pc(self.h, _lib.AUX_PC[pc_type] if isinstance(pc_type, str) else int(pc_type), int(asm_overlap),
+                                     int(ilu_levels), _lib.SUB_PC[sub_pc] if isinstance(sub_pc, str) else int(sub_pc)), "set_aux_pc")
+
+    def get_aux_pc(self):
+        """dict(pc_type, asm_overlap, ilu_levels, sub_pc) as set_aux_pc takes them; pc_type "follow" on a fresh context"""
+        v = [C.c_int(0) for _ in range(4)]
+        self._chk(LIB.wai_get_aux_pc(self.h, *[C.byref(x) for x in v]), "get_aux_pc")
+        name = {n: k for k, n in _lib.AUX_PC.items()}
+        sub = {n: k for k, n in _lib.SUB_PC.items()}
+        return dict(pc_type=name[v[0].value], asm_overlap=v[1].value, ilu_levels=v[2].value, sub_pc=sub[v[3].value])
 
     def aux_lhs(self, t, interval, Al):
         return self._chk(LIB.wai_tracer_lhs(self.h, _lib.ptr(Al)), "tracer_lhs")

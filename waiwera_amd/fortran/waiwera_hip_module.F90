@@ -492,6 +492,18 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        integer(c_int), value :: sub
      end function wai_set_sub_pc
+     ! the auxiliary (tracer) solver's own preconditioner (time.step.solver.auxiliary.preconditioner): a WAI_PC_* value, or
+     ! WAI_AUX_PC_FOLLOW (-1, default): the flow solver's.  The reference's default is WAI_PC_BJACOBI
+     integer(c_int) function wai_set_aux_pc(ctx, pc_type, asm_overlap, ilu_levels, sub_pc) bind(c, name = "wai_set_aux_pc")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: pc_type, asm_overlap, ilu_levels, sub_pc
+     end function wai_set_aux_pc
+     integer(c_int) function wai_get_aux_pc(ctx, pc_type, asm_overlap, ilu_levels, sub_pc) bind(c, name = "wai_get_aux_pc")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: pc_type, asm_overlap, ilu_levels, sub_pc
+     end function wai_get_aux_pc
      integer(c_int) function wai_synchronize(ctx) bind(c, name = "wai_synchronize")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -512,6 +524,7 @@ module waiwera_hip_module
 
   integer, parameter, public :: WAI_METHOD_BEULER = 0, WAI_METHOD_BDF2 = 1, WAI_METHOD_DIRECTSS = 2
   integer, parameter, public :: WAI_SUB_ILU = 0, WAI_SUB_LU = 1
+  integer, parameter, public :: WAI_PC_BJACOBI = 0, WAI_PC_ASM = 1, WAI_PC_NONE = 2, WAI_PC_LU = 3, WAI_AUX_PC_FOLLOW = -1
 
   type, public :: hip_flow_simulation_type
      !! Concrete ode_type whose hot loops run on the GPU.
@@ -535,6 +548,7 @@ module waiwera_hip_module
      procedure, public :: set_residual_form => hip_sim_set_residual_form
      procedure, public :: set_timestep_method => hip_sim_set_timestep_method
      procedure, public :: set_sub_pc => hip_sim_set_sub_pc
+     procedure, public :: set_aux_pc => hip_sim_set_aux_pc
      procedure, public :: aux_lhs => hip_sim_aux_lhs
      procedure, public :: aux_solve => hip_sim_aux_solve
      procedure, public :: residual => hip_sim_residual
@@ -551,7 +565,7 @@ module waiwera_hip_module
        wai_comm_init, wai_comm_size, wai_halo_exchange, wai_jacobian_set_values, wai_spmv, wai_pc_setup, wai_pc_apply, &
        wai_max_scaled, wai_tracer_system, wai_synchronize, wai_network_evaluate
   public :: wai_set_tracers, wai_set_tracer_bc, wai_set_tracer_injection, wai_set_aux_solver
-  public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc
+  public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc, wai_set_aux_pc, wai_get_aux_pc
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_default_eos, wai_default_opts, wai_set_bc, wai_set_sources, wai_update_sources, wai_set_source_controls, wai_get_source_rates, wai_separator_enthalpies, wai_set_regions, &
@@ -790,6 +804,16 @@ contains
     integer, intent(out) :: err
     err = wai_set_sub_pc(self%ctx, int(sub, c_int))
   end subroutine hip_sim_set_sub_pc
+
+  subroutine hip_sim_set_aux_pc(self, pc_type, asm_overlap, ilu_levels, sub_pc, err)
+    !! Preconditioner of the auxiliary (tracer) solver (timestepper_configure_auxiliary_linear_solver,
+    !! src/timestepper.F90:2057-2065): WAI_PC_* or WAI_AUX_PC_FOLLOW (the flow solver's; the reference's default is
+    !! WAI_PC_BJACOBI), PCASM overlap, ILU(k) levels, WAI_SUB_ILU | WAI_SUB_LU.
+    class(hip_flow_simulation_type), intent(in out) :: self
+    integer, intent(in) :: pc_type, asm_overlap, ilu_levels, sub_pc
+    integer, intent(out) :: err
+    err = wai_set_aux_pc(self%ctx, int(pc_type, c_int), int(asm_overlap, c_int), int(ilu_levels, c_int), int(sub_pc, c_int))
+  end subroutine hip_sim_set_aux_pc
 
   subroutine hip_sim_aux_lhs(self, t, interval, Al, err)
     !! ode_type aux_lhs (src/ode.F90, flow_simulation_tracer_cell_balances

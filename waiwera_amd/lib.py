@@ -28,6 +28,7 @@ pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
 THERMO = {"iapws": 0, "ifc67": 1}   # "thermodynamics" (src/thermodynamics_setup.F90)
 TRACER_SOLVE = {"per_tracer": 0, "coupled": 1}   # wai_set_tracer_solve_mode
 SUB_PC = {"ilu": 0, "lu": 1}   # wai_set_sub_pc: sub-preconditioner of bjacobi / asm
+AUX_PC = dict(PC, follow=-1)   # wai_set_aux_pc: the tracer solver's own preconditioner, or the flow solver's ("follow", default)
 METHOD_KIND = {"beuler": 0, "bdf2": 1, "directss": 2}  # src/timestepper.F90:2262-2275
 
 
@@ -184,6 +185,8 @@ def _load():
         "wai_tracer_solve": (i32, [vp, i32, d, d, vp, vp, vp, vp, pi, pi]),
         "wai_set_tracer_solve_mode": (i32, [vp, i32]),
         "wai_set_sub_pc": (i32, [vp, i32]),
+        "wai_set_aux_pc": (i32, [vp, i32, i32, i32, i32]),
+        "wai_get_aux_pc": (i32, [vp, pi, pi, pi, pi]),
         "wai_tracer_block_system": (i32, [vp, i32, d, d, vp, vp, vp, vp]),
         "wai_tracer_stats": (i32, [vp, C.POINTER(C.c_longlong)]),
         "wai_timer_start": (i32, [vp]),

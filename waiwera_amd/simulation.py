@@ -21,7 +21,7 @@ src/timestepper.F90:1960-2275; src/tracer.F90:63-140; utils/input_schema.json):
               linear|step and "averaging": integrate|endpoint), component, deliverability {productivity,
               pressure}, recharge | injectivity {coefficient, pressure}, limiter {type, limit,
               separator_pressure}, separator {pressure}, direction, factor
-  time        start, stop, step {size, adapt, maximum, method, solver.nonlinear, solver.linear}
+  time        start, stop, step {size, adapt, maximum, method, solver.nonlinear, solver.linear, solver.auxiliary}
   tracer      name, phase, decay, activation, diffusion
 
   output      filename, initial, final, frequency, checkpoint {time, tolerance} (cell fields, source
@@ -36,6 +36,11 @@ Jacobi -- under "asm" this DROPS the overlap, a deviation from the reference -- 
 sub_lu="device" (python -m waiwera_amd.run --sub-lu device) keeps the outer preconditioner and sets the library's
 sub-preconditioner lu (wai_set_sub_pc): bjacobi + exact block solves, or asm (overlap 1, PETSc's default: the input format has no key for it) +
 exact local solves, which is the reference's meaning; factored and applied on the device.  pc_choice records the mapping taken.
+
+The tracer solver reads "time.step.solver.auxiliary" (the keys of "linear").  What the object leaves out takes the
+reference's auxiliary defaults: gmres, rtol 1e-5, bjacobi.  An input WITHOUT the object differs from the reference: its
+tracer solves use the flow solver's preconditioner (asm for an unmodified input), not bjacobi; default_aux_pc="bjacobi"
+(python -m waiwera_amd.run --aux-pc bjacobi) gives the reference's.  aux_pc_choice records what was taken.
 
 Output: `Simulation.run` returns the final cell
 fields under the reference's HDF5 dataset names (fluid_pressure, ...) and writes "output.filename"
@@ -60,6 +65,69 @@ def _get(d, path, default=None):
             return default
         d = d[k]
     return d
+
+
+# the reference's defaults of the auxiliary (tracer) solver where its "auxiliary" object leaves a key out
+# (default_auxiliary_ksp_type_str / default_auxiliary_pc_type_str, src/timestepper.F90:2021-2022; PETSc's rtol)
+AUXILIARY_DEFAULTS = {"ksp_type": "gmres", "ksp_rtol": 1.0e-5}
+AUXILIARY_DEFAULT_PC = "bjacobi"
+
+
+def linear_solver_options(obj, default_pc, sub_lu="host", defaults=None):
+    """One linear-solver object of the input ("time.step.solver.linear" or "time.step.solver.auxiliary": the same keys,
+    src/timestepper.F90:1645-1836, 2057-2065) -> the library's options.  Pure: no library, no device.
+
+    Keys read: type, tolerance.relative, maximum.iterations, options.gmres.restart, preconditioner.type,
+    preconditioner.sub.preconditioner.{type, factor.levels}.  default_pc: the preconditioner of an object that names none;
+    sub_lu: the mapping of sub-preconditioner lu under bjacobi / asm (module docstring); defaults: options an object that
+    leaves them out gets (None: only what the object names is set).
+
+    Returns dict(opts: ksp_type, ksp_rtol, ksp_max_its, gmres_restart (where named, or in defaults), pc_type, ilu_levels;
+    sub_device: the library's sub-preconditioner lu is to be set; pc: the preconditioner's name as taken; named: whether the
+    object named it; note: () or one sentence on how sub lu was mapped).  Unknown types raise NotImplementedError."""
+    lin = obj or {}
+    opts = dict(defaults or {})
+    if lin.get("type") in ("bcgs", "gmres", "bcgsl", "lgmres"):
+        opts["ksp_type"] = lin["type"]
+    elif lin.get("type") is not None:
+        raise NotImplementedError("linear solver type %r" % lin["type"])
+    if _get(lin, "tolerance.relative") is not None:
+        opts["ksp_rtol"] = lin["tolerance"]["relative"]
+    if _get(lin, "maximum.iterations") is not None:
+        opts["ksp_max_its"] = lin["maximum"]["iterations"]
+    if _get(lin, "options.gmres.restart") is not None:
+        opts["gmres_restart"] = lin["options"]["gmres"]["restart"]
+    # preconditioner (src/timestepper.F90:1745-1757); "ilu" of a serial run is the one-block case of bjacobi / asm.
+    # Sub-preconditioner ilu with "factor.levels" k (ILU(k), :1716-1718, 1827) or lu.
+    pct_in = _get(lin, "preconditioner.type")
+    pct = (pct_in or default_pc).lower()
+    if pct not in ("asm", "bjacobi", "ilu", "lu", "none"):
+        raise NotImplementedError("preconditioner type %r" % pct)
+    opts["pc_type"] = {"ilu": "bjacobi"}.get(pct, pct)
+    sub = _get(lin, "preconditioner.sub.preconditioner", {}) or {}
+    subt = (sub.get("type") or "ilu").lower()
+    sub_device, note = False, ()
+    if subt == "lu" and pct in ("bjacobi", "asm") and sub_lu == "device":
+        # exact solves of the (overlapped) blocks on the device: the outer preconditioner stays what the input names
+        sub_device = True
+        note = ("sub lu: exact block solves on the device (wai_set_sub_pc)",)
+    elif subt == "lu" and pct in ("bjacobi", "asm"):
+        opts["pc_type"] = "lu"       # exact block solves (block Jacobi; no overlap)
+        note = ("sub lu: dense block inverses from the host, block Jacobi%s" % (" (the overlap is dropped)" if pct == "asm" else ""),)
+    elif subt != "ilu":
+        raise NotImplementedError("sub-preconditioner %r" % (sub,))
+    else:
+        levels = int(_get(sub, "factor.levels") or 0)
+        if levels and opts["pc_type"] not in ("asm", "bjacobi"):
+            raise NotImplementedError("factor.levels needs a block Jacobi or ASM preconditioner")
+        opts["ilu_levels"] = levels
+    return dict(opts=opts, sub_device=sub_device, pc=pct, named=pct_in is not None, note=note)
+
+
+def covers_coupled(lso):
+    """does the coupled tracer solve cover the preconditioner of linear_solver_options' result: block Jacobi ILU(0) or none"""
+    o = lso["opts"]
+    return o.get("pc_type", "bjacobi") in ("bjacobi", "none") and not o.get("ilu_levels") and not lso["sub_device"]
 
 
 def relperm_spec(rp):
@@ -240,7 +308,7 @@ class Simulation:
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
-                 sub_lu="host"):
+                 sub_lu="host", default_aux_pc=None):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering) and runs the same step sequence -- what
@@ -256,6 +324,12 @@ class Simulation:
         if default_pc not in ("asm", "bjacobi"):
             raise ValueError("default_pc 'asm' (the reference's default) or 'bjacobi' (the library's fused path)")
         self.default_pc, self.pc_choice = default_pc, None
+        # default_aux_pc: the tracer solver's preconditioner for an input without "time.step.solver.auxiliary" -- None: the
+        # flow solver's (the library's default, as before), "bjacobi": the reference's auxiliary default, or "asm".  An input
+        # WITH the object gets what it names, and the reference's auxiliary defaults for what it leaves out
+        if default_aux_pc not in (None, "asm", "bjacobi"):
+            raise ValueError("default_aux_pc None (the tracer solves follow the flow solver), 'bjacobi' (the reference's default) or 'asm'")
+        self.default_aux_pc, self.aux_pc_choice = default_aux_pc, None
         # sub_lu: how sub-preconditioner "lu" under bjacobi / asm is mapped (module docstring): "host" dense block inverses
         # without overlap (the default: no earlier result moves), "device" the library's sub-preconditioner lu
         if sub_lu not in ("host", "device"):
@@ -501,52 +575,39 @@ class Simulation:
             opts["max_newton_its"] = nl["maximum"]["iterations"]
         if _get(nl, "minimum.iterations") is not None:
             opts["min_newton_its"] = nl["minimum"]["iterations"]
-        lin = _get(step, "solver.linear", {}) or {}
-        if lin.get("type") in ("bcgs", "gmres", "bcgsl", "lgmres"):
-            opts["ksp_type"] = lin["type"]
-        elif lin.get("type") is not None:
-            raise NotImplementedError("linear solver type %r" % lin["type"])
-        if _get(lin, "tolerance.relative") is not None:
-            opts["ksp_rtol"] = lin["tolerance"]["relative"]
-        if _get(lin, "maximum.iterations") is not None:
-            opts["ksp_max_its"] = lin["maximum"]["iterations"]
-        if _get(lin, "options.gmres.restart") is not None:
-            opts["gmres_restart"] = lin["options"]["gmres"]["restart"]
-        # preconditioner (src/timestepper.F90:1745-1757, default "asm"); "ilu" of a serial run is the
-        # one-block case of either.  Sub-preconditioner ilu with "factor.levels" k (ILU(k), :1716-1718, 1827) or lu.
+        # the flow solver: "time.step.solver.linear" (linear_solver_options).
         # An input that names no preconditioner gets the REFERENCE's default, restricted PCASM with overlap 1 over ILU(0)
         # (default_flow_pc_type_str = "asm", src/timestepper.F90:2019-2020) -- not the library's own default
         # (wai_default_opts: brick block Jacobi, the fused fast path).  Measured on the 216^3 bench system (round 6,
         # profiles/pc_compare_r6.log): asm 74 Krylov iterations at 7.83 ms, bjacobi 98 at 1.39 ms; a host that wants the
         # fast path for an unmodified input passes default_pc="bjacobi".  pc_choice records what was taken and why.
-        pct_in = _get(lin, "preconditioner.type")
-        pct = (pct_in or self.default_pc).lower()
-        if pct not in ("asm", "bjacobi", "ilu", "lu", "none"):
-            raise NotImplementedError("preconditioner type %r" % pct)
-        self.pc_choice = (pct, "input" if pct_in else ("reference default" if self.default_pc == "asm" else "default_pc argument"))
-        opts["pc_type"] = {"ilu": "bjacobi"}.get(pct, pct)
-        sub = _get(lin, "preconditioner.sub.preconditioner", {}) or {}
-        subt = (sub.get("type") or "ilu").lower()
-        sub_device = False
-        if subt == "lu" and pct in ("bjacobi", "asm") and self.sub_lu == "device":
-            # exact solves of the (overlapped) blocks on the device: the outer preconditioner stays what the input names
-            sub_device = True
-            self.pc_choice += ("sub lu: exact block solves on the device (wai_set_sub_pc)",)
-        elif subt == "lu" and pct in ("bjacobi", "asm"):
-            opts["pc_type"] = "lu"       # exact block solves (block Jacobi; no overlap)
-            self.pc_choice += ("sub lu: dense block inverses from the host, block Jacobi%s" % (" (the overlap is dropped)" if pct == "asm" else ""),)
-        elif subt != "ilu":
-            raise NotImplementedError("sub-preconditioner %r" % (sub,))
-        else:
-            levels = int(_get(sub, "factor.levels") or 0)
-            if levels and opts["pc_type"] not in ("asm", "bjacobi"):
-                raise NotImplementedError("factor.levels needs a block Jacobi or ASM preconditioner")
-            opts["ilu_levels"] = levels
+        lso = linear_solver_options(_get(step, "solver.linear"), self.default_pc, self.sub_lu)
+        opts.update(lso["opts"])
+        self.pc_choice = (lso["pc"], "input" if lso["named"] else ("reference default" if self.default_pc == "asm" else "default_pc argument")) + lso["note"]
         if opts:
             self.ode.set_opts(**opts)
-        if sub_device:
+        if lso["sub_device"]:
             self.ode.set_sub_pc("lu")
-        self._pc_covers_coupled = opts.get("pc_type", "bjacobi") in ("bjacobi", "none") and not opts.get("ilu_levels") and not sub_device
+        self._pc_covers_coupled = covers_coupled(lso)
+        # the auxiliary (tracer) solver: "time.step.solver.auxiliary", the same keys (src/timestepper.F90:2057-2065).  The
+        # reference's defaults for it are gmres and bjacobi (:2021-2022) whatever the flow solver uses; the library's tracer
+        # solves FOLLOW the flow solver's preconditioner until told otherwise (wai_set_aux_pc), and an input without the
+        # object keeps that -- no earlier result moves -- unless default_aux_pc asks for the reference's.  aux_pc_choice
+        # records what was taken and why, like pc_choice
+        aux_in = _get(step, "solver.auxiliary")
+        if aux_in is None and self.default_aux_pc is None:
+            self.aux_pc_choice = ("follow", "no auxiliary object: the flow solver's preconditioner (%s)" % self.pc_choice[0])
+            self._aux_ilu_levels = opts.get("ilu_levels")
+        else:
+            als = linear_solver_options(aux_in, self.default_aux_pc or AUXILIARY_DEFAULT_PC, self.sub_lu, AUXILIARY_DEFAULTS)
+            ao = als["opts"]
+            why = "input" if als["named"] else ("reference default" if (self.default_aux_pc or AUXILIARY_DEFAULT_PC) == AUXILIARY_DEFAULT_PC
+                                                else "default_aux_pc argument")
+            self.aux_pc_choice = (als["pc"], why) + als["note"]
+            self.ode.set_aux_solver(ao["ksp_type"], ao.get("gmres_restart", 30), ao["ksp_rtol"], 1e-50, ao.get("ksp_max_its", 10000))
+            self.ode.set_aux_pc(ao["pc_type"], 1, ao.get("ilu_levels", 0), "lu" if als["sub_device"] else "ilu")
+            self._pc_covers_coupled = covers_coupled(als)
+            self._aux_ilu_levels = ao.get("ilu_levels")
         # tracers
         tr = inp.get("tracer")
         self.tracer_names = []
@@ -583,9 +644,13 @@ class Simulation:
             self.X = np.tile(np.asarray(tvals(init.get("tracer")), dtype=np.float64), lm.n_owned)
             if self.tracer_solve == "coupled" and nt > 1 and not self._pc_covers_coupled:
                 # (one tracer takes the per-tracer path in either mode: nothing to refuse)
-                raise ValueError("tracer_solve='coupled' covers the bjacobi (ILU(0)) and none preconditioners; this run's is %r (%s)"
-                                 "%s: pass default_pc='bjacobi' or tracer_solve='per_tracer'"
-                                 % (self.pc_choice[0], self.pc_choice[1], " with ILU(k)" if opts.get("ilu_levels") else ""))
+                if self.aux_pc_choice[0] == "follow":
+                    raise ValueError("tracer_solve='coupled' covers the bjacobi (ILU(0)) and none preconditioners; this run's is %r (%s)"
+                                     "%s: pass default_pc='bjacobi' or tracer_solve='per_tracer'"
+                                     % (self.pc_choice[0], self.pc_choice[1], " with ILU(k)" if opts.get("ilu_levels") else ""))
+                raise ValueError("tracer_solve='coupled' covers the bjacobi (ILU(0)) and none preconditioners; this run's auxiliary "
+                                 "preconditioner is %r (%s)%s: pass tracer_solve='per_tracer', or name 'bjacobi' in the auxiliary solver object"
+                                 % (self.aux_pc_choice[0], self.aux_pc_choice[1], " with ILU(k)" if self._aux_ilu_levels else ""))
         ad = step.get("adapt", {}) or {}
         mx = step.get("maximum", {}) or {}
         self.ts = Timestepper(
