@@ -709,8 +709,10 @@ int wai_separator_enthalpies(wai_ctx* c, double pressure, double* hf, double* hg
 int wai_get_source_rates(wai_ctx* c, double* rate, double* enthalpy) {
   if (!c || !rate) return -2;
   const size_t n = (size_t)c->src.n;
+  // on the fluid state in force, like the residual's pass.  A network across ranks gathers every rank's sources in it: a
+  // rank without sources takes part before it returns
+  if (c->net.on && network_update(c)) return -1;
   if (!n) return 0;
-  if (c->net.on && network_update(c)) return -1;   // on the fluid state in force, like the residual's pass
   DevBuf<double> tmp;
   if (tmp.alloc(c, 2 * n)) return -1;
   launch_source_rates(c, tmp);
@@ -741,9 +743,8 @@ int wai_num_flux_dof(wai_ctx* c) { return c ? c->np + c->nmob : -2; }
 int wai_get_source_separated(wai_ctx* c, double* out4) {
   if (!c || !out4) return -2;
   const int n = c->src.n;
-  if (!n) return 0;
-  std::vector<double> q(n), h(n);
-  if (int e = wai_get_source_rates(c, q.data(), h.data())) return e;
+  std::vector<double> q(std::max(n, 1)), h(std::max(n, 1));
+  if (int e = wai_get_source_rates(c, q.data(), h.data())) return e;   // (the network pass in it: made without sources too)
   for (int i = 0; i < n; i++) {
     NetNode nd;
     nd.rate = q[i]; nd.enth = h[i];

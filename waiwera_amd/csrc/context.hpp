@@ -156,7 +156,8 @@ struct Network {
   // A network whose sources live on several ranks (source_network_group.F90:494-515, 579-596: gathers over the
   // group's communicator): every rank holds the whole description, numbered by GLOBAL source index; the sources' own
   // rates are all-gathered (an all-reduce of a vector each rank fills at its own entries) before the pass, which
-  // every rank then evaluates identically.  gidx: global index of each local source; empty: one rank, identity
+  // every rank then evaluates identically.  gidx: global index of each local source (none on a rank without sources);
+  // n_global: the sources of all ranks, 0: one rank, identity
   std::vector<int> gidx;
   int n_global = 0;
   DevBuf<double> d_all;                            // [2 n_global] all-reduce buffer

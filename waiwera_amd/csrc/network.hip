@@ -200,7 +200,7 @@ int network_update(wai_ctx* c) {
   Network& nw = c->net;
   const int n = c->src.n;           // local sources
   if (!nw.on) return 0;
-  const bool span = !nw.gidx.empty();
+  const bool span = nw.n_global > 0;   // (not "gidx is not empty": a rank WITHOUT sources takes part in the gather too)
   const int ng = span ? nw.n_global : n;
   if (ng == 0) return 0;
   // the sources' own (controlled) rates and flowing enthalpies on the current fluid
@@ -519,6 +519,8 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
   Network& nw = c->net;
   const int n = c->src.n;
   auto ctl = nw.h_ctl; auto e0 = nw.h_enth0; auto cells = nw.h_cell;
+  // a network set AGAIN on several ranks (its time tables, once per step): the copies above are numbered globally by now
+  const std::vector<int> was = nw.gidx;
   const bool coupling = nw.coupling;
   c->src.net.reset();
   nw = Network();
@@ -539,11 +541,12 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
     std::vector<double> all((size_t)NG * ng, 0.0);
     for (int i = 0; i < n; i++) {
       const int g = nw.gidx[i];
-      if (i < (int)ctl.size()) {
-        all[(size_t)NG * g] = ctl[i].sep_hf; all[(size_t)NG * g + 1] = ctl[i].sep_hg;
-        for (int q = 0; q < 6; q++) all[(size_t)NG * g + 2 + q] = ctl[i].sep_more[q];
+      const int k = (int)was.size() == n ? was[i] : i;   // source i in ctl and e0
+      if (k < (int)ctl.size()) {
+        all[(size_t)NG * g] = ctl[k].sep_hf; all[(size_t)NG * g + 1] = ctl[k].sep_hg;
+        for (int q = 0; q < 6; q++) all[(size_t)NG * g + 2 + q] = ctl[k].sep_more[q];
       }
-      all[(size_t)NG * g + 8] = i < (int)e0.size() ? e0[i] : 0.0;
+      all[(size_t)NG * g + 8] = k < (int)e0.size() ? e0[k] : 0.0;
       all[(size_t)NG * g + 9] = (double)c->comm->rank * 4294967296.0 + (double)(i < (int)cells.size() ? cells[i] : 0);
     }
     DevBuf<double> tmp;

@@ -154,10 +154,11 @@ class FlowSimulation:
         self._chk(LIB.wai_separator_enthalpies(self.h, pressure, C.byref(hf), C.byref(hg)), "separator_enthalpies")
         return hf.value, hg.value
 
-    def source_rates(self):
-        """(rate, enthalpy) of every source on the current fluid"""
+    def source_rates(self, collective=False):
+        """(rate, enthalpy) of every source on the current fluid.  collective: a source network across ranks -- the call
+        runs the network pass, which gathers all ranks' sources, so a rank WITHOUT sources makes it too"""
         r, e = np.zeros(self.mesh.n_src), np.zeros(self.mesh.n_src)
-        if self.mesh.n_src:
+        if self.mesh.n_src or collective:
             self._chk(LIB.wai_get_source_rates(self.h, r.ctypes.data_as(_lib.pd), e.ctypes.data_as(_lib.pd)), "get_source_rates")
         return r, e
 
@@ -252,10 +253,11 @@ class FlowSimulation:
         self._chk(LIB.wai_get_fluxes(self.h, out.ctypes.data), "get_fluxes")
         return out
 
-    def source_separated(self):
-        """(n_sources, 4): water_rate, water_enthalpy, steam_rate, steam_enthalpy behind each source's separator"""
+    def source_separated(self, collective=False):
+        """(n_sources, 4): water_rate, water_enthalpy, steam_rate, steam_enthalpy behind each source's separator
+        (collective: as source_rates)"""
         out = np.zeros((max(self.mesh.n_src, 1), 4))
-        if self.mesh.n_src:
+        if self.mesh.n_src or collective:
             self._chk(LIB.wai_get_source_separated(self.h, out.ctypes.data_as(_lib.pd)), "get_source_separated")
         return out[: self.mesh.n_src]
 

@@ -21,6 +21,41 @@ def block_owner(n_cells, world):
     return (np.arange(n_cells, dtype=np.int64) * world) // max(n_cells, 1)
 
 
+def family_owner(lm, world, owner=None):
+    """Owner of every cell of a one-rank mesh, in the mesh's own (storage) order, with every MINC family -- a fracture cell
+    and the matrix cells nested behind it -- on one rank: the reference distributes the mesh before it adds the MINC cells
+    (src/mesh.F90:143-171, then 3026-3186), so it never splits one either.
+
+    owner None: contiguous blocks of the input's cells (block_owner), each matrix cell with its fracture cell
+    (lm.extras["minc_parent"]).  Given: one rank per input cell (extended to the matrix cells), or -- a MINC mesh -- one per
+    cell in the order of the run's output (lm.extras["waiwera_order"]: the input's cells, then the matrix cells level by
+    level); one that puts a matrix cell on another rank than its fracture cell is a ValueError naming the first such cell."""
+    ex = lm.extras
+    if "minc_parent" not in ex:
+        own = block_owner(lm.n_owned, world) if owner is None else np.asarray(owner, dtype=np.int64)
+        if own.size != lm.n_owned:
+            raise ValueError("one owner per cell: %d given, %d cells" % (own.size, lm.n_owned))
+        return own
+    parent = np.asarray(ex["minc_parent"], dtype=np.int64)          # the input's number of every cell's original cell
+    frac = np.asarray(ex["fracture_index"], dtype=np.int64)         # where the mesh keeps each original (fracture) cell
+    order = np.asarray(ex["waiwera_order"], dtype=np.int64)
+    n_orig = frac.size
+    own = block_owner(n_orig, world) if owner is None else np.asarray(owner, dtype=np.int64)
+    if own.size == n_orig:
+        return own[parent]
+    if own.size != lm.n_owned:
+        raise ValueError("one owner per input cell (%d) or per cell of the MINC mesh (%d): %d given" % (n_orig, lm.n_owned, own.size))
+    stored = np.empty(lm.n_owned, dtype=np.int64)
+    stored[order] = own
+    split = stored[order] != stored[frac[parent[order]]]             # walked in the order the caller numbered the cells
+    if split.any():
+        i = int(np.nonzero(split)[0][0])
+        q = order[i]
+        raise ValueError("owner splits a MINC family: cell %d (level %d behind cell %d) on rank %d, its fracture cell on rank %d"
+                         % (i, int(np.asarray(ex["minc_level"])[q]), int(parent[q]), int(stored[q]), int(stored[frac[parent[q]]])))
+    return stored
+
+
 def partition_mesh(lm, owner, rank, chunk=512, world=None):
     """(LocalMesh of `rank`, gid) from the one-rank LocalMesh `lm` and owner[cell] in 0 .. world - 1.
 
@@ -81,6 +116,7 @@ def partition_mesh(lm, owner, rank, chunk=512, world=None):
         m.bc_region = np.asarray(lm.bc_region)[bcs - N].copy()
         if "bc_spec" in lm.extras:
             m.extras["bc_spec"] = np.asarray(lm.extras["bc_spec"])[bcs - N].copy()
+        m.extras["bc_global_index"] = (bcs - N).astype(np.int64)     # their index in the one-rank list (per-boundary-cell data)
     else:
         m.bc_primary, m.bc_region = None, None
     # send lists: for neighbour q, my cells across a kept face from q's cells -- ascending global index, which is the
@@ -101,7 +137,10 @@ def partition_mesh(lm, owner, rank, chunk=512, world=None):
     if lm.sub_ptr is not None:
         sub_of = np.searchsorted(np.asarray(lm.sub_ptr), mine, side="right") - 1
         cuts.update((np.nonzero(np.diff(sub_of))[0] + 1).tolist())
-    cuts.update((np.nonzero(np.diff(mine) != 1)[0] + 1).tolist())       # not consecutive in the one-rank numbering
+    if "minc_parent" not in lm.extras:
+        cuts.update((np.nonzero(np.diff(mine) != 1)[0] + 1).tolist())   # not consecutive in the one-rank numbering
+    # (a MINC mesh keeps a subdomain's matrix cells behind its original cells: what a rank owns of one subdomain is several
+    # runs of that numbering, and stays one subdomain -- the matrix cells with their fracture cells, as on one rank)
     pts = sorted(cuts)
     sub = [0]
     for a, b in zip(pts[:-1], pts[1:]):
@@ -117,6 +156,13 @@ def partition_mesh(lm, owner, rank, chunk=512, world=None):
     for key in ("minc_level", "minc_parent"):
         if key in lm.extras:
             m.extras[key] = np.asarray(lm.extras[key])[mine].copy()
+    if "waiwera_order" in lm.extras:
+        # the rank's cells in the reference's output order (local indices), and where each stands in the whole run's output
+        wo = np.asarray(lm.extras["waiwera_order"], dtype=np.int64)
+        here = owner[wo] == rank
+        m.extras["waiwera_order"] = loc[wo[here]]
+        m.extras["waiwera_gid"] = np.nonzero(here)[0]
+    m.extras.pop("fracture_index", None)      # (numbers the one-rank mesh)
     # sources of my cells, with their index in the one-rank list (wai_set_source_global_index)
     if lm.n_src:
         sc = np.asarray(lm.src_cell)

@@ -6,7 +6,9 @@ prints one line per accepted time step, like the reference's log of `timestep en
 Several ranks, one per GPU (the reference: mpiexec -np N waiwera input.json):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 -m waiwera_amd.run input.json
 every rank reads the whole input and keeps its own cells (waiwera_amd/partition.py); -o writes one file per rank
-(results.rank<r>.npz, with `owned_gid`: the cells' numbers in the input)."""
+(results.rank<r>.npz: the rank's cell fields -- tracers among them -- with `owned_gid`, the cells' numbers in the one-rank
+output, its sources' fields with `owned_source`, their numbers in the input, and the network's group and reinjector fields,
+the same in every file).  The input's own "output.filename" is not written on several ranks."""
 import argparse
 import sys
 

@@ -46,6 +46,20 @@ Output: `Simulation.run` returns the final cell
 fields under the reference's HDF5 dataset names (fluid_pressure, ...) and writes "output.filename"
 in the reference's HDF5 layout (waiwera_amd/hdf5io.py, HDF5 C library through ctypes); `save`
 writes a .npz archive.
+
+N ranks (rank, world, comm_id; one process per rank, python -m waiwera_amd.run under a launcher): every rank reads the
+whole input, builds the whole mesh -- MINC cells included -- and keeps its cells with one ghost layer
+(waiwera_amd/partition.py).  Covered: everything above but the output file -- sources with their tables and
+state-dependent controls, MINC zones (a family never leaves its fracture cell's rank), rock table controls (each rank
+updates the controlled cells it holds, ghosts included), tracers in both solve modes (boundary values through the rank's
+boundary cells, injection through its sources) and source networks (every rank holds the whole network, its sources
+numbered as in the input; the library gathers their rates).  fields() returns the rank's cells, owned_gid their numbers
+in the one-rank output (the input's numbering; a MINC mesh: the reference's cell order), source fields the rank's own
+sources with owned_source their numbers in the input, group and reinjector fields the same on every rank.  NOT on
+N ranks: "output.filename" is skipped there without a message -- the library has no gather of host data; save() /
+python -m waiwera_amd.run -o write one .npz per rank instead -- and PCASM overlap deeper than 1, which the library refuses.
+Collective-call discipline: nothing that exchanges data stands under a condition that can differ
+between ranks; what must be refused is refused from the input and the arguments alone, so on every rank alike.
 """
 import json
 import os
@@ -311,10 +325,10 @@ class Simulation:
                  sub_lu="host", default_aux_pc=None):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
-        every cell, default contiguous blocks of the input's numbering) and runs the same step sequence -- what
-        DMPlexDistribute (src/mesh.F90:143-171) does for the reference.  On several ranks: constant or tabulated sources
-        and their device-side controls; not (yet) MINC zones, source networks, tracers, rock table controls, output files
-        (fields() returns the rank's cells, self.owned_gid their index in the input's numbering)."""
+        every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
+        output's order with every family on one rank, waiwera_amd.partition.family_owner) and runs the same step sequence --
+        what DMPlexDistribute (src/mesh.F90:143-171) does for the reference.  What N ranks cover: the module docstring
+        (fields() returns the rank's cells, self.owned_gid their index in the one-rank output's numbering)."""
         self.rank, self.world = int(rank), int(world)
         # tracer_solve: "per_tracer" (one scalar solve per tracer) or "coupled" (all tracers in one Krylov solve, as the
         # reference; needs the bjacobi or no preconditioner).  Not a key of the input file: the reference has none
@@ -492,16 +506,33 @@ class Simulation:
             self._order = lm.extras["waiwera_order"]
         self.owned_gid = np.arange(lm.n_owned)
         self._src_pick = None
+        # what the initial conditions below need of the whole MINC mesh: its cell count, each cell's original cell and the
+        # reference's cell order (on N ranks self._order becomes the rank's own)
+        minc_all = (lm.n_owned, lm.extras["minc_parent"], self._order) if self._order is not None else None
+        self._cell_index = None     # several ranks: the input's cell number -> the cell's place in the one-rank mesh
         if self.world > 1:
-            if minc_in or self._rock_controls or inp.get("tracer") or inp.get("network"):
-                raise NotImplementedError("MINC zones, rock table controls, tracers and source networks of an input file on several ranks")
-            from .partition import block_owner, partition_mesh
-            own = block_owner(lm.n_owned, self.world) if owner is None else np.asarray(owner)
+            if _get(inp, "time.step.adapt.method", "iteration") == "change":
+                # (Timestepper._relative_change takes its maximum over the rank's own cells: the ranks would choose
+                # different step sizes and part ways.  The same on every rank, before anything collective)
+                raise NotImplementedError("step size adaption by the 'change' monitor on N ranks")
+            from .partition import family_owner, partition_mesh
+            # the owner of every cell, MINC families whole (each matrix cell with its fracture cell, family_owner)
+            own = family_owner(lm, self.world, owner)
+            if self._order is not None:
+                self._cell_index = np.asarray(lm.extras["fracture_index"])
             lm, self._gid = partition_mesh(lm, own, self.rank, world=self.world)
+            # owned_gid: the rank's cells as the one-rank run's output numbers them -- the input's numbering; on a MINC mesh
+            # the reference's order (the input's cells, then the matrix cells level by level), in which fields() lists them
             self.owned_gid = lm.owned_gid
+            if self._order is not None:
+                self._order, self.owned_gid = lm.extras["waiwera_order"], lm.extras["waiwera_gid"]
+            # everything per source goes through _src_pick: the rank's sources as their numbers in the input, in the rank's order
             self._src_pick = lm.extras.get("src_global_index", np.zeros(0, dtype=np.int32))
-            self._tables = [(int(np.nonzero(self._src_pick == i)[0][0]), key, tab) for (i, key, tab) in self._tables
-                            if i in set(self._src_pick.tolist())]
+            self._tables = self._pick_sources(self._tables)
+            # rock table controls: the controlled cells this rank holds, ghosts included -- the permeability of a face
+            # between two ranks reads the rock of both its cells
+            self._rock_controls = [(fields, np.nonzero(np.isin(self._gid, cells))[0].astype(np.int32), tab)
+                                   for fields, cells, tab in self._rock_controls]
         self.mesh = lm
         self.relperm = relperm_spec(rock.get("relative_permeability"))
         self.capillary = capillary_spec(rock.get("capillary_pressure"))
@@ -526,22 +557,23 @@ class Simulation:
             elif npv > 2:
                 cols.append(st["fluid_CO2_partial_pressure" if self.eos == "wce" else "fluid_air_partial_pressure"])
             prim = np.stack(cols, axis=1)
-            if prim.shape[0] != n and not (self._order is not None and prim.shape[0] == lm.n_owned):
+            if prim.shape[0] != n and not (minc_all is not None and prim.shape[0] == minc_all[0]):
                 raise ValueError("initial conditions file has %d cells, mesh has %d" % (prim.shape[0], n))
         else:
             prim = np.asarray(init.get("primary", [1.0e5, 20.0, 0.0][:npv]), dtype=np.float64)
             prim = np.tile(prim, (n, 1)) if prim.ndim == 1 else prim
             region = np.asarray(init.get("region", 1))
             region = np.full(n, int(region), dtype=np.int32) if region.ndim == 0 else region.astype(np.int32)
-        if self._order is not None:
+        if minc_all is not None:
             # matrix cells start from their fracture cell's state (src/initial.F90: MINC cells copy
-            # the original cell's values unless the file holds them); file order = reference order
-            nt = lm.n_owned
+            # the original cell's values unless the file holds them); file order = reference order.
+            # On the WHOLE mesh, for either kind of initial conditions: the rank's share is cut out below
+            nt, parent_all, order_all = minc_all
             src = np.empty(nt, dtype=np.int64)
             if prim.shape[0] == nt:        # restart file of a MINC run: already one record per cell
-                src[self._order] = np.arange(nt)
+                src[order_all] = np.arange(nt)
             else:
-                src[:] = lm.extras["minc_parent"]
+                src[:] = parent_all
             prim, region = prim[src], region[src]
         if self.world > 1:
             prim, region = prim[self._gid], region[self._gid]
@@ -636,6 +668,14 @@ class Simulation:
                     v = float(tab.interpolate(_get(inp, "time.start", 0.0))[0])
                 rows.append(tvals(v))
             inj = np.array(rows) if srcs else None
+            if self.world > 1:
+                # the rank's share: boundary values of its boundary cells, injection rows and tables of its sources.  (The
+                # initial value is one number per tracer: nothing to cut.)  None of this is collective; a rank without
+                # tracer source or boundary still makes every assembly and solve call, the time stepper's (Timestepper.step)
+                if lm.n_bc:
+                    bc = bc[lm.extras["bc_global_index"]]
+                inj = inj[self._src_pick] if srcs and len(self._src_pick) else None
+                self._tracer_tables = self._pick_sources(self._tracer_tables)
             self._tracer_injection = inj
             self.ode.set_tracers(phases, decay=[t.get("decay", 0.0) for t in tr],
                                  activation=[t.get("activation", 0.0) for t in tr],
@@ -643,7 +683,8 @@ class Simulation:
                                  bc=bc if lm.n_bc else None, injection=inj)
             self.X = np.tile(np.asarray(tvals(init.get("tracer")), dtype=np.float64), lm.n_owned)
             if self.tracer_solve == "coupled" and nt > 1 and not self._pc_covers_coupled:
-                # (one tracer takes the per-tracer path in either mode: nothing to refuse)
+                # (one tracer takes the per-tracer path in either mode: nothing to refuse.  Decided on the input and the
+                # arguments alone, before the first collective call after comm_init: every rank raises, none waits)
                 if self.aux_pc_choice[0] == "follow":
                     raise ValueError("tracer_solve='coupled' covers the bjacobi (ILU(0)) and none preconditioners; this run's is %r (%s)"
                                      "%s: pass default_pc='bjacobi' or tracer_solve='per_tracer'"
@@ -673,12 +714,15 @@ class Simulation:
         # decided on the unfiltered source list -- a rank without such a source would otherwise never issue the matching
         # exchange (advisor, round 5)
         need_fluid = self.world > 1 and any(k in s_ for s_ in src_in for k in ("deliverability", "recharge", "injectivity"))
+        # the sources as the input numbers them, for the rank's own: fields()["source_*"] and save()'s owned_source
+        self.owned_source = np.arange(len(src_in)) if self._src_pick is None else np.asarray(self._src_pick, dtype=np.int64)
         if self._src_pick is not None:      # the sources of this rank's cells, in the rank's order
             src_in = [src_in[i] for i in self._src_pick]
         self._setup_source_controls(src_in, _get(inp, "time.start", 0.0), collective_fluid=need_fluid)
         self._setup_network(inp)
         if (self._tables or self._ctl_tables or getattr(self, "_tracer_tables", None) or getattr(self, "_network_timed", False)
                 or self._rock_controls):
+            # (decided on what the INPUT holds, not on this rank's share, where a control is collective: _network_timed)
             self.ts.controls = self._update_controls
 
     # ---- source network --------------------------------------------------------------------------
@@ -690,6 +734,12 @@ class Simulation:
         self.network_names = names
         self._network_timed = timed
         if spec is not None:
+            if self.world > 1:
+                # EVERY rank holds the whole network (the reference broadcasts the JSON too), its sources numbered as in the
+                # input; the library is told which of them are this rank's.  set_source_network is collective there (the
+                # separators and injection enthalpies of all ranks' sources are gathered): made on every rank, with or
+                # without a source of the network -- `spec` depends on the input alone
+                self.ode.set_source_global_index(len(inp.get("source", []) or []), self._src_pick)
             self.ode.set_source_network(spec)
 
     # ---- state-dependent source controls -------------------------------------------------------
@@ -701,7 +751,7 @@ class Simulation:
         self._ctl, self._ctl_tables = None, []
         fl = None
         if collective_fluid:      # every rank together, whether or not it owns such a source
-            assert self.ode.pre_eval(t0, self.y) == 0
+            self._pre_eval(t0)
             fl = np.asarray(self.ode.fluid())
         if not any(k in s for s in sources for k in ("deliverability", "recharge", "injectivity", "limiter",
                                                      "direction", "factor", "separator")):
@@ -721,10 +771,12 @@ class Simulation:
             if fl is None:
                 if self.world > 1:
                     raise RuntimeError("initial fluid state asked for on one rank only: the evaluation is collective")
-                assert self.ode.pre_eval(t0, self.y) == 0
+                self._pre_eval(t0)
                 fl = np.asarray(self.ode.fluid())
             if self.world > 1:      # the input's cell number -> this rank's (the source is on this rank: its cell is owned)
-                cell = int(np.nonzero(self.owned_gid == cell)[0][0])
+                if self._cell_index is not None:      # a MINC mesh keeps the input's cells elsewhere
+                    cell = int(self._cell_index[cell])
+                cell = int(np.nonzero(self.mesh.owned_gid == cell)[0][0])
             return fl[cell]
 
         nc = {"w": 1, "we": 1, "wce": 2, "wse": 2, "wae": 2, "wsce": 3, "wsae": 3}[self.eos]
@@ -811,6 +863,18 @@ class Simulation:
         for r in self._ctl:
             r.pop("threshold_pi", None)     # from now on the index the device notes (wai_set_source_controls keeps it)
 
+    def _pre_eval(self, t):
+        """the fluid state of self.y (a halo exchange on N ranks: collective).  Not inside an assert: python -O would
+        take the call away with the check"""
+        rc = self.ode.pre_eval(t, self.y)
+        if rc != 0:
+            raise RuntimeError("the fluid state at t = %g could not be evaluated (pre_eval returned %d)" % (t, rc))
+
+    def _pick_sources(self, entries):
+        """(source, ...) entries numbered as in the input -> those of this rank's sources, numbered as the rank holds them"""
+        local = {int(g): i for i, g in enumerate(self._src_pick)}
+        return [(local[e[0]],) + tuple(e[1:]) for e in entries if e[0] in local]
+
     def _apply_controls(self, interval):
         for i, key, tab in self._ctl_tables:
             self._ctl[i][key] = float(tab.average(interval)[0])
@@ -823,6 +887,8 @@ class Simulation:
         # rock controls: flow_simulation_pre_try_timestep(t) with t the time the try ends at (timestepper.F90:2333),
         # the table's value AT that time (rock_control.F90:66, 102: interpolate, not an interval average); a scalar
         # permeability fills all directions
+        # (wai_update_rock copies one plane of the rock record to the host and back: nothing in it is collective.  Every
+        # rank still makes the call, with the cells it holds -- none, for a rank without the rock type)
         for fields, cells, tab in self._rock_controls:
             v = tab.interpolate(float(interval[1]))
             for q, f in enumerate(fields):
@@ -852,7 +918,7 @@ class Simulation:
         """timestepper_run with the output schedule of "output" (initial / frequency / final,
         src/timestepper.F90:2478-2560); returns the final cell fields under the reference's names
         and, if "output.filename" is given (and the HDF5 library is there), writes that file"""
-        assert self.ode.pre_eval(self.ts.time, self.y) == 0
+        self._pre_eval(self.ts.time)
         if self.X is not None:
             self.ts.init_auxiliary()
         oc = self.inp.get("output")
@@ -944,8 +1010,12 @@ class Simulation:
             for k, name in enumerate(self.tracer_names):
                 xk = self.X.reshape(n, -1)[:, k]
                 out["tracer_" + name] = (xk[self._order] if self._order is not None else xk).copy()
-        if self.mesh.n_src and hasattr(self.ode, "source_rates"):
-            out["source_rate"], out["source_enthalpy"] = self.ode.source_rates()
+        # A source network on N ranks: reading the sources' rates runs the network pass, which gathers every rank's
+        # sources -- a rank without any reads them too (`together`; decided on the input alone)
+        together = self.world > 1 and bool(getattr(self, "network_names", None)) and \
+            bool(self.network_names["group"] or self.network_names["reinject"])
+        if (self.mesh.n_src or together) and hasattr(self.ode, "source_rates"):
+            out["source_rate"], out["source_enthalpy"] = self.ode.source_rates(True) if together else self.ode.source_rates()
         oc = self.inp.get("output")
         want = (oc.get("fields") if isinstance(oc, dict) else None) or {}
         # face fields: "output.fields.flux" (src/flow_simulation.F90:460-504): the flux vector's
@@ -968,9 +1038,9 @@ class Simulation:
             out["face_geometry_area"] = np.asarray(self.mesh.face_geom)[:, 0].copy()
         # separated water / steam flows of the sources and the source network's nodes
         src_want = want.get("source") or []
-        if self.mesh.n_src and hasattr(self.ode, "source_separated") and \
+        if (self.mesh.n_src or together) and hasattr(self.ode, "source_separated") and \
                 any(k in src_want for k in ("water_rate", "water_enthalpy", "steam_rate", "steam_enthalpy")):
-            sep = self.ode.source_separated()
+            sep = self.ode.source_separated(True) if together else self.ode.source_separated()
             for j, k in enumerate(("water_rate", "water_enthalpy", "steam_rate", "steam_enthalpy")):
                 if k in src_want:
                     out["source_" + k] = sep[:, j].copy()
@@ -990,4 +1060,4 @@ class Simulation:
         return out
 
     def save(self, path):
-        np.savez(path, owned_gid=self.owned_gid, **self.fields())
+        np.savez(path, owned_gid=self.owned_gid, owned_source=self.owned_source, **self.fields())
