@@ -300,6 +300,31 @@ int wai_comm_init(wai_ctx *ctx, int rank, int nranks, const char id[128]);
 int wai_halo_exchange(wai_ctx *ctx, double *vec, int dof);  /* vec has dof*(n_owned+n_halo) */
 int wai_comm_size(wai_ctx *ctx);   /* ranks the RCCL communicator reports (1 without one) */
 
+/* ---- gathers to one rank: the output file of a run on N ranks --------------------------------
+ * (the reference views its global Vecs into the HDF5 file, src/flow_simulation.F90:2695-2800; PETSc brings the
+ * ranks' parts to the writers).  Both calls are collective: every rank of the communicator enters them, with the
+ * same root, ncomp / fields and n_global.  Without a communicator (one rank) they are the permutation copy alone.
+ *
+ * wai_gather_rows: local[n_local][ncomp] doubles (host or device) of this rank, index[n_local] (int32, host or
+ * device) the place of each row in the result.  On `root`, out[n_global][ncomp] (host or device) receives the rows
+ * of all ranks; on the other ranks out is ignored (may be NULL).  Places nobody sends keep what out held -- a host
+ * that fills out with NaN first sees a hole.  n_local = 0 is legal on any rank, the root included (local and index
+ * may then be NULL).  A place outside [0, n_global), or one claimed by two rows, is an error on the root (-2;
+ * wai_last_error names the place, and the rank and row of whoever sent it -- of both claimants); the other ranks
+ * have sent their rows and return 0.  After such an error a host out is untouched, a device out unspecified at the
+ * places received.  Places travel as doubles beside the rows (exact: they are int32); the row counts by one
+ * all-reduce of a vector as long as the communicator; the rows by grouped send / receive on the library's stream.
+ *
+ * wai_gather_fluid: the same gather fed from the device-resident fluid record -- columns fields[0 .. nf) (indices
+ * into the wai_num_fluid_dof doubles of a cell's record, as wai_get_fluid lays them out; nf <= 32) of this rank's
+ * n_owned cells, index[n_owned] their places; out[n_global][nf] on the root.  `which` selects the record as in
+ * wai_get_fluid, with the same refusal.  The columns are packed on the device: nothing but the root's result
+ * reaches a host. */
+int wai_gather_rows(wai_ctx *ctx, int root, int ncomp, const double *local, int n_local, const int *index,
+                    int n_global, double *out);
+int wai_gather_fluid(wai_ctx *ctx, int root, int which, int nf, const int *fields, const int *index, int n_global,
+                     double *out);
+
 /* ---- ode_type surface (src/ode.F90:39-108 as overridden by src/flow_simulation.F90) ------ */
 int wai_pre_timestep(wai_ctx *ctx);                 /* flow_simulation.F90:2022-2035 */
 int wai_pre_retry_timestep(wai_ctx *ctx);           /* :2093-2104 */

@@ -11,6 +11,9 @@ extern "C" {
 /* collectives enqueued on this rank so far: all-reduces (Krylov inner products, flags, norms) and
  * neighbour exchanges (halos); a BiCGStab iteration costs 2 all-reduces and 2 exchanges */
 int wai_comm_stats(wai_ctx *ctx, long long *allreduces, long long *exchanges);
+/* gathers to a root enqueued on this rank so far (wai_gather_rows, wai_gather_fluid on more than one rank: one each; the
+ * all-reduce of the row counts inside each is counted by wai_comm_stats) */
+int wai_gather_stats(wai_ctx *ctx, long long *gathers);
 /* kernels launched and copies enqueued by the linear-solver helpers so far (SpMV, preconditioner, vector
  * updates, reductions, halo pack / unpack, scalar read-backs): a BiCGStab iteration on one rank is 3 kernels (2 x 2 and
  * 3 x 3 blocks: the second fused launch forms its operand itself; 4 with a stored S), on several ranks 7,

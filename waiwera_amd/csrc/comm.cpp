@@ -11,6 +11,8 @@
 // reused instead of a second one.
 #include "comm.hpp"
 #include <dlfcn.h>
+#include <algorithm>
+#include <vector>
 #include <cstdlib>
 #include <cstring>
 
@@ -132,6 +134,58 @@ int comm_exchange(Comm* c, int n_nbr, const int* nbr_rank, const int* send_ptr, 
   }
   const int r2 = g_api.GroupEnd();
   if (r || r2) { err = g_api.GetErrorString(r ? r : r2); return -1; }
+  return 0;
+}
+
+// Gather of row slabs to a root, from the entry points the library binds already: one all-reduce of the row counts, then
+// grouped ncclSend / ncclRecv.  Only doubles travel: a caller with integers to send (wai_gather_rows' places) puts them
+// into the rows as doubles, exact below 2^53.  A slab goes in messages of at most kGatherPiece doubles, one group per
+// round, so that a transport with bounded mailboxes (tests/loopback_rccl: 512 KB per pair and group) carries any size;
+// all ranks know all counts and walk the same rounds.
+constexpr size_t kGatherPiece = (size_t)1 << 16;
+
+int comm_gatherv(Comm* c, int root, const double* sendbuf, size_t rows, int width, double* counts, long long* h_counts,
+                 const std::function<double*(size_t)>& recvbuf, hipStream_t stream, std::string& err) {
+  if (!c || c->nranks == 1) { h_counts[0] = (long long)rows; return 0; }
+  const int nr = c->nranks, me = c->rank;
+  c->n_gather++;
+  std::vector<double> h(nr, 0.0);
+  h[me] = (double)rows;
+  auto hip_ok = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    err = std::string(what) + ": " + hipGetErrorString(e);
+    return false;
+  };
+  if (!hip_ok(hipMemcpyAsync(counts, h.data(), nr * sizeof(double), hipMemcpyHostToDevice, stream), "comm_gatherv counts")) return -1;
+  if (comm_allreduce(c, counts, nr, 0, stream, err)) return -1;
+  if (!hip_ok(hipMemcpyAsync(h.data(), counts, nr * sizeof(double), hipMemcpyDeviceToHost, stream), "comm_gatherv counts")) return -1;
+  if (!hip_ok(hipStreamSynchronize(stream), "comm_gatherv counts")) return -1;
+  for (int r = 0; r < nr; r++) h_counts[r] = (long long)h[r];
+  if (c->mute) return 0;
+  std::vector<size_t> off(nr + 1, 0);
+  for (int r = 0; r < nr; r++) off[r + 1] = off[r] + (size_t)h_counts[r] * width;
+  double* rb = nullptr;
+  if (me == root) {
+    rb = recvbuf(off[nr] / width);
+    if (!rb) return -1;
+    if (rows && !hip_ok(hipMemcpyAsync(rb + off[me], sendbuf, rows * width * sizeof(double), hipMemcpyDeviceToDevice, stream),
+                        "comm_gatherv own slab"))
+      return -1;
+  }
+  size_t longest = 0;
+  for (int r = 0; r < nr; r++) if (r != root) longest = std::max(longest, off[r + 1] - off[r]);
+  for (size_t at = 0; at < longest; at += kGatherPiece) {
+    int e = g_api.GroupStart();
+    for (int r = 0; r < nr && !e; r++) {
+      const size_t len = off[r + 1] - off[r];
+      if (r == root || at >= len || (me != root && me != r)) continue;
+      const size_t piece = std::min(kGatherPiece, len - at);
+      if (me == root) e = g_api.Recv(rb + off[r] + at, piece, kFloat64, r, c->handle, stream);
+      else e = g_api.Send(sendbuf + at, piece, kFloat64, root, c->handle, stream);
+    }
+    const int e2 = g_api.GroupEnd();
+    if (e || e2) { err = g_api.GetErrorString(e ? e : e2); return -1; }
+  }
   return 0;
 }
 

@@ -470,6 +470,20 @@ struct LinSys {
   bool net_blocks = false;   // the source network's coupling blocks E belong to its operator (the flow system only)
 };
 
+// Gather of output rows to one rank (wai_gather_rows, wai_gather_fluid; gather.hip).  Every buffer is sized on first use,
+// grown when a call needs more and kept: a run's snapshots ask for the same sizes every time.
+struct Gather {
+  DevBuf<double> in;      // a host `local` staged
+  DevBuf<double> send;    // [rows][ncomp + 1]: the packed rows, each followed by its place as a double
+  DevBuf<double> recv;    // root: every rank's slab, in rank order
+  DevBuf<double> out;     // root: a host `out` staged
+  DevBuf<double> counts;  // [nranks] row counts, all-reduced
+  DevBuf<int> idx;        // a host `index` staged
+  DevBuf<int> claim;      // root: [n_global] received row that took the place, -1: free
+  DevBuf<int> flag;       // root: [4] error code (0 none, 1 place out of range, 2 place claimed twice), place, the two received rows
+  size_t n_in = 0, n_send = 0, n_recv = 0, n_out = 0, n_counts = 0, n_idx = 0, n_claim = 0;   // elements each buffer holds
+};
+
 }  // namespace wai
 
 namespace wai {
@@ -524,6 +538,7 @@ struct wai_ctx : wai::Handles {
   wai::LuBlocks lu;
   wai::Krylov ks;
   wai::Tracers tr;
+  wai::Gather gat;
   wai::DevBuf<double> tr_bc, tr_inj, tr_rhsb;   // what tr.bc, tr.inj and tr.rhsb point to (Tracers is a kernel argument: views only)
   // fluid state, SoA df x n_local each; perturbed states np x df x n_prim
   wai::DevBuf<double> flu, flu_last_iter, flu_last_step, flu_pert;

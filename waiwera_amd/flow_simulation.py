@@ -60,6 +60,7 @@ class FlowSimulation:
         self.tracer_solve_mode = "per_tracer"
         self.sub_pc = "ilu"
         self.time = 0.0
+        self.rank, self.world = 0, 1      # comm_init: this rank in the library's communicator
         if mesh.n_bc:
             bp, br = _lib._f64(mesh.bc_primary), _lib._i32(mesh.bc_region)
             self._chk(LIB.wai_set_bc(h, bp.ctypes.data_as(_lib.pd), br.ctypes.data_as(_lib.pi)), "set_bc")
@@ -190,6 +191,7 @@ class FlowSimulation:
 
     def comm_init(self, rank, nranks, unique_id):
         self._chk(LIB.wai_comm_init(self.h, rank, nranks, unique_id), "comm_init")
+        self.rank, self.world = int(rank), int(nranks)
 
     def comm_size(self):
         return LIB.wai_comm_size(self.h)
@@ -198,6 +200,54 @@ class FlowSimulation:
         a, e = C.c_longlong(0), C.c_longlong(0)
         LIB.wai_comm_stats(self.h, C.byref(a), C.byref(e))
         return a.value, e.value
+
+    def gather_stats(self):
+        """gathers to a root enqueued on this rank so far (wai_gather_stats)"""
+        g = C.c_longlong(0)
+        LIB.wai_gather_stats(self.h, C.byref(g))
+        return g.value
+
+    @staticmethod
+    def _gather_out(out, n_global, ncomp, is_root):
+        """the root's result array: the caller's (numpy or torch, n_global x ncomp doubles) or a NaN-filled one -- a place
+        nobody sends stays NaN"""
+        if not is_root:
+            return None
+        if out is None:
+            out = np.full((int(n_global), int(ncomp)), np.nan)
+        return out
+
+    def gather_rows(self, local, index, n_global, root=0, out=None):
+        """wai_gather_rows (collective): this rank's rows local (n_local, ncomp) -- numpy or a torch device tensor -- to
+        out[index] on `root`; returns the (n_global, ncomp) array there (out, or a new one filled with NaN), None on the
+        other ranks"""
+        if hasattr(local, "data_ptr"):
+            loc, n_local = local, int(local.shape[0])
+            ncomp = int(local.numel() // max(n_local, 1)) if n_local else int(local.shape[1])
+        else:
+            loc = _lib._f64(local)
+            loc = loc[:, None] if loc.ndim == 1 else loc
+            if loc.ndim != 2 or loc.shape[1] < 1:
+                raise ValueError("local: (n_local, ncomp) rows")
+            n_local, ncomp = loc.shape
+        idx = _lib._i32(index)
+        if idx.size != n_local:
+            raise ValueError("one place per row: %d rows, %d places" % (n_local, idx.size))
+        res = self._gather_out(out, n_global, ncomp, self.rank == root)
+        self._chk(LIB.wai_gather_rows(self.h, int(root), int(ncomp), _lib.ptr(loc) if n_local else None, n_local,
+                                      idx.ctypes.data if n_local else None, int(n_global), _lib.ptr(res)), "gather_rows")
+        return res
+
+    def gather_fluid(self, fields, index, n_global, root=0, which=0, out=None):
+        """wai_gather_fluid (collective): columns `fields` of the fluid record of this rank's owned cells, packed on the
+        device, to out[index] on `root`; returns the (n_global, len(fields)) array there, None elsewhere"""
+        fl, idx = _lib._i32(fields), _lib._i32(index)
+        if idx.size != self.n_owned:
+            raise ValueError("one place per owned cell")
+        res = self._gather_out(out, n_global, fl.size, self.rank == root)
+        self._chk(LIB.wai_gather_fluid(self.h, int(root), int(which), fl.size, fl.ctypes.data_as(_lib.pi), idx.ctypes.data,
+                                       int(n_global), _lib.ptr(res)), "gather_fluid")
+        return res
 
     def mute_comm(self, on):
         """timing probe: collectives return without calling RCCL (every rank together)"""

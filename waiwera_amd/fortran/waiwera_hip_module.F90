@@ -428,6 +428,28 @@ module waiwera_hip_module
        real(c_double), intent(in out) :: vec(*)
        integer(c_int), value :: dof
      end function wai_halo_exchange
+     ! gathers to one rank (the output file of a run on N ranks; collective).  local: n_local rows of ncomp doubles,
+     ! index: each row's 0-based place in the result; on root out(ncomp, n_global) receives every rank's rows and keeps
+     ! what it held where nobody sent (fill it with NaN to see a hole); elsewhere out is ignored.  n_local = 0 is legal
+     integer(c_int) function wai_gather_rows(ctx, root, ncomp, local, n_local, index, n_global, out) &
+          bind(c, name = "wai_gather_rows")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: root, ncomp, n_local, n_global
+       real(c_double), intent(in) :: local(*)
+       integer(c_int), intent(in) :: index(*)
+       real(c_double), intent(in out) :: out(*)
+     end function wai_gather_rows
+     ! the same from the device-resident fluid record: columns fields(1:nf) (0-based, as wai_get_fluid lays a cell's
+     ! record out) of the owned cells, index(n_owned) their places; which as wai_get_fluid; out(nf, n_global) on root
+     integer(c_int) function wai_gather_fluid(ctx, root, which, nf, fields, index, n_global, out) &
+          bind(c, name = "wai_gather_fluid")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: root, which, nf, n_global
+       integer(c_int), intent(in) :: fields(*), index(*)
+       real(c_double), intent(in out) :: out(*)
+     end function wai_gather_fluid
      integer(c_int) function wai_jacobian_set_values(ctx, val) bind(c, name = "wai_jacobian_set_values")
        import :: c_int, c_ptr, c_double
        type(c_ptr), value :: ctx
@@ -568,6 +590,7 @@ module waiwera_hip_module
   public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc, wai_set_aux_pc, wai_get_aux_pc
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
+  public :: wai_gather_rows, wai_gather_fluid
   public :: wai_default_eos, wai_default_opts, wai_set_bc, wai_set_sources, wai_update_sources, wai_set_source_controls, wai_get_source_rates, wai_separator_enthalpies, wai_set_regions, &
        wai_get_regions, wai_jacobian_nnzb, wai_jacobian_pattern, wai_jacobian_get_values
 

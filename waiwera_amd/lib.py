@@ -145,6 +145,9 @@ def _load():
         "wai_halo_exchange": (i32, [vp, vp, i32]),
         "wai_comm_size": (i32, [vp]),
         "wai_comm_stats": (i32, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+        "wai_gather_stats": (i32, [vp, C.POINTER(C.c_longlong)]),
+        "wai_gather_rows": (i32, [vp, i32, i32, vp, i32, vp, i32, vp]),
+        "wai_gather_fluid": (i32, [vp, i32, i32, i32, pi, vp, i32, vp]),
         "wai_launch_stats": (i32, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "wai_bench_mute_comm": (i32, [vp, i32]),
         "wai_test_drop_partials": (i32, [vp, i32]),

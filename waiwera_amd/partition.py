@@ -56,11 +56,25 @@ def family_owner(lm, world, owner=None):
     return stored
 
 
+def face_owner(face_cells, owner):
+    """The rank that contributes each face of a one-rank mesh to a gathered face array: the owner of the face's cell 1.  A
+    face between two ranks exists on both -- each computes the flux through it (module docstring) -- so exactly one of them
+    must send it.  A boundary face (its other cell a Dirichlet boundary cell, numbered from owner.size on) goes with its
+    interior cell, whichever side that is.  Pure: face_cells (n_faces, 2) of the whole mesh, owner per cell."""
+    fc = np.asarray(face_cells, dtype=np.int64).reshape(-1, 2)
+    owner = np.asarray(owner, dtype=np.int64)
+    n = owner.size
+    if fc.size and (fc.min(axis=1) >= n).any():
+        raise ValueError("face %d joins two boundary cells" % int(np.nonzero(fc.min(axis=1) >= n)[0][0]))
+    return owner[np.where(fc[:, 0] < n, fc[:, 0], fc[:, 1])]
+
+
 def partition_mesh(lm, owner, rank, chunk=512, world=None):
     """(LocalMesh of `rank`, gid) from the one-rank LocalMesh `lm` and owner[cell] in 0 .. world - 1.
 
     gid: the one-rank index of every local owned-or-ghost cell (initial states, regions and results are gathered with it;
-    also LocalMesh.extras["prim_gid"]).  Preconditioner subdomains: the one-rank mesh's subdomains cut at the ownership
+    also LocalMesh.extras["prim_gid"]).  Faces: extras["face_gid"] (index in the one-rank face list), ["face_flip"] (local
+    orientation reversed against it) and ["face_owned"] (this rank contributes the face: face_owner).  Preconditioner subdomains: the one-rank mesh's subdomains cut at the ownership
     boundaries, then chunks of at most `chunk` consecutive owned cells."""
     if lm.n_halo:
         raise ValueError("partition_mesh wants a one-rank mesh")
@@ -108,6 +122,12 @@ def partition_mesh(lm, owner, rank, chunk=512, world=None):
     assert (m.face_cells >= 0).all()
     m.face_geom = np.asarray(lm.face_geom).reshape(-1, 12)[keep].copy()
     m.n_faces = int(keep.sum())
+    # the global identity of every local face: its index in the one-rank mesh's face list, and whether the local orientation
+    # is reversed against that mesh's cell 1 -> cell 2 (never, here: the faces keep their orientation; a builder that
+    # reorders a face's cells says so, and whoever gathers a flux applies the sign).  face_owned: the faces this rank sends
+    m.extras["face_gid"] = np.nonzero(keep)[0]
+    m.extras["face_flip"] = np.zeros(m.n_faces, dtype=bool)
+    m.extras["face_owned"] = face_owner(fc, owner)[keep] == rank
     sel = np.concatenate([mine, ghosts, bcs])
     m.cell_geom = np.asarray(lm.cell_geom)[sel].copy()
     m.rock = np.asarray(lm.rock)[sel].copy()

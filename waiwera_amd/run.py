@@ -8,7 +8,8 @@ Several ranks, one per GPU (the reference: mpiexec -np N waiwera input.json):
 every rank reads the whole input and keeps its own cells (waiwera_amd/partition.py); -o writes one file per rank
 (results.rank<r>.npz: the rank's cell fields -- tracers among them -- with `owned_gid`, the cells' numbers in the one-rank
 output, its sources' fields with `owned_source`, their numbers in the input, and the network's group and reinjector fields,
-the same in every file).  The input's own "output.filename" is not written on several ranks."""
+the same in every file).  The input's own "output.filename" is written once, by rank 0, from snapshots gathered through
+the library (waiwera_amd/simulation.py); a failure to write it is rank 0's exit status."""
 import argparse
 import sys
 

@@ -49,15 +49,17 @@ writes a .npz archive.
 
 N ranks (rank, world, comm_id; one process per rank, python -m waiwera_amd.run under a launcher): every rank reads the
 whole input, builds the whole mesh -- MINC cells included -- and keeps its cells with one ghost layer
-(waiwera_amd/partition.py).  Covered: everything above but the output file -- sources with their tables and
+(waiwera_amd/partition.py).  Covered: everything above -- sources with their tables and
 state-dependent controls, MINC zones (a family never leaves its fracture cell's rank), rock table controls (each rank
 updates the controlled cells it holds, ghosts included), tracers in both solve modes (boundary values through the rank's
 boundary cells, injection through its sources) and source networks (every rank holds the whole network, its sources
 numbered as in the input; the library gathers their rates).  fields() returns the rank's cells, owned_gid their numbers
 in the one-rank output (the input's numbering; a MINC mesh: the reference's cell order), source fields the rank's own
-sources with owned_source their numbers in the input, group and reinjector fields the same on every rank.  NOT on
-N ranks: "output.filename" is skipped there without a message -- the library has no gather of host data; save() /
-python -m waiwera_amd.run -o write one .npz per rank instead -- and PCASM overlap deeper than 1, which the library refuses.
+sources with owned_source their numbers in the input, group and reinjector fields the same on every rank.
+"output.filename" on N ranks: every snapshot is gathered to rank 0 through the library (_gathered_fields: wai_gather_fluid
+for the fluid record's columns, wai_gather_rows for geometry, tracers, source and flux fields), rank 0 writes the file a
+one-rank run writes and carries output_error; save() / python -m waiwera_amd.run -o still write one .npz per rank.  NOT on
+N ranks: PCASM overlap deeper than 1, which the library refuses.
 Collective-call discipline: nothing that exchanges data stands under a condition that can differ
 between ranks; what must be refused is refused from the input and the arguments alone, so on every rank alike.
 """
@@ -317,6 +319,46 @@ def network_spec(inp, interval, separator_enthalpies=None):
     return spec, names, timed[0]
 
 
+def face_output(face_cells, n_prim, n_bc, bc_spec, area):
+    """(face_cell_1, face_cell_2, face_geometry_area) of an output file from a mesh's faces: a face's second cell that is a
+    Dirichlet boundary cell (numbered from n_prim on) reads -1 - the index of the boundary specification it belongs to"""
+    fc = np.asarray(face_cells).reshape(-1, 2)
+    c2 = fc[:, 1].astype(np.int64)
+    bnd = c2 >= n_prim
+    spec = np.asarray(bc_spec)
+    c2 = np.where(bnd, -1 - spec[np.clip(c2 - n_prim, 0, max(n_bc - 1, 0))], c2) if spec.size else c2
+    return fc[:, 0].copy(), c2, np.asarray(area).copy()
+
+
+def output_datasets(outs, n_cells, minc_level=None, minc_parent=None):
+    """The datasets of an output file in the reference's layout from a list of snapshots (dicts as Simulation.fields()
+    returns them, each of the same n_cells cells): /time, /cell_index, /cell_fields/*, /source_fields/* (sources and network
+    nodes), /face_fields/* with /face_cell_1 and /face_cell_2, and -- given the MINC level and parent of every cell in the
+    output's cell order (flow_simulation_output_minc_data, src/flow_simulation.F90:2625-2691: level 0 a fracture or
+    single-porosity cell, parent the natural index of the original cell) -- /minc/level and /minc/parent.  Pure: no
+    library, no file; one rank and the root of N ranks build the file's contents here."""
+    data = {"/time": np.array([[o["time"]] for o in outs]), "/cell_index": np.arange(n_cells, dtype=np.int32)[:, None]}
+    if minc_level is not None:
+        data["/minc/level"] = np.asarray(minc_level).astype(np.int32)[:, None]
+        data["/minc/parent"] = np.asarray(minc_parent).astype(np.int32)[:, None]
+    for k in outs[0]:
+        if k == "time":
+            continue
+        if k.startswith("source_") or k.startswith("network_"):
+            data["/source_fields/" + k] = np.stack([o[k] for o in outs])
+        elif k.startswith("flux_"):
+            data["/face_fields/" + k] = np.stack([o[k] for o in outs])
+        elif k.startswith("face_geometry"):
+            data["/face_fields/" + k] = outs[0][k]
+        elif k.startswith("face_cell_"):
+            data["/" + k] = np.asarray(outs[0][k], dtype=np.int32)[:, None]
+        elif k.startswith("cell_geometry"):
+            data["/cell_fields/" + k] = outs[0][k]
+        else:
+            data["/cell_fields/" + k] = np.stack([o[k] for o in outs])
+    return data
+
+
 class Simulation:
     """One Waiwera input file -> mesh, flow simulation object and time stepper."""
 
@@ -520,12 +562,23 @@ class Simulation:
             own = family_owner(lm, self.world, owner)
             if self._order is not None:
                 self._cell_index = np.asarray(lm.extras["fracture_index"])
+            # what the output file takes from the whole mesh, which every rank has built anyway: sizes, the faces' cells and
+            # areas, MINC level and parent in the output's order.  Not gathered (_gathered_fields)
+            wo = self._order
+            self._whole = dict(
+                n_cells=lm.n_owned, n_bc=lm.n_bc, n_faces=lm.n_faces, face_cells=np.asarray(lm.face_cells).reshape(-1, 2).copy(),
+                face_area=np.asarray(lm.face_geom).reshape(-1, 12)[:, 0].copy(),
+                bc_spec=np.asarray(lm.extras.get("bc_spec", np.zeros(lm.n_bc, dtype=np.int64))),
+                minc=None if wo is None else (np.asarray(lm.extras["minc_level"])[wo], np.asarray(lm.extras["minc_parent"])[wo]))
             lm, self._gid = partition_mesh(lm, own, self.rank, world=self.world)
             # owned_gid: the rank's cells as the one-rank run's output numbers them -- the input's numbering; on a MINC mesh
             # the reference's order (the input's cells, then the matrix cells level by level), in which fields() lists them
             self.owned_gid = lm.owned_gid
             if self._order is not None:
                 self._order, self.owned_gid = lm.extras["waiwera_order"], lm.extras["waiwera_gid"]
+            # the place of every owned cell, in the rank's own (storage) order, in the one-rank output: what the gathers are keyed by
+            self._cell_place = np.empty(lm.n_owned, dtype=np.int32)
+            self._cell_place[np.arange(lm.n_owned) if self._order is None else self._order] = self.owned_gid
             # everything per source goes through _src_pick: the rank's sources as their numbers in the input, in the rank's order
             self._src_pick = lm.extras.get("src_global_index", np.zeros(0, dtype=np.int32))
             self._tables = self._pick_sources(self._tables)
@@ -917,27 +970,37 @@ class Simulation:
     def run(self):
         """timestepper_run with the output schedule of "output" (initial / frequency / final,
         src/timestepper.F90:2478-2560); returns the final cell fields under the reference's names
-        and, if "output.filename" is given (and the HDF5 library is there), writes that file"""
+        and, if "output.filename" is given (and the HDF5 library is there), writes that file -- on several ranks rank 0
+        does, from snapshots gathered through the library (the returned fields stay the rank's own)"""
         self._pre_eval(self.ts.time)
         if self.X is not None:
             self.ts.init_auxiliary()
         oc = self.inp.get("output")
         oc = {} if oc in (None, True) else ({"frequency": 0, "initial": False, "final": False} if oc is False else oc)
         freq, self.outputs = oc.get("frequency", 1), []
+        # Several ranks and an output file: every snapshot is a collective gather to rank 0 (_gathered_fields), which keeps the
+        # list and writes the file; the other ranks keep nothing.  Whether a snapshot is taken depends on the input and the
+        # step history alone, the same on every rank -- never on what a rank holds or on whether its HDF5 library loads
+        gathered = self._gathered = self.world > 1 and bool(oc.get("filename"))
+
+        def snapshot():
+            f = self._gathered_fields() if gathered else self.fields()
+            if f is not None:
+                self.outputs.append(f)
         if oc.get("initial", True):
-            self.outputs.append(self.fields())
+            snapshot()
         try:
             while not self.ts.finished:
                 self.ts.step()
                 hit = self.ts.checkpoint_hit
                 if hit or (freq and self.ts.taken % freq == 0) or (self.ts.finished and oc.get("final", True)):
-                    self.outputs.append(self.fields())
+                    snapshot()
                 if hit:
                     self.ts.checkpoint_update()
         finally:
             # the reference keeps what it has written when a step aborts; a file that cannot be written
-            # is reported, not swallowed (the results are still returned)
-            if oc.get("filename") and self.outputs and self.world == 1:     # (several ranks: no output file yet; fields())
+            # is reported, not swallowed (the results are still returned).  Several ranks: rank 0 holds the snapshots
+            if oc.get("filename") and self.outputs and (self.world == 1 or self.rank == 0):
                 try:
                     self.save_hdf5(os.path.join(self.output_dir, oc["filename"]))
                 except Exception as e:
@@ -946,35 +1009,137 @@ class Simulation:
                     print("waiwera_amd: output file %r not written: %s" % (oc["filename"], e), file=sys.stderr)
         return self.fields()
 
+    def datasets(self):
+        """{HDF5 path: array} of the collected snapshots (output_datasets), or of the state in force when there are none.
+        Several ranks: the snapshots gathered on rank 0 by a run with "output.filename"; None on a rank that holds none"""
+        outs = getattr(self, "outputs", None)
+        if self.world > 1:
+            if not outs or not getattr(self, "_gathered", False):
+                return None
+            minc = self._whole["minc"]
+            return output_datasets(outs, self._whole["n_cells"], *(minc or ()))
+        outs = outs or [self.fields()]
+        if self._order is None:
+            return output_datasets(outs, self.mesh.n_owned)
+        ex = self.mesh.extras
+        return output_datasets(outs, self.mesh.n_owned, np.asarray(ex["minc_level"])[self._order], np.asarray(ex["minc_parent"])[self._order])
+
     def save_hdf5(self, path):
-        """the collected outputs in the reference's layout: /time, /cell_index, /cell_fields/*,
-        /source_fields/source_rate and source_enthalpy, /minc/level and /minc/parent of a MINC mesh"""
+        """the collected outputs in the reference's layout (output_datasets) written through waiwera_amd.hdf5io"""
         from . import hdf5io
-        outs = getattr(self, "outputs", None) or [self.fields()]
-        n = self.mesh.n_owned
-        data = {"/time": np.array([[o["time"]] for o in outs]), "/cell_index": np.arange(n, dtype=np.int32)[:, None]}
-        if self._order is not None:
-            # flow_simulation_output_minc_data (src/flow_simulation.F90:2625-2691): per cell, in the output's cell
-            # order, its MINC level (0: fracture or single-porosity cell) and the natural index of the original cell
-            ex = self.mesh.extras
-            data["/minc/level"] = np.asarray(ex["minc_level"])[self._order].astype(np.int32)[:, None]
-            data["/minc/parent"] = np.asarray(ex["minc_parent"])[self._order].astype(np.int32)[:, None]
-        for k in outs[0]:
-            if k == "time":
-                continue
-            if k.startswith("source_") or k.startswith("network_"):
-                data["/source_fields/" + k] = np.stack([o[k] for o in outs])
-            elif k.startswith("flux_"):
-                data["/face_fields/" + k] = np.stack([o[k] for o in outs])
-            elif k.startswith("face_geometry"):
-                data["/face_fields/" + k] = outs[0][k]
-            elif k.startswith("face_cell_"):
-                data["/" + k] = np.asarray(outs[0][k], dtype=np.int32)[:, None]
-            elif k.startswith("cell_geometry"):
-                data["/cell_fields/" + k] = outs[0][k]
-            else:
-                data["/cell_fields/" + k] = np.stack([o[k] for o in outs])
+        data = self.datasets()
+        if data is None:
+            raise RuntimeError("no gathered snapshots on rank %d of %d: run() with \"output.filename\" collects them on rank 0" % (self.rank, self.world))
         hdf5io.write_file(path, data)
+
+    def _fluid_columns(self):
+        """[(output field, column of the fluid record)] of the cell fields taken from the fluid vector, in fields()' order"""
+        nc = {"w": 1, "we": 1, "wce": 2, "wse": 2, "wae": 2, "wsce": 3, "wsae": 3}[self.eos]
+        f0, pd = 6 + nc, 7 + nc
+        cols = [("fluid_pressure", 0), ("fluid_temperature", 1), ("fluid_region", 2), ("fluid_liquid_saturation", f0 + 2),
+                ("fluid_liquid_density", f0)]
+        if self.eos != "w":
+            cols += [("fluid_vapour_saturation", f0 + pd + 2), ("fluid_vapour_density", f0 + pd)]
+        if self.eos in ("wse", "wsce", "wsae"):
+            cols += [("fluid_liquid_salt_mass_fraction", f0 + 8), ("fluid_solid_saturation", f0 + 2 * pd + 2)]
+        if self.eos in ("wsce", "wsae"):
+            gas = "CO2" if self.eos == "wsce" else "air"
+            cols += [("fluid_%s_partial_pressure" % gas, 8), ("fluid_liquid_%s_mass_fraction" % gas, f0 + 9),
+                     ("fluid_vapour_%s_mass_fraction" % gas, f0 + pd + 9)]
+        if self.eos in ("wce", "wae"):
+            gas = "CO2" if self.eos == "wce" else "air"
+            cols += [("fluid_%s_partial_pressure" % gas, 7), ("fluid_liquid_%s_mass_fraction" % gas, f0 + 8),
+                     ("fluid_vapour_%s_mass_fraction" % gas, f0 + pd + 8)]
+        return cols
+
+    def _flux_names(self):
+        """(names of the flux vector's columns, those "output.fields.flux" asks for) -- src/flow_simulation.F90:460-504"""
+        oc = self.inp.get("output")
+        want = ((oc.get("fields") if isinstance(oc, dict) else None) or {}).get("flux") or []
+        comps = {"w": ["water"], "we": ["water", "energy"], "wce": ["water", "CO2", "energy"],
+                 "wae": ["water", "air", "energy"], "wse": ["water", "salt", "energy"],
+                 "wsce": ["water", "salt", "CO2", "energy"], "wsae": ["water", "salt", "air", "energy"]}[self.eos]
+        names = comps + (["liquid"] if self.eos == "w" else ["liquid", "vapour"])
+        return names, (names if want == "all" or "all" in want else list(want))
+
+    def _gathered_fields(self):
+        """One snapshot of a run on several ranks, gathered to rank 0 through the library (wai_gather_fluid,
+        wai_gather_rows): fields() of the WHOLE mesh there, None on the other ranks.  COLLECTIVE: every rank makes every
+        call below, in this order, whatever it holds -- each condition reads the input alone.
+        Cell fields are keyed by the cells' places in the one-rank output, source fields by the sources' numbers in the
+        input, flux fields by face_gid (each face from the rank that owns it, partition.face_owner; the sign turned where
+        face_flip says the local orientation is reversed).  The network's nodes are the same on every rank and are taken
+        from rank 0; cell indices, MINC levels, the faces' cells and areas come from the whole mesh (self._whole)."""
+        ode, W, n, root = self.ode, self._whole, self.mesh.n_owned, self.rank == 0
+        self.ode.pre_eval(self.ts.time, self.y)
+        cols = self._fluid_columns()
+        F = ode.gather_fluid([c for _, c in cols], self._cell_place, W["n_cells"])
+        # geometry and tracers: host rows of the owned cells, in the rank's own order like the places
+        geom = np.asarray(self.mesh.cell_geom)[:n]
+        rows = [geom[:, : self.dim], geom[:, 3:4]] + ([self.X.reshape(n, -1)] if self.X is not None else [])
+        G = ode.gather_rows(np.hstack(rows), self._cell_place, W["n_cells"])
+        out = None
+        if root:
+            out = {"time": self.ts.time}
+            for k, (name, _) in enumerate(cols[:5]):
+                out[name] = F[:, k].copy()
+            out["cell_geometry_centroid"], out["cell_geometry_volume"] = G[:, : self.dim].copy(), G[:, self.dim].copy()
+            for k, (name, _) in enumerate(cols[5:]):
+                out[name] = F[:, 5 + k].copy()
+            for k, name in enumerate(self.tracer_names if self.X is not None else []):
+                out["tracer_" + name] = G[:, self.dim + 1 + k].copy()
+        oc = self.inp.get("output")
+        want = (oc.get("fields") if isinstance(oc, dict) else None) or {}
+        ns = len(self.inp.get("source", []) or [])
+        together = bool(self.network_names["group"] or self.network_names["reinject"])
+        sep_names = ("water_rate", "water_enthalpy", "steam_rate", "steam_enthalpy")
+        src_want = want.get("source") or []
+        if ns:      # the input has sources: every rank gathers, with the rows of its own -- none on a rank without
+            names = ["source_rate", "source_enthalpy"]
+            loc = list(ode.source_rates(together))
+            if any(k in src_want for k in sep_names):
+                sep = ode.source_separated(together)
+                for j, k in enumerate(sep_names):
+                    if k in src_want:
+                        names.append("source_" + k)
+                        loc.append(sep[:, j])
+            S = ode.gather_rows(np.stack(loc, axis=1).reshape(self.mesh.n_src, len(names)), self.owned_source, ns)
+            if root:
+                out["source_rate"], out["source_enthalpy"] = S[:, 0].copy(), S[:, 1].copy()
+        fnames, fwant = self._flux_names()
+        if fwant:
+            ex = self.mesh.extras
+            own = np.asarray(ex["face_owned"], dtype=bool)
+            fx = ode.fluxes()[:, [fnames.index(nm) for nm in fwant]]
+            fx = np.where(np.asarray(ex["face_flip"], dtype=bool)[:, None], -fx, fx)[own]
+            X = ode.gather_rows(fx.reshape(int(own.sum()), len(fwant)), np.asarray(ex["face_gid"])[own], W["n_faces"])
+            if root:
+                for k, nm in enumerate(fwant):
+                    out["flux_" + nm] = X[:, k].copy()
+                out["face_cell_1"], out["face_cell_2"], out["face_geometry_area"] = \
+                    face_output(W["face_cells"], W["n_cells"], W["n_bc"], W["bc_spec"], W["face_area"])
+        if root and ns:      # (the separated flows stand behind the face fields, as in fields())
+            for k, name in enumerate(names[2:]):
+                out[name] = S[:, 2 + k].copy()
+        if root and together:
+            out.update(self._network_fields(want))
+        return out
+
+    def _network_fields(self, want):
+        """the source network's group and reinjector fields after the last pass"""
+        out = {}
+        G, R = self.ode.source_network()
+        gcols = ("rate", "enthalpy", "water_rate", "water_enthalpy", "steam_rate", "steam_enthalpy")
+        for k in (want.get("network_group") or []):
+            if k in gcols and len(G):
+                out["network_group_" + k] = G[:, gcols.index(k)].copy()
+        rcols = ("output_water_rate", "output_steam_rate", "overflow_rate", "overflow_enthalpy", "overflow_water_rate",
+                 "overflow_water_enthalpy", "overflow_steam_rate", "overflow_steam_enthalpy")
+        for k in (want.get("network_reinject") or ["output_water_rate", "output_steam_rate", "overflow_water_rate",
+                                                   "overflow_steam_rate"]):
+            if k in rcols and len(R):
+                out["network_reinject_" + k] = R[:, rcols.index(k)].copy()
+        return out
 
     def fields(self):
         n = self.mesh.n_owned
@@ -983,29 +1148,13 @@ class Simulation:
         geom = self.mesh.cell_geom[:n]
         if self._order is not None:      # MINC: the reference's cell order (original cells, then level by level)
             fl, geom = fl[self._order], geom[self._order]
-        nc = {"w": 1, "we": 1, "wce": 2, "wse": 2, "wae": 2, "wsce": 3, "wsae": 3}[self.eos]
-        f0, pd = 6 + nc, 7 + nc
-        out = {"time": self.ts.time, "fluid_pressure": fl[:, 0].copy(), "fluid_temperature": fl[:, 1].copy(),
-               "fluid_region": fl[:, 2].copy(), "fluid_liquid_saturation": fl[:, f0 + 2].copy(),
-               "fluid_liquid_density": fl[:, f0].copy(),
-               "cell_geometry_centroid": geom[:, : self.dim].copy(),
-               "cell_geometry_volume": geom[:, 3].copy()}
-        if self.eos != "w":
-            out["fluid_vapour_saturation"] = fl[:, f0 + pd + 2].copy()
-            out["fluid_vapour_density"] = fl[:, f0 + pd].copy()
-        if self.eos in ("wse", "wsce", "wsae"):
-            out["fluid_liquid_salt_mass_fraction"] = fl[:, f0 + 8].copy()
-            out["fluid_solid_saturation"] = fl[:, f0 + 2 * pd + 2].copy()
-        if self.eos in ("wsce", "wsae"):
-            gas = "CO2" if self.eos == "wsce" else "air"
-            out["fluid_%s_partial_pressure" % gas] = fl[:, 8].copy()
-            out["fluid_liquid_%s_mass_fraction" % gas] = fl[:, f0 + 9].copy()
-            out["fluid_vapour_%s_mass_fraction" % gas] = fl[:, f0 + pd + 9].copy()
-        if self.eos in ("wce", "wae"):
-            gas = "CO2" if self.eos == "wce" else "air"
-            out["fluid_%s_partial_pressure" % gas] = fl[:, 7].copy()
-            out["fluid_liquid_%s_mass_fraction" % gas] = fl[:, f0 + 8].copy()
-            out["fluid_vapour_%s_mass_fraction" % gas] = fl[:, f0 + pd + 8].copy()
+        cols = self._fluid_columns()
+        out = {"time": self.ts.time}
+        for name, col in cols[:5]:
+            out[name] = fl[:, col].copy()
+        out["cell_geometry_centroid"], out["cell_geometry_volume"] = geom[:, : self.dim].copy(), geom[:, 3].copy()
+        for name, col in cols[5:]:
+            out[name] = fl[:, col].copy()
         if self.X is not None:
             for k, name in enumerate(self.tracer_names):
                 xk = self.X.reshape(n, -1)[:, k]
@@ -1020,22 +1169,14 @@ class Simulation:
         want = (oc.get("fields") if isinstance(oc, dict) else None) or {}
         # face fields: "output.fields.flux" (src/flow_simulation.F90:460-504): the flux vector's
         # components and phases by name, per unit area, positive from face_cell_1 to face_cell_2
-        flux_names = want.get("flux") or []
+        names, flux_names = self._flux_names()
         if flux_names and hasattr(self.ode, "fluxes"):
-            comps = {"w": ["water"], "we": ["water", "energy"], "wce": ["water", "CO2", "energy"],
-                     "wae": ["water", "air", "energy"], "wse": ["water", "salt", "energy"],
-                     "wsce": ["water", "salt", "CO2", "energy"], "wsae": ["water", "salt", "air", "energy"]}[self.eos]
-            names = comps + (["liquid"] if self.eos == "w" else ["liquid", "vapour"])
             fx = self.ode.fluxes()
-            for nm in (names if flux_names == "all" or "all" in flux_names else flux_names):
+            for nm in flux_names:
                 out["flux_" + nm] = fx[:, names.index(nm)].copy()
-            fc = np.asarray(self.mesh.face_cells)
-            c2 = fc[:, 1].astype(np.int64)
-            bnd = c2 >= self.mesh.n_owned + self.mesh.n_halo
-            spec = np.asarray(self.mesh.extras.get("bc_spec", np.zeros(self.mesh.n_bc, dtype=np.int64)))
-            c2 = np.where(bnd, -1 - spec[np.clip(c2 - self.mesh.n_owned - self.mesh.n_halo, 0, max(self.mesh.n_bc - 1, 0))], c2)
-            out["face_cell_1"], out["face_cell_2"] = fc[:, 0].copy(), c2
-            out["face_geometry_area"] = np.asarray(self.mesh.face_geom)[:, 0].copy()
+            out["face_cell_1"], out["face_cell_2"], out["face_geometry_area"] = face_output(
+                self.mesh.face_cells, self.mesh.n_owned + self.mesh.n_halo, self.mesh.n_bc,
+                self.mesh.extras.get("bc_spec", np.zeros(self.mesh.n_bc, dtype=np.int64)), np.asarray(self.mesh.face_geom)[:, 0])
         # separated water / steam flows of the sources and the source network's nodes
         src_want = want.get("source") or []
         if (self.mesh.n_src or together) and hasattr(self.ode, "source_separated") and \
@@ -1046,17 +1187,7 @@ class Simulation:
                     out["source_" + k] = sep[:, j].copy()
         if getattr(self, "network_names", None) and hasattr(self.ode, "source_network") and \
                 (self.network_names["group"] or self.network_names["reinject"]):
-            G, R = self.ode.source_network()
-            gcols = ("rate", "enthalpy", "water_rate", "water_enthalpy", "steam_rate", "steam_enthalpy")
-            for k in (want.get("network_group") or []):
-                if k in gcols and len(G):
-                    out["network_group_" + k] = G[:, gcols.index(k)].copy()
-            rcols = ("output_water_rate", "output_steam_rate", "overflow_rate", "overflow_enthalpy", "overflow_water_rate",
-                     "overflow_water_enthalpy", "overflow_steam_rate", "overflow_steam_enthalpy")
-            for k in (want.get("network_reinject") or ["output_water_rate", "output_steam_rate", "overflow_water_rate",
-                                                       "overflow_steam_rate"]):
-                if k in rcols and len(R):
-                    out["network_reinject_" + k] = R[:, rcols.index(k)].copy()
+            out.update(self._network_fields(want))
         return out
 
     def save(self, path):
