@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/waiwera_hip.h"
 #include "devbuf.hpp"
+#include "mesh_pattern.hpp"   // MAX_CELL_FACES
 #include "physics.hip.h"
 
 namespace wai {
@@ -57,10 +58,6 @@ __host__ __device__ __forceinline__ size_t ell_size(int bs, size_t n, int W) {
   if (bs >= 3) return (size_t)((W + 7) / 8) * 8 * bs * bs * ell_ld(n);
   return (size_t)W * bs * bs * ell_rows(bs, n);
 }
-
-// most faces of an owned cell (boundary faces included) and most blocks of a matrix row -- the cell itself and at most 15
-// neighbouring cells (include/waiwera_hip.h)
-constexpr int MAX_CELL_FACES = 16;
 
 enum KClass { KC_EOS = 0, KC_RESIDUAL = 1, KC_JACOBIAN = 2, KC_SPMV = 3, KC_PC_APPLY = 4,
               KC_PC_SETUP = 5, KC_VECTOR = 6, KC_TRANSITIONS = 7, KC_COUNT = 8 };
@@ -500,7 +497,7 @@ struct LuBlocks {
 int launch_lu_apply(wai_ctx* c, int bs, const double* r, double* z);
 
 // The streams, the events and the communicator of a context.  A base of wai_ctx, so that its destructor runs after the
-// members' -- every device buffer is released first, then the events and streams, then the communicator (capi.hip)
+// members' -- every device buffer is released first, then the events and streams, then the communicator (context.hip)
 struct Handles {
   hipStream_t stream = nullptr;
   Comm* comm = nullptr;

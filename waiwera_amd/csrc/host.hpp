@@ -1,6 +1,7 @@
-// Host-side internals of libwaiwera_hip.so shared by its translation units (capi.hip: context and ABI; pc_setup.hip:
-// symbolic phases and factorisations; krylov.hip: the Krylov drivers and the preconditioned operator; network.hip: the
-// source network; measure.hip: measurement entry points).  Not part of the ABI.
+// Host-side internals of libwaiwera_hip.so shared by its translation units (capi.hip: the ode_type hooks and the Newton
+// iteration; context.hip: the context and its set-up; sources.hip: sources and their controls; tracers.hip: the tracer
+// problem; pc_setup.hip: symbolic phases and factorisations; krylov.hip: the Krylov drivers and the preconditioned
+// operator; network.hip: the source network; measure.hip: measurement entry points).  Not part of the ABI.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -31,7 +32,22 @@ inline bool is_device_ptr(const void* p) {
   return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-// vector argument handling: device pointers pass through, host arrays are staged
+// The one place that decides a copy's direction.  One side is the caller's vector -- device or host memory, asked of the
+// runtime -- the other the library's device memory: n doubles on the context's stream, not synchronised.
+enum CopyDir { FROM_CALLER, TO_CALLER };
+inline int copy_vec(wai_ctx* c, double* dst, const double* src, size_t n, CopyDir dir, bool caller_on_device) {
+  const hipMemcpyKind kind = caller_on_device ? hipMemcpyDeviceToDevice : (dir == TO_CALLER ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
+  HIPCHK(c, hipMemcpyAsync(dst, src, n * sizeof(double), kind, c->stream));
+  return 0;
+}
+inline int copy_vec(wai_ctx* c, double* dst, const double* src, size_t n, CopyDir dir) {
+  return copy_vec(c, dst, src, n, dir, is_device_ptr(dir == TO_CALLER ? dst : src));
+}
+
+// the device flags' rest state (fetch_flags): flag 1 is a minimum
+inline constexpr int FLAGS_RESET[4] = {0, 0x7fffffff, 0, 0};
+
+// vector argument handling: device pointers pass through, host arrays are staged (asked once: the staged side is host memory)
 struct VecArg {
   wai_ctx* c; double* dev = nullptr; double* host = nullptr; size_t n = 0; bool staged = false;
   int in(const double* p, size_t n_, int slot) {
@@ -40,8 +56,7 @@ struct VecArg {
     if (is_device_ptr(p)) { dev = const_cast<double*>(p); return 0; }
     if (n > c->stage_len) { c->err = "vector longer than staging buffer"; return -1; }
     host = const_cast<double*>(p); dev = c->stage[slot]; staged = true;
-    HIPCHK(c, hipMemcpyAsync(dev, p, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return 0;
+    return copy_vec(c, dev, p, n, FROM_CALLER, false);
   }
   int out_only(double* p, size_t n_, int slot) {
     n = n_;
@@ -53,7 +68,7 @@ struct VecArg {
   }
   int back() {
     if (staged && host) {
-      HIPCHK(c, hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      if (copy_vec(c, host, dev, n, TO_CALLER, false)) return -1;
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return 0;
@@ -136,8 +151,12 @@ void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n);   // s
 int network_update(wai_ctx* c);
 int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old);
 int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t);   // t = A x, + E x where the source network's blocks belong to sys
-// ---- capi.hip ----------------------------------------------------------------------------------------------------
+// ---- context.hip -------------------------------------------------------------------------------------------------
+int alloc_krylov_vecs(wai_ctx* c, KrylovVecs& k, size_t nl);
+int ensure_basis(wai_ctx* c, LinSys& sys, int m);
 int ensure_bcgsl_vecs(wai_ctx* c, KrylovVecs& k, size_t nl);
+Bcsr matrix_on(const Pattern& p, int bs, double* val);
+// ---- capi.hip ----------------------------------------------------------------------------------------------------
 int fetch_flags(wai_ctx* c, int out[4]);
 int do_pre_eval(wai_ctx* c, double* y);
 int do_residual(wai_ctx* c, double dt, double* y, const double* lhs_old, double* f);
