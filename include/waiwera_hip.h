@@ -109,14 +109,21 @@ typedef struct wai_solver_opts {
                                   wai_default_opts sets WAI_PC_BJACOBI -- NOT the reference's default: Waiwera defaults to
                                   PCASM, overlap 1, sub-PC ILU(0) (default_flow_pc_type_str = "asm", src/timestepper.F90:2019-2020;
                                   one subdomain per rank, :1668-1669).  Block Jacobi over the mesh descriptor's subdomains is
-                                  the only preconditioner with a fused fast path here; WAI_PC_ASM runs the unfused
+                                  the only preconditioner with a fused fast path here -- with ILU(0), and with ILU(k > 0)
+                                  where the filled rows have at most 16 blocks (ilu_levels below); WAI_PC_ASM runs the unfused
                                   extended-system path (measured at 216^3: 74 Krylov iterations at 7.8 ms against 98 at 1.4 ms,
                                   profiles/pc_compare_r6.log).  A host that mirrors an unmodified Waiwera input sets WAI_PC_ASM
                                   itself (the JSON front end of waiwera_amd/simulation.py does) */
   int asm_overlap;             /* PCASM overlap, PETSc default 1; reaches one cell layer across rank boundaries (the
                                   partition-ghost cells' matrix rows come from their owners at every set-up) */
   int ilu_levels;              /* linear.sub_preconditioner.factor.levels (src/timestepper.F90:1716-1718, PCFactorSetLevels
-                                  :1827): levels of fill of the sub-preconditioner's ILU(k), default 0; with block Jacobi or PCASM */
+                                  :1827): levels of fill of the sub-preconditioner's ILU(k), default 0; with block Jacobi or PCASM.
+                                  Block Jacobi with k > 0 on the flow system is applied by one fused launch (k_pc_wide on the
+                                  filled factor) where every filled row of a subdomain has at most 16 blocks and every
+                                  subdomain at most 1024 rows, on a mesh of at most 8 blocks per row and one rank.  The
+                                  launch-per-level path serves the rest: wider fill, larger subdomains, meshes with cells of
+                                  more than 7 faces, PCASM, source-network blocks in the factor, the auxiliary systems,
+                                  several ranks */
 } wai_solver_opts;
 
 void wai_default_eos(wai_eos_desc *e, int kind);

@@ -70,7 +70,8 @@ int wai_timer_stop(wai_ctx *ctx, float *ms);
  * five products, scalars and the post to the host in the launch), 18 / 19 a device-to-device copy of half the perturbed-fluid
  * scratch onto the other half (hipMemcpyAsync / a streaming copy kernel): the box's copy ceiling, 2 x bytes / time; 22 a
  * read-only stream over the whole scratch: its read ceiling; 23 z = B^-1 (A x) by the launch-per-level path (k_spmv + k_lvl_solve
- * per level) on the factor in force, for a block-Jacobi schedule of a mesh with 9 .. 16-block rows (the path k_pc_wide replaces),
+ * per level) on the factor in force, for a block-Jacobi schedule of a mesh with 9 .. 16-block rows or the filled factor of fused
+ * ILU(k) (the path k_pc_wide replaces),
  * 20 / 21 GMRES's Gram-Schmidt inner products / its update w -= sum h_j v_j with |w|^2 over a whole restart cycle as
  * ksp_gmres issues them, reported per Krylov iteration (needs ksp_type gmres: the basis vectors) */
 int wai_bench_kernel(wai_ctx *ctx, int which, int reps, float *ms_per_launch);

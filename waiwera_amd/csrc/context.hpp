@@ -324,6 +324,11 @@ struct AsmSystem {
   int overlap = -1;           // what E was built for (-1: not built; 0: no overlap, fill only)
   int levels = 0;             // ILU(k) fill levels E's pattern carries
   bool sublu = false;         // ... or the complete fill of sub-preconditioner lu (levels is 0 then)
+  // block-Jacobi ILU(k), k > 0, in one fused launch: no overlap, so E's rows are the system's own rows in their order and
+  // E's pattern is the factor's (the Jacobian's in-brick blocks + fill, <= 16 per row); `sched` is wide and k_pc_wide's
+  // two-pattern form multiplies by A on the Jacobian's planes and sweeps the factor on E's (fuse_asked: what the set-up
+  // asked for -- the schedule may still have said no: fill wider than 16 blocks, a subdomain of more than 1024 rows)
+  bool fused = false, fuse_asked = false;
   int n_ext = 0;
   Bcsr E;                     // block-ELL over the n_ext rows, columns in ext numbering: a view of ...
   DevBuf<int> E_col;          // ... its column planes and
@@ -550,7 +555,9 @@ struct wai_ctx : wai::Handles {
   size_t stage_len = 0;
   // run-time switches of the fused launches, read from the environment once per solve / set-up / probe (read_env),
   // not per launch: WAI_FIN_SEPARATE, WAI_NO_COL16 (k_pc_park on the int32 column planes), WAI_BCGS_SCALAR_KERNELS
-  struct EnvSw { bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; } env;
+  // WAI_ILUK_LEVEL_PATH: block-Jacobi ILU(k) keeps the launch-per-level path where the fused launch would serve (tests
+  // that compare the two paths in one process; read at the preconditioner's set-up)
+  struct EnvSw { bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false; } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
   // halo
   int n_nbr = 0;
@@ -610,9 +617,11 @@ int launch_spmv(wai_ctx* c, const Bcsr& M, const double* x, double* y);
 // ILU(0) of any (matrix, schedule) pair: a system's matrix with the brick schedule, or its extended ASM system with its own
 int launch_ilu_factor_on(wai_ctx* c, const Bcsr& M, IluSchedule& s);
 // in2 (optional, fused kernels that can: pc_axpy_capable): the input is in - alpha in2, alpha = the device scalar S_ALPHA
+// F (optional, wide schedules): the factor has a pattern of its own (ILU(k) fill: AsmSystem::E of a fused system) -- M is
+// the operator A, read on its own planes, `s` the schedule of F, whose column planes the sweeps follow
 int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z,
                  int dot_mode, const double* aux, const int* list = nullptr, int nrun = 0, const Fin* fin = nullptr,
-                 const double* in2 = nullptr);
+                 const double* in2 = nullptr, const Bcsr* F = nullptr);
 // which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc,
 // -1 the coupled tracer system's k_dg_pc
 int pc_kernel_kind(const wai_ctx* c, const Bcsr& M, const IluSchedule& s);

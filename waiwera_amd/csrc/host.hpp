@@ -107,8 +107,18 @@ inline PcOpts pc_of(const wai_ctx* c, const LinSys& sys) {
 }
 // sub-preconditioner lu is in force (wai_set_sub_pc; it acts under bjacobi and asm alone, and ilu_levels is ignored then)
 inline bool pc_sub_lu(const PcOpts& p) { return p.sub == WAI_SUB_LU && (p.type == WAI_PC_BJACOBI || p.type == WAI_PC_ASM); }
+// block-Jacobi ILU(k), k > 0, on the flow system, applied by ONE launch: the set-up in force built the filled factor on a
+// wide schedule (AsmSystem::fused -- fill of <= 16 blocks per row, subdomains of <= 1024 rows, one rank, no network
+// blocks); k_pc_wide's two-pattern form then serves pc_amul / pc_solve (launch_pc_sys, krylov.hip)
+inline bool pc_fill_fused(const wai_ctx* c, const LinSys& sys) {
+  const PcOpts p = pc_of(c, sys);
+  const AsmSystem& a = sys.as;
+  return &sys == &c->flow && p.type == WAI_PC_BJACOBI && p.ilu_levels > 0 && !pc_with_net(c, sys) && !pc_sub_lu(p) &&
+         a.fused && a.overlap == 0 && a.levels == p.ilu_levels && a.sched.wide;
+}
 inline bool pc_fused(const wai_ctx* c, const LinSys& sys) {
   const PcOpts p = pc_of(c, sys);
+  if (pc_fill_fused(c, sys)) return true;
   return p.type == WAI_PC_BJACOBI && !c->ilu.big && p.ilu_levels <= 0 && !pc_with_net(c, sys) && !pc_sub_lu(p);
 }
 // the extended-system path: PCASM's overlapped row sets and / or ILU(k)'s filled pattern and / or the network's blocks
@@ -122,7 +132,8 @@ inline void pc_invalidate(wai_ctx* c) { c->ilu.owner = nullptr; }
 
 // ---- pc_setup.hip ------------------------------------------------------------------------------------------------
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true, bool sublu = false);
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true, bool sublu = false,
+                   bool fill = false);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell
 int do_pc_setup(wai_ctx* c, LinSys& sys);
 // ---- krylov.hip --------------------------------------------------------------------------------------------------
@@ -139,6 +150,9 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
 // z = B^-1 A x (x has halo room); x2: the operand is x - alpha x2 (fused kernels); post: the scalars to the host
 int pc_amul(wai_ctx* c, LinSys& sys, double* x, double* z, int dot_mode = PC_DOT_NONE, const double* aux = nullptr, int fin_phase = -2,
             const double* x2 = nullptr, bool post = false);
+// launch_pc for a system on the fused path: the brick schedule's factor, or the filled ILU(k) factor of pc_fill_fused
+int launch_pc_sys(wai_ctx* c, const LinSys& sys, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
+                  const int* list = nullptr, int nrun = 0, const Fin* fin = nullptr, const double* in2 = nullptr);
 int do_ksp(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm);
 int bcgs_mode(const wai_ctx* c);
 bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys);

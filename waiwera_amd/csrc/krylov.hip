@@ -55,6 +55,12 @@ int read_scal_end(wai_ctx* c) {
   return 0;
 }
 
+int launch_pc_sys(wai_ctx* c, const LinSys& sys, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
+                  const int* list, int nrun, const Fin* fin, const double* in2) {
+  if (pc_fill_fused(c, sys)) return launch_pc_on(c, sys.A, sys.as.sched, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, &sys.as.E);
+  return launch_pc(c, sys.A, spmv, in, z, dot_mode, aux, list, nrun, fin, in2);
+}
+
 // the dot mode's products of a preconditioner result (context.hpp, PcDot), reduced by separate launches: general path
 int pc_dots(wai_ctx* c, int n, int dot_mode, const double* x, const double* z, const double* aux) {
   const int s = pc_dot_slot0(dot_mode);
@@ -87,15 +93,15 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
     // the fused kernels take the partner of modes 2 and 4 from their own input vector (the x of
     // z = B^-1 A x); here the input is r = (A + E) x, so those inner products are reduced separately
     if (dot_mode == PC_DOT_XZ || dot_mode == PC_DOT_MERGED) {
-      if (launch_pc(c, sys.A, false, r, z, PC_DOT_NONE, nullptr)) return -1;
+      if (launch_pc_sys(c, sys, false, r, z, PC_DOT_NONE, nullptr)) return -1;
       if (pc_dots(c, sys.n, dot_mode, x, z, aux)) return -1;
       return fin_phase >= -1 ? pc_finalize(c, dot_mode, fin_phase) : 0;
     }
     if (fin_phase >= -1 && dot_mode) {
       const Fin fin = make_fin_dots(c, dot_mode, fin_phase);
-      return launch_pc(c, sys.A, false, r, z, dot_mode, aux, nullptr, 0, &fin);
+      return launch_pc_sys(c, sys, false, r, z, dot_mode, aux, nullptr, 0, &fin);
     }
-    return launch_pc(c, sys.A, false, r, z, dot_mode, aux);
+    return launch_pc_sys(c, sys, false, r, z, dot_mode, aux);
   }
   const size_t n = (size_t)sys.n;
   const int pc_type = pc_of(c, sys).type;
@@ -174,7 +180,7 @@ int pc_amul(wai_ctx* c, LinSys& sys, double* x, double* z, int dot_mode, const d
     } else if (halo_exchange(c, x, bs)) return -1;
   }
   Prof p(c, KC_PC_APPLY);
-  return launch_pc(c, sys.A, true, x, z, dot_mode, aux, nullptr, 0, fp, x2);
+  return launch_pc_sys(c, sys, true, x, z, dot_mode, aux, nullptr, 0, fp, x2);
 }
 
 // wait for the scalars a kernel posted to the host mirror with sequence number `seq` (Fin / k_bcgs_scalars):
@@ -243,7 +249,7 @@ int bcgs_mode(const wai_ctx* c) {
 // (profiles/compose_full_c4c5_ab_r5.log): C4 1.303 -> 1.265, C5 0.486 -> 0.467.  WAI_BCGS_COMPOSE=0 / 1 forces it off / on
 // (k_pc_rows -- 4 x 4 blocks, MINC inside 3-D bricks -- not measured: on request).
 bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys) {
-  if (!(pc_fused(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
+  if (!(pc_fused(c, sys) && !pc_fill_fused(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
   if (const char* e = getenv("WAI_BCGS_COMPOSE")) return e[0] == '1';
   return pc_axpy_default(c, sys.A);
 }

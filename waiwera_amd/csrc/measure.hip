@@ -30,7 +30,9 @@ __global__ __launch_bounds__(256) void k_stream_read(const stream_d2* __restrict
   if (t == 1.2345678e300) *sink = t;   // never: keeps the loads
 }
 // can pc_amul form its operand x - alpha x2 inside the launch?  (pc_axpy_ok without the switch and the default)
-bool pc_operand_composable(const wai_ctx* c) { return pc_fused(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A); }
+bool pc_operand_composable(const wai_ctx* c) {
+  return pc_fused(c, c->flow) && !pc_fill_fused(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A);
+}
 }  // namespace
 
 extern "C" {
@@ -48,7 +50,12 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   KrylovVecs& k = *sys.kv;
   if ((which == 20 || which == 21) && !k.basis) { c->err = "wai_bench_kernel 20 / 21: no Krylov basis (ksp_type gmres)"; return -2; }
   if (which > 0 && c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
-  if (which == 23 && (!pc_fused(c, sys) || !c->ilu.ord_f)) { c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh)"; return -2; }
+  const bool fill = pc_fill_fused(c, sys);   // the filled ILU(k) factor: its own pattern and schedule (sys.as)
+  if (which == 23 && (!pc_fused(c, sys) || !(fill ? sys.as.sched.ord_f : c->ilu.ord_f))) {
+    c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh, or fused ILU(k))";
+    return -2;
+  }
+  if (fill && (which == 9 || which == 10 || which == 16)) { c->err = "wai_bench_kernel 9 / 10 / 16: the brick schedule's kernels, not fused ILU(k)"; return -2; }
   const size_t copy_n = (size_t)c->np * c->df * c->mesh.n_prim / 2;   // modes 18 / 19 (the scratch is rewritten by every Jacobian)
   auto run = [&]() {
     switch (which) {
@@ -56,7 +63,8 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
       case 1: case 3: pc_solve(c, sys, k.P, k.V, PC_DOT_NONE, nullptr, nullptr); break;
       case 23:   // the launch-per-level path on the schedule in force (wide schedules: the factor k_pc_wide applies), for comparison
         launch_spmv(c, sys.A, k.P, k.V);
-        launch_big_solve(c, sys.A, c->ilu, k.V);
+        if (fill) launch_big_solve(c, sys.as.E, sys.as.sched, k.V);   // (no overlap: E's rows are the system's own, in order)
+        else launch_big_solve(c, sys.A, c->ilu, k.V);
         break;
       case 9: if (c->ilu.n_int > 0) launch_pc(c, sys.A, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_int, c->ilu.n_int); break;   // interior bricks only
       case 10: if (c->ilu.n_bnd > 0) launch_pc(c, sys.A, true, k.P, k.V, PC_DOT_ZA, k.RP, c->ilu.sub_bnd, c->ilu.n_bnd); break;  // face bricks only
@@ -169,6 +177,10 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
              pc.type == WAI_PC_ASM ? "ASM" : "block Jacobi");
     return buf;
   }
+  if (pc_fill_fused(c, sys)) {   // one launch: A on the Jacobian's planes, the sweeps on the filled factor's
+    snprintf(buf, sizeof(buf), "k_pc_wide<%d,spmv> on the filled factor (block Jacobi, ILU(%d))", bs, pc.ilu_levels);
+    return buf;
+  }
   if (pc_extended(c, sys)) {
     snprintf(buf, sizeof(buf), "k_spmv + %s on the extended system (%s, ILU(%d))",
              sys.as.sched.big ? "k_lvl_solve per level" : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),
@@ -223,7 +235,7 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   LinSys& sys = c->flow;
   if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
   if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
-  if (split && (!spmv || !pc_fused(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
+  if (split && (!spmv || !pc_fused(c, sys) || pc_fill_fused(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
     c->err = "wai_test_pc_operator: no interior / face brick lists to split the launch over";
     return -1;
   }

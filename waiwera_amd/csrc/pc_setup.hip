@@ -14,7 +14,7 @@ namespace wai {
 // compact / parked kernel conditions -- or, for subdomains of more than 1024 rows, the level sets
 // of the launch-per-level path.  `ghosts`: rows may have columns >= n (partition ghosts).
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide, bool sublu) {
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide, bool sublu, bool fill) {
   s.nsub = (int)sub.size() - 1;
   if (sub.front() != 0 || sub.back() != N) { c->err = "sub_ptr must cover [0, n_owned]"; return -2; }
   std::vector<int> diag(N);
@@ -104,9 +104,17 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
   // fill stays on the launch-per-level path).  A mesh of at most 8 blocks per row keeps the schedule it always had.
   // Sub-preconditioner lu (complete fill: one row per level) has kernels of its own, k_sublu_factor / k_sublu_solve, on
   // the 8-bit descriptor and without level sets.
+  // `fill`: the filled pattern of block-Jacobi ILU(k), k > 0, on a mesh of at most 8 blocks per row (build_asm).  W is the
+  // filled width -- ILU(1) of a 7-point stencil inside a brick: 13 -- and the wide schedule serves it whatever it is up to
+  // 16, the factor on this pattern's own column planes and the operator on the Jacobian's (k_pc_wide<.., FILL>).  LDS: one
+  // solution entry per thread and the reduction scratch must fit the 64 KB a workgroup may ask for (1024 rows of 4 x 4
+  // blocks: 33 408 bytes); what is left parks upper blocks, rows that do not fit re-read theirs (launch_pc_bs: ucap).
+  // Wider fill or larger subdomains keep the launch-per-level path.
   s.sublu = sublu;
-  s.wide = !sublu && allow_wide && c->pat.W > 8 && W > 8 && W <= 16 && s.max_rows <= 1024;
-  s.big = sublu || s.max_rows > 1024 || (W > 8 && !s.wide);
+  const size_t lds_fill = ((size_t)(((s.max_rows + 63) / 64) * 64) * np + 80) * sizeof(double);
+  s.wide = !sublu && allow_wide && W <= 16 && s.max_rows <= 1024 &&
+           (fill ? c->pat.W <= 8 && lds_fill <= 64 * 1024 && s.max_lev <= 1023 : c->pat.W > 8 && W > 8);
+  s.big = sublu || s.max_rows > 1024 || (W > 8 && !s.wide) || (fill && !s.wide);
   if (!s.big && s.max_lev > 1023) { c->err = "more than 1023 dependency levels in a subdomain"; return -2; }
   for (int i = 0; i < N; i++)
     info[i] = (s.big || s.wide) ? (lfirst[i] | (diag[i] << 8) | (ulast[i] << 16))
@@ -401,6 +409,14 @@ int ghost_rows(wai_ctx* c, const LinSys& sys, std::vector<int>& grp, std::vector
   return 0;
 }
 
+// Does block-Jacobi ILU(k) on `sys` ask for the fused launch (AsmSystem::fuse_asked)?  The flow system alone, on a mesh of at
+// most 8 blocks per row, on one rank, without the source network's blocks in the factor.  Several ranks keep the
+// launch-per-level path: the extended system's schedule carries no interior / face lists for the overlapped halo exchange.
+static bool iluk_fuse_wanted(const wai_ctx* c, const LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
+  return levels > 0 && overlap == 0 && !with_net && !sublu && &sys == &c->flow && !sys.A.dg && c->pat.W <= 8 &&
+         !(c->comm && c->comm->nranks > 1) && !c->env.iluk_level_path;
+}
+
 // sublu: complete fill instead (sub-preconditioner lu; levels is 0 then)
 int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
   AsmSystem& a = sys.as;
@@ -531,7 +547,10 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, b
       a.E_val.alloc(c, ell_size(np, n_ext, W)) || a.r_ext.alloc(c, (size_t)np * n_ext + 16))
     return -1;
   a.E.col = a.E_col; a.E.val = a.E_val;
-  if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0, sublu)) return e;
+  const bool fuse = iluk_fuse_wanted(c, sys, overlap, levels, with_net, sublu);
+  if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0 || fuse, sublu, fuse)) return e;
+  a.fuse_asked = fuse;
+  a.fused = fuse && a.sched.wide && n_ext == N;
   a.with_net = with_net;
   a.n_net = 0;
   if (mnet > 0) {   // where the blocks of the network's E land in the extended planes
@@ -641,7 +660,8 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
       const bool sl = pc_sub_lu(pc);
       const int lv = sl ? 0 : std::max(pc.ilu_levels, 0);   // (ilu_levels is ignored under sub-preconditioner lu)
       const bool wn = pc_with_net(c, sys);
-      if (as.overlap != ov || as.levels != lv || as.sublu != sl || as.E.bs != A.bs || as.with_net != wn) {
+      if (as.overlap != ov || as.levels != lv || as.sublu != sl || as.E.bs != A.bs || as.with_net != wn ||
+          as.fuse_asked != iluk_fuse_wanted(c, sys, ov, lv, wn, sl)) {
         // (a refusal of sub-preconditioner lu is the caller's to read: -2 with its text)
         if (int e = build_asm(c, sys, ov, lv, wn, sl)) return sl && e == -2 ? -2 : (e < 0 ? -1 : e);
       }

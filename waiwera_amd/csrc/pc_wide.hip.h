@@ -19,7 +19,46 @@ namespace wai {
 // Every factor block is read once per application, so the launch moves about what the launch-per-level path moves
 // without its 2 x levels launches and the separate SpMV.  One workgroup per subdomain (<= 1024 rows), one thread per block
 // row; k_pc's interface: dot modes, finaliser workgroups, sub_list (the interior / face split of the halo exchange).
-template <int BS, bool SPMV>
+// FILL: two patterns in one launch -- block-Jacobi ILU(k), k > 0, on a mesh of at most 8 blocks per row.  The operator keeps
+// the Jacobian's narrow rows (W <= 8 slots on `col`, neighbour gathers included: ell_row_mult as the narrow kernels call
+// it); the factor has the filled pattern (<= 16 slots per row, in-brick columns only) on column planes of its own, `fcol`,
+// which the descriptor's slots, the two sweeps and the parked upper blocks refer to.  Both have n rows in the same order.
+// NS > 0 (FILL, 1 x 1 and 2 x 2 blocks; rows of at most NS lower and NS upper in-brick blocks): nothing is fetched inside a
+// level.  In the form above a row waits for its lower blocks at its own level, so every one of a brick's levels pays a
+// memory round trip -- and ILU(1) in a 16 x 16 x 2 brick has about three times the levels of ILU(0).  Here all rows of the
+// brick fetch their lower blocks and columns into registers at once before the forward sweep, and their upper blocks into
+// the SAME registers at once between the sweeps: two round trips per brick instead of two per level, the sweeps touch LDS
+// alone, and nothing is parked (LDS: the solution and the reduction scratch).  Same arithmetic in the same order as the
+// form above.  tools/iluk_fused_timing.py times both forms against the launch-per-level path on the same factor.
+// stage_blocks issues NS column and block loads for every row, branch-free: a row with fewer blocks re-reads its own pivot
+// slot as filler (in bounds, never used; the same lines the pivot load fetches, so cache hits rather than HBM bytes).
+template <int BS, int NS>
+__device__ __forceinline__ void stage_blocks(int n, int i, int lo, int q0, int cnt, int dslot, const int* __restrict__ fc,
+                                             const double* __restrict__ fval, int (&kc)[NS], double (&m)[NS][BS * BS]) {
+#pragma unroll
+  for (int p = 0; p < NS; p++) {
+    const int q = p < cnt ? q0 + p : dslot;   // a slot of the row's own either way (the pivot's: not used)
+    kc[p] = fc[(size_t)q * n + i] - lo;
+    load_block<BS>(fval, n, q, i, m[p]);
+  }
+}
+template <int BS, int NS>
+__device__ __forceinline__ void staged_row_sub(int cnt, const int (&kc)[NS], const double (&m)[NS][BS * BS], const double* ys, double* a) {
+#pragma unroll
+  for (int p = 0; p < NS; p++) {
+    if (p < cnt) {
+      double yk[BS];
+#pragma unroll
+      for (int c = 0; c < BS; c++) yk[c] = ys[kc[p] * BS + c];
+#pragma unroll
+      for (int r = 0; r < BS; r++)
+#pragma unroll
+        for (int c = 0; c < BS; c++) a[r] -= m[p][r * BS + c] * yk[c];
+    }
+  }
+}
+
+template <int BS, bool SPMV, bool FILL = false, int NS = 0>
 __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const int* __restrict__ sub_ptr,
                                                   const int* __restrict__ sub_nlev,
                                                   const unsigned long long* __restrict__ row_infow,
@@ -27,8 +66,10 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
                                                   const int* __restrict__ rowptr, const double* __restrict__ aval,
                                                   const double* __restrict__ fval, const double* __restrict__ in,
                                                   double* __restrict__ z, const double* __restrict__ aux, double* partials,
-                                                  int nb_max, int dot, int ucap, const int* __restrict__ sub_list, Fin fin) {
+                                                  int nb_max, int dot, int ucap, const int* __restrict__ sub_list, Fin fin,
+                                                  const int* __restrict__ fcol) {
   constexpr int BB = BS * BS;
+  const int* __restrict__ fc = FILL ? fcol : col;   // the factor's column planes
   extern __shared__ __attribute__((aligned(16))) double lds[];  // [T * BS] solution, 80 doubles reduction scratch, [ucap][BB] parked upper blocks
   if (fin_block(fin, partials, nb_max)) return;
   int s = xcd_remap(blockIdx.x, nsub);
@@ -43,18 +84,25 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
   double* park = red + 80;
   int lfirst = 0, dslot = 0, ulast = 0, lf = -1, lb = -1, uo = 0;
   bool parked = false;
+  constexpr int NSR = NS > 0 ? NS : 1;
+  int kc[NSR];            // NS > 0: the staged blocks' columns (brick-local) and values
+  double mb[NSR][BB];
   if (active) {
     unpack_info_w(row_infow[i], lfirst, dslot, ulast, lf, lb);
     double acc[BS];
     if constexpr (SPMV) {
 #pragma unroll
       for (int r = 0; r < BS; r++) acc[r] = 0.0;
-      ell_row_mult<BS, WMAX_WIDE>(n, rowptr ? rowptr[i + 1] - rowptr[i] : W, i, col, aval, in, acc);
+      ell_row_mult<BS, FILL ? WMAX : WMAX_WIDE>(n, rowptr ? rowptr[i + 1] - rowptr[i] : W, i, col, aval, in, acc);
     } else {
       load_x<BS>(in, i, acc);
     }
-    uo = row_uoffw[i];
-    parked = uo + (ulast - dslot - 1) <= ucap;
+    if constexpr (NS > 0) {
+      stage_blocks<BS, NS>(n, i, lo, lfirst, dslot - lfirst, dslot, fc, fval, kc, mb);
+    } else {
+      uo = row_uoffw[i];
+      parked = uo + (ulast - dslot - 1) <= ucap;
+    }
     if (parked) {
       for (int q = dslot + 1; q < ulast; q++) {
         double blk[BB];
@@ -73,16 +121,20 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
       double a[BS];
 #pragma unroll
       for (int r = 0; r < BS; r++) a[r] = ys[tid * BS + r];
-      for (int q = lfirst; q < dslot; q++) {
-        const int k = col[(size_t)q * n + i] - lo;
-        double m[BB], yk[BS];
-        load_block<BS>(fval, n, q, i, m);
+      if constexpr (NS > 0) {
+        staged_row_sub<BS, NS>(dslot - lfirst, kc, mb, ys, a);
+      } else {
+        for (int q = lfirst; q < dslot; q++) {
+          const int k = fc[(size_t)q * n + i] - lo;
+          double m[BB], yk[BS];
+          load_block<BS>(fval, n, q, i, m);
 #pragma unroll
-        for (int c = 0; c < BS; c++) yk[c] = ys[k * BS + c];
+          for (int c = 0; c < BS; c++) yk[c] = ys[k * BS + c];
 #pragma unroll
-        for (int r = 0; r < BS; r++)
+          for (int r = 0; r < BS; r++)
 #pragma unroll
-          for (int c = 0; c < BS; c++) a[r] -= m[r * BS + c] * yk[c];
+            for (int c = 0; c < BS; c++) a[r] -= m[r * BS + c] * yk[c];
+        }
       }
 #pragma unroll
       for (int r = 0; r < BS; r++) ys[tid * BS + r] = a[r];
@@ -97,13 +149,17 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
 #pragma unroll
   for (int e = 0; e < BB; e++) dv[e] = 0.0;
   if (active) load_block<BS>(fval, n, dslot, i, dv);
+  if constexpr (NS > 0) {   // the upper blocks take the lower blocks' registers
+    if (active) stage_blocks<BS, NS>(n, i, lo, dslot + 1, ulast - dslot - 1, dslot, fc, fval, kc, mb);
+  }
   for (int lev = 0; lev < nlb; lev++) {
     if (lb == lev) {
       double a[BS];
 #pragma unroll
       for (int r = 0; r < BS; r++) a[r] = ys[tid * BS + r];
-      for (int q = dslot + 1; q < ulast; q++) {
-        const int k = col[(size_t)q * n + i] - lo;
+      if constexpr (NS > 0) staged_row_sub<BS, NS>(ulast - dslot - 1, kc, mb, ys, a);
+      for (int q = dslot + 1; NS == 0 && q < ulast; q++) {
+        const int k = fc[(size_t)q * n + i] - lo;
         double m[BB], xk[BS];
         if (parked) {
           const double* p = park + (size_t)(uo + q - dslot - 1) * BB;
