@@ -51,6 +51,36 @@ int wai_test_pc_operator(wai_ctx *ctx, int spmv, const double *x, const double *
                          const double *aux, int split, int fin_phase, const double *scal_in, double *z, double *scal_out);
 /* 1 when the fused preconditioned-operator launch can form its operand x - alpha x2 itself (wai_test_pc_operator's x2) */
 int wai_pc_axpy_capable(wai_ctx *ctx);
+/* partial sums per reduction slot the last preconditioner application (or vec_dots) left: one per brick, one per workgroup
+ * of four bricks under k_pc_wave; more than 1024 means the finalisation ran in slices (tests/test_hip_fused_operator.py) */
+int wai_test_partial_count(wai_ctx *ctx);
+/* one vector / reduction step of the Krylov drivers, issued through the drivers' own launchers, for the tests
+ * (tests/test_hip_krylov_vec.py).  n >= 1 entries per vector, whatever the context's mesh.  vecs: seven host vectors of
+ * len >= n doubles each, X R RP P V S T in this order, in and out whole (the entries behind n are guards); basis (GMRES ops):
+ * (k + 1) * ld host doubles, 1 <= k <= 40 vectors ld >= n apart, in and out whole; scal: all 128 device scalars in and out
+ * (0 rho, 1 rho_old, 2 alpha, 3 omega, 4 beta, 5-9 the sums S_D1 S_D2 S_DP2 S_RHONEW S_W2, 15 the breakdown code, 16 + j
+ * the Gram-Schmidt coefficient h_j); post[2]: the (R,R) and breakdown code a launch posted to the host, written only where
+ * the op posts.  Every partial slot is emptied first, as a driver empties them before its first producer.
+ *   op (variant)
+ *   DOT            S_W2 = (X, R)                                              vec_dot
+ *   DOTS           0: S_D1 = (X, R), S_D2 = (P, V); 1: S_D1 alone             vec_dots + vec_finalize (host_dots)
+ *   WAXPY          0: T = alpha X + R; 1: X = (w == x); 2: R = (w == y)       vec_waxpy
+ *   BCGS_P / _S    P = R + beta (P - omega V) / S = R - alpha V               bcgs_update_p / bcgs_update_s
+ *   BCGS_XR        X += alpha P + omega S, R = S - omega T.  0: no inner products; 1: (R,R), (R,RP) finished in the launch
+ *                  (by a k_finalize launch under WAI_FIN_SEPARATE=1); 2: the same with phase 4 and the post; 3: left as
+ *                  partial sums and finished here by vec_finalize                bcgs_update_xr
+ *   BCGS_XRP       X, R, P in one pass                                        bcgs_update_xrp
+ *   BCGS_XRP_DERIVE  the same, omega, (R,R), rho, beta derived in the launch and posted    bcgs_update_xrp_derive
+ *   SCALARS        variant = phase 0, 2, 3, 4, 5 or 6 (6 posts)               bcgs_scalars
+ *   MDOT           scal[16 + j] = (T, v_j), j < k                             gmres_mdot
+ *   MAXPY_NORM     T -= sum h_j v_j, S_W2 = |T|^2                             gmres_maxpy_norm
+ *   SCALE_TO       0: T = X / sqrt(S_W2); 1: X in place                       gmres_scale_to
+ *   UPDATE_X       X += sum coef[j] v_j (coef: k host doubles; they travel through scal[64 ..])    gmres_update_x
+ * n < 1, k out of range, ld < n, len < n, an unknown op or variant: -2 with the error text set, nothing launched. */
+enum { WAI_KV_DOT = 0, WAI_KV_DOTS, WAI_KV_WAXPY, WAI_KV_BCGS_P, WAI_KV_BCGS_S, WAI_KV_BCGS_XR, WAI_KV_BCGS_XRP,
+       WAI_KV_BCGS_XRP_DERIVE, WAI_KV_SCALARS, WAI_KV_MDOT, WAI_KV_MAXPY_NORM, WAI_KV_SCALE_TO, WAI_KV_UPDATE_X };
+int wai_test_krylov_vec(wai_ctx *ctx, int op, int variant, int n, int k, long long ld, long long len, double alpha,
+                        double *vecs, double *basis, const double *coef, double *scal, double *post);
 /* bytes this rank sends per halo exchange of a dof-per-cell vector, and its number of neighbours */
 int wai_halo_size(wai_ctx *ctx, int dof, long long *bytes_sent, int *n_neighbours);
 

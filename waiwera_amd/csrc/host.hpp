@@ -144,6 +144,7 @@ int launch_pc_split(wai_ctx* c, const Bcsr& M, const double* x, double* z, int d
                     hipEvent_t after);
 int allreduce_scal(wai_ctx* c, int slot, int count);
 int read_scal(wai_ctx* c, int first, int count);
+int wait_post(wai_ctx* c, int seq);   // the scalars a launch posted under `seq`: h_scal[S_DP2], h_scal[S_BREAK]
 // z = B^-1 r; dot_mode as launch_pc, with `x` the partner of mode 2.  fin_phase >= -1: the partial sums of the dot
 // products are summed into the device scalars (and the BiCGStab scalars of that phase derived); -2: left as partials
 int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase = -2);

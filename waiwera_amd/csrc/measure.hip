@@ -275,6 +275,79 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   return 0;
 }
 int wai_pc_axpy_capable(wai_ctx* c) { return c ? (pc_operand_composable(c) ? 1 : 0) : -2; }
+int wai_test_partial_count(wai_ctx* c) { return c ? c->ks.nb_pc : -2; }
+// one vector / reduction step of the Krylov drivers through the drivers' own launchers (waiwera_hip_bench.h): temporaries of
+// the caller's padded lengths, all NSCAL scalars seeded, every partial slot emptied as ksp_gmres empties them before its
+// first producer, the launchers unchanged, everything back to the caller -- guard elements included
+int wai_test_krylov_vec(wai_ctx* c, int op, int variant, int n, int k, long long ld, long long len, double alpha, double* vecs,
+                        double* basis, const double* coef, double* scal, double* post) {
+  if (!c || !vecs || !scal || !post) return -2;
+  const bool gmres = op == WAI_KV_MDOT || op == WAI_KV_MAXPY_NORM || op == WAI_KV_UPDATE_X;
+  auto refuse = [&](const char* why) { c->err = std::string("wai_test_krylov_vec: ") + why; return -2; };
+  if (op < WAI_KV_DOT || op > WAI_KV_UPDATE_X) return refuse("no such op");
+  if (n < 1) return refuse("n < 1");
+  if (k < 0 || k > MAX_RESTART || (gmres && k < 1)) return refuse("basis count out of range");
+  if (len < (long long)n) return refuse("len < n");
+  if (gmres && (ld < (long long)n || !basis)) return refuse("ld < n, or no basis");
+  if (op == WAI_KV_UPDATE_X && !coef) return refuse("no coefficients");
+  const int vmax[] = {0, 1, 2, 0, 0, 3, 0, 0, 6, 0, 0, 1, 0};   // per op: the largest variant
+  if (variant < 0 || variant > vmax[op] || (op == WAI_KV_SCALARS && variant == 1)) return refuse("no such variant");
+  read_env(c);
+  enum { X, R, RP, P, V, S, T, NV };
+  KrylovVecs kv;   // owners of this call's temporaries: returned when it ends, whichever way
+  DevBuf<double>* own[NV] = {&kv.X_own, &kv.R, &kv.RP, &kv.P, &kv.V, &kv.S, &kv.T};
+  const size_t L = (size_t)len, nbasis = gmres ? (size_t)(k + 1) * (size_t)ld : 0;
+  for (int i = 0; i < NV; i++) {
+    if (own[i]->alloc(c, L)) return -1;
+    HIPCHK(c, hipMemcpyAsync(own[i]->get(), vecs + (size_t)i * L, L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  kv.X = kv.X_own;
+  if (gmres) {
+    if (kv.basis.alloc(c, nbasis)) return -1;
+    HIPCHK(c, hipMemcpyAsync(kv.basis.get(), basis, nbasis * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->ks.scal, scal, NSCAL * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  partials_clear(c, 0, NSLOTS);
+  int seq = 0;   // > 0: the launch posts to the host under this sequence number
+  switch (op) {
+    case WAI_KV_DOT: vec_dot(c, kv.X, kv.R, n, S_W2); break;
+    case WAI_KV_DOTS:   // host_dots
+      vec_dots(c, kv.X, kv.R, S_D1, variant ? nullptr : kv.P.get(), variant ? nullptr : kv.V.get(), S_D2, n);
+      vec_finalize(c, c->ks.nb_pc, S_D1, variant ? 1 : 2, -1);
+      break;
+    case WAI_KV_WAXPY:
+      vec_waxpy(c, variant == 0 ? kv.T.get() : (variant == 1 ? kv.X : kv.R.get()), alpha, kv.X, kv.R, n);
+      break;
+    case WAI_KV_BCGS_P: bcgs_update_p(c, kv, n); break;
+    case WAI_KV_BCGS_S: bcgs_update_s(c, kv, n); break;
+    case WAI_KV_BCGS_XR:
+      if (variant == 0) bcgs_update_xr(c, kv, n, false);
+      else if (variant == 1) bcgs_update_xr(c, kv, n, true, -1, false);
+      else if (variant == 2) { bcgs_update_xr(c, kv, n, true, 4, true); seq = c->ks.seq; }
+      else { bcgs_update_xr(c, kv, n, true, -2, false); vec_finalize(c, c->ks.nblocks, S_DP2, 2, -1); }
+      break;
+    case WAI_KV_BCGS_XRP: bcgs_update_xrp(c, kv, n); break;
+    case WAI_KV_BCGS_XRP_DERIVE: bcgs_update_xrp_derive(c, kv, n); seq = c->ks.seq; break;
+    case WAI_KV_SCALARS:
+      bcgs_scalars(c, variant, variant == 6);
+      if (variant == 6) seq = c->ks.seq;
+      break;
+    case WAI_KV_MDOT: gmres_mdot(c, kv.basis, (size_t)ld, n, kv.T, k); break;
+    case WAI_KV_MAXPY_NORM: gmres_maxpy_norm(c, kv.basis, (size_t)ld, n, kv.T, k); break;
+    case WAI_KV_SCALE_TO: gmres_scale_to(c, variant ? kv.X : kv.T.get(), kv.X, S_W2, n); break;
+    default: gmres_update_x(c, kv.basis, (size_t)ld, n, kv.X, coef, k); break;
+  }
+  if (seq > 0) {
+    if (wait_post(c, seq)) return -1;
+    post[0] = c->ks.h_scal[S_DP2]; post[1] = c->ks.h_scal[S_BREAK];
+  }
+  for (int i = 0; i < NV; i++)
+    HIPCHK(c, hipMemcpyAsync(vecs + (size_t)i * L, own[i]->get(), L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (gmres) HIPCHK(c, hipMemcpyAsync(basis, kv.basis.get(), nbasis * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(scal, c->ks.scal, NSCAL * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
 int wai_test_drop_stream_wait(wai_ctx* c, int which) { if (!c) return -2; c->test_drop_wait = which; return 0; }
 int wai_bench_mute_comm(wai_ctx* c, int on) {
   if (!c) return -2;

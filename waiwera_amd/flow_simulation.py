@@ -428,6 +428,31 @@ class FlowSimulation:
         """can the fused launch form its operand x - alpha x2 itself (pc_operator's x2)?"""
         return LIB.wai_pc_axpy_capable(self.h) == 1
 
+    def partial_count(self):
+        """partial sums per reduction slot the last preconditioner application left (wai_test_partial_count)"""
+        return self._chk(LIB.wai_test_partial_count(self.h), "test_partial_count")
+
+    KV_OPS = ("dot", "dots", "waxpy", "bcgs_p", "bcgs_s", "bcgs_xr", "bcgs_xrp", "bcgs_xrp_derive", "scalars", "mdot",
+              "maxpy_norm", "scale_to", "update_x")
+    KV_VECS = ("X", "R", "RP", "P", "V", "S", "T")
+
+    def krylov_vec(self, op, n, vecs, scal, variant=0, k=0, ld=0, basis=None, coef=None, alpha=0.0):
+        """one vector / reduction step of the Krylov drivers through their own launchers (tests; wai_test_krylov_vec):
+        vecs (7, len) in KV_VECS order, scal the 128 device scalars, basis (k + 1) * ld doubles.  Nothing passed in is
+        changed; (vecs, basis, scal, post) after, post = [(R,R), breakdown code] as posted to the host or NaNs"""
+        v = np.array(vecs, dtype=np.float64, order="C")
+        s = np.array(scal, dtype=np.float64)
+        assert v.ndim == 2 and v.shape[0] == len(self.KV_VECS) and s.shape == (128,)
+        b = np.array(basis, dtype=np.float64).ravel() if basis is not None else None
+        assert b is None or b.size == (k + 1) * ld
+        cf = _lib._f64(coef) if coef is not None else None
+        assert cf is None or cf.size >= k
+        post = np.full(2, np.nan)
+        P = lambda a: a.ctypes.data_as(_lib.pd) if a is not None else None   # noqa: E731
+        self._chk(LIB.wai_test_krylov_vec(self.h, self.KV_OPS.index(op), int(variant), int(n), int(k), int(ld), v.shape[1],
+                                          float(alpha), P(v), P(b), P(cf), P(s), P(post)), "test_krylov_vec")
+        return v, b, s, post
+
     def ksp_solve(self, b, x):
         its, reason, rn = C.c_int(0), C.c_int(0), C.c_double(0)
         self._chk(LIB.wai_ksp_solve(self.h, _lib.ptr(b), _lib.ptr(x), C.byref(its), C.byref(reason),
