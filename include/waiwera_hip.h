@@ -110,8 +110,10 @@ typedef struct wai_solver_opts {
                                   PCASM, overlap 1, sub-PC ILU(0) (default_flow_pc_type_str = "asm", src/timestepper.F90:2019-2020;
                                   one subdomain per rank, :1668-1669).  Block Jacobi over the mesh descriptor's subdomains is
                                   the only preconditioner with a fused fast path here -- with ILU(0), and with ILU(k > 0)
-                                  where the filled rows have at most 16 blocks (ilu_levels below); WAI_PC_ASM runs the unfused
-                                  extended-system path (measured at 216^3: 74 Krylov iterations at 7.8 ms against 98 at 1.4 ms,
+                                  where the filled rows have at most 16 blocks (ilu_levels below); WAI_PC_ASM is applied by one
+                                  fused launch too where every overlapped block has at most 1024 rows (flow system, one rank,
+                                  WAI_ASM_UNFUSED unset) and by the unfused extended-system path otherwise -- the bench's
+                                  16 x 16 x 2 bricks extend to 1152 rows and stay there (measured at 216^3: 74 Krylov iterations at 7.8 ms against 98 at 1.4 ms,
                                   profiles/pc_compare_r6.log).  A host that mirrors an unmodified Waiwera input sets WAI_PC_ASM
                                   itself (the JSON front end of waiwera_amd/simulation.py does) */
   int asm_overlap;             /* PCASM overlap, PETSc default 1; reaches one cell layer across rank boundaries (the

@@ -319,7 +319,8 @@ inline int eos_traits(int kind, EosTraits& t) {
 // PCASM (restricted additive Schwarz) system: every subdomain's overlapped row set is stored as
 // its own block of an extended matrix E (couplings leaving the set dropped), so the block-Jacobi
 // machinery applies to E unchanged: gather r -> r_ext, ILU(0) solve per block, scatter the owned
-// rows back (src/timestepper.F90:1668-1669,1753-1757; PETSc PCASM defaults: overlap 1, restrict)
+// rows back (src/timestepper.F90:1668-1669,1753-1757; PETSc PCASM defaults: overlap 1, restrict).  Where every block of E
+// fits one workgroup the gather, the sweeps, the scatter and the SpMV before them are ONE launch instead (`fused` below)
 struct AsmSystem {
   int overlap = -1;           // what E was built for (-1: not built; 0: no overlap, fill only)
   int levels = 0;             // ILU(k) fill levels E's pattern carries
@@ -328,6 +329,11 @@ struct AsmSystem {
   // E's pattern is the factor's (the Jacobian's in-brick blocks + fill, <= 16 per row); `sched` is wide and k_pc_wide's
   // two-pattern form multiplies by A on the Jacobian's planes and sweeps the factor on E's (fuse_asked: what the set-up
   // asked for -- the schedule may still have said no: fill wider than 16 blocks, a subdomain of more than 1024 rows)
+  // PCASM in one fused launch (overlap > 0, ILU(k), k >= 0): E's rows are the overlapped blocks' (n_ext > N), the same
+  // two-pattern form reads the operator through ext_row (k_pc_wide<.., MAP>: host.hpp, pc_asm_fused) and writes the rows a
+  // block owns.  Same two flags: asked for on the flow system, one rank, a mesh of <= 8 blocks per row, no network blocks,
+  // no sub lu, WAI_ASM_UNFUSED unset; refused by the schedule where an extended block has more than 1024 rows (a
+  // 16 x 16 x 2 brick at overlap 1: 1152) or a row of E more than 16 blocks
   bool fused = false, fuse_asked = false;
   int n_ext = 0;
   Bcsr E;                     // block-ELL over the n_ext rows, columns in ext numbering: a view of ...
@@ -556,8 +562,12 @@ struct wai_ctx : wai::Handles {
   // run-time switches of the fused launches, read from the environment once per solve / set-up / probe (read_env),
   // not per launch: WAI_FIN_SEPARATE, WAI_NO_COL16 (k_pc_park on the int32 column planes), WAI_BCGS_SCALAR_KERNELS
   // WAI_ILUK_LEVEL_PATH: block-Jacobi ILU(k) keeps the launch-per-level path where the fused launch would serve (tests
-  // that compare the two paths in one process; read at the preconditioner's set-up)
-  struct EnvSw { bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false; } env;
+  // that compare the two paths in one process; read at the preconditioner's set-up); WAI_ASM_UNFUSED: PCASM likewise keeps
+  // its launches (k_spmv, gather, the sweeps on the extended system, scatter, the reductions) where the fused one would serve
+  struct EnvSw {
+    bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false;
+    bool asm_unfused = false;
+  } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
   // halo
   int n_nbr = 0;
@@ -619,9 +629,11 @@ int launch_ilu_factor_on(wai_ctx* c, const Bcsr& M, IluSchedule& s);
 // in2 (optional, fused kernels that can: pc_axpy_capable): the input is in - alpha in2, alpha = the device scalar S_ALPHA
 // F (optional, wide schedules): the factor has a pattern of its own (ILU(k) fill: AsmSystem::E of a fused system) -- M is
 // the operator A, read on its own planes, `s` the schedule of F, whose column planes the sweeps follow
+// row_map (optional, with F): F's rows are not M's -- PCASM's extended system; AsmSystem::ext_row maps each to its row of M
+// and marks the rows its block owns, the only ones written (k_pc_wide<.., MAP>); z != in
 int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z,
                  int dot_mode, const double* aux, const int* list = nullptr, int nrun = 0, const Fin* fin = nullptr,
-                 const double* in2 = nullptr, const Bcsr* F = nullptr);
+                 const double* in2 = nullptr, const Bcsr* F = nullptr, const int* row_map = nullptr);
 // which fused kernel serves (matrix, schedule): 4 k_pc_wide, 3 k_pc_wave, 2 k_pc_rows, 1 k_pc_park, 0 the generic k_pc,
 // -1 the coupled tracer system's k_dg_pc
 int pc_kernel_kind(const wai_ctx* c, const Bcsr& M, const IluSchedule& s);

@@ -116,9 +116,21 @@ inline bool pc_fill_fused(const wai_ctx* c, const LinSys& sys) {
   return &sys == &c->flow && p.type == WAI_PC_BJACOBI && p.ilu_levels > 0 && !pc_with_net(c, sys) && !pc_sub_lu(p) &&
          a.fused && a.overlap == 0 && a.levels == p.ilu_levels && a.sched.wide;
 }
+// PCASM (any overlap, sub-preconditioner ILU(k), k >= 0) on the flow system, applied by ONE launch: the set-up in force put
+// the extended system on a wide schedule (AsmSystem::fused -- extended blocks of <= 1024 rows, rows of E of <= 16 blocks,
+// one rank, no network blocks, WAI_ASM_UNFUSED unset); k_pc_wide's two-pattern form with a row map serves it
+inline bool pc_asm_fused(const wai_ctx* c, const LinSys& sys) {
+  const PcOpts p = pc_of(c, sys);
+  const AsmSystem& a = sys.as;
+  return &sys == &c->flow && p.type == WAI_PC_ASM && !pc_with_net(c, sys) && !pc_sub_lu(p) && a.fused && a.overlap > 0 &&
+         a.overlap == (p.asm_overlap > 0 ? p.asm_overlap : 1) && a.levels == (p.ilu_levels > 0 ? p.ilu_levels : 0) &&
+         !a.cross && a.sched.wide;
+}
+// either: the factor has a pattern of its own (sys.as.E on sys.as.sched) -- no composed operand, no interior / face split
+inline bool pc_own_factor(const wai_ctx* c, const LinSys& sys) { return pc_fill_fused(c, sys) || pc_asm_fused(c, sys); }
 inline bool pc_fused(const wai_ctx* c, const LinSys& sys) {
   const PcOpts p = pc_of(c, sys);
-  if (pc_fill_fused(c, sys)) return true;
+  if (pc_own_factor(c, sys)) return true;
   return p.type == WAI_PC_BJACOBI && !c->ilu.big && p.ilu_levels <= 0 && !pc_with_net(c, sys) && !pc_sub_lu(p);
 }
 // the extended-system path: PCASM's overlapped row sets and / or ILU(k)'s filled pattern and / or the network's blocks
@@ -151,7 +163,8 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
 // z = B^-1 A x (x has halo room); x2: the operand is x - alpha x2 (fused kernels); post: the scalars to the host
 int pc_amul(wai_ctx* c, LinSys& sys, double* x, double* z, int dot_mode = PC_DOT_NONE, const double* aux = nullptr, int fin_phase = -2,
             const double* x2 = nullptr, bool post = false);
-// launch_pc for a system on the fused path: the brick schedule's factor, or the filled ILU(k) factor of pc_fill_fused
+// launch_pc for a system on the fused path: the brick schedule's factor, the filled ILU(k) factor of pc_fill_fused, or
+// PCASM's extended factor through its row map (pc_asm_fused)
 int launch_pc_sys(wai_ctx* c, const LinSys& sys, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
                   const int* list = nullptr, int nrun = 0, const Fin* fin = nullptr, const double* in2 = nullptr);
 int do_ksp(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* reason, double* rnorm);

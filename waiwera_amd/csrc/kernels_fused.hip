@@ -22,6 +22,7 @@ void read_env(wai_ctx* c) {
   c->env.no_col16 = getenv("WAI_NO_COL16") != nullptr;
   c->env.scalar_kernels = getenv("WAI_BCGS_SCALAR_KERNELS") != nullptr;   // several ranks: the one-thread kernels behind the all-reduces (rounds 3-4)
   c->env.iluk_level_path = getenv("WAI_ILUK_LEVEL_PATH") != nullptr;
+  c->env.asm_unfused = getenv("WAI_ASM_UNFUSED") != nullptr;
 }
 
 // which fused kernel serves (matrix, schedule; context.hpp).  Kinds 1 .. 3 can form their input on the fly (in - alpha in2:
@@ -46,7 +47,7 @@ bool pc_axpy_default(const wai_ctx* c, const Bcsr& M) {
 template <int BS>
 static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool spmv, const double* in, double* z,
                          int dot_mode, const double* aux, const int* list, int nrun, const Fin* finp, const double* in2,
-                         const Bcsr* F) {
+                         const Bcsr* F, const int* row_map) {
   if (!list) { nrun = s.nsub; list = s.sub_order; }   // all subdomains: in the schedule's launch order, if it has one
   const bool with_fin = finp && dot_mode != 0;
   Fin fin;
@@ -66,12 +67,26 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
     // the filled ILU(k) factor of 1 x 1 and 2 x 2 blocks whose rows have at most NSB lower and NSB upper in-brick blocks (ILU(1)
     // of a 7-point stencil: 6 + 6): both sweeps on blocks staged in registers, nothing parked
     constexpr int NSB = BS == 1 ? 8 : (BS == 2 ? 6 : 0);
+    // PCASM's extended ILU(0) factor of 2 x 2 blocks has 3 + 3 in-block couplings per row: staged on 3 slots it keeps two
+    // 1024-thread workgroups on a CU where the 6-slot form's registers allow one
+    if constexpr (BS == 2) {
+      if (F && row_map && s.max_nlu <= 3) {
+        with_flag(spmv, [&](auto sp) {
+          hipLaunchKernelGGL((k_pc_wide<2, decltype(sp)::value, true, 3, true>), grid, T, lds, c->stream, J.n, J.W, nrun, s.sub_ptr,
+                             s.sub_nlev, s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux, c->ks.partials, c->ks.nb_max,
+                             dot_mode, 0, list, fin, F->col, F->n, row_map);
+        });
+        return;
+      }
+    }
     if constexpr (NSB > 0) {
       if (F && s.max_nlu <= NSB) {
         with_flag(spmv, [&](auto sp) {
-          hipLaunchKernelGGL((k_pc_wide<BS, decltype(sp)::value, true, NSB>), grid, T, lds, c->stream, J.n, J.W, nrun, s.sub_ptr,
-                             s.sub_nlev, s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux, c->ks.partials, c->ks.nb_max,
-                             dot_mode, 0, list, fin, F->col);
+          with_flag(row_map != nullptr, [&](auto map) {
+            hipLaunchKernelGGL((k_pc_wide<BS, decltype(sp)::value, true, NSB, decltype(map)::value>), grid, T, lds, c->stream, J.n, J.W,
+                               nrun, s.sub_ptr, s.sub_nlev, s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux,
+                               c->ks.partials, c->ks.nb_max, dot_mode, 0, list, fin, F->col, F->n, row_map);
+          });
         });
         return;
       }
@@ -80,13 +95,16 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
     const size_t room = (size_t)64 * 1024 > lds ? (size_t)64 * 1024 - lds : 0;
     const int ucap = (int)std::min((size_t)s.max_ublocks_w, room / ((size_t)BS * BS * sizeof(double)));
     const size_t lds_w = lds + (size_t)ucap * BS * BS * sizeof(double);
-    // (F: the filled ILU(k) factor on its own column planes, the operator on J's narrow rows)
+    // (F: the filled ILU(k) factor on its own column planes, the operator on J's narrow rows; row_map: PCASM's extended
+    // system -- F's rows are the overlapped blocks', mapped to the operator's by row_map)
+    auto wide = [&](auto sp, auto fill, auto map) {
+      hipLaunchKernelGGL((k_pc_wide<BS, decltype(sp)::value, decltype(fill)::value, 0, decltype(map)::value>), grid, T, lds_w, c->stream,
+                         J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux,
+                         c->ks.partials, c->ks.nb_max, dot_mode, ucap, list, fin, F ? F->col : J.col, F ? F->n : J.n, row_map);
+    };
     with_flag(spmv, [&](auto sp) {
-      with_flag(F != nullptr, [&](auto fill) {
-        hipLaunchKernelGGL((k_pc_wide<BS, decltype(sp)::value, decltype(fill)::value>), grid, T, lds_w, c->stream, J.n, J.W, nrun,
-                           s.sub_ptr, s.sub_nlev, s.row_infow, s.row_uoffw, J.col, rp, J.val, s.fval, in, z, aux, c->ks.partials,
-                           c->ks.nb_max, dot_mode, ucap, list, fin, F ? F->col : J.col);
-      });
+      if (F && row_map) wide(sp, std::true_type{}, std::true_type{});
+      else with_flag(F != nullptr, [&](auto fill) { wide(sp, fill, std::false_type{}); });
     });
     return;
   }
@@ -163,8 +181,11 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
 }
 
 int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, const double* in, double* z,
-                 int dot_mode, const double* aux, const int* list, int nrun, const Fin* fin, const double* in2, const Bcsr* F) {
-  if (F && (!s.wide || M.dg || M.W > WMAX || F->n != M.n || F->bs != M.bs)) { c->err = "a factor pattern of its own asked of a kernel that has none"; return -1; }
+                 int dot_mode, const double* aux, const int* list, int nrun, const Fin* fin, const double* in2, const Bcsr* F,
+                 const int* row_map) {
+  if (F && (!s.wide || M.dg || M.W > WMAX || (!row_map && F->n != M.n) || F->bs != M.bs)) { c->err = "a factor pattern of its own asked of a kernel that has none"; return -1; }
+  if (row_map && !F) { c->err = "a row map without a factor pattern of its own"; return -1; }
+  if (row_map && z == in) { c->err = "the fused PCASM application cannot run in place: a block reads rows another block writes"; return -1; }
   if (in2 && (!spmv || !kind_composes(pc_kernel_kind(c, M, s)))) { c->err = "composed input asked of a kernel that cannot form it"; return -1; }
   const Fin* fin_later = nullptr;
   if (fin && dot_mode != 0 && c->env.fin_separate) { fin_later = fin; fin = nullptr; }
@@ -188,7 +209,7 @@ int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, con
     return 0;
   }
   c->ks.nb_pc = s.nsub;   // partial sums per slot this application leaves: one per brick (k_pc_wave: per workgroup, set there)
-  if (with_bs(M.bs, [&](auto bs) { launch_pc_bs<decltype(bs)::value>(c, M, s, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, F); }) != 0)
+  if (with_bs(M.bs, [&](auto bs) { launch_pc_bs<decltype(bs)::value>(c, M, s, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, F, row_map); }) != 0)
     return -1;
   if (fin_later) {
     vec_finalize(c, c->ks.nb_pc, fin_later->slot0, fin_later->nslots, fin_later->phase);

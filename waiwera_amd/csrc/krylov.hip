@@ -58,6 +58,8 @@ int read_scal_end(wai_ctx* c) {
 int launch_pc_sys(wai_ctx* c, const LinSys& sys, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
                   const int* list, int nrun, const Fin* fin, const double* in2) {
   if (pc_fill_fused(c, sys)) return launch_pc_on(c, sys.A, sys.as.sched, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, &sys.as.E);
+  if (pc_asm_fused(c, sys))
+    return launch_pc_on(c, sys.A, sys.as.sched, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, &sys.as.E, sys.as.ext_row);
   return launch_pc(c, sys.A, spmv, in, z, dot_mode, aux, list, nrun, fin, in2);
 }
 
@@ -249,7 +251,7 @@ int bcgs_mode(const wai_ctx* c) {
 // (profiles/compose_full_c4c5_ab_r5.log): C4 1.303 -> 1.265, C5 0.486 -> 0.467.  WAI_BCGS_COMPOSE=0 / 1 forces it off / on
 // (k_pc_rows -- 4 x 4 blocks, MINC inside 3-D bricks -- not measured: on request).
 bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys) {
-  if (!(pc_fused(c, sys) && !pc_fill_fused(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
+  if (!(pc_fused(c, sys) && !pc_own_factor(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
   if (const char* e = getenv("WAI_BCGS_COMPOSE")) return e[0] == '1';
   return pc_axpy_default(c, sys.A);
 }

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_stream_read(const stream_d2* __restrict
 }
 // can pc_amul form its operand x - alpha x2 inside the launch?  (pc_axpy_ok without the switch and the default)
 bool pc_operand_composable(const wai_ctx* c) {
-  return pc_fused(c, c->flow) && !pc_fill_fused(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A);
+  return pc_fused(c, c->flow) && !pc_own_factor(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A);
 }
 }  // namespace
 
@@ -53,6 +53,12 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   const bool fill = pc_fill_fused(c, sys);   // the filled ILU(k) factor: its own pattern and schedule (sys.as)
   if (which == 23 && (!pc_fused(c, sys) || !(fill ? sys.as.sched.ord_f : c->ilu.ord_f))) {
     c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh, or fused ILU(k))";
+    return -2;
+  }
+  // PCASM's fused form: the factor's rows are the extended system's (n_ext > N), the probes of one kernel class work on
+  // vectors of the system's own length
+  if (pc_asm_fused(c, sys) && (which == 9 || which == 10 || which == 16 || which == 23)) {
+    c->err = "wai_bench_kernel 9 / 10 / 16 / 23: the brick schedule's kernels and the level sets of a factor on the system's own rows, not fused PCASM";
     return -2;
   }
   if (fill && (which == 9 || which == 10 || which == 16)) { c->err = "wai_bench_kernel 9 / 10 / 16: the brick schedule's kernels, not fused ILU(k)"; return -2; }
@@ -181,6 +187,10 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
     snprintf(buf, sizeof(buf), "k_pc_wide<%d,spmv> on the filled factor (block Jacobi, ILU(%d))", bs, pc.ilu_levels);
     return buf;
   }
+  if (pc_asm_fused(c, sys)) {   // one launch: A on the Jacobian's planes by the row map, the sweeps on the extended factor's
+    snprintf(buf, sizeof(buf), "k_pc_wide<%d,spmv,map> on the extended system (ASM, ILU(%d))", bs, std::max(pc.ilu_levels, 0));
+    return buf;
+  }
   if (pc_extended(c, sys)) {
     snprintf(buf, sizeof(buf), "k_spmv + %s on the extended system (%s, ILU(%d))",
              sys.as.sched.big ? "k_lvl_solve per level" : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),
@@ -235,7 +245,7 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   LinSys& sys = c->flow;
   if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
   if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
-  if (split && (!spmv || !pc_fused(c, sys) || pc_fill_fused(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
+  if (split && (!spmv || !pc_fused(c, sys) || pc_own_factor(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
     c->err = "wai_test_pc_operator: no interior / face brick lists to split the launch over";
     return -1;
   }

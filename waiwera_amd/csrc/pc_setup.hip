@@ -109,7 +109,8 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
   // 16, the factor on this pattern's own column planes and the operator on the Jacobian's (k_pc_wide<.., FILL>).  LDS: one
   // solution entry per thread and the reduction scratch must fit the 64 KB a workgroup may ask for (1024 rows of 4 x 4
   // blocks: 33 408 bytes); what is left parks upper blocks, rows that do not fit re-read theirs (launch_pc_bs: ucap).
-  // Wider fill or larger subdomains keep the launch-per-level path.
+  // Wider fill or larger subdomains keep the launch-per-level path.  PCASM's extended system asks the same way (build_asm,
+  // asm_fuse_wanted: any k >= 0, so W may be 8 or less): blocks that do not fit keep the schedule they always had.
   s.sublu = sublu;
   const size_t lds_fill = ((size_t)(((s.max_rows + 63) / 64) * 64) * np + 80) * sizeof(double);
   s.wide = !sublu && allow_wide && W <= 16 && s.max_rows <= 1024 &&
@@ -409,12 +410,24 @@ int ghost_rows(wai_ctx* c, const LinSys& sys, std::vector<int>& grp, std::vector
   return 0;
 }
 
-// Does block-Jacobi ILU(k) on `sys` ask for the fused launch (AsmSystem::fuse_asked)?  The flow system alone, on a mesh of at
+// Does the extended system of `sys` ask for a fused launch (AsmSystem::fuse_asked)?  Block-Jacobi ILU(k), k > 0:  The flow system alone, on a mesh of at
 // most 8 blocks per row, on one rank, without the source network's blocks in the factor.  Several ranks keep the
 // launch-per-level path: the extended system's schedule carries no interior / face lists for the overlapped halo exchange.
 static bool iluk_fuse_wanted(const wai_ctx* c, const LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
   return levels > 0 && overlap == 0 && !with_net && !sublu && &sys == &c->flow && !sys.A.dg && c->pat.W <= 8 &&
          !(c->comm && c->comm->nranks > 1) && !c->env.iluk_level_path;
+}
+
+// Does PCASM on `sys` ask for the fused launch?  The same conditions with an overlap and any k >= 0: the extended system's
+// rows are then not the system's own, and k_pc_wide's two-pattern form reads the operator through AsmSystem::ext_row
+// (k_pc_wide<.., MAP>).  Several ranks keep today's launches: the overlap's ghost rows need (A x) two layers deep.
+// WAI_ASM_UNFUSED=1 keeps them everywhere (the tests' comparison, and the way back).
+static bool asm_fuse_wanted(const wai_ctx* c, const LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
+  return overlap > 0 && levels >= 0 && !with_net && !sublu && &sys == &c->flow && !sys.A.dg && c->pat.W <= 8 &&
+         !(c->comm && c->comm->nranks > 1) && !c->env.asm_unfused;
+}
+static bool fuse_wanted(const wai_ctx* c, const LinSys& sys, int overlap, int levels, bool with_net, bool sublu) {
+  return iluk_fuse_wanted(c, sys, overlap, levels, with_net, sublu) || asm_fuse_wanted(c, sys, overlap, levels, with_net, sublu);
 }
 
 // sublu: complete fill instead (sub-preconditioner lu; levels is 0 then)
@@ -547,10 +560,11 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, b
       a.E_val.alloc(c, ell_size(np, n_ext, W)) || a.r_ext.alloc(c, (size_t)np * n_ext + 16))
     return -1;
   a.E.col = a.E_col; a.E.val = a.E_val;
-  const bool fuse = iluk_fuse_wanted(c, sys, overlap, levels, with_net, sublu);
+  // (`fill` of build_schedule: the factor has column planes of its own -- ILU(k)'s filled rows, or PCASM's extended blocks)
+  const bool fuse = fuse_wanted(c, sys, overlap, levels, with_net, sublu) && !cross;
   if (int e = build_schedule(c, a.sched, erp, ecol, ext_ptr, n_ext, W, np, false, levels == 0 || fuse, sublu, fuse)) return e;
   a.fuse_asked = fuse;
-  a.fused = fuse && a.sched.wide && n_ext == N;
+  a.fused = fuse && a.sched.wide && (overlap > 0 || n_ext == N);   // (no overlap: E's rows are the system's own, in order)
   a.with_net = with_net;
   a.n_net = 0;
   if (mnet > 0) {   // where the blocks of the network's E land in the extended planes
@@ -661,7 +675,7 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
       const int lv = sl ? 0 : std::max(pc.ilu_levels, 0);   // (ilu_levels is ignored under sub-preconditioner lu)
       const bool wn = pc_with_net(c, sys);
       if (as.overlap != ov || as.levels != lv || as.sublu != sl || as.E.bs != A.bs || as.with_net != wn ||
-          as.fuse_asked != iluk_fuse_wanted(c, sys, ov, lv, wn, sl)) {
+          as.fuse_asked != fuse_wanted(c, sys, ov, lv, wn, sl)) {
         // (a refusal of sub-preconditioner lu is the caller's to read: -2 with its text)
         if (int e = build_asm(c, sys, ov, lv, wn, sl)) return sl && e == -2 ? -2 : (e < 0 ? -1 : e);
       }

@@ -30,6 +30,15 @@ namespace wai {
 // the SAME registers at once between the sweeps: two round trips per brick instead of two per level, the sweeps touch LDS
 // alone, and nothing is parked (LDS: the solution and the reduction scratch).  Same arithmetic in the same order as the
 // form above.  tools/iluk_fused_timing.py times both forms against the launch-per-level path on the same factor.
+// MAP (with FILL): the factor's rows are not the operator's -- PCASM's extended system (AsmSystem::E, any overlap, ILU(k),
+// k >= 0).  Two row counts: thread tid of block s is FACTOR row fi = sub_ptr[s] + tid of nf = n_ext rows, and everything read
+// through the factor's planes (fval, fcol, row_infow, row_uoffw, the parked blocks) is indexed by fi with plane stride nf;
+// it stands for OPERATOR row i = ext_row[fi] & 0x7fffffff of n rows, and everything of the operator (col, aval, rowptr,
+// in, aux, z) is indexed by i with plane stride n.  The load phase is t_fi = (A x)_i by the same ell_row_mult call as
+// k_spmv makes on row i (the bits the unfused path gathers), or in[i]; the sweeps are unchanged; z[i] is stored only where
+// ext_row[fi] < 0 -- the rows the block owns (restricted Schwarz), each owned by exactly one block, so the inner products
+// masked the same way are the whole-vector products.  NOT in place: a block reads `in` at rows another block writes
+// (launch_pc_on refuses z == in).
 // stage_blocks issues NS column and block loads for every row, branch-free: a row with fewer blocks re-reads its own pivot
 // slot as filler (in bounds, never used; the same lines the pivot load fetches, so cache hits rather than HBM bytes).
 template <int BS, int NS>
@@ -58,7 +67,7 @@ __device__ __forceinline__ void staged_row_sub(int cnt, const int (&kc)[NS], con
   }
 }
 
-template <int BS, bool SPMV, bool FILL = false, int NS = 0>
+template <int BS, bool SPMV, bool FILL = false, int NS = 0, bool MAP = false>
 __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const int* __restrict__ sub_ptr,
                                                   const int* __restrict__ sub_nlev,
                                                   const unsigned long long* __restrict__ row_infow,
@@ -67,8 +76,11 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
                                                   const double* __restrict__ fval, const double* __restrict__ in,
                                                   double* __restrict__ z, const double* __restrict__ aux, double* partials,
                                                   int nb_max, int dot, int ucap, const int* __restrict__ sub_list, Fin fin,
-                                                  const int* __restrict__ fcol) {
+                                                  const int* __restrict__ fcol, int nf_map,
+                                                  const int* __restrict__ ext_row) {
+  static_assert(FILL || !MAP, "a row map needs the factor's own column planes");
   constexpr int BB = BS * BS;
+  const int nf = MAP ? nf_map : n;   // rows (plane stride) of the factor; n: of the operator
   const int* __restrict__ fc = FILL ? fcol : col;   // the factor's column planes
   extern __shared__ __attribute__((aligned(16))) double lds[];  // [T * BS] solution, 80 doubles reduction scratch, [ucap][BB] parked upper blocks
   if (fin_block(fin, partials, nb_max)) return;
@@ -77,8 +89,15 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
   if (sub_list) s = sub_list[s];
   const int lo = sub_ptr[s], R = sub_ptr[s + 1] - lo;
   const int nl = sub_nlev[s], nlf = nl & 0xffff, nlb = nl >> 16;
-  const int tid = threadIdx.x, i = lo + tid;
+  const int tid = threadIdx.x, fi = lo + tid;   // the factor's row ...
   const bool active = tid < R;
+  int i = fi;                                   // ... and the operator's
+  bool own = active;                            // z[i] is this block's to write
+  if constexpr (MAP) {
+    const int er = active ? ext_row[fi] : 0;
+    i = er & 0x7fffffff;
+    own = er < 0;
+  }
   double* ys = lds;
   double* red = lds + (size_t)blockDim.x * BS;
   double* park = red + 80;
@@ -88,7 +107,7 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
   int kc[NSR];            // NS > 0: the staged blocks' columns (brick-local) and values
   double mb[NSR][BB];
   if (active) {
-    unpack_info_w(row_infow[i], lfirst, dslot, ulast, lf, lb);
+    unpack_info_w(row_infow[fi], lfirst, dslot, ulast, lf, lb);
     double acc[BS];
     if constexpr (SPMV) {
 #pragma unroll
@@ -98,15 +117,15 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
       load_x<BS>(in, i, acc);
     }
     if constexpr (NS > 0) {
-      stage_blocks<BS, NS>(n, i, lo, lfirst, dslot - lfirst, dslot, fc, fval, kc, mb);
+      stage_blocks<BS, NS>(nf, fi, lo, lfirst, dslot - lfirst, dslot, fc, fval, kc, mb);
     } else {
-      uo = row_uoffw[i];
+      uo = row_uoffw[fi];
       parked = uo + (ulast - dslot - 1) <= ucap;
     }
     if (parked) {
       for (int q = dslot + 1; q < ulast; q++) {
         double blk[BB];
-        load_block<BS>(fval, n, q, i, blk);
+        load_block<BS>(fval, nf, q, fi, blk);
         double* p = park + (size_t)(uo + q - dslot - 1) * BB;
 #pragma unroll
         for (int e = 0; e < BB; e++) p[e] = blk[e];
@@ -125,9 +144,9 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
         staged_row_sub<BS, NS>(dslot - lfirst, kc, mb, ys, a);
       } else {
         for (int q = lfirst; q < dslot; q++) {
-          const int k = fc[(size_t)q * n + i] - lo;
+          const int k = fc[(size_t)q * nf + fi] - lo;
           double m[BB], yk[BS];
-          load_block<BS>(fval, n, q, i, m);
+          load_block<BS>(fval, nf, q, fi, m);
 #pragma unroll
           for (int c = 0; c < BS; c++) yk[c] = ys[k * BS + c];
 #pragma unroll
@@ -148,9 +167,9 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
   for (int r = 0; r < BS; r++) out[r] = 0.0;
 #pragma unroll
   for (int e = 0; e < BB; e++) dv[e] = 0.0;
-  if (active) load_block<BS>(fval, n, dslot, i, dv);
+  if (active) load_block<BS>(fval, nf, dslot, fi, dv);
   if constexpr (NS > 0) {   // the upper blocks take the lower blocks' registers
-    if (active) stage_blocks<BS, NS>(n, i, lo, dslot + 1, ulast - dslot - 1, dslot, fc, fval, kc, mb);
+    if (active) stage_blocks<BS, NS>(nf, fi, lo, dslot + 1, ulast - dslot - 1, dslot, fc, fval, kc, mb);
   }
   for (int lev = 0; lev < nlb; lev++) {
     if (lb == lev) {
@@ -159,14 +178,14 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
       for (int r = 0; r < BS; r++) a[r] = ys[tid * BS + r];
       if constexpr (NS > 0) staged_row_sub<BS, NS>(ulast - dslot - 1, kc, mb, ys, a);
       for (int q = dslot + 1; NS == 0 && q < ulast; q++) {
-        const int k = fc[(size_t)q * n + i] - lo;
+        const int k = fc[(size_t)q * nf + fi] - lo;
         double m[BB], xk[BS];
         if (parked) {
           const double* p = park + (size_t)(uo + q - dslot - 1) * BB;
 #pragma unroll
           for (int e = 0; e < BB; e++) m[e] = p[e];
         } else {
-          load_block<BS>(fval, n, q, i, m);
+          load_block<BS>(fval, nf, q, fi, m);
         }
 #pragma unroll
         for (int c = 0; c < BS; c++) xk[c] = ys[k * BS + c];
@@ -187,16 +206,20 @@ __global__ __launch_bounds__(1024) void k_pc_wide(int n, int W, int nsub, const 
     }
     if (lev + 1 < nlb) __syncthreads();
   }
-  if (active) {
+  if (own) {
 #pragma unroll
     for (int r = 0; r < BS; r++) z[(size_t)i * BS + r] = out[r];
   }
   if (dot != 0) {
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    pc_row_dots<BS, false, false>(dot, v, out, active, [&](double (&x)[BS]) {   // the operand again (an L2 hit), not held
+    if constexpr (MAP) {   // an overlap row's result is some other block's term (modes 2 and 3 sum unmasked rows)
+#pragma unroll
+      for (int r = 0; r < BS; r++) out[r] = own ? out[r] : 0.0;
+    }
+    pc_row_dots<BS, false, false>(dot, v, out, own, [&](double (&x)[BS]) {   // the operand again (an L2 hit), not held
 #pragma unroll
       for (int r = 0; r < BS; r++) x[r] = 0.0;
-      if (active) load_x<BS>(in, i, x);
+      if (own) load_x<BS>(in, i, x);
     }, [&](double (&a)[BS]) { load_x_stream<BS>(aux, i, a); });
     __syncthreads();
     pc_reduce_dots(dot, v, red, partials, nb_max, s);
