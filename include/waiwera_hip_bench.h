@@ -54,6 +54,9 @@ int wai_pc_axpy_capable(wai_ctx *ctx);
 /* partial sums per reduction slot the last preconditioner application (or vec_dots) left: one per brick, one per workgroup
  * of four bricks under k_pc_wave; more than 1024 means the finalisation ran in slices (tests/test_hip_fused_operator.py) */
 int wai_test_partial_count(wai_ctx *ctx);
+/* the brick schedule's shared descriptor tables (k_pc_park on its 16-bit column indices): returns the number of distinct
+ * templates, bricks and rows the number of bricks and of template rows (24 bytes each); 0 when the schedule has none */
+int wai_test_desc_templates(wai_ctx *ctx, int *bricks, int *rows);
 /* one vector / reduction step of the Krylov drivers, issued through the drivers' own launchers, for the tests
  * (tests/test_hip_krylov_vec.py).  n >= 1 entries per vector, whatever the context's mesh.  vecs: seven host vectors of
  * len >= n doubles each, X R RP P V S T in this order, in and out whole (the entries behind n are guards); basis (GMRES ops):

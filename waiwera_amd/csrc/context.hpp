@@ -251,6 +251,16 @@ struct IluSchedule {
   // its six neighbour bricks).  Null when some brick would need more than 8 segments: the int32 planes serve then.
   DevBuf<unsigned short> col16;      // [n][8]: the (<= 8) slots of a row together, 16 bytes -- one load per row instead of one per slot
   DevBuf<int> sub_seg;               // [nsub][8]
+  // With the indices brick-local, everything a row's descriptors say -- row_info, row_uoff, its col16 record: 24 bytes -- is
+  // brick-local, and bricks of the same shape and surroundings have the same descriptors byte for byte (216^3 in 16 x 16 x 2
+  // bricks: 13 x 13 x 108 of the 14 x 14 x 108 are full interior bricks).  k_pc_park on col16 reads ONE copy of each
+  // distinct table (a template: rows [sub_desc[s], sub_desc[s] + rows of brick s) of t_*), small enough to stay in L2,
+  // instead of streaming every brick's own from HBM.  A mesh without repeats gets one template per brick.
+  // WAI_NO_DESC_SHARE (read_env): the same kernel on the per-row arrays, sub_desc = sub_ptr.
+  DevBuf<int> t_info, t_uoff;        // [template rows]
+  DevBuf<unsigned short> t_col16;    // [template rows][8]
+  DevBuf<int> sub_desc;              // [nsub]: first row of the brick's template
+  int n_templates = 0, template_rows = 0;
   bool level_sorted = false;  // every subdomain's rows are stored in dependency-level order (forward levels non-decreasing,
                               // backward levels non-increasing with the row index)
   // subdomains of more than 1024 rows ("one block per rank", sub_ptr = NULL, is the reference's
@@ -563,10 +573,11 @@ struct wai_ctx : wai::Handles {
   // not per launch: WAI_FIN_SEPARATE, WAI_NO_COL16 (k_pc_park on the int32 column planes), WAI_BCGS_SCALAR_KERNELS
   // WAI_ILUK_LEVEL_PATH: block-Jacobi ILU(k) keeps the launch-per-level path where the fused launch would serve (tests
   // that compare the two paths in one process; read at the preconditioner's set-up); WAI_ASM_UNFUSED: PCASM likewise keeps
-  // its launches (k_spmv, gather, the sweeps on the extended system, scatter, the reductions) where the fused one would serve
+  // its launches (k_spmv, gather, the sweeps on the extended system, scatter, the reductions) where the fused one would serve;
+  // WAI_NO_DESC_SHARE: k_pc_park on col16 reads every brick's own descriptors instead of the shared templates
   struct EnvSw {
     bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false;
-    bool asm_unfused = false;
+    bool asm_unfused = false; bool no_desc_share = false;
   } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
   // halo

@@ -23,6 +23,7 @@ void read_env(wai_ctx* c) {
   c->env.scalar_kernels = getenv("WAI_BCGS_SCALAR_KERNELS") != nullptr;   // several ranks: the one-thread kernels behind the all-reduces (rounds 3-4)
   c->env.iluk_level_path = getenv("WAI_ILUK_LEVEL_PATH") != nullptr;
   c->env.asm_unfused = getenv("WAI_ASM_UNFUSED") != nullptr;
+  c->env.no_desc_share = getenv("WAI_NO_DESC_SHARE") != nullptr;
 }
 
 // which fused kernel serves (matrix, schedule; context.hpp).  Kinds 1 .. 3 can form their input on the fly (in - alpha in2:
@@ -156,10 +157,18 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
       stagger.ncu = c->n_cu;
       stagger.per_cu = std::max(1, std::min(3, (int)((size_t)160 * 1024 / (lds_park + 704))));
       stagger.ticks = 600;
-      with_flag(s.col16 && !c->env.no_col16, [&](auto c16) {
+      const bool on16 = s.col16 && !c->env.no_col16;
+      // on col16 the descriptors come from the shared templates (IluSchedule::sub_desc), or -- WAI_NO_DESC_SHARE -- from the
+      // per-row arrays through the same indexing: a brick's first row is its template's
+      const bool shared = on16 && s.sub_desc && !c->env.no_desc_share;
+      const int* d_info = shared ? s.t_info.get() : s.row_info.get();
+      const int* d_uoff = shared ? s.t_uoff.get() : s.row_uoff.get();
+      const unsigned short* d_c16 = shared ? s.t_col16.get() : s.col16.get();
+      const int* d_desc = shared ? s.sub_desc.get() : s.sub_ptr.get();
+      with_flag(on16, [&](auto c16) {
         sp_ax([&](auto sp, auto ax) {
           hipLaunchKernelGGL((k_pc_park<decltype(sp)::value, decltype(ax)::value, decltype(c16)::value>), grid, T, lds_park, c->stream,
-                             J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, s.row_info, s.row_uoff, J.col, s.col16, s.sub_seg, s.fval, s.dinv,
+                             J.n, J.W, nrun, s.sub_ptr, s.sub_nlev, d_desc, d_info, d_uoff, J.col, d_c16, s.sub_seg, s.fval, s.dinv,
                              in, in2, scal, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, list, fin, stagger);
         });
       });

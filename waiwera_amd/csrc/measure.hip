@@ -286,6 +286,13 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
 }
 int wai_pc_axpy_capable(wai_ctx* c) { return c ? (pc_operand_composable(c) ? 1 : 0) : -2; }
 int wai_test_partial_count(wai_ctx* c) { return c ? c->ks.nb_pc : -2; }
+int wai_test_desc_templates(wai_ctx* c, int* bricks, int* rows) {
+  if (!c) return -2;
+  const bool have = c->ilu.sub_desc != nullptr;
+  if (bricks) *bricks = c->ilu.nsub;
+  if (rows) *rows = have ? c->ilu.template_rows : 0;
+  return have ? c->ilu.n_templates : 0;
+}
 // one vector / reduction step of the Krylov drivers through the drivers' own launchers (waiwera_hip_bench.h): temporaries of
 // the caller's padded lengths, all NSCAL scalars seeded, every partial slot emptied as ksp_gmres empties them before its
 // first producer, the launchers unchanged, everything back to the caller -- guard elements included

@@ -42,7 +42,7 @@ namespace wai {
 template <bool SPMV, bool AX, bool C16>
 __global__ __launch_bounds__(512, 6) void k_pc_park(
     int n, int W, int nsub, const int* __restrict__ sub_ptr, const int* __restrict__ sub_nlev,
-    const int* __restrict__ row_info, const int* __restrict__ row_uoff, const int* __restrict__ col,
+    const int* __restrict__ sub_desc, const int* __restrict__ row_info, const int* __restrict__ row_uoff, const int* __restrict__ col,
     const unsigned short* __restrict__ col16, const int* __restrict__ sub_seg,
     const double* __restrict__ sval, const double* __restrict__ dinv, const double* __restrict__ in,
     const double* __restrict__ in2, const double* __restrict__ scal,
@@ -57,9 +57,13 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   if (s >= nsub) return;
   if (sub_list) s = sub_list[s];
   const int lo = sub_ptr[s], R = sub_ptr[s + 1] - lo;
+  // C16: row_info, row_uoff and col16 are the descriptor templates, the brick's rows from sub_desc[s] on (requested beside
+  // sub_ptr, not behind it); otherwise the per-row arrays
+  int dlo = lo;
+  if constexpr (C16) dlo = sub_desc[s];
   const int nl = sub_nlev[s];
   const int nlf = nl & 0xffff, nlb = nl >> 16;
-  const int tid = threadIdx.x, i = lo + tid;
+  const int tid = threadIdx.x, i = lo + tid, di = dlo + tid;
   const bool active = tid < R;
   const double nalpha = AX ? -scal[S_ALPHA] : 0.0;   // input = in - alpha in2 (uniform: a scalar load)
   stagger_start(stagger);
@@ -77,8 +81,8 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   int lfirst = 0, dslot = 0, ulast = 0;
   int cgs[WMAX];
   if (active) {
-    unpack_info(row_info[i], lfirst, dslot, ulast, lf, lb);
-    uo = row_uoff[i];
+    unpack_info(row_info[di], lfirst, dslot, ulast, lf, lb);
+    uo = row_uoff[di];
     nU = ulast - dslot - 1;
     // (MEASURED AND REMOVED, round 6: slot 0's block -- which needs nothing but the row number -- requested here, together with
     // the descriptors and the index record, one dependent round trip less per brick: 77 VGPRs, no scratch, same bits, and
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       const int* sg = sub_seg + (size_t)s * 8;     // wave-uniform
       const int g0 = sg[0], g1 = sg[1], g2 = sg[2], g3 = sg[3], g4 = sg[4], g5 = sg[5], g6 = sg[6], g7 = sg[7];
       typedef unsigned wai_u4v __attribute__((ext_vector_type(4)));
-      const wai_u4v pk = __builtin_nontemporal_load(reinterpret_cast<const wai_u4v*>(col16) + i);   // the row's eight 16-bit entries
+      const wai_u4v pk = reinterpret_cast<const wai_u4v*>(col16)[di];   // the row's eight 16-bit entries (no streaming hint: a template's lines are meant to stay cached)
       const unsigned pw[4] = {pk.x, pk.y, pk.z, pk.w};
       unsigned cu[WMAX];
 #pragma unroll
@@ -126,6 +130,10 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
           load_xs<BS, AX>(in, in2, nalpha, cg, xv);
           acc[0] += blk[0] * xv[0] + blk[1] * xv[1];
           acc[1] += blk[2] * xv[0] + blk[3] * xv[1];
+          // the diagonal slot gathered the row's own operand entry: kept for the inner products (the slot, not cg == i --
+          // the padding slots of a short row carry the own column too)
+          xin[0] = q == dslot ? xv[0] : xin[0];
+          xin[1] = q == dslot ? xv[1] : xin[1];
         }
         const bool isl = (q >= lfirst) && (q < dslot), isu = (q > dslot) && (q < ulast);
 #pragma unroll
@@ -149,8 +157,10 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       load_pivot<BS>(dinv, n, i, dv);
       acc[0] = dv[0] * r[0] + dv[1] * r[1];
       acc[1] = dv[2] * r[0] + dv[3] * r[1];
+      xin[0] = r[0]; xin[1] = r[1];
     }
-    if (dot == PC_DOT_XZ || dot == PC_DOT_MERGED) load_xs<BS, AX>(in, in2, nalpha, i, xin);
+    // (xin: no load of its own -- until round 7 a second fetch of the row's entry here, waited for in front of the first
+    // barrier)
     if (dot == PC_DOT_ZA || dot == PC_DOT_MERGED) load_x_stream<BS>(aux, i, avp);   // the dot product's partner: in flight through the sweeps
   }
   if (active) *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(acc[0], acc[1]);

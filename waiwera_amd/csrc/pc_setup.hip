@@ -3,6 +3,7 @@
 // boundaries, level-of-fill patterns), the dense block inverses of PCLU, and the numeric set-up that PCSetUp stands for
 // (src/timestepper.F90:1645-1836).
 #include "host.hpp"
+#include <unordered_map>
 
 using namespace wai;
 
@@ -259,6 +260,9 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
     }
     if (any && s.sub_split.upload(c, split)) return -1;
   }
+  // (a schedule built again keeps nothing of the one before: a mesh that bails out below must not run on, or report, stale tables)
+  s.col16.reset(); s.sub_seg.reset(); s.t_info.reset(); s.t_uoff.reset(); s.t_col16.reset(); s.sub_desc.reset();
+  s.n_templates = 0; s.template_rows = 0;
   if (np == 2 && W <= 8 && !s.big && s.park && s.diag_only && s.scaled && s.fast3 && s.max_rows <= 512) {
     // k_pc_park will serve: its column indices as 16-bit (segment, offset) pairs -- 14 of a row's 304 bytes less per launch
     std::vector<unsigned short> c16((size_t)8 * N, 0);      // [row][8]: a row's indices are ONE 16-byte load
@@ -300,6 +304,44 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       }
     }
     if (ok && (s.col16.upload(c, c16) || s.sub_seg.upload(c, seg))) return -1;
+    if (ok) {
+      // one copy of identical brick descriptors (IluSchedule::t_*): two bricks share a template when they have the same row
+      // count and the same row_info, row_uoff and col16 bytes.  The hash finds candidates, memcmp decides
+      std::vector<int> tinfo, tuoff, desc(s.nsub), tfirst, trows;   // template k: rows [tfirst[k], tfirst[k] + trows[k]) of t*
+      std::vector<unsigned short> tc16;
+      std::unordered_map<unsigned long long, std::vector<int>> seen;   // hash -> templates
+      auto mix = [](unsigned long long h, const void* p, size_t bytes) {
+        const unsigned* w = static_cast<const unsigned*>(p);
+        for (size_t k = 0; k < bytes / 4; k++) h = (h ^ w[k]) * 0x100000001b3ull;
+        return h;
+      };
+      for (int sd = 0; sd < s.nsub; sd++) {
+        const int lo = sub[sd], R = sub[sd + 1] - lo;
+        unsigned long long h = mix(0xcbf29ce484222325ull, &R, sizeof(int));
+        h = mix(h, info.data() + lo, sizeof(int) * R);
+        h = mix(h, uoff.data() + lo, sizeof(int) * R);
+        h = mix(h, c16.data() + (size_t)lo * 8, sizeof(unsigned short) * 8 * R);
+        std::vector<int>& cand = seen[h];
+        int t = -1;
+        for (int k : cand) {
+          const int f = tfirst[k];
+          if (trows[k] == R && !memcmp(tinfo.data() + f, info.data() + lo, sizeof(int) * R) &&
+              !memcmp(tuoff.data() + f, uoff.data() + lo, sizeof(int) * R) &&
+              !memcmp(tc16.data() + (size_t)f * 8, c16.data() + (size_t)lo * 8, sizeof(unsigned short) * 8 * R)) { t = k; break; }
+        }
+        if (t < 0) {
+          t = (int)tfirst.size();
+          tfirst.push_back((int)tinfo.size()); trows.push_back(R);
+          tinfo.insert(tinfo.end(), info.begin() + lo, info.begin() + lo + R);
+          tuoff.insert(tuoff.end(), uoff.begin() + lo, uoff.begin() + lo + R);
+          tc16.insert(tc16.end(), c16.begin() + (size_t)lo * 8, c16.begin() + (size_t)(lo + R) * 8);
+          cand.push_back(t);
+        }
+        desc[sd] = tfirst[t];
+      }
+      s.n_templates = (int)tfirst.size(); s.template_rows = (int)tinfo.size();
+      if (s.t_info.upload(c, tinfo) || s.t_uoff.upload(c, tuoff) || s.t_col16.upload(c, tc16) || s.sub_desc.upload(c, desc)) return -1;
+    }
   }
   s.built = true;
   return 0;

@@ -432,6 +432,13 @@ class FlowSimulation:
         """partial sums per reduction slot the last preconditioner application left (wai_test_partial_count)"""
         return self._chk(LIB.wai_test_partial_count(self.h), "test_partial_count")
 
+    def desc_templates(self):
+        """(distinct descriptor templates, bricks, template rows) of the brick schedule k_pc_park reads on its 16-bit column
+        indices (wai_test_desc_templates); (0, bricks, 0) when the schedule has none"""
+        nb, nr = C.c_int(0), C.c_int(0)
+        nt = self._chk(LIB.wai_test_desc_templates(self.h, C.byref(nb), C.byref(nr)), "test_desc_templates")
+        return nt, nb.value, nr.value
+
     KV_OPS = ("dot", "dots", "waxpy", "bcgs_p", "bcgs_s", "bcgs_xr", "bcgs_xrp", "bcgs_xrp_derive", "scalars", "mdot",
               "maxpy_norm", "scale_to", "update_x")
     KV_VECS = ("X", "R", "RP", "P", "V", "S", "T")
