@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/waiwera_hip.h"
 #include "devbuf.hpp"
+#include "ilu_schedule.hpp"   // ScheduleFacts
 #include "mesh_pattern.hpp"   // MAX_CELL_FACES
 #include "physics.hip.h"
 
@@ -212,39 +213,25 @@ struct Pattern {
 };
 
 struct LinSys;
-// Block-Jacobi ILU(0): one workgroup per subdomain, one thread per block row.
-struct IluSchedule {
-  int nsub = 0, max_rows = 0, max_lev = 0;
+// Block-Jacobi ILU(0): one workgroup per subdomain, one thread per block row.  The facts (sizes, extremes, the flags the
+// kernel selection reads, the host copy `sub` of sub_ptr, the level sets' row ranges) are ScheduleFacts' (ilu_schedule.hpp,
+// where build_host_schedule makes them and every table on the host); here are the tables on the device.
+struct IluSchedule : ScheduleFacts {
   DevBuf<int> sub_ptr;      // nsub+1 row ranges
   DevBuf<int> sub_nlev;     // per subdomain: forward levels | backward levels << 16
   DevBuf<int> sub_split;    // per subdomain: leading rows longer than half the block-ELL width (k_pc_rows: MINC bricks), or null
   DevBuf<int> row_info;     // per row: lfirst | dslot<<4 | ulast<<8 | lev_f<<12 | lev_b<<22 (big, wide: lfirst | dslot<<8 | ulast<<16)
-  // rows of 9 .. 16 blocks in subdomains of <= 1024 rows (cells with up to 16 faces): k_ilu_factor_wide and k_pc_wide read
-  // the 64-bit descriptor, lfirst | dslot<<5 | ulast<<10 in the low word, lev_f | lev_b<<10 in the high one
-  bool wide = false;
-  DevBuf<unsigned long long> row_infow;
+  DevBuf<unsigned long long> row_infow;   // wide: the 64-bit descriptor
   DevBuf<double> fval;      // factor in the matrix' block-ELL layout; the diagonal slot holds
                             // the inverted pivot block
   DevBuf<double> dinv;      // inverted pivot blocks, SoA [bb][n]
-  bool diag_only = false;   // ILU(0) touches no off-diagonal block in any subdomain (== DILU)
-  bool scaled = true;       // diag_only: rows pre-scaled by the inverted pivots
-  bool park = true;         // k_pc_park: upper blocks parked in LDS
   DevBuf<int> row_uoff;     // first parked upper block of a row inside its subdomain
   DevBuf<int> row_tslot;    // per row: slot of A_ki in row k for each of its (<= 4) in-subdomain lower couplings k, 4 bits each (15: none)
-  int max_nl = 0;           // most in-subdomain lower couplings of any row
-  bool park2 = false;
   DevBuf<int> sub_int;      // subdomains none of whose rows has a partition-ghost column ...
   DevBuf<int> sub_bnd;      // ... and the others (device lists; null on a single rank)
-  int n_int = 0, n_bnd = 0;
   DevBuf<int> sub_order;    // launch order of all subdomains when they differ in cost (ragged bricks): inside each XCD's
                             // contiguous eighth the long ones first, so the short ones make the tail; null: uniform
-  int max_ublocks = 0;      // most in-subdomain upper blocks of any subdomain
-  bool fast3 = false;         // <= 3 lower and <= 3 upper in-subdomain couplings per row, offsets < 4
-  int max_nlu = 0;            // most lower or upper in-subdomain couplings of any row
-  bool rows_kernel = false;   // k_pc_rows (one thread per scalar row) applies and is selected
-  bool wave_kernel = false;   // k_pc_wave (one wave per brick of <= 64 block rows) applies and is selected
   DevBuf<int> row_uoffw;      // first parked upper block of a row inside its subdomain, all (<= 4) uppers counted
-  int max_ublocks_w = 0;
   // Brick-local 16-bit column indices for k_pc_park (2 x 2 blocks): entry = segment << 13 | offset, column = the brick's
   // sub_seg[segment] + offset.  Segment 0 starts at the brick's own first row; the others cover what its rows reach in
   // other bricks and among the ghost columns, windows of 8192 columns each (a 16 x 16 x 2 brick of a structured mesh:
@@ -260,23 +247,8 @@ struct IluSchedule {
   DevBuf<int> t_info, t_uoff;        // [template rows]
   DevBuf<unsigned short> t_col16;    // [template rows][8]
   DevBuf<int> sub_desc;              // [nsub]: first row of the brick's template
-  int n_templates = 0, template_rows = 0;
-  bool level_sorted = false;  // every subdomain's rows are stored in dependency-level order (forward levels non-decreasing,
-                              // backward levels non-increasing with the row index)
-  // subdomains of more than 1024 rows ("one block per rank", sub_ptr = NULL, is the reference's
-  // PCBJACOBI / PCASM default): rows of equal dependency level are independent across all
-  // subdomains, so the factorisation and the two substitutions run as one launch per level over
-  // the rows of that level (stored factor, unfused)
-  bool big = false;
-  // sub-preconditioner lu (wai_set_sub_pc): the pattern carries the complete fill of every block -- one row per dependency
-  // level -- and k_sublu_factor / k_sublu_solve (pc_lu.hip.h) serve it: one workgroup per block, rows in order.  Such a
-  // schedule is `big` as well (8-bit slot descriptors) but has no level sets
-  bool sublu = false;
-  int nlev_f = 0, nlev_b = 0;
-  DevBuf<int> ord_f;          // rows sorted by forward level, ...
-  DevBuf<int> ord_b;          // ... by backward level
-  std::vector<int> lev_f_ptr, lev_b_ptr;   // host: row ranges of each level in ord_f / ord_b
-  bool built = false;
+  DevBuf<int> ord_f;          // big, wide: rows sorted by forward level, ...
+  DevBuf<int> ord_b;          // ... by backward level (row ranges of each level: lev_f_ptr / lev_b_ptr)
   // wai_ctx::ilu only: the system whose preconditioner is set up now (null: none) -- the factor buffers above are shared by
   // the flow and the scalar tracer systems, and one record serves the extended systems' and the coupled system's own
   // buffers too.  Set by do_pc_setup; pc_invalidate when a system's values or the preconditioner's kind change

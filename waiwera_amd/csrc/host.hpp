@@ -1,7 +1,8 @@
 // Host-side internals of libwaiwera_hip.so shared by its translation units (capi.hip: the ode_type hooks and the Newton
 // iteration; context.hip: the context and its set-up; sources.hip: sources and their controls; tracers.hip: the tracer
-// problem; pc_setup.hip: symbolic phases and factorisations; krylov.hip: the Krylov drivers and the preconditioned
-// operator; network.hip: the source network; measure.hip: measurement entry points).  Not part of the ABI.
+// problem; pc_setup.hip: symbolic phases -- made on the host alone by ilu_schedule.hpp and asm_pattern.hpp, which
+// tests/pc_setup_host runs without a device, and uploaded there -- and factorisations; krylov.hip: the Krylov drivers and
+// the preconditioned operator; network.hip: the source network; measure.hip: measurement entry points).  Not part of the ABI.
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -34,7 +34,7 @@ int pc_kernel_kind(const wai_ctx* c, const Bcsr& J, const IluSchedule& s) {
   if (c->dbg) return 0;
   if (s.wave_kernel && J.bs >= 3) return 3;
   if (s.rows_kernel) return 2;
-  if (J.bs == 2 && s.park && s.diag_only && s.scaled && s.fast3 && pc_threads(s) <= 512) return 1;
+  if (park_serves(s, J.bs)) return 1;   // (ilu_schedule.hpp: the rule the col16 tables are built by)
   return 0;
 }
 static bool kind_composes(int kind) { return kind >= 1 && kind <= 3; }

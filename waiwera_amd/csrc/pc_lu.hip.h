@@ -1,5 +1,5 @@
 // Sub-preconditioner lu (wai_set_sub_pc, WAI_SUB_LU): the exact LU factorisation of every subdomain block of the extended
-// system -- ILU with every level of fill kept (pc_setup.hip: iluk_fill without a level bound) -- and its two substitutions.
+// system -- ILU with every level of fill kept (asm_pattern.hpp: iluk_fill without a level bound) -- and its two substitutions.
 // Complete fill gives rows of tens to a few hundred blocks and a dependency chain as long as the block (one row per
 // level), so neither the thread-per-row brick kernels nor a launch per level fit: both kernels here give a block to ONE
 // workgroup that walks its rows in order and spreads the entries of a row over its lanes.  Rows are ordered by
