@@ -57,6 +57,12 @@ int wai_test_partial_count(wai_ctx *ctx);
 /* the brick schedule's shared descriptor tables (k_pc_park on its 16-bit column indices): returns the number of distinct
  * templates, bricks and rows the number of bricks and of template rows (24 bytes each); 0 when the schedule has none */
 int wai_test_desc_templates(wai_ctx *ctx, int *bricks, int *rows);
+/* short bricks packed into shared k_pc_park workgroups, for launch list `list` (0 all subdomains, 1 the interior bricks, 2 the
+ * face bricks): returns the number of groups -- the workgroups of the packed launch -- as the launcher would run them now, 0
+ * where it launches one workgroup per brick (nothing packs, another kernel or index form, WAI_NO_PACK); shared: the bricks
+ * that share a workgroup; table: the first min(cap, 32 x groups) ints of the device's group table, per group and wave
+ * {brick or -1, thread offset, first parked block, forward | backward << 16 level counts of the group} */
+int wai_test_pack_groups(wai_ctx *ctx, int list, int *shared, int *table, int cap);
 /* one vector / reduction step of the Krylov drivers, issued through the drivers' own launchers, for the tests
  * (tests/test_hip_krylov_vec.py).  n >= 1 entries per vector, whatever the context's mesh.  vecs: seven host vectors of
  * len >= n doubles each, X R RP P V S T in this order, in and out whole (the entries behind n are guards); basis (GMRES ops):

@@ -247,6 +247,9 @@ struct IluSchedule : ScheduleFacts {
   DevBuf<int> t_info, t_uoff;        // [template rows]
   DevBuf<unsigned short> t_col16;    // [template rows][8]
   DevBuf<int> sub_desc;              // [nsub]: first row of the brick's template
+  // short bricks packed into shared k_pc_park workgroups (ilu_schedule.hpp, phase 10): per launch list -- 0 all subdomains,
+  // 1 sub_int, 2 sub_bnd -- the (group, wave) records [n_groups][8][4], or null where nothing packs
+  DevBuf<int> pack_tab[3];
   DevBuf<int> ord_f;          // big, wide: rows sorted by forward level, ...
   DevBuf<int> ord_b;          // ... by backward level (row ranges of each level: lev_f_ptr / lev_b_ptr)
   // wai_ctx::ilu only: the system whose preconditioner is set up now (null: none) -- the factor buffers above are shared by
@@ -547,9 +550,10 @@ struct wai_ctx : wai::Handles {
   // that compare the two paths in one process; read at the preconditioner's set-up); WAI_ASM_UNFUSED: PCASM likewise keeps
   // its launches (k_spmv, gather, the sweeps on the extended system, scatter, the reductions) where the fused one would serve;
   // WAI_NO_DESC_SHARE: k_pc_park on col16 reads every brick's own descriptors instead of the shared templates
+  // WAI_NO_PACK: one k_pc_park workgroup per brick on a schedule that has packed groups (the A/B and the bit-identity tests)
   struct EnvSw {
     bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false;
-    bool asm_unfused = false; bool no_desc_share = false;
+    bool asm_unfused = false; bool no_desc_share = false; bool no_pack = false;
   } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
   // halo

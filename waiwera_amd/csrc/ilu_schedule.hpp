@@ -32,6 +32,9 @@ struct ScheduleFacts {
   bool rows_kernel = false; // k_pc_rows (one thread per scalar row) applies and is selected
   bool wave_kernel = false; // k_pc_wave (one wave per brick of <= 64 block rows) applies and is selected
   int n_templates = 0, template_rows = 0;   // shared brick descriptors (t_info, t_uoff, t_c16): 0 without col16
+  // short bricks packed into shared k_pc_park workgroups (phase 10), per launch list -- 0 all subdomains, 1 sub_int, 2 sub_bnd:
+  // workgroups of the packed launch (0: nothing packs, no table) and bricks that share theirs
+  int n_groups[3] = {0, 0, 0}, n_shared[3] = {0, 0, 0};
   // subdomains of more than 1024 rows ("one block per rank", sub_ptr = NULL, is the reference's
   // PCBJACOBI / PCASM default): rows of equal dependency level are independent across all
   // subdomains, so the factorisation and the two substitutions run as one launch per level over
@@ -62,6 +65,8 @@ struct HostSchedule : ScheduleFacts {
   std::vector<int> t_info, t_uoff;     // [template rows] one copy of identical brick descriptors
   std::vector<unsigned short> t_c16;   // [template rows][8]
   std::vector<int> desc;               // [nsub] first row of the brick's template
+  std::vector<int> ucount;             // [nsub] parked upper blocks of the brick (min(uppers, 3) counted per row): max_ublocks is their maximum
+  std::vector<int> groups[3];          // per launch list: [n_groups][8 waves][4] brick (-1: none), thread offset, park base, group levels
 };
 
 // What build_host_schedule is told besides the pattern.
@@ -171,6 +176,7 @@ inline void sub_upper_offsets(int lo, int hi, ScheduleRows& r, HostSchedule& out
     ucountw += nU;
     r.max_nu = std::max(r.max_nu, nU);
   }
+  out.ucount.push_back(ucount);
   out.max_ublocks = std::max(out.max_ublocks, ucount);
   out.max_ublocks_w = std::max(out.max_ublocks_w, ucountw);
 }
@@ -416,6 +422,88 @@ inline void descriptor_templates(HostSchedule& out) {
   out.template_rows = (int)out.t_info.size();
 }
 
+// ---- phase 10: short bricks packed into shared workgroups --------------------------------------------------------
+// A k_pc_park workgroup has one thread per row of the LARGEST brick, and a brick's life -- descriptors, indices, seven slot
+// round trips, two LDS round trips per level, epilogue -- hardly shortens with fewer rows: a ragged brick at the upper end
+// of the box holds its slot nearly as long as a full one (216 = 13 x 16 + 8: 27 of a layer pair's 196 workgroups carry
+// 7 % of its rows).  So the short bricks of a launch list share workgroups: a GROUP is 1 .. 8 bricks of one list, each on
+// whole waves of its own (thread offsets are multiples of 64: a wave never holds rows of two bricks), together within the
+// workgroup's threads and within max_ublocks parked blocks -- the launch's LDS request and the workgroups per CU stay what
+// they are.  The bricks, their arithmetic and their partial sums are untouched; only which workgroup, and which of its
+// waves, runs a brick changes.  First-fit decreasing over the list's short bricks (ties by brick index); bricks as wide as
+// the workgroup stay alone.  A group takes the place of its first member, then the eighths and the longest-first order of
+// phase 3 on the group's cost: its largest level counts, then its rows.
+// The record of (group, wave), one 16-byte scalar load: the wave's brick or -1, the thread offset of that brick in the
+// workgroup, its first block in the park, the group's level counts (forward | backward << 16, each the maximum over the
+// members: every wave takes part in every barrier).  A list in which nothing packs has no table and launches as before.
+constexpr int PACK_WAVES = 8, PACK_REC = 4;
+inline void pack_list(const HostSchedule& s, std::vector<int> list, std::vector<int>& table, int& n_groups, int& n_shared) {
+  table.clear(); n_groups = 0; n_shared = 0;
+  const int T = ((s.max_rows + 63) / 64) * 64;
+  auto rows = [&](int sd) { return s.sub[sd + 1] - s.sub[sd]; };
+  auto threads = [&](int sd) { return ((rows(sd) + 63) / 64) * 64; };
+  if (T > 64 * PACK_WAVES) return;
+  std::sort(list.begin(), list.end());        // the list's natural order: the lists themselves are kept longest-first
+  std::vector<int> shorts;
+  for (int sd : list) if (threads(sd) < T) shorts.push_back(sd);
+  std::stable_sort(shorts.begin(), shorts.end(), [&](int a, int b) { return rows(a) > rows(b); });
+  struct Bin { std::vector<int> members; int threads = 0, ublocks = 0; };
+  std::vector<Bin> bins;
+  std::unordered_map<int, int> opens;         // a bin's first member -> the bin
+  bool any = false;
+  for (int sd : shorts) {
+    size_t b = 0;
+    while (b < bins.size() && (bins[b].threads + threads(sd) > T || bins[b].ublocks + s.ucount[sd] > s.max_ublocks)) b++;
+    if (b == bins.size()) { bins.emplace_back(); opens[sd] = (int)b; }
+    else any = true;
+    bins[b].members.push_back(sd); bins[b].threads += threads(sd); bins[b].ublocks += s.ucount[sd];
+  }
+  if (!any) return;
+  std::vector<std::vector<int>> groups;       // in the order of their first members
+  for (int sd : list) {
+    if (threads(sd) >= T) groups.push_back({sd});
+    else if (opens.count(sd)) groups.push_back(bins[opens[sd]].members);
+  }
+  auto levels = [&](const std::vector<int>& g, int& nlf, int& nlb) {
+    nlf = 0; nlb = 0;
+    for (int sd : g) { nlf = std::max(nlf, s.nlev[sd] & 0xffff); nlb = std::max(nlb, s.nlev[sd] >> 16); }
+  };
+  auto cost = [&](const std::vector<int>& g) {
+    int nlf, nlb, r = 0;
+    levels(g, nlf, nlb);
+    for (int sd : g) r += rows(sd);
+    return (nlf + nlb) * 4096 + r;
+  };
+  const int n = (int)groups.size(), per = (n + 7) >> 3;
+  for (int j = 0; j < 8; j++) {
+    const int a = std::min(j * per, n), b = std::min((j + 1) * per, n);
+    std::stable_sort(groups.begin() + a, groups.begin() + b,
+                     [&](const std::vector<int>& x, const std::vector<int>& y) { return cost(x) > cost(y); });
+  }
+  table.assign((size_t)n * PACK_WAVES * PACK_REC, 0);
+  for (int g = 0; g < n; g++) {
+    int nlf, nlb, toff = 0, ubase = 0;
+    levels(groups[g], nlf, nlb);
+    int* rec = table.data() + (size_t)g * PACK_WAVES * PACK_REC;
+    for (int w = 0; w < PACK_WAVES; w++) { rec[w * PACK_REC] = -1; rec[w * PACK_REC + 1] = w * 64; rec[w * PACK_REC + 3] = nlf | (nlb << 16); }
+    for (int sd : groups[g]) {
+      for (int w = toff / 64; w < (toff + threads(sd)) / 64; w++) {
+        rec[w * PACK_REC] = sd; rec[w * PACK_REC + 1] = toff; rec[w * PACK_REC + 2] = ubase;
+      }
+      toff += threads(sd); ubase += s.ucount[sd];
+    }
+    if (groups[g].size() > 1) n_shared += (int)groups[g].size();
+  }
+  n_groups = n;
+}
+inline void pack_groups(HostSchedule& out) {
+  std::vector<int> all(out.nsub);
+  std::iota(all.begin(), all.end(), 0);
+  pack_list(out, all, out.groups[0], out.n_groups[0], out.n_shared[0]);
+  if (!out.sub_int.empty()) pack_list(out, out.sub_int, out.groups[1], out.n_groups[1], out.n_shared[1]);
+  if (!out.sub_bnd.empty()) pack_list(out, out.sub_bnd, out.groups[2], out.n_groups[2], out.n_shared[2]);
+}
+
 // The schedule of the N x N block matrix (rowptr, colidx: rows of at most W blocks, of np x np entries each) under the
 // subdomains sub[0] = 0 <= .. <= sub[nsub] = N.  Returns 0, or -2 with `err` set; `out` is built from nothing either way.
 inline int build_host_schedule(const std::vector<int>& rowptr, const std::vector<int>& colidx, const std::vector<int>& sub,
@@ -435,6 +523,7 @@ inline int build_host_schedule(const std::vector<int>& rowptr, const std::vector
   select_kernels(W, np, opts, r, out);
   if (out.rows_kernel) rows_split_record(A, W, out);
   if (park_serves(out, np) && col16_indices(A, N, W, opts.max_seg, out)) descriptor_templates(out);
+  if (park_serves(out, np)) pack_groups(out);
   return 0;
 }
 

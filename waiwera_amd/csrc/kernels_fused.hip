@@ -24,6 +24,7 @@ void read_env(wai_ctx* c) {
   c->env.iluk_level_path = getenv("WAI_ILUK_LEVEL_PATH") != nullptr;
   c->env.asm_unfused = getenv("WAI_ASM_UNFUSED") != nullptr;
   c->env.no_desc_share = getenv("WAI_NO_DESC_SHARE") != nullptr;
+  c->env.no_pack = getenv("WAI_NO_PACK") != nullptr;
 }
 
 // which fused kernel serves (matrix, schedule; context.hpp).  Kinds 1 .. 3 can form their input on the fly (in - alpha in2:
@@ -49,6 +50,8 @@ template <int BS>
 static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool spmv, const double* in, double* z,
                          int dot_mode, const double* aux, const int* list, int nrun, const Fin* finp, const double* in2,
                          const Bcsr* F, const int* row_map) {
+  // the launch list asked for, as the packed groups number them (0 all subdomains, 1 sub_int, 2 sub_bnd; -1: some other list)
+  const int which = !list ? 0 : (list == s.sub_int ? 1 : (list == s.sub_bnd ? 2 : -1));
   if (!list) { nrun = s.nsub; list = s.sub_order; }   // all subdomains: in the schedule's launch order, if it has one
   const bool with_fin = finp && dot_mode != 0;
   Fin fin;
@@ -165,6 +168,17 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
       const int* d_uoff = shared ? s.t_uoff.get() : s.row_uoff.get();
       const unsigned short* d_c16 = shared ? s.t_col16.get() : s.col16.get();
       const int* d_desc = shared ? s.sub_desc.get() : s.sub_ptr.get();
+      // short bricks sharing workgroups (col16 with shared descriptors only): the list's groups instead of its bricks.  Each
+      // brick still leaves its own partial, so the finalisers and fin.nb stay what they are; WAI_NO_PACK: one workgroup per brick
+      if (shared && which >= 0 && s.pack_tab[which] && !c->env.no_pack) {
+        const int ngrp = s.n_groups[which], gridp = ((ngrp + 7) / 8) * 8 + (with_fin ? fin.nf : 0);
+        sp_ax([&](auto sp, auto ax) {
+          hipLaunchKernelGGL((k_pc_park<decltype(sp)::value, decltype(ax)::value, true, true>), gridp, T, lds_park, c->stream,
+                             J.n, J.W, ngrp, s.sub_ptr, s.sub_nlev, d_desc, d_info, d_uoff, J.col, d_c16, s.sub_seg, s.fval, s.dinv,
+                             in, in2, scal, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, s.pack_tab[which].get(), fin, stagger);
+        });
+        return;
+      }
       with_flag(on16, [&](auto c16) {
         sp_ax([&](auto sp, auto ax) {
           hipLaunchKernelGGL((k_pc_park<decltype(sp)::value, decltype(ax)::value, decltype(c16)::value>), grid, T, lds_park, c->stream,

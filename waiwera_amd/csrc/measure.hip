@@ -293,6 +293,19 @@ int wai_test_desc_templates(wai_ctx* c, int* bricks, int* rows) {
   if (rows) *rows = have ? c->ilu.template_rows : 0;
   return have ? c->ilu.n_templates : 0;
 }
+int wai_test_pack_groups(wai_ctx* c, int list, int* shared, int* table, int cap) {
+  if (!c || list < 0 || list > 2 || cap < 0 || (cap > 0 && !table)) return -2;
+  read_env(c);
+  const IluSchedule& s = c->ilu;
+  // the launcher's own condition (launch_pc_bs): k_pc_park on col16 with shared descriptors, a table for the list, no WAI_NO_PACK
+  const bool packed = !s.big && pc_kernel_kind(c, c->flow.A, s) == 1 && s.col16 && !c->env.no_col16 && s.sub_desc &&
+                      !c->env.no_desc_share && s.pack_tab[list] && !c->env.no_pack;
+  if (shared) *shared = packed ? s.n_shared[list] : 0;
+  if (!packed) return 0;
+  const int n = std::min(cap, s.n_groups[list] * 32);
+  if (n > 0) HIPCHK(c, hipMemcpy(table, s.pack_tab[list].get(), sizeof(int) * n, hipMemcpyDeviceToHost));
+  return s.n_groups[list];
+}
 // one vector / reduction step of the Krylov drivers through the drivers' own launchers (waiwera_hip_bench.h): temporaries of
 // the caller's padded lengths, all NSCAL scalars seeded, every partial slot emptied as ksp_gmres empties them before its
 // first producer, the launchers unchanged, everything back to the caller -- guard elements included

@@ -39,7 +39,13 @@ namespace wai {
 // start-up cohorts were introduced against in round 4, now for the whole launch).
 // (Staging the brick's own operand segment in LDS, the in-brick columns read from there, was slower at C3, the 108^3
 // share and C2 -- two more barriers per brick replace the gathers' latency: profiles/stage_ab_r6_*.log.)
-template <bool SPMV, bool AX, bool C16>
+// PACK (round 9): short bricks share a workgroup (ilu_schedule.hpp, phase 10).  The workgroup's position selects a GROUP of
+// 1 .. 8 bricks and `sub_list` is the groups' table: each wave reads its record -- its brick (or none: the wave only takes part
+// in the barriers), the brick's thread offset in the workgroup, its base in the park, the group's level counts -- with one
+// 16-byte scalar load, and runs its brick as the brick's own workgroup would: the same rows on the same lanes of whole waves,
+// the same sums, one partial per brick at the brick's own index, the brick's waves added in ascending order (what its own
+// workgroup does, where the absent waves add +0.0).  Same bits.  nsub is then the number of groups.
+template <bool SPMV, bool AX, bool C16, bool PACK = false>
 __global__ __launch_bounds__(512, 6) void k_pc_park(
     int n, int W, int nsub, const int* __restrict__ sub_ptr, const int* __restrict__ sub_nlev,
     const int* __restrict__ sub_desc, const int* __restrict__ row_info, const int* __restrict__ row_uoff, const int* __restrict__ col,
@@ -55,20 +61,29 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   if (fin_block(fin, partials, nb_max)) return;
   int s = xcd_remap(blockIdx.x, nsub);
   if (s >= nsub) return;
-  if (sub_list) s = sub_list[s];
-  const int lo = sub_ptr[s], R = sub_ptr[s + 1] - lo;
+  int toff = 0, ubase = 0, nl_grp = 0;   // PACK: the wave's member of the group (all wave-uniform)
+  if constexpr (PACK) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int4 rec = reinterpret_cast<const int4*>(sub_list)[(size_t)s * 8 + w];
+    s = rec.x; toff = rec.y; ubase = rec.z; nl_grp = rec.w;
+  } else {
+    if (sub_list) s = sub_list[s];
+  }
+  const bool member = !PACK || s >= 0;
+  const int lo = member ? sub_ptr[s] : 0, R = member ? sub_ptr[s + 1] - lo : 0;
   // C16: row_info, row_uoff and col16 are the descriptor templates, the brick's rows from sub_desc[s] on (requested beside
   // sub_ptr, not behind it); otherwise the per-row arrays
   int dlo = lo;
-  if constexpr (C16) dlo = sub_desc[s];
-  const int nl = sub_nlev[s];
+  if constexpr (C16) dlo = member ? sub_desc[s] : 0;
+  const int nl = PACK ? nl_grp : sub_nlev[s];
   const int nlf = nl & 0xffff, nlb = nl >> 16;
-  const int tid = threadIdx.x, i = lo + tid, di = dlo + tid;
-  const bool active = tid < R;
+  // a member's rows sit on the threads from its offset on: brick-local numbers are thread numbers less the offset
+  const int tid = threadIdx.x, lob = lo - toff, i = lob + tid, di = dlo - toff + tid;
+  const bool active = tid - toff < R;
   const double nalpha = AX ? -scal[S_ALPHA] : 0.0;   // input = in - alpha in2 (uniform: a scalar load)
   stagger_start(stagger);
   double* ys = lds;
-  double* upark = lds + (size_t)blockDim.x * BS + 80;
+  double* upark = lds + (size_t)blockDim.x * BS + 80 + (size_t)ubase * BB;
   double Lf[MLU][BB];
   int Lc[MLU], Uc[MLU], lf = -1, lb = -1, uo = 0, nU = 0;
   double xin[BS] = {0.0, 0.0}, avp[BS] = {0.0, 0.0};
@@ -139,8 +154,8 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
 #pragma unroll
         for (int p = 0; p < MLU; p++) {
           const bool tl = isl && (q - lfirst == p), tu = isu && (q - dslot - 1 == p);
-          Lc[p] = tl ? cg - lo : Lc[p];
-          Uc[p] = tu ? cg - lo : Uc[p];
+          Lc[p] = tl ? cg - lob : Lc[p];
+          Uc[p] = tu ? cg - lob : Uc[p];
 #pragma unroll
           for (int e = 0; e < BB; e++) Lf[p][e] = tl ? blk[e] : Lf[p][e];
         }
@@ -217,7 +232,8 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
     // the reduction scratch is touched by nothing before this point; dropping the barrier was not felt (0.5704 / 0.6942
     // against 0.5714 / 0.6924 ms at 216^3, profiles/nobar_ab_r6_c3.log), so it stays
     __syncthreads();
-    pc_reduce_dots(dot, v, red, partials, nb_max, s);
+    if constexpr (PACK) pc_reduce_dots_waves(dot, v, red, partials, nb_max, s, toff >> 6, (R + 63) >> 6);
+    else pc_reduce_dots(dot, v, red, partials, nb_max, s);
   }
 }
 

@@ -41,7 +41,8 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       put(s.row_uoff, h.uoff) || put(s.row_uoffw, h.uoffw) || put(s.row_tslot, h.tslot) || put(s.sub_split, h.split) ||
       put(s.sub_order, h.order) || put(s.sub_int, h.sub_int) || put(s.sub_bnd, h.sub_bnd) || put(s.ord_f, h.ord_f) ||
       put(s.ord_b, h.ord_b) || put(s.col16, h.c16) || put(s.sub_seg, h.seg) || put(s.t_info, h.t_info) ||
-      put(s.t_uoff, h.t_uoff) || put(s.t_col16, h.t_c16) || put(s.sub_desc, h.desc))
+      put(s.t_uoff, h.t_uoff) || put(s.t_col16, h.t_c16) || put(s.sub_desc, h.desc) || put(s.pack_tab[0], h.groups[0]) ||
+      put(s.pack_tab[1], h.groups[1]) || put(s.pack_tab[2], h.groups[2]))
     return -1;
   static_cast<ScheduleFacts&>(s) = std::move(h);
   if (s.fval.alloc(c, ell_size(np, N, W)) || s.dinv.alloc(c, (size_t)np * np * ell_rows(np, N))) return -1;

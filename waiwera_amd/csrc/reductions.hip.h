@@ -355,6 +355,48 @@ __device__ __forceinline__ void pc_reduce_dots(int mode, double (&v)[5], double*
   else { double v1[1] = {v[0]}; wg_reduce_store<1>(v1, red, partials, nb_max, slot0, blk); }
 }
 
+// The same for a workgroup that several bricks share (k_pc_park<.., PACK>): the sums over the waves [w0, w0 + nwm) of the
+// calling wave's brick into entry blk, the brick's own index; blk < 0: a wave without a brick, which only takes part in
+// the barrier.  The brick's waves are added in ascending order from +0.0, as wg_reduce_store adds them in the brick's own
+// workgroup (whose further waves, all inactive, add +0.0): the same bits.  One wave per slot where the brick has that many
+// waves (its k-th wave takes slot slot0 + k), else the brick's first wave takes the slots one after the other.
+template <int NS>
+__device__ __forceinline__ void wg_reduce_store_waves(double (&v)[NS], double* red, double* partials, int nb_max, int slot0,
+                                                      int blk, int w0, int nwm) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    const double t = wave_sum(v[s]);
+    if (lane == 0) red[s * 16 + w] = t;
+  }
+  __syncthreads();
+  if (blk < 0 || lane != 0) return;
+  const int k = w - w0;
+  if (nwm >= NS) {
+    if (k < NS) {
+      double t = 0.0;
+      for (int q = w0; q < w0 + nwm; q++) t += red[k * 16 + q];
+      store_partial(partials + (size_t)(slot0 + k) * nb_max + blk, t);
+    }
+    return;
+  }
+  if (k == 0) {
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+      double t = 0.0;
+      for (int q = w0; q < w0 + nwm; q++) t += red[s * 16 + q];
+      store_partial(partials + (size_t)(slot0 + s) * nb_max + blk, t);
+    }
+  }
+}
+__device__ __forceinline__ void pc_reduce_dots_waves(int mode, double (&v)[5], double* red, double* partials, int nb_max, int blk,
+                                                     int w0, int nwm) {
+  const int slot0 = pc_dot_slot0(mode);
+  if (mode == PC_DOT_MERGED) wg_reduce_store_waves<5>(v, red, partials, nb_max, slot0, blk, w0, nwm);
+  else if (mode == PC_DOT_XZ) { double v2[2] = {v[0], v[1]}; wg_reduce_store_waves<2>(v2, red, partials, nb_max, slot0, blk, w0, nwm); }
+  else { double v1[1] = {v[0]}; wg_reduce_store_waves<1>(v1, red, partials, nb_max, slot0, blk, w0, nwm); }
+}
+
 // One row's (k_pc_rows, k_pc_wave: one scalar's) terms of dot mode `mode`'s products (context.hpp, PcDot), for a mode
 // other than none: v[0 .. pc_dot_nslots(mode)) gain x.o, o.o, ... over N components, with o the result z, x the operand
 // and a the partner aux.  get_x(x) / get_a(a) fill in the operand and the partner inside the branch of a mode that

@@ -439,6 +439,18 @@ class FlowSimulation:
         nt = self._chk(LIB.wai_test_desc_templates(self.h, C.byref(nb), C.byref(nr)), "test_desc_templates")
         return nt, nb.value, nr.value
 
+    def pack_groups(self, which=0):
+        """(groups, bricks that share a workgroup, table [groups][8][4]) of the packed k_pc_park launch over list `which` -- 0
+        all subdomains, 1 interior bricks, 2 face bricks (wai_test_pack_groups); (0, 0, empty) where every brick has its own
+        workgroup"""
+        shared = C.c_int(0)
+        ng = self._chk(LIB.wai_test_pack_groups(self.h, which, C.byref(shared), None, 0), "test_pack_groups")
+        table = np.zeros(ng * 32, dtype=np.int32)
+        if ng:
+            self._chk(LIB.wai_test_pack_groups(self.h, which, C.byref(shared), table.ctypes.data_as(C.POINTER(C.c_int)), table.size),
+                      "test_pack_groups")
+        return ng, shared.value, table.reshape(ng, 8, 4)
+
     KV_OPS = ("dot", "dots", "waxpy", "bcgs_p", "bcgs_s", "bcgs_xr", "bcgs_xrp", "bcgs_xrp_derive", "scalars", "mdot",
               "maxpy_norm", "scale_to", "update_x")
     KV_VECS = ("X", "R", "RP", "P", "V", "S", "T")

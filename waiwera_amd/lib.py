@@ -157,6 +157,7 @@ def _load():
         "wai_pc_axpy_capable": (i32, [vp]),
         "wai_test_partial_count": (i32, [vp]),
         "wai_test_desc_templates": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "wai_test_pack_groups": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), i32]),
         "wai_test_krylov_vec": (i32, [vp, i32, i32, i32, i32, C.c_longlong, C.c_longlong, d, pd, pd, pd, pd, pd]),
         "wai_halo_size": (i32, [vp, i32, C.POINTER(C.c_longlong), C.POINTER(i32)]),
         "wai_pc_kernel_name": (C.c_char_p, [vp]),
