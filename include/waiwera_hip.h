@@ -53,6 +53,8 @@ enum { WAI_PC_BJACOBI = 0, WAI_PC_ASM = 1, WAI_PC_NONE = 2, WAI_PC_LU = 3 };   /
  * reference's layout.  Blocks of up to 1024 rows (bricks of the mesh) run on the fused
  * one-workgroup-per-block kernels; larger ones -- any size -- on the launch-per-dependency-level
  * path, which is general but several times slower per application.
+ * wai_set_pc_tiles cuts such a larger block into tiles of at most 1024 rows -- the bricks it is made of -- and its
+ * substitution sweeps then take one launch per level of TILES instead of one per level of rows, where that is fewer.
  * Limit: at most 16 faces per owned cell, boundary faces included, and at most 15 neighbouring
  * cells, so at most 16 blocks per matrix row: a polygonal column of a middle layer may have up to 13
  * lateral neighbours (14 with a boundary face above or below it, e.g. in the top layer).
@@ -462,6 +464,18 @@ int wai_tracer_block_system(wai_ctx *ctx, int method, double dt, double ratio, c
  * own, which carries its own sub-preconditioner (the reference reads one per solver object; its default is ilu for both). */
 enum { WAI_SUB_ILU = 0, WAI_SUB_LU = 1 };
 int wai_set_sub_pc(wai_ctx *ctx, int sub);
+
+/* Tiles of the preconditioner's subdomains: tile_ptr[n_tiles + 1] lists contiguous owned-row ranges, like sub_ptr, from 0 to
+ * n_owned, each of 1 .. 1024 rows, and every subdomain boundary is a tile boundary (the mesh's bricks under sub_ptr = NULL, one
+ * block per rank).  A subdomain of more than 1024 rows -- and PCASM's or ILU(k)'s extended block built on it, whose rows
+ * inherit their tiles -- then runs its two substitution sweeps with one launch per dependency level of TILES, one workgroup per
+ * tile, instead of one launch per dependency level of rows: the same subtractions in the same order, the same bits.  Only
+ * where that takes fewer launches (tile levels forward + backward < row levels forward + backward): a tiling that is a chain
+ * keeps the level path.  Unchanged by the tiles: subdomains of up to 1024 rows, the factorisation, the coupled tracer
+ * system, sub-preconditioner lu, PCASM whose overlap reaches other ranks.  n_tiles = 0 or tile_ptr = NULL clears the tiles.
+ * Refused with -1 and a text that names the tile: a tile_ptr that does not ascend from 0 to n_owned, an empty tile, a tile of
+ * more than 1024 rows, a tile that straddles a subdomain boundary.  The preconditioner is set up again by its next use. */
+int wai_set_pc_tiles(wai_ctx *ctx, int n_tiles, const int *tile_ptr);
 
 /* The auxiliary (tracer) solver's own preconditioner: time.step.solver.auxiliary.preconditioner.{type, sub.preconditioner.{type,
  * factor.levels}} (timestepper_configure_auxiliary_linear_solver, src/timestepper.F90:2057-2065; the same keys as the flow

@@ -63,6 +63,12 @@ int wai_test_desc_templates(wai_ctx *ctx, int *bricks, int *rows);
  * that share a workgroup; table: the first min(cap, 32 x groups) ints of the device's group table, per group and wave
  * {brick or -1, thread offset, first parked block, forward | backward << 16 level counts of the group} */
 int wai_test_pack_groups(wai_ctx *ctx, int list, int *shared, int *table, int cap);
+/* the tile schedule (wai_set_pc_tiles) of the flow system's preconditioner as set up now -- the set-up is made if it is not
+ * in force -- `extended` 0: the system's own schedule (block Jacobi), 1: its extended system's (PCASM, ILU(k)).  facts[8]:
+ * tiles, tile levels forward, backward, rows of the largest tile, most in-tile levels of a tile, serve (1: the sweeps run
+ * k_tile_solve per tile level), row levels forward, backward (the level path's launches).  Returns the number of tiles, 0
+ * where the schedule has none (no tiles set, a subdomain schedule of <= 1024 rows, sub lu, PCASM across ranks) */
+int wai_test_tile_schedule(wai_ctx *ctx, int extended, int *facts);
 /* one vector / reduction step of the Krylov drivers, issued through the drivers' own launchers, for the tests
  * (tests/test_hip_krylov_vec.py).  n >= 1 entries per vector, whatever the context's mesh.  vecs: seven host vectors of
  * len >= n doubles each, X R RP P V S T in this order, in and out whole (the entries behind n are guards); basis (GMRES ops):

@@ -305,6 +305,26 @@ int wai_set_sub_pc(wai_ctx* c, int sub) {
   return 0;
 }
 
+int wai_set_pc_tiles(wai_ctx* c, int n_tiles, const int* tile_ptr) {
+  if (!c) return -2;
+  if (n_tiles < 0) { c->err = "wai_set_pc_tiles: n_tiles < 0"; return -1; }
+  const Pattern& J = c->pat;
+  std::vector<int> tiles;
+  if (n_tiles > 0 && tile_ptr) {
+    tiles.assign(tile_ptr, tile_ptr + n_tiles + 1);
+    if (check_tiles(tiles, c->ilu.sub, J.n, c->err)) return -1;
+  }
+  // what depends on the tiles goes: the factor in force, the extended systems (built again by the next set-up: do_pc_setup)
+  // and the tile tables of the systems' own schedule, which is made again here
+  pc_invalidate(c);
+  c->flow.as = AsmSystem(); c->aux.as = AsmSystem(); c->coupled.as = AsmSystem();
+  c->pc_tiles.swap(tiles);
+  c->ilu.tiles.clear();
+  if (c->pc_tiles.empty() || !c->ilu.big) return 0;
+  const std::vector<int> sub = c->ilu.sub, id = tile_of_rows(c->pc_tiles, J.n);
+  return build_schedule(c, c->ilu, J.h_rowptr, J.h_colidx, sub, J.n, J.W, c->np, true, true, false, false, &id);
+}
+
 int wai_set_regions(wai_ctx* c, const int* region) {
   if (!c || !region) return -2;
   const int n = c->mesh.n_prim;

@@ -10,6 +10,7 @@
 #include "ilu_schedule.hpp"   // ScheduleFacts
 #include "mesh_pattern.hpp"   // MAX_CELL_FACES
 #include "physics.hip.h"
+#include "tile_schedule.hpp"  // TileFacts
 
 namespace wai {
 
@@ -213,6 +214,18 @@ struct Pattern {
 };
 
 struct LinSys;
+// The tile schedule of a big IluSchedule (wai_set_pc_tiles; tile_schedule.hpp, where build_tile_schedule makes the facts and
+// every table on the host): the tables on the device.  n_tiles = 0 and null tables: the schedule has no tiles
+struct TileTables : TileFacts {
+  DevBuf<int> tile_ptr;     // [n_tiles + 1] row ranges
+  DevBuf<int> tile_nin;     // [n_tiles] in-tile levels: forward | backward << 16
+  DevBuf<int> ord_f, ord_b; // tiles sorted by forward / backward tile level (tile ranges of each level: tl_f_ptr / tl_b_ptr)
+  DevBuf<int> row_lev;      // [n] in-tile level of the row: forward | backward << 16
+  void clear() {
+    static_cast<TileFacts&>(*this) = TileFacts();
+    tile_ptr.reset(); tile_nin.reset(); ord_f.reset(); ord_b.reset(); row_lev.reset();
+  }
+};
 // Block-Jacobi ILU(0): one workgroup per subdomain, one thread per block row.  The facts (sizes, extremes, the flags the
 // kernel selection reads, the host copy `sub` of sub_ptr, the level sets' row ranges) are ScheduleFacts' (ilu_schedule.hpp,
 // where build_host_schedule makes them and every table on the host); here are the tables on the device.
@@ -252,6 +265,8 @@ struct IluSchedule : ScheduleFacts {
   DevBuf<int> pack_tab[3];
   DevBuf<int> ord_f;          // big, wide: rows sorted by forward level, ...
   DevBuf<int> ord_b;          // ... by backward level (row ranges of each level: lev_f_ptr / lev_b_ptr)
+  // big, not sublu, tiles set: the substitution sweeps run one launch per TILE level where tiles.serve (launch_big_solve)
+  TileTables tiles;
   // wai_ctx::ilu only: the system whose preconditioner is set up now (null: none) -- the factor buffers above are shared by
   // the flow and the scalar tracer systems, and one record serves the extended systems' and the coupled system's own
   // buffers too.  Set by do_pc_setup; pc_invalidate when a system's values or the preconditioner's kind change
@@ -519,6 +534,7 @@ struct wai_ctx : wai::Handles {
   wai::EosParams ep{};
   wai_solver_opts opts{};
   int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
+  std::vector<int> pc_tiles;    // wai_set_pc_tiles: row ranges [n_tiles + 1] of the tiles that refine the subdomains; empty: none
   wai::DeviceMesh mesh;
   wai::Sources src;
   wai::Network net;

@@ -146,7 +146,7 @@ inline void pc_invalidate(wai_ctx* c) { c->ilu.owner = nullptr; }
 // ---- pc_setup.hip ------------------------------------------------------------------------------------------------
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
                    const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide = true, bool sublu = false,
-                   bool fill = false);
+                   bool fill = false, const std::vector<int>* row_tile = nullptr);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell
 int do_pc_setup(wai_ctx* c, LinSys& sys);
 // ---- krylov.hip --------------------------------------------------------------------------------------------------

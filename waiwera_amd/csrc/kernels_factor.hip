@@ -458,34 +458,29 @@ __global__ __launch_bounds__(TPB) void k_lvl_factor(int n, int cnt, const int* _
 }
 
 // forward (FWD): y_i = t_i - sum_{k < i} L_ik y_k; backward: x_i = inv(D_i) (y_i - sum_{j > i} U_ij x_j); in place
-template <int BS, bool FWD>
-__global__ __launch_bounds__(TPB) void k_lvl_solve(int n, int cnt, const int* __restrict__ ord,
-                                                   const int* __restrict__ row_info, const int* __restrict__ col,
-                                                   const double* __restrict__ fval, const double* __restrict__ dinv,
-                                                   double* z) {
+// The update of ONE row, shared by k_lvl_solve and k_tile_solve so that both do the same operations in the same order -- the
+// same contraction, the same bits: acc holds the row's entry on entry; its couplings are subtracted in slot order -- `begin(k)`
+// announces the coupled row, `operand(k, c)` is entry c of its value (finished by an earlier level) --; backward the result is
+// multiplied by the inverted pivot; `store(r, v)` takes entry r of the result.
+template <int BS, bool FWD, class Begin, class Operand, class Store>
+__device__ __forceinline__ void lvl_row_update(int n, int i, int lfirst, int dslot, int ulast, const int* col, const double* fval,
+                                               const double* dinv, double (&acc)[BS], Begin begin, Operand operand, Store store) {
   constexpr int BB = BS * BS;
-  const int t = blockIdx.x * TPB + threadIdx.x;
-  if (t >= cnt) return;
-  const int i = ord[t];
-  int lfirst, dslot, ulast;
-  unpack_info_wide(row_info[i], lfirst, dslot, ulast);
-  double acc[BS];
-#pragma unroll
-  for (int r = 0; r < BS; r++) acc[r] = z[(size_t)i * BS + r];
   const int q0 = FWD ? lfirst : dslot + 1, q1 = FWD ? dslot : ulast;
   for (int q = q0; q < q1; q++) {
     const int k = col[(size_t)q * n + i];
     double m[BB];
 #pragma unroll
     for (int e = 0; e < BB; e++) m[e] = fval[vix<BS>(n, q, e, i)];
+    begin(k);
 #pragma unroll
     for (int r = 0; r < BS; r++)
 #pragma unroll
-      for (int c = 0; c < BS; c++) acc[r] -= m[r * BS + c] * z[(size_t)k * BS + c];
+      for (int c = 0; c < BS; c++) acc[r] -= m[r * BS + c] * operand(k, c);
   }
   if constexpr (FWD) {
 #pragma unroll
-    for (int r = 0; r < BS; r++) z[(size_t)i * BS + r] = acc[r];
+    for (int r = 0; r < BS; r++) store(r, acc[r]);
   } else {
     double d[BB];
 #pragma unroll
@@ -495,8 +490,78 @@ __global__ __launch_bounds__(TPB) void k_lvl_solve(int n, int cnt, const int* __
       double o = 0.0;
 #pragma unroll
       for (int c = 0; c < BS; c++) o += d[r * BS + c] * acc[c];
-      z[(size_t)i * BS + r] = o;
+      store(r, o);
     }
+  }
+}
+
+template <int BS, bool FWD>
+__global__ __launch_bounds__(TPB) void k_lvl_solve(int n, int cnt, const int* __restrict__ ord,
+                                                   const int* __restrict__ row_info, const int* __restrict__ col,
+                                                   const double* __restrict__ fval, const double* __restrict__ dinv,
+                                                   double* z) {
+  const int t = blockIdx.x * TPB + threadIdx.x;
+  if (t >= cnt) return;
+  const int i = ord[t];
+  int lfirst, dslot, ulast;
+  unpack_info_wide(row_info[i], lfirst, dslot, ulast);
+  double acc[BS];
+#pragma unroll
+  for (int r = 0; r < BS; r++) acc[r] = z[(size_t)i * BS + r];
+  lvl_row_update<BS, FWD>(n, i, lfirst, dslot, ulast, col, fval, dinv, acc, [](int) {},
+                          [z](int k, int c) { return z[(size_t)k * BS + c]; }, [z, i](int r, double v) { z[(size_t)i * BS + r] = v; });
+}
+
+// ---- big subdomains cut into tiles: one launch per TILE level (wai_set_pc_tiles, tile_schedule.hpp) ---------------------
+// The grid is the tiles of one tile level, one workgroup per tile, one thread per row.  The tile walks its in-tile row levels
+// with one barrier each, as a brick kernel does: a row at its level subtracts its couplings in slot order through
+// lvl_row_update -- what k_lvl_solve does for the row, bit for bit -- taking a coupled row's entry from the tile's copy in LDS
+// where the column lies in the tile and from z in global memory otherwise, where a launch of an earlier tile level finished
+// it.  No flag, no polling, nothing atomic between workgroups: kernel boundaries order the tile levels.  z is read and
+// written by the same launch (a plain pointer); no tile of a launch reads a row another tile of that launch writes.
+// LDS: max_tile_rows * BS doubles, at most 32 KB.
+template <int BS, bool FWD>
+__global__ __launch_bounds__(1024) void k_tile_solve(int n, const int* __restrict__ tiles, const int* __restrict__ tile_ptr,
+                                                     const int* __restrict__ tile_nin, const int* __restrict__ row_lev,
+                                                     const int* __restrict__ row_info, const int* __restrict__ col,
+                                                     const double* __restrict__ fval, const double* __restrict__ dinv, double* z) {
+  extern __shared__ double zt[];   // [rows of the tile][BS]
+  const int t = tiles[blockIdx.x];
+  const int lo = tile_ptr[t], R = tile_ptr[t + 1] - lo;
+  const int nin = FWD ? (tile_nin[t] & 0xffff) : (int)((unsigned)tile_nin[t] >> 16);
+  const int tid = threadIdx.x, i = lo + tid;
+  const bool active = tid < R;
+  int lfirst = 0, dslot = 0, ulast = 0, mine = -1;
+  double acc[BS];
+#pragma unroll
+  for (int r = 0; r < BS; r++) acc[r] = 0.0;
+  if (active) {
+    unpack_info_wide(row_info[i], lfirst, dslot, ulast);
+    mine = FWD ? (row_lev[i] & 0xffff) : (int)((unsigned)row_lev[i] >> 16);
+#pragma unroll
+    for (int r = 0; r < BS; r++) acc[r] = z[(size_t)i * BS + r];
+  }
+  for (int lev = 0; lev < nin; lev++) {
+    if (mine == lev) {
+      double zk[BS];   // the coupled row's value: the tile's copy, or what an earlier launch left in z
+      lvl_row_update<BS, FWD>(n, i, lfirst, dslot, ulast, col, fval, dinv, acc,
+                              [&](int k) {
+                                const int kt = k - lo;
+                                if ((unsigned)kt < (unsigned)R) {
+#pragma unroll
+                                  for (int c = 0; c < BS; c++) zk[c] = zt[kt * BS + c];
+                                } else {
+#pragma unroll
+                                  for (int c = 0; c < BS; c++) zk[c] = z[(size_t)k * BS + c];
+                                }
+                              },
+                              [&](int, int c) { return zk[c]; },
+                              [&](int r, double v) {
+                                zt[tid * BS + r] = v;
+                                z[(size_t)i * BS + r] = v;
+                              });
+    }
+    __syncthreads();
   }
 }
 
@@ -592,6 +657,23 @@ static void lvl_sweep(wai_ctx* c, const Bcsr& J, const IluSchedule& s, const int
     const int a = ptr[lev], cnt = ptr[lev + 1] - a, g = (cnt + TPB - 1) / TPB;
     if (cnt <= 0) continue;
     hipLaunchKernelGGL((k_lvl_solve<BS, FWD>), g, TPB, 0, c->stream, J.n, cnt, ord + a, s.row_info, J.col, s.fval, s.dinv, z);
+    c->ks.n_launch++;
+  }
+}
+// the tiles of each tile level of one sweep, a launch per tile level: one workgroup per tile, a thread per row of the largest
+template <int BS, bool FWD>
+static void tile_sweep(wai_ctx* c, const Bcsr& J, const IluSchedule& s, double* z) {
+  const TileTables& t = s.tiles;
+  const std::vector<int>& ptr = FWD ? t.tl_f_ptr : t.tl_b_ptr;
+  const int* ord = FWD ? t.ord_f : t.ord_b;
+  const int nlev = FWD ? t.ntl_f : t.ntl_b, T = ((t.max_tile_rows + 63) / 64) * 64;
+  const size_t lds = (size_t)t.max_tile_rows * BS * sizeof(double);
+  for (int lev = 0; lev < nlev; lev++) {
+    const int a = ptr[lev], cnt = ptr[lev + 1] - a;
+    if (cnt <= 0) continue;
+    hipLaunchKernelGGL((k_tile_solve<BS, FWD>), cnt, T, lds, c->stream, J.n, ord + a, t.tile_ptr, t.tile_nin, t.row_lev, s.row_info, J.col,
+                       s.fval, s.dinv, z);
+    c->ks.n_launch++;
   }
 }
 // sub-preconditioner lu: both substitutions of every block in one launch, in place on z.  The block's part of the vector
@@ -613,6 +695,11 @@ int launch_big_solve(wai_ctx* c, const Bcsr& J, const IluSchedule& s, double* z)
   if (J.dg) return launch_dg_big_solve(c, J, s, z);
   return with_bs(J.bs, [&](auto bs) {
     constexpr int BS = decltype(bs)::value;
+    if (s.tiles.serve && !s.sublu) {   // tiles set and fewer tile levels than row levels: a launch per tile level
+      tile_sweep<BS, true>(c, J, s, z);
+      tile_sweep<BS, false>(c, J, s, z);
+      return;
+    }
     lvl_sweep<BS, true>(c, J, s, s.ord_f, s.lev_f_ptr, s.nlev_f, z);   // level-0 rows of the forward sweep have nothing to subtract, but the launch is harmless
     lvl_sweep<BS, false>(c, J, s, s.ord_b, s.lev_b_ptr, s.nlev_b, z);
   });

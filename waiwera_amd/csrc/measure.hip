@@ -193,11 +193,12 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
   }
   if (pc_extended(c, sys)) {
     snprintf(buf, sizeof(buf), "k_spmv + %s on the extended system (%s, ILU(%d))",
-             sys.as.sched.big ? "k_lvl_solve per level" : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),
+             sys.as.sched.big ? (sys.as.sched.tiles.serve && !sys.as.sched.sublu ? "k_tile_solve per tile level" : "k_lvl_solve per level")
+                              : (sys.as.sched.wide ? "k_pc_wide" : "k_pc"),
              pc.type == WAI_PC_ASM ? "ASM" : "block Jacobi", std::max(pc.ilu_levels, 0));
     return buf;
   }
-  if (s.big) return "k_spmv + k_lvl_solve per level";
+  if (s.big) return s.tiles.serve ? "k_spmv + k_tile_solve per tile level" : "k_spmv + k_lvl_solve per level";
   switch (pc_kernel_kind(c, sys.A, s)) {   // the launcher's own rule (kernels_fused.hip)
     case 4: snprintf(buf, sizeof(buf), "k_pc_wide<%d,spmv>", bs); break;
     case 3: snprintf(buf, sizeof(buf), "k_pc_wave<%d,spmv>", bs); break;
@@ -305,6 +306,18 @@ int wai_test_pack_groups(wai_ctx* c, int list, int* shared, int* table, int cap)
   const int n = std::min(cap, s.n_groups[list] * 32);
   if (n > 0) HIPCHK(c, hipMemcpy(table, s.pack_tab[list].get(), sizeof(int) * n, hipMemcpyDeviceToHost));
   return s.n_groups[list];
+}
+int wai_test_tile_schedule(wai_ctx* c, int extended, int* facts) {
+  if (!c || !facts) return -2;
+  read_env(c);
+  LinSys& sys = c->flow;
+  if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
+  if (extended && !pc_extended(c, sys)) { c->err = "wai_test_tile_schedule: the preconditioner in force has no extended system"; return -1; }
+  const IluSchedule& s = extended ? sys.as.sched : c->ilu;
+  const TileFacts& t = s.tiles;
+  const int f[8] = {t.n_tiles, t.ntl_f, t.ntl_b, t.max_tile_rows, t.max_in_levels, t.serve ? 1 : 0, s.nlev_f, s.nlev_b};
+  std::copy(f, f + 8, facts);
+  return t.n_tiles;
 }
 // one vector / reduction step of the Krylov drivers through the drivers' own launchers (waiwera_hip_bench.h): temporaries of
 // the caller's padded lengths, all NSCAL scalars seeded, every partial slot emptied as ksp_gmres empties them before its

@@ -12,8 +12,11 @@ namespace wai {
 // The schedule of block-Jacobi ILU(0) on a block matrix given as host CSR (ascending columns), on the device: the options
 // from the context, the environment and the build's switches; every fact and table from build_host_schedule
 // (ilu_schedule.hpp); the uploads; the factor's own buffers.  `ghosts`: rows may have columns >= n (partition ghosts).
+// row_tile (optional; wai_set_pc_tiles): a tile id per row -- a schedule that comes out big (by its row count or its fill, not
+// sub lu) gets the tile schedule of tile_schedule.hpp beside its level sets.
 int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, const std::vector<int>& colidx,
-                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide, bool sublu, bool fill) {
+                   const std::vector<int>& sub, int N, int W, int np, bool ghosts, bool allow_wide, bool sublu, bool fill,
+                   const std::vector<int>* row_tile) {
   ScheduleOpts o;
   o.ghosts = ghosts; o.allow_wide = allow_wide; o.sublu = sublu; o.fill = fill;
   o.mesh_W = c->pat.W;
@@ -32,10 +35,14 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
 #endif
   HostSchedule h;
   if (int e = build_host_schedule(rowptr, colidx, sub, N, W, np, o, h, c->err)) return e;
+  HostTiles t;
+  if (row_tile && h.big && !h.sublu)
+    if (int e = build_tile_schedule(rowptr, colidx, sub, h.info, *row_tile, N, h.nlev_f, h.nlev_b, t, c->err)) return e;
   // A schedule built again keeps nothing of the one before: every table is reset, also those the new schedule does not have
   // (a table the host did not make is a null buffer -- a mesh that bails out of col16 must not run on, or report, stale
   // tables), and the facts say "no schedule" until every upload has succeeded
   static_cast<ScheduleFacts&>(s) = ScheduleFacts();
+  s.tiles.clear();
   auto put = [c](auto& buf, const auto& v) { buf.reset(); return !v.empty() && buf.upload(c, v); };
   if (put(s.sub_ptr, h.sub) || put(s.sub_nlev, h.nlev) || put(s.row_info, h.info) || put(s.row_infow, h.infow) ||
       put(s.row_uoff, h.uoff) || put(s.row_uoffw, h.uoffw) || put(s.row_tslot, h.tslot) || put(s.sub_split, h.split) ||
@@ -44,6 +51,14 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
       put(s.t_uoff, h.t_uoff) || put(s.t_col16, h.t_c16) || put(s.sub_desc, h.desc) || put(s.pack_tab[0], h.groups[0]) ||
       put(s.pack_tab[1], h.groups[1]) || put(s.pack_tab[2], h.groups[2]))
     return -1;
+  if (t.n_tiles > 0) {
+    TileTables& d = s.tiles;
+    if (put(d.tile_ptr, t.tile_ptr) || put(d.tile_nin, t.tile_nin) || put(d.ord_f, t.ord_f) || put(d.ord_b, t.ord_b) || put(d.row_lev, t.row_lev)) {
+      d.clear();
+      return -1;
+    }
+    static_cast<TileFacts&>(d) = std::move(t);
+  }
   static_cast<ScheduleFacts&>(s) = std::move(h);
   if (s.fval.alloc(c, ell_size(np, N, W)) || s.dinv.alloc(c, (size_t)np * np * ell_rows(np, N))) return -1;
   return 0;
@@ -155,7 +170,17 @@ int build_asm(wai_ctx* c, LinSys& sys, int overlap, int levels, bool with_net, b
   if (cross && (a.hval.alloc(c, ell_size(np, H, J.W)) || a.r_full.alloc_zeroed(c, (size_t)np * (N + H) + 16))) return -1;
   // (`fill` of build_schedule: the factor has column planes of its own -- ILU(k)'s filled rows, or PCASM's extended blocks)
   const bool fuse = fuse_wanted(c, sys, overlap, levels, with_net, sublu) && !cross;
-  if (int e = build_schedule(c, a.sched, p.erp, p.ecol, p.ext_ptr, n_ext, W, np, false, levels == 0 || fuse, sublu, fuse)) return e;
+  // tiles (wai_set_pc_tiles): a row of E inherits the tile of the row it stands for; with ghost rows from other ranks in E
+  // (cross) the level path stays
+  std::vector<int> etile;
+  if (!c->pc_tiles.empty() && !cross && !sublu) {
+    const std::vector<int> id = tile_of_rows(c->pc_tiles, N);
+    etile.resize(n_ext);
+    for (int q = 0; q < n_ext; q++) etile[q] = id[p.ext_rows[q]];
+  }
+  if (int e = build_schedule(c, a.sched, p.erp, p.ecol, p.ext_ptr, n_ext, W, np, false, levels == 0 || fuse, sublu, fuse,
+                             etile.empty() ? nullptr : &etile))
+    return e;
   a.fuse_asked = fuse;
   a.fused = fuse && a.sched.wide && (overlap > 0 || n_ext == N);   // (no overlap: E's rows are the system's own, in order)
   a.with_net = with_net;

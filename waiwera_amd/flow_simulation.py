@@ -536,6 +536,25 @@ class FlowSimulation:
         self._chk(LIB.wai_set_sub_pc(self.h, _lib.SUB_PC[sub]), "set_sub_pc")
         self.sub_pc = sub
 
+    def set_pc_tiles(self, tile_ptr):
+        """tiles of the preconditioner's subdomains (wai_set_pc_tiles): contiguous owned-row ranges of 1 .. 1024 rows from 0 to
+        n_owned that refine the subdomains -- the mesh's bricks under one block per rank.  A subdomain of more than 1024 rows then
+        runs its substitution sweeps with one launch per level of tiles where that is fewer launches; None clears the tiles"""
+        if tile_ptr is None:
+            self._chk(LIB.wai_set_pc_tiles(self.h, 0, None), "set_pc_tiles")
+            self.pc_tiles = None
+            return
+        tp = _lib._i32(tile_ptr)
+        self._chk(LIB.wai_set_pc_tiles(self.h, tp.size - 1, tp.ctypes.data_as(_lib.pi)), "set_pc_tiles")
+        self.pc_tiles = tp
+
+    def tile_schedule(self, extended=False):
+        """the tile schedule of the flow system's preconditioner as set up now (wai_test_tile_schedule): a dict of tiles, ntl_f,
+        ntl_b, max_tile_rows, max_in_levels, serve, nlev_f, nlev_b; extended: of the extended system (PCASM, ILU(k))"""
+        f = (C.c_int * 8)()
+        self._chk(LIB.wai_test_tile_schedule(self.h, 1 if extended else 0, f), "test_tile_schedule")
+        return dict(zip("tiles ntl_f ntl_b max_tile_rows max_in_levels serve nlev_f nlev_b".split(), list(f)))
+
     def aux_block_system(self, method, dt, ratio, alx_last, alx_last2):
         """(values (nnzb, nt): the diagonals of the coupled system's blocks on setup_jacobian()'s pattern, rhs
         (n_owned * nt) interleaved [cell][tracer])"""

@@ -514,6 +514,14 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        integer(c_int), value :: sub
      end function wai_set_sub_pc
+     ! tiles of the preconditioner's subdomains: tile_ptr(n_tiles + 1) row ranges of 1 .. 1024 rows from 0 to n_owned that refine
+     ! the subdomains; subdomains of more than 1024 rows then sweep with one launch per level of tiles.  n_tiles = 0: none
+     integer(c_int) function wai_set_pc_tiles(ctx, n_tiles, tile_ptr) bind(c, name = "wai_set_pc_tiles")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: n_tiles
+       integer(c_int), intent(in) :: tile_ptr(*)
+     end function wai_set_pc_tiles
      ! the auxiliary (tracer) solver's own preconditioner (time.step.solver.auxiliary.preconditioner): a WAI_PC_* value, or
      ! WAI_AUX_PC_FOLLOW (-1, default): the flow solver's.  The reference's default is WAI_PC_BJACOBI
      integer(c_int) function wai_set_aux_pc(ctx, pc_type, asm_overlap, ilu_levels, sub_pc) bind(c, name = "wai_set_aux_pc")
@@ -570,6 +578,7 @@ module waiwera_hip_module
      procedure, public :: set_residual_form => hip_sim_set_residual_form
      procedure, public :: set_timestep_method => hip_sim_set_timestep_method
      procedure, public :: set_sub_pc => hip_sim_set_sub_pc
+     procedure, public :: set_pc_tiles => hip_sim_set_pc_tiles
      procedure, public :: set_aux_pc => hip_sim_set_aux_pc
      procedure, public :: aux_lhs => hip_sim_aux_lhs
      procedure, public :: aux_solve => hip_sim_aux_solve
@@ -588,6 +597,7 @@ module waiwera_hip_module
        wai_max_scaled, wai_tracer_system, wai_synchronize, wai_network_evaluate
   public :: wai_set_tracers, wai_set_tracer_bc, wai_set_tracer_injection, wai_set_aux_solver
   public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc, wai_set_aux_pc, wai_get_aux_pc
+  public :: wai_set_pc_tiles
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_gather_rows, wai_gather_fluid
@@ -827,6 +837,16 @@ contains
     integer, intent(out) :: err
     err = wai_set_sub_pc(self%ctx, int(sub, c_int))
   end subroutine hip_sim_set_sub_pc
+
+  subroutine hip_sim_set_pc_tiles(self, n_tiles, tile_ptr, err)
+    !! Tiles of the preconditioner's subdomains (0-based row ranges, tile_ptr(1) = 0 .. tile_ptr(n_tiles + 1) = owned cells):
+    !! the bricks of the mesh under one block per rank.  n_tiles = 0 clears them.
+    class(hip_flow_simulation_type), intent(in out) :: self
+    integer, intent(in) :: n_tiles
+    integer(c_int), intent(in) :: tile_ptr(*)
+    integer, intent(out) :: err
+    err = wai_set_pc_tiles(self%ctx, int(n_tiles, c_int), tile_ptr)
+  end subroutine hip_sim_set_pc_tiles
 
   subroutine hip_sim_set_aux_pc(self, pc_type, asm_overlap, ilu_levels, sub_pc, err)
     !! Preconditioner of the auxiliary (tracer) solver (timestepper_configure_auxiliary_linear_solver,

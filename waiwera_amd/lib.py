@@ -158,6 +158,7 @@ def _load():
         "wai_test_partial_count": (i32, [vp]),
         "wai_test_desc_templates": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "wai_test_pack_groups": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), i32]),
+        "wai_test_tile_schedule": (i32, [vp, i32, C.POINTER(i32)]),
         "wai_test_krylov_vec": (i32, [vp, i32, i32, i32, i32, C.c_longlong, C.c_longlong, d, pd, pd, pd, pd, pd]),
         "wai_halo_size": (i32, [vp, i32, C.POINTER(C.c_longlong), C.POINTER(i32)]),
         "wai_pc_kernel_name": (C.c_char_p, [vp]),
@@ -192,6 +193,7 @@ def _load():
         "wai_tracer_solve": (i32, [vp, i32, d, d, vp, vp, vp, vp, pi, pi]),
         "wai_set_tracer_solve_mode": (i32, [vp, i32]),
         "wai_set_sub_pc": (i32, [vp, i32]),
+        "wai_set_pc_tiles": (i32, [vp, i32, pi]),
         "wai_set_aux_pc": (i32, [vp, i32, i32, i32, i32]),
         "wai_get_aux_pc": (i32, [vp, pi, pi, pi, pi]),
         "wai_tracer_block_system": (i32, [vp, i32, d, d, vp, vp, vp, vp]),

@@ -36,6 +36,9 @@ def main(argv=None):
     ap.add_argument("--aux-pc", choices=("follow", "bjacobi", "asm"), default="follow",
                     help="tracer solver's preconditioner for an input without time.step.solver.auxiliary: the flow solver's "
                          "(default), bjacobi (the reference's default) or asm")
+    ap.add_argument("--subdomains", choices=("chunks", "rank"), default="chunks",
+                    help="the preconditioner's blocks: the mesh's chunks (default) or one block per rank, the reference's layout, "
+                         "with the chunks as its tiles")
     a = ap.parse_args(argv)
     import os
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -51,7 +54,7 @@ def main(argv=None):
         # one rank per GPU; WAI_BENCH_LOOPBACK=1 (tests on a one-GPU box, with a stand-in for librccl): every rank on --device
         if os.environ.get("WAI_BENCH_LOOPBACK") != "1":
             a.device = int(os.environ.get("LOCAL_RANK", a.device))
-    sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu,
+    sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
                                default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, **kw)
     out = sim.run()
     if rank != 0:

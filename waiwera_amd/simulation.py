@@ -364,7 +364,7 @@ class Simulation:
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
-                 sub_lu="host", default_aux_pc=None):
+                 sub_lu="host", default_aux_pc=None, subdomains="chunks"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -391,6 +391,14 @@ class Simulation:
         if sub_lu not in ("host", "device"):
             raise ValueError("sub_lu 'host' (dense block inverses, no overlap) or 'device' (exact LU of the blocks on the device)")
         self.sub_lu = sub_lu
+        # subdomains: the preconditioner's blocks on a rank -- "chunks" (the default, as before): the chunks of consecutive cells
+        # the mesh builders make (mesh.sub_ptr), each on the fused one-workgroup kernels; "rank": ONE block per rank, the
+        # reference's own layout (its bjacobi / asm subdomains are the ranks), with the same chunks handed to the library as
+        # tiles (set_pc_tiles), so that the block's sweeps take a launch per level of chunks instead of one per level of rows
+        # where that is fewer.  subdomain_choice records what was taken
+        if subdomains not in ("chunks", "rank"):
+            raise ValueError("subdomains 'chunks' (the mesh's chunks, the default) or 'rank' (one block per rank, the reference's layout)")
+        self.subdomains, self.subdomain_choice = subdomains, None
         # output files go to output_dir (default: $WAIWERA_OUTPUT_DIR, else beside the input file)
         self.output_dir = output_dir or os.environ.get("WAIWERA_OUTPUT_DIR") or base_dir
         self.output_error = None
@@ -632,6 +640,14 @@ class Simulation:
             prim, region = prim[self._gid], region[self._gid]
         self.primary, self.region = prim, region
         # the flow object
+        tiles = None
+        if self.subdomains == "rank":
+            tiles = None if lm.sub_ptr is None else np.asarray(lm.sub_ptr, dtype=np.int32).copy()
+            lm.sub_ptr = None       # one block per rank
+            self.subdomain_choice = ("rank", "one block per rank, %s" % ("no tiles: the mesh has no chunks" if tiles is None
+                                                                         else "tiles: the rank's %d chunks" % (tiles.size - 1)))
+        else:
+            self.subdomain_choice = ("chunks", "the mesh's chunks" if lm.sub_ptr is not None else "the mesh has no chunks: one block per rank")
         if ode_factory is None:
             from .flow_simulation import FlowSimulation
             self.ode = FlowSimulation(lm, eos=self.eos, device=device, temperature=temperature,
@@ -642,6 +658,8 @@ class Simulation:
                                    permeability_modifier=self.permeability_modifier)
         else:
             self.ode = ode_factory(lm, self.eos, self.thermo, self.relperm, self.capillary, temperature)
+        if tiles is not None:
+            self.ode.set_pc_tiles(tiles)
         self.ode.set_regions(region)
         if self.world > 1:
             if comm_id is None:
