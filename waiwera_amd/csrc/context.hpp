@@ -567,9 +567,11 @@ struct wai_ctx : wai::Handles {
   // its launches (k_spmv, gather, the sweeps on the extended system, scatter, the reductions) where the fused one would serve;
   // WAI_NO_DESC_SHARE: k_pc_park on col16 reads every brick's own descriptors instead of the shared templates
   // WAI_NO_PACK: one k_pc_park workgroup per brick on a schedule that has packed groups (the A/B and the bit-identity tests)
+  // WAI_PARK_STAGE=0|1: k_pc_park's operator launches without / with the brick's operand segment staged in LDS
   struct EnvSw {
     bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false;
     bool asm_unfused = false; bool no_desc_share = false; bool no_pack = false;
+    int park_stage = -1;   // WAI_PARK_STAGE: 0 / 1 k_pc_park's staged operand off / on for every launch kind, -1 the compiled-in defaults
   } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
   // halo

@@ -25,6 +25,22 @@ void read_env(wai_ctx* c) {
   c->env.asm_unfused = getenv("WAI_ASM_UNFUSED") != nullptr;
   c->env.no_desc_share = getenv("WAI_NO_DESC_SHARE") != nullptr;
   c->env.no_pack = getenv("WAI_NO_PACK") != nullptr;
+  const char* st = getenv("WAI_PARK_STAGE");
+  c->env.park_stage = st && (st[0] == '0' || st[0] == '1') ? st[0] - '0' : -1;
+}
+
+// k_pc_park<.., STAGE> (pc_park.hip.h): is the brick's own operand segment staged in LDS?  Per launch kind -- the composed
+// second launch of a BiCGStab iteration (its operand formed from two vectors) and the first launch (one vector) -- as
+// MEASURED (profiles/stage_ab_r10_*.log); WAI_PARK_STAGE=0|1 forces both kinds off or on.
+#ifndef WAI_PARK_STAGE_COMPOSED
+#define WAI_PARK_STAGE_COMPOSED 1
+#endif
+#ifndef WAI_PARK_STAGE_FIRST
+#define WAI_PARK_STAGE_FIRST 0
+#endif
+static bool park_staged(const wai_ctx* c, bool composed) {
+  if (c->env.park_stage >= 0) return c->env.park_stage == 1;
+  return composed ? WAI_PARK_STAGE_COMPOSED != 0 : WAI_PARK_STAGE_FIRST != 0;
 }
 
 // which fused kernel serves (matrix, schedule; context.hpp).  Kinds 1 .. 3 can form their input on the fly (in - alpha in2:
@@ -168,10 +184,20 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
       const int* d_uoff = shared ? s.t_uoff.get() : s.row_uoff.get();
       const unsigned short* d_c16 = shared ? s.t_col16.get() : s.col16.get();
       const int* d_desc = shared ? s.sub_desc.get() : s.sub_ptr.get();
+      // the operator on col16 with shared descriptors may stage its operand (park_staged); the plain application never does
+      const bool stage = shared && spmv && park_staged(c, in2 != nullptr);
+      auto staged = [&](auto pack, int g, int count, const int* lst) {
+        with_flag(in2 != nullptr, [&](auto ax) {
+          hipLaunchKernelGGL((k_pc_park<true, decltype(ax)::value, true, decltype(pack)::value, true>), g, T, lds_park, c->stream,
+                             J.n, J.W, count, s.sub_ptr, s.sub_nlev, d_desc, d_info, d_uoff, J.col, d_c16, s.sub_seg, s.fval, s.dinv,
+                             in, in2, scal, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, lst, fin, stagger);
+        });
+      };
       // short bricks sharing workgroups (col16 with shared descriptors only): the list's groups instead of its bricks.  Each
       // brick still leaves its own partial, so the finalisers and fin.nb stay what they are; WAI_NO_PACK: one workgroup per brick
       if (shared && which >= 0 && s.pack_tab[which] && !c->env.no_pack) {
         const int ngrp = s.n_groups[which], gridp = ((ngrp + 7) / 8) * 8 + (with_fin ? fin.nf : 0);
+        if (stage) { staged(std::true_type{}, gridp, ngrp, s.pack_tab[which].get()); return; }
         sp_ax([&](auto sp, auto ax) {
           hipLaunchKernelGGL((k_pc_park<decltype(sp)::value, decltype(ax)::value, true, true>), gridp, T, lds_park, c->stream,
                              J.n, J.W, ngrp, s.sub_ptr, s.sub_nlev, d_desc, d_info, d_uoff, J.col, d_c16, s.sub_seg, s.fval, s.dinv,
@@ -179,6 +205,7 @@ static void launch_pc_bs(wai_ctx* c, const Bcsr& J, const IluSchedule& s, bool s
         });
         return;
       }
+      if (stage) { staged(std::false_type{}, grid, nrun, list); return; }
       with_flag(on16, [&](auto c16) {
         sp_ax([&](auto sp, auto ax) {
           hipLaunchKernelGGL((k_pc_park<decltype(sp)::value, decltype(ax)::value, decltype(c16)::value>), grid, T, lds_park, c->stream,

@@ -37,15 +37,34 @@ namespace wai {
 // epilogue drains), and the dispatcher's hand-out -- whichever slot frees first -- decorrelates the bricks of a CU, which a
 // fixed stride never does: workgroups that started together stay in step, all loading, then all sweeping (the effect the
 // start-up cohorts were introduced against in round 4, now for the whole launch).
-// (Staging the brick's own operand segment in LDS, the in-brick columns read from there, was slower at C3, the 108^3
-// share and C2 -- two more barriers per brick replace the gathers' latency: profiles/stage_ab_r6_*.log.)
+// STAGE (round 10; the operator on the 16-bit column indices only): the brick's own operand segment staged in LDS.  Each
+// thread requests its row's own entry beside the descriptors, stores S_i = R_i - alpha V_i (the fma of load_xs; one vector:
+// the entry) to the idle solution area, and behind a barrier the in-brick columns -- the sweeps' couplings, slots
+// [lfirst, ulast), 79 % of a 16 x 16 x 2 brick's -- are 16-byte LDS reads at the brick-local number the sweeps use; far
+// columns keep their gathers, the products and their order are unchanged, a second barrier gives the area back to t = A S.
+// Same bits (tests/test_hip_park_stage.py).  Round 6 built this once (profiles/stage_ab_r6_*.log: composed launch 0.651 ->
+// 0.673 ms, first 0.529 -> 0.571) and blamed the two barriers.  The barriers were not it: __syncthreads() with plain loads
+// outstanding is `s_waitcnt lgkmcnt(0); s_barrier` on this compiler too, it never drained vmcnt.  What that form paid was the
+// ORDER -- own entry requested, waited for, stored, barrier, and only then slot 0's loads: one whole exposed round trip per
+// brick.  Here slot 0's block and, for a far slot 0, its gather are requested BEFORE the store and are in flight across the
+// barrier (lds_barrier: fences on the local address space only), so the round trip the brick waits for behind the barrier is
+// the one it waited for anyway.  Three things the compiler needed telling (profiles/stage_kernel_asm_r10.log): the explicit
+// vmcnt(0) behind the barrier (else every later reuse of a register drains the dot product's partner, which is meant to fly
+// through the sweeps), the opaque copy of the far slot 0's pair (else S is formed of it, and waited for, in front of the
+// barrier), and the inner products' FMAs written out (else (S, S) is contracted the other way round: one ulp).
+// MEASURED (profiles/stage_ab_r10_*.log, alternating same-box rounds, two boxes): composed launch 0.600-0.606 -> 0.578-0.582
+// ms at C3 in all seven rounds (-3.7 %), 0.0783 -> 0.0768-0.0775 at C2, 0.0929 -> 0.0918 at the 108^3 share; L1 -> L2 read
+// requests 42.1 M -> 32.2 M per launch, memory reads unchanged at 22.67 M lines (pmc_stage_r10_c3.txt).  The FIRST launch,
+// which gathers one vector where the composed one gathers two, LOSES: 0.505-0.507 -> 0.519 ms at C3, 0.0662 -> 0.0675 at C2
+// -- so the compiled-in default stages the composed launch only (kernels_fused.hip: park_staged; WAI_PARK_STAGE=0|1 forces
+// both kinds).  80 / 76 VGPRs (composed / first), no scratch, three workgroups per CU as before.
 // PACK (round 9): short bricks share a workgroup (ilu_schedule.hpp, phase 10).  The workgroup's position selects a GROUP of
 // 1 .. 8 bricks and `sub_list` is the groups' table: each wave reads its record -- its brick (or none: the wave only takes part
 // in the barriers), the brick's thread offset in the workgroup, its base in the park, the group's level counts -- with one
 // 16-byte scalar load, and runs its brick as the brick's own workgroup would: the same rows on the same lanes of whole waves,
 // the same sums, one partial per brick at the brick's own index, the brick's waves added in ascending order (what its own
 // workgroup does, where the absent waves add +0.0).  Same bits.  nsub is then the number of groups.
-template <bool SPMV, bool AX, bool C16, bool PACK = false>
+template <bool SPMV, bool AX, bool C16, bool PACK = false, bool STAGE = false>   // (PACK && STAGE: brick-local numbers are tid - toff, a wave without a brick only takes part in the barriers)
 __global__ __launch_bounds__(512, 6) void k_pc_park(
     int n, int W, int nsub, const int* __restrict__ sub_ptr, const int* __restrict__ sub_nlev,
     const int* __restrict__ sub_desc, const int* __restrict__ row_info, const int* __restrict__ row_uoff, const int* __restrict__ col,
@@ -55,6 +74,7 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
     double* __restrict__ z, const double* __restrict__ aux, double* partials, int nb_max, int dot,
     const int* __restrict__ sub_list, Fin fin, Stagger stagger) {
   constexpr int BS = 2, BB = 4, MLU = 3;
+  static_assert(!STAGE || (SPMV && C16), "the staged operand is the operator's, on the 16-bit column indices");
   extern __shared__ __attribute__((aligned(16))) double lds[];  // [T*2] solution, [80] reduction scratch, then parked U blocks
   // nsub subdomains to run: all of them, or (sub_list) the listed ones -- the bricks that touch no
   // partition ghost while the halo exchange is in flight, the others after it
@@ -95,10 +115,18 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   }
   int lfirst = 0, dslot = 0, ulast = 0;
   int cgs[WMAX];
+  // STAGE: the own entry's second operand, slot 0's block and, for a far column, its operand entry, requested in front of the barrier
+  [[maybe_unused]] double own2[BS], blk0[BB], xr0[BS], xv0[BS];
+  [[maybe_unused]] bool far0 = false;
   if (active) {
     unpack_info(row_info[di], lfirst, dslot, ulast, lf, lb);
     uo = row_uoff[di];
     nU = ulast - dslot - 1;
+    // STAGE: the row's own operand entry, requested beside the descriptors (S_i is formed where it is stored, below)
+    if constexpr (STAGE) {
+      load_x<BS>(in, i, xin);
+      if constexpr (AX) load_x<BS>(in2, i, own2);
+    }
     // (MEASURED AND REMOVED, round 6: slot 0's block -- which needs nothing but the row number -- requested here, together with
     // the descriptors and the index record, one dependent round trip less per brick: 77 VGPRs, no scratch, same bits, and
     // 3 % SLOWER at 108^3 and 100^3 (first launch 0.0840 -> 0.0868, 0.0741 -> 0.0764 ms), no better at 216^3:
@@ -131,6 +159,30 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
         if (q < W) cgs[q] = load_col(col, (size_t)q * n + i);
       }
     }
+    if constexpr (STAGE) {
+      // slot 0's block (a row has its diagonal: W >= 1) goes out first, then the wait for the OLDER own-entry loads alone
+      // -- loads return in order, the block stays in flight -- and S_i = R_i - alpha V_i, the fma of load_xs, into the idle
+      // solution area, where the brick's other rows find it.  A far slot 0's gather follows the store.
+      load_block<BS>(sval, n, 0, i, blk0);
+      if constexpr (AX) {
+#pragma unroll
+        for (int k = 0; k < BS; k++) xin[k] = __builtin_fma(nalpha, own2[k], xin[k]);
+      }
+      *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(xin[0], xin[1]);
+      far0 = lfirst > 0;
+      if (far0) {
+        load_x<BS>(in, cgs[0], xr0);
+        if constexpr (AX) load_x<BS>(in2, cgs[0], xv0);
+      }
+    }
+  }
+  if constexpr (STAGE) {
+    lds_barrier();   // S is in place; slot 0's loads are still in flight
+    // Slot 0's loads are waited for HERE, by every wave, and not at their first use inside `if (active)`: a wave could --
+    // for all the compiler knows -- skip that region with them pending, and it then drains vmcnt in front of the next
+    // register it reuses, with the dot product's partner (requested at the end of the slot loop, meant to stay in flight
+    // through the sweeps) among what is drained.
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0) alone (gfx9 encoding: expcnt 7 and lgkmcnt 15 wait for nothing)
   }
   double acc[BS] = {0.0, 0.0};
   if (active) {
@@ -139,8 +191,28 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
       if (q < W) {
         const int cg = cgs[q];
         double blk[BB];
-        load_block<BS>(sval, n, q, i, blk);
-        if constexpr (SPMV) {
+        if constexpr (STAGE) {
+          if (q == 0) {
+#pragma unroll
+            for (int e = 0; e < BB; e++) blk[e] = blk0[e];
+          } else load_block<BS>(sval, n, q, i, blk);
+          // in-brick columns -- the sweeps' couplings, slots [lfirst, ulast) -- read S from the solution area at the
+          // brick-local number the sweeps use (a far column: the own entry, unused); the diagonal slot has it in registers
+          const bool inb = (q >= lfirst) && (q < ulast);
+          const double2 sv = *reinterpret_cast<const double2*>(ys + ((inb && q != dslot) ? cg - lob : tid) * 2);
+          double xv[BS] = {q == dslot ? xin[0] : sv.x, q == dslot ? xin[1] : sv.y};
+          if (!inb) {
+            if (q == 0) {
+              // (the compiler must not form S of the gathered pair where the pair was requested, in front of the barrier)
+              asm volatile("" : "+v"(xr0[0]), "+v"(xr0[1]));
+              xv[0] = xr0[0]; xv[1] = xr0[1];
+              if constexpr (AX) { xv[0] = __builtin_fma(nalpha, xv0[0], xv[0]); xv[1] = __builtin_fma(nalpha, xv0[1], xv[1]); }
+            } else load_xs<BS, AX>(in, in2, nalpha, cg, xv);
+          }
+          acc[0] += blk[0] * xv[0] + blk[1] * xv[1];
+          acc[1] += blk[2] * xv[0] + blk[3] * xv[1];
+        } else load_block<BS>(sval, n, q, i, blk);
+        if constexpr (SPMV && !STAGE) {
           double xv[BS];
           load_xs<BS, AX>(in, in2, nalpha, cg, xv);
           acc[0] += blk[0] * xv[0] + blk[1] * xv[1];
@@ -178,6 +250,7 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
     // barrier)
     if (dot == PC_DOT_ZA || dot == PC_DOT_MERGED) load_x_stream<BS>(aux, i, avp);   // the dot product's partner: in flight through the sweeps
   }
+  if constexpr (STAGE) lds_barrier();   // every row has read the S it needs: the area is the solution's again
   if (active) *reinterpret_cast<double2*>(ys + tid * 2) = make_double2(acc[0], acc[1]);
   __syncthreads();
   auto gather3 = [&](const int (&cc)[MLU], const double (&ff)[MLU][BB], double* sum) {
@@ -227,6 +300,25 @@ __global__ __launch_bounds__(512, 6) void k_pc_park(
   if (dot != 0) {
     double* red = lds + (size_t)blockDim.x * BS;
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if constexpr (STAGE) {
+      // The products of pc_row_dots<BS, true, false>, with the FMA each is contracted into written out.  The compiler is free
+      // to fuse either multiplication of p0 r0 + p1 r1 into the addition, the two choices round apart, and what it chooses
+      // depends on where the operands come from: with xin a plain fma's result instead of the slot loop's select it chose
+      // otherwise for (x, x), and the staged launch's (S, S) was one ulp off the unstaged one's.  These are the forms the
+      // unstaged instantiations compile to (profiles/stage_kernel_asm_r10.log); tests/test_hip_park_stage.py holds the two
+      // kernels to the same bits.
+      auto hi = [](const double (&p)[BS], const double (&r)[BS]) { return __builtin_fma(p[0], r[0], p[1] * r[1]); };
+      auto lo = [](const double (&p)[BS], const double (&r)[BS]) { return __builtin_fma(p[1], r[1], p[0] * r[0]); };
+      if (dot == PC_DOT_ZA) {
+        if (active) v[0] = hi(out, avp);
+      } else if (dot == PC_DOT_XZ) {
+        v[0] = hi(xin, out); v[1] = hi(out, out);
+      } else if (dot == PC_DOT_MERGED) {
+        if (active) { v[0] = hi(xin, out); v[1] = hi(out, out); v[2] = lo(xin, xin); v[3] = lo(xin, avp); v[4] = hi(out, avp); }
+      } else {
+        v[0] = hi(out, out);
+      }
+    } else
     pc_row_dots<BS, true, false>(dot, v, out, active, [&](double (&x)[BS]) { x[0] = xin[0]; x[1] = xin[1]; },
                                  [&](double (&a)[BS]) { a[0] = avp[0]; a[1] = avp[1]; });
     // the reduction scratch is touched by nothing before this point; dropping the barrier was not felt (0.5704 / 0.6942

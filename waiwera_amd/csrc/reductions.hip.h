@@ -301,6 +301,18 @@ __device__ __forceinline__ bool fin_block(const Fin& f, const double* partials, 
 // bricks per CU, in workgroups of four) gains 1.5 % with 4 us per cohort (C5 0.1981-0.1993 -> 0.1954-0.1959, C4's quarter
 // 0.1687-0.1695 -> 0.1661-0.1666).  (Round 3 tried the same on the all-loads-at-once experiment k_pc_rows3 and saw no
 // change: there a brick's loads ARE one burst.)
+// A workgroup barrier that orders LDS accesses only: what the waves wrote to LDS before it is what they read after it, and
+// nothing waits for vector memory -- global loads requested in front of it are still in flight behind it.  The fences name
+// the local address space, so the only counter the compiler may wait on here is lgkmcnt.
+// (__syncthreads() fences every address space.  With only plain global loads outstanding this compiler emits the same
+// `s_waitcnt lgkmcnt(0); s_barrier` for it -- profiles/stage_kernel_asm_r10.log -- but nothing promises that; this form says
+// what is meant.)
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 struct Stagger { int ticks = 0, ncu = 256, per_cu = 3; };
 static_assert(std::is_trivially_copyable<Stagger>::value, "a kernel argument holds views, never an owner");
 __device__ __forceinline__ void stagger_start(const Stagger& st) {
