@@ -477,6 +477,28 @@ int wai_set_sub_pc(wai_ctx *ctx, int sub);
  * more than 1024 rows, a tile that straddles a subdomain boundary.  The preconditioner is set up again by its next use. */
 int wai_set_pc_tiles(wai_ctx *ctx, int n_tiles, const int *tile_ptr);
 
+/* Order in which block-Jacobi ILU(0) eliminates the rows of a subdomain.  WAI_PC_ORDER_NATURAL (the default): as numbered --
+ * the reference's ILU(0), whose two substitutions are dependency chains as long as the subdomain is deep.
+ * WAI_PC_ORDER_MULTICOLOUR: the rows of every subdomain of sub_ptr (one block per rank where it is NULL) are coloured --
+ * ascending row index, each row the smallest colour none of its already coloured in-subdomain neighbours has -- and the
+ * factor of subdomain s is the block ILU(0) of P A_ss P^T, P sorting the subdomain's rows by (colour, row index).  Rows of
+ * one colour do not couple, so each substitution has as many levels as the subdomain has colours (2 on hexahedral and
+ * MINC meshes, at most 16); the factorisation and the 2 colours - 1 sweeps of an application run as one launch per colour
+ * over the rows of that colour in all subdomains (k_colour_sweep, stored factor).  NOT the reference's preconditioner: a
+ * different incomplete factorisation of the same blocks, usually worth more Krylov iterations each of which is shorter.
+ * Nothing is renumbered for the caller: matrix, vectors and results keep their rows.
+ * The setting is the flow system's, under WAI_PC_BJACOBI with WAI_SUB_ILU and ilu_levels 0; under WAI_PC_NONE and
+ * WAI_PC_LU it is ignored.  The set-up refuses with -2 and a text that names the setting and what it met: WAI_PC_ASM,
+ * ilu_levels > 0, WAI_SUB_LU, source-network blocks in the factor's pattern, a row of more than 16 blocks.  A zero pivot is
+ * reported like ILU's (the solve's reason is PC_FAILED).  The tracer systems, per tracer and coupled, keep the natural
+ * order whatever the flow solver has; wai_set_pc_tiles has no effect on a multicolour factor.  Unknown value: -2 with a
+ * text.  The preconditioner is set up again by its next use.
+ * wai_get_pc_ordering returns the setting and the most colours of any subdomain, 0 before a set-up under
+ * WAI_PC_ORDER_MULTICOLOUR (out-arguments may be NULL). */
+enum { WAI_PC_ORDER_NATURAL = 0, WAI_PC_ORDER_MULTICOLOUR = 1 };
+int wai_set_pc_ordering(wai_ctx *ctx, int ordering);
+int wai_get_pc_ordering(wai_ctx *ctx, int *ordering, int *max_colours);
+
 /* The auxiliary (tracer) solver's own preconditioner: time.step.solver.auxiliary.preconditioner.{type, sub.preconditioner.{type,
  * factor.levels}} (timestepper_configure_auxiliary_linear_solver, src/timestepper.F90:2057-2065; the same keys as the flow
  * solver's).  pc_type: a WAI_PC_* value, or WAI_AUX_PC_FOLLOW (the default): the tracer solves use the flow solver's

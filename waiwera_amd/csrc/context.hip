@@ -305,6 +305,23 @@ int wai_set_sub_pc(wai_ctx* c, int sub) {
   return 0;
 }
 
+int wai_set_pc_ordering(wai_ctx* c, int ordering) {
+  if (!c) return -2;
+  if (ordering != WAI_PC_ORDER_NATURAL && ordering != WAI_PC_ORDER_MULTICOLOUR) {
+    c->err = "unknown preconditioner ordering (WAI_PC_ORDER_NATURAL or WAI_PC_ORDER_MULTICOLOUR)";
+    return -2;
+  }
+  if (ordering != c->pc_ordering) pc_invalidate(c);   // (what the setting refuses is refused by the next set-up: do_pc_setup)
+  c->pc_ordering = ordering;
+  return 0;
+}
+int wai_get_pc_ordering(wai_ctx* c, int* ordering, int* max_colours) {
+  if (!c) return -2;
+  if (ordering) *ordering = c->pc_ordering;
+  if (max_colours) *max_colours = c->colour.built ? c->colour.max_colours : 0;
+  return 0;
+}
+
 int wai_set_pc_tiles(wai_ctx* c, int n_tiles, const int* tile_ptr) {
   if (!c) return -2;
   if (n_tiles < 0) { c->err = "wai_set_pc_tiles: n_tiles < 0"; return -1; }

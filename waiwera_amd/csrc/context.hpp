@@ -6,6 +6,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/waiwera_hip.h"
+#include "colour_order.hpp"   // ColourFacts
 #include "devbuf.hpp"
 #include "ilu_schedule.hpp"   // ScheduleFacts
 #include "mesh_pattern.hpp"   // MAX_CELL_FACES
@@ -272,6 +273,20 @@ struct IluSchedule : ScheduleFacts {
   // buffers too.  Set by do_pc_setup; pc_invalidate when a system's values or the preconditioner's kind change
   const LinSys* owner = nullptr;
 };
+// Block-Jacobi ILU(0) in multicolour order (wai_set_pc_ordering; colour_order.hpp, where build_colour_order makes the facts
+// and every table on the host): the tables on the device.  The flow system's alone; the factor itself goes to the shared
+// buffers of wai_ctx::ilu (fval: L multipliers, U and, in the diagonal slot, the inverted pivot; dinv), one system's factor at
+// a time as ever (IluSchedule::owner).  built: the tables stand for the subdomains and the pattern in force
+struct ColourSchedule : ColourFacts {
+  bool built = false;
+  bool fused = false;       // k_pc_colour serves (pc_colour_serves, recorded by the set-up): diag_only, rows of <= 8 blocks, subdomains that fit a
+                            // workgroup (1024 rows at block sizes 1 and 2, 512 at 3, 256 at 4), one rank, WAI_COLOUR_SWEEPS unset
+  DevBuf<int> sub_ptr;      // [nsub + 1] row ranges
+  DevBuf<int> sub_ncol;     // [nsub] colours of the subdomain
+  DevBuf<int> rows;         // the launch lists: all rows sorted by (colour, row); colour c is rows [col_ptr[c], col_ptr[c + 1])
+  DevBuf<unsigned long long> slots;   // per row: its in-subdomain slots in elimination order, 4 bits each, lower ones first
+  DevBuf<int> counts;       // per row: lower | upper << 8 | diagonal slot << 16 | colour << 24
+};
 // threads of a brick kernel's workgroup: one per row of the largest subdomain, whole waves
 inline int pc_threads(const IluSchedule& s) { return ((s.max_rows + 63) / 64) * 64; }
 
@@ -534,6 +549,8 @@ struct wai_ctx : wai::Handles {
   wai::EosParams ep{};
   wai_solver_opts opts{};
   int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
+  int pc_ordering = WAI_PC_ORDER_NATURAL;   // wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
+  wai::ColourSchedule colour;   // ... its symbolic phase under WAI_PC_ORDER_MULTICOLOUR, built by the first set-up that needs it
   std::vector<int> pc_tiles;    // wai_set_pc_tiles: row ranges [n_tiles + 1] of the tiles that refine the subdomains; empty: none
   wai::DeviceMesh mesh;
   wai::Sources src;
@@ -568,9 +585,12 @@ struct wai_ctx : wai::Handles {
   // WAI_NO_DESC_SHARE: k_pc_park on col16 reads every brick's own descriptors instead of the shared templates
   // WAI_NO_PACK: one k_pc_park workgroup per brick on a schedule that has packed groups (the A/B and the bit-identity tests)
   // WAI_PARK_STAGE=0|1: k_pc_park's operator launches without / with the brick's operand segment staged in LDS
+  // WAI_COLOUR_SWEEPS: the multicolour ordering keeps its launch-per-colour path (k_colour_sweep) where the fused launch
+  // k_pc_colour would serve (the tests' comparison and the timing tool; read at the preconditioner's set-up)
   struct EnvSw {
     bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false;
     bool asm_unfused = false; bool no_desc_share = false; bool no_pack = false;
+    bool colour_sweeps = false;
     int park_stage = -1;   // WAI_PARK_STAGE: 0 / 1 k_pc_park's staged operand off / on for every launch kind, -1 the compiled-in defaults
   } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
@@ -646,6 +666,15 @@ bool pc_axpy_capable(const wai_ctx* c, const Bcsr& M);
 bool pc_axpy_default(const wai_ctx* c, const Bcsr& M);   // is the composed second launch the default for the kernel in force (k_pc_park with col16)
 // subdomains of any size: level-by-level launches, in place on z (z = r on entry)
 int launch_big_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
+// multicolour order (ColourSchedule): the factor of M into s.fval / s.dinv, one launch per colour; both substitutions in place
+// on z, 2 colours - 1 launches of k_colour_sweep
+int launch_colour_factor(wai_ctx* c, const Bcsr& M, const ColourSchedule& k, IluSchedule& s);
+int launch_colour_solve(wai_ctx* c, const Bcsr& M, const ColourSchedule& k, const IluSchedule& s, double* z);
+// the fused launch of the multicolour ordering (k_pc_colour): does it serve (the set-up records the answer in k.fused), and
+// z = B^-1 (A in) or B^-1 in with launch_pc's dot modes and finalisation
+bool pc_colour_serves(const wai_ctx* c, const Bcsr& M, const ColourSchedule& k, bool one_rank);
+int launch_pc_colour(wai_ctx* c, const Bcsr& M, const ColourSchedule& k, const IluSchedule& s, bool spmv, const double* in, double* z,
+                     int dot_mode, const double* aux, const Fin* fin = nullptr);
 // sub-preconditioner lu (IluSchedule::sublu): both substitutions of every block in one launch, in place on z
 int launch_sublu_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
 bool sublu_vector_in_lds(const IluSchedule& s, int bs);   // does k_sublu_solve hold a block's part of the vector in LDS

@@ -129,8 +129,18 @@ inline bool pc_asm_fused(const wai_ctx* c, const LinSys& sys) {
 }
 // either: the factor has a pattern of its own (sys.as.E on sys.as.sched) -- no composed operand, no interior / face split
 inline bool pc_own_factor(const wai_ctx* c, const LinSys& sys) { return pc_fill_fused(c, sys) || pc_asm_fused(c, sys); }
+// block-Jacobi ILU(0) in multicolour order is in force for `sys` (wai_set_pc_ordering): the flow system's alone, where the
+// set-up does not refuse the combination (do_pc_setup); the tracer systems keep the natural order.  Its factor is the stored
+// one on the matrix' own planes (wai_ctx::ilu's buffers), its tables wai_ctx::colour's; one fused launch (k_pc_colour) applies it
+// where ColourSchedule::fused says so, pc_solve's launch-per-colour sweeps everywhere else
+inline bool pc_colour(const wai_ctx* c, const LinSys& sys) {
+  const PcOpts p = pc_of(c, sys);
+  return c->pc_ordering == WAI_PC_ORDER_MULTICOLOUR && &sys == &c->flow && p.type == WAI_PC_BJACOBI && p.ilu_levels <= 0 &&
+         !pc_sub_lu(p) && !pc_with_net(c, sys);
+}
 inline bool pc_fused(const wai_ctx* c, const LinSys& sys) {
   const PcOpts p = pc_of(c, sys);
+  if (pc_colour(c, sys)) return c->colour.fused;   // k_pc_colour, or the launch-per-colour path: the unfused branches of pc_amul and pc_solve
   if (pc_own_factor(c, sys)) return true;
   return p.type == WAI_PC_BJACOBI && !c->ilu.big && p.ilu_levels <= 0 && !pc_with_net(c, sys) && !pc_sub_lu(p);
 }

@@ -565,6 +565,161 @@ __global__ __launch_bounds__(1024) void k_tile_solve(int n, const int* __restric
   }
 }
 
+// ---- multicolour order (wai_set_pc_ordering, colour_order.hpp): one launch per COLOUR ----------------------------------------
+// Every subdomain's rows are eliminated sorted by (colour, row index) and rows of one colour do not couple, so the rows of a
+// colour are independent across all subdomains: the factorisation is one launch per colour, a substitution sweep one launch
+// per colour too, and kernel boundaries order the colours -- the launch-per-level path above with 2 levels (hexahedral and
+// MINC meshes) where the natural order has hundreds.  A row's descriptor (ColourSchedule::slots, counts) lists its
+// in-subdomain slots in elimination order, the lower ones first; nothing is renumbered, the factor sits on the matrix' own
+// column planes: L multipliers (already multiplied by the inverted pivot of their column's row), U, and the inverted pivot in
+// the diagonal slot and in dinv.
+// The general IKJ row elimination on that order: for each lower coupling k in elimination order, L_ik = A_ik inv(P_k), then
+// A_ij -= L_ik U_kj for every j that follows k in row k's order and is in row i's pattern too: the diagonal (j = i), a later
+// lower coupling or an upper one.  Rows k belong to earlier colours: an earlier launch finished them.
+template <int BS>
+__global__ __launch_bounds__(TPB) void k_colour_factor(int n, int cnt, const int* __restrict__ rows,
+                                                       const unsigned long long* __restrict__ slots, const int* __restrict__ counts,
+                                                       const int* __restrict__ col, double* fval, double* __restrict__ dinv, int* flags) {
+  constexpr int BB = BS * BS;
+  const int t = blockIdx.x * TPB + threadIdx.x;
+  if (t >= cnt) return;
+  const int i = rows[t];
+  const unsigned long long sl = slots[i];
+  const int ct = counts[i], nl = colour_nlower(ct), nu = colour_nupper(ct), dslot = colour_dslot(ct);
+  for (int p = 0; p < nl; p++) {
+    const int q = colour_slot(sl, p);
+    const int k = col[(size_t)q * n + i];
+    double w[BB], d[BB], tt[BB];
+#pragma unroll
+    for (int z = 0; z < BB; z++) { w[z] = fval[vix<BS>(n, q, z, i)]; d[z] = dinv[dix<BS>(n, z, k)]; }
+#pragma unroll
+    for (int r = 0; r < BS; r++)
+#pragma unroll
+      for (int c = 0; c < BS; c++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int e = 0; e < BS; e++) acc += w[r * BS + e] * d[e * BS + c];
+        tt[r * BS + c] = acc;
+      }
+#pragma unroll
+    for (int z = 0; z < BB; z++) fval[vix<BS>(n, q, z, i)] = tt[z];
+    const unsigned long long ksl = slots[k];
+    const int kct = counts[k], knl = colour_nlower(kct), knu = colour_nupper(kct);
+    for (int p2 = knl; p2 < knl + knu; p2++) {   // row k's upper blocks U_kj
+      const int r2 = colour_slot(ksl, p2);
+      const int j = col[(size_t)r2 * n + k];
+      int q2 = -1;                               // the slot of A_ij in row i
+      if (j == i) q2 = dslot;
+      else
+        for (int p3 = p + 1; p3 < nl + nu; p3++) {
+          const int s3 = colour_slot(sl, p3);
+          if (col[(size_t)s3 * n + i] == j) { q2 = s3; break; }
+        }
+      if (q2 < 0) continue;
+      double u[BB];
+#pragma unroll
+      for (int z = 0; z < BB; z++) u[z] = fval[vix<BS>(n, r2, z, k)];
+#pragma unroll
+      for (int r = 0; r < BS; r++)
+#pragma unroll
+        for (int c = 0; c < BS; c++) {
+          double acc = 0.0;
+#pragma unroll
+          for (int e = 0; e < BS; e++) acc += tt[r * BS + e] * u[e * BS + c];
+          fval[vix<BS>(n, q2, r * BS + c, i)] -= acc;
+        }
+    }
+  }
+  double piv[BB], inv[BB];
+#pragma unroll
+  for (int z = 0; z < BB; z++) piv[z] = fval[vix<BS>(n, dslot, z, i)];
+  if (!block_inverse<BS>(piv, inv)) atomicMax(&flags[0], 1);
+#pragma unroll
+  for (int z = 0; z < BB; z++) {
+    fval[vix<BS>(n, dslot, z, i)] = inv[z];
+    dinv[dix<BS>(n, z, i)] = inv[z];
+  }
+}
+
+// One colour of one substitution, in place on z.  Forward (FWD): y_i = t_i - sum over the row's lower couplings L_ik y_k;
+// backward: x_i = inv(P_i) (y_i - sum over its upper couplings U_ij x_j); both in the descriptor's order.  The coupled rows
+// have other colours: an earlier launch of the sweep finished them, and no row of this launch is read by another.
+template <int BS, bool FWD>
+__global__ __launch_bounds__(TPB) void k_colour_sweep(int n, int cnt, const int* __restrict__ rows,
+                                                      const unsigned long long* __restrict__ slots, const int* __restrict__ counts,
+                                                      const int* __restrict__ col, const double* __restrict__ fval,
+                                                      const double* __restrict__ dinv, double* z) {
+  constexpr int BB = BS * BS;
+  const int t = blockIdx.x * TPB + threadIdx.x;
+  if (t >= cnt) return;
+  const int i = rows[t];
+  const unsigned long long sl = slots[i];
+  const int ct = counts[i], nl = colour_nlower(ct), nu = colour_nupper(ct);
+  double acc[BS];
+#pragma unroll
+  for (int r = 0; r < BS; r++) acc[r] = z[(size_t)i * BS + r];
+  const int p0 = FWD ? 0 : nl, p1 = FWD ? nl : nl + nu;
+  for (int p = p0; p < p1; p++) {
+    const int q = colour_slot(sl, p);
+    const int k = col[(size_t)q * n + i];
+    double m[BB], zk[BS];
+#pragma unroll
+    for (int e = 0; e < BB; e++) m[e] = fval[vix<BS>(n, q, e, i)];
+#pragma unroll
+    for (int c = 0; c < BS; c++) zk[c] = z[(size_t)k * BS + c];
+#pragma unroll
+    for (int r = 0; r < BS; r++)
+#pragma unroll
+      for (int c = 0; c < BS; c++) acc[r] -= m[r * BS + c] * zk[c];
+  }
+  if constexpr (FWD) {
+#pragma unroll
+    for (int r = 0; r < BS; r++) z[(size_t)i * BS + r] = acc[r];
+  } else {
+    double d[BB];
+#pragma unroll
+    for (int e = 0; e < BB; e++) d[e] = dinv[dix<BS>(n, e, i)];
+#pragma unroll
+    for (int r = 0; r < BS; r++) {
+      double o = 0.0;
+#pragma unroll
+      for (int c = 0; c < BS; c++) o += d[r * BS + c] * acc[c];
+      z[(size_t)i * BS + r] = o;
+    }
+  }
+}
+
+int launch_colour_factor(wai_ctx* c, const Bcsr& J, const ColourSchedule& k, IluSchedule& s) {
+  if (J.dg) { c->err = "launch_colour_factor: the coupled tracer system keeps the natural order"; return -1; }
+  return with_bs(J.bs, [&](auto bs) {
+    constexpr int BS = decltype(bs)::value;
+    // the factor starts as a copy of the matrix; colour 0 has nothing to eliminate and inverts its pivots
+    hipMemcpyAsync(s.fval, J.val, sizeof(double) * ell_size(J.bs, J.n, J.W), hipMemcpyDeviceToDevice, c->stream);
+    for (int col = 0; col < k.max_colours; col++) {
+      const int a = k.col_ptr[col], cnt = k.col_ptr[col + 1] - a;
+      if (cnt <= 0) continue;
+      hipLaunchKernelGGL(k_colour_factor<BS>, (cnt + TPB - 1) / TPB, TPB, 0, c->stream, J.n, cnt, k.rows + a, k.slots, k.counts, J.col, s.fval,
+                         s.dinv, c->d_flags);
+    }
+  });
+}
+
+// forward over colours 1 .. C - 1 (colour 0 has no lower coupling), backward over C - 1 .. 0: 2 C - 1 launches
+int launch_colour_solve(wai_ctx* c, const Bcsr& J, const ColourSchedule& k, const IluSchedule& s, double* z) {
+  if (J.dg) { c->err = "launch_colour_solve: the coupled tracer system keeps the natural order"; return -1; }
+  return with_bs(J.bs, [&](auto bs) {
+    constexpr int BS = decltype(bs)::value;
+    auto sweep = [&](auto fwd, int col) {
+      const int a = k.col_ptr[col], cnt = k.col_ptr[col + 1] - a;
+      hipLaunchKernelGGL((k_colour_sweep<BS, decltype(fwd)::value>), (cnt + TPB - 1) / TPB, TPB, 0, c->stream, J.n, cnt, k.rows + a, k.slots,
+                         k.counts, J.col, s.fval, s.dinv, z);
+      c->ks.n_launch++;
+    };
+    for (int col = 1; col < k.max_colours; col++) sweep(std::true_type{}, col);
+    for (int col = k.max_colours - 1; col >= 0; col--) sweep(std::false_type{}, col);
+  });
+}
+
 // z_b = inv(A_b) r_b: one workgroup per block, one wave per output row at a time (coalesced row reads)
 __global__ __launch_bounds__(256) void k_lu_apply(int nsub, int bs, const int* __restrict__ sub_ptr,
                                                   const size_t* __restrict__ inv_ptr, const double* __restrict__ inv,

@@ -1,11 +1,12 @@
 // Every kernel that stores or finalises a partial sum -- the five fused preconditioned-operator kernels and the K9 vector
 // kernels -- with their launchers, the run-time switches and the tests' fault-injection hook (reductions.hip.h says why
-// they share one translation unit).
+// they share one translation unit); the multicolour ordering's k_pc_colour is the sixth fused kernel.
 #include "pc_generic.hip.h"
 #include "pc_wide.hip.h"
 #include "pc_park.hip.h"
 #include "pc_rows.hip.h"
 #include "pc_wave.hip.h"
+#include "pc_colour.hip.h"
 #include "krylov_vec.hip.h"
 
 namespace wai {
@@ -25,6 +26,7 @@ void read_env(wai_ctx* c) {
   c->env.asm_unfused = getenv("WAI_ASM_UNFUSED") != nullptr;
   c->env.no_desc_share = getenv("WAI_NO_DESC_SHARE") != nullptr;
   c->env.no_pack = getenv("WAI_NO_PACK") != nullptr;
+  c->env.colour_sweeps = getenv("WAI_COLOUR_SWEEPS") != nullptr;
   const char* st = getenv("WAI_PARK_STAGE");
   c->env.park_stage = st && (st[0] == '0' || st[0] == '1') ? st[0] - '0' : -1;
 }
@@ -267,6 +269,40 @@ int launch_pc_on(wai_ctx* c, const Bcsr& M, const IluSchedule& s, bool spmv, con
   }
   return 0;
 }
+// The multicolour ordering's fused launch (k_pc_colour; ColourSchedule::fused says whether it serves): one workgroup per
+// subdomain on the matrix' own planes, the inverted pivots from s.dinv; partial sums and finalisers as launch_pc_on's
+bool pc_colour_serves(const wai_ctx* c, const Bcsr& M, const ColourSchedule& k, bool one_rank) {
+  const int T = ((k.max_rows + 63) / 64) * 64;
+  return k.built && k.diag_only && !M.dg && M.W <= WMAX && k.max_blocks <= WMAX && M.bs >= 1 && M.bs <= 4 && T <= pc_colour_threads(M.bs) &&
+         one_rank && !c->env.colour_sweeps;
+}
+int launch_pc_colour(wai_ctx* c, const Bcsr& M, const ColourSchedule& k, const IluSchedule& s, bool spmv, const double* in, double* z,
+                     int dot_mode, const double* aux, const Fin* finp) {
+  if (!k.fused) { c->err = "launch_pc_colour: the colour schedule is not served by the fused launch"; return -1; }
+  const Fin* fin_later = nullptr;
+  if (finp && dot_mode != 0 && c->env.fin_separate) { fin_later = finp; finp = nullptr; }
+  const bool with_fin = finp && dot_mode != 0;
+  Fin fin;
+  if (with_fin) { fin = *finp; fin.count = k.nsub; fin.nb = k.nsub; fin.nf = fin_slices(k.nsub); }
+  c->ks.nb_pc = k.nsub;   // one partial sum per subdomain and slot
+  c->ks.n_launch++;
+  const int grid = ((k.nsub + 7) / 8) * 8 + (with_fin ? fin.nf : 0), T = ((k.max_rows + 63) / 64) * 64;
+  if (with_bs(M.bs, [&](auto bs) {
+        constexpr int BS = decltype(bs)::value;
+        const size_t lds = ((size_t)T * BS + 80) * sizeof(double);
+        with_flag(spmv, [&](auto sp) {
+          hipLaunchKernelGGL((k_pc_colour<BS, decltype(sp)::value>), grid, T, lds, c->stream, M.n, M.W, k.nsub, k.sub_ptr, k.sub_ncol,
+                             k.slots, k.counts, M.col, M.val, s.dinv, in, z, aux, c->ks.partials, c->ks.nb_max, dot_mode, nullptr, fin);
+        });
+      }) != 0)
+    return -1;
+  if (fin_later) {
+    vec_finalize(c, c->ks.nb_pc, fin_later->slot0, fin_later->nslots, fin_later->phase);
+    if (fin_later->seq > 0) bcgs_post(c, fin_later->seq);
+  }
+  return 0;
+}
+
 int launch_pc(wai_ctx* c, const Bcsr& M, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
               const int* list, int nrun, const Fin* fin, const double* in2) {
   return launch_pc_on(c, M, c->ilu, spmv, in, z, dot_mode, aux, list, nrun, fin, in2);

@@ -57,6 +57,10 @@ int read_scal_end(wai_ctx* c) {
 
 int launch_pc_sys(wai_ctx* c, const LinSys& sys, bool spmv, const double* in, double* z, int dot_mode, const double* aux,
                   const int* list, int nrun, const Fin* fin, const double* in2) {
+  if (pc_colour(c, sys)) {   // the multicolour ordering's fused launch: all subdomains, no composed operand (pc_axpy_ok)
+    if (list || in2) { c->err = "launch_pc_sys: a launch list or a composed operand asked of k_pc_colour"; return -1; }
+    return launch_pc_colour(c, sys.A, c->colour, c->ilu, spmv, in, z, dot_mode, aux, fin);
+  }
   if (pc_fill_fused(c, sys)) return launch_pc_on(c, sys.A, sys.as.sched, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, &sys.as.E);
   if (pc_asm_fused(c, sys))
     return launch_pc_on(c, sys.A, sys.as.sched, spmv, in, z, dot_mode, aux, list, nrun, fin, in2, &sys.as.E, sys.as.ext_row);
@@ -122,6 +126,9 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
     else if (a.sched.big) { if (launch_big_solve(c, a.E, a.sched, a.r_ext)) return -1; }
     else if (launch_pc_on(c, a.E, a.sched, false, a.r_ext, a.r_ext, PC_DOT_NONE, nullptr)) return -1;
     launch_asm_scatter(c, a, z);
+  } else if (pc_colour(c, sys)) {   // block Jacobi in multicolour order: a launch per colour, subdomains of any size
+    if (z != r) vec_copy(c, z, r, n);
+    if (launch_colour_solve(c, sys.A, c->colour, c->ilu, z)) return -1;
   } else {   // block Jacobi with subdomains of more than 1024 rows
     if (z != r) vec_copy(c, z, r, n);
     if (launch_big_solve(c, sys.A, c->ilu, z)) return -1;
@@ -251,7 +258,7 @@ int bcgs_mode(const wai_ctx* c) {
 // (profiles/compose_full_c4c5_ab_r5.log): C4 1.303 -> 1.265, C5 0.486 -> 0.467.  WAI_BCGS_COMPOSE=0 / 1 forces it off / on
 // (k_pc_rows -- 4 x 4 blocks, MINC inside 3-D bricks -- not measured: on request).
 bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys) {
-  if (!(pc_fused(c, sys) && !pc_own_factor(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
+  if (!(pc_fused(c, sys) && !pc_own_factor(c, sys) && !pc_colour(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
   if (const char* e = getenv("WAI_BCGS_COMPOSE")) return e[0] == '1';
   return pc_axpy_default(c, sys.A);
 }

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_stream_read(const stream_d2* __restrict
 }
 // can pc_amul form its operand x - alpha x2 inside the launch?  (pc_axpy_ok without the switch and the default)
 bool pc_operand_composable(const wai_ctx* c) {
-  return pc_fused(c, c->flow) && !pc_own_factor(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A);
+  return pc_fused(c, c->flow) && !pc_own_factor(c, c->flow) && !pc_colour(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A);
 }
 }  // namespace
 
@@ -50,6 +50,8 @@ int wai_bench_kernel(wai_ctx* c, int which, int reps, float* ms_per_launch) {
   KrylovVecs& k = *sys.kv;
   if ((which == 20 || which == 21) && !k.basis) { c->err = "wai_bench_kernel 20 / 21: no Krylov basis (ksp_type gmres)"; return -2; }
   if (which > 0 && c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
+  // the probes launch the natural order's kernels on the brick schedule: the multicolour factor is not theirs to read
+  if (which > 0 && pc_colour(c, sys)) { c->err = "wai_bench_kernel: the natural order's kernels, not the multicolour ordering (tools/pc_colour_timing.py times it)"; return -2; }
   const bool fill = pc_fill_fused(c, sys);   // the filled ILU(k) factor: its own pattern and schedule (sys.as)
   if (which == 23 && (!pc_fused(c, sys) || !(fill ? sys.as.sched.ord_f : c->ilu.ord_f))) {
     c->err = "wai_bench_kernel 23: no level sets (a block-Jacobi schedule of a wide mesh, or fused ILU(k))";
@@ -183,6 +185,11 @@ const char* wai_pc_kernel_name(wai_ctx* c) {
              pc.type == WAI_PC_ASM ? "ASM" : "block Jacobi");
     return buf;
   }
+  if (pc_colour(c, sys)) {
+    if (!c->colour.fused) return "k_spmv + k_colour_sweep per colour (block Jacobi, multicolour ILU(0))";
+    snprintf(buf, sizeof(buf), "k_pc_colour<%d,spmv>", bs);
+    return buf;
+  }
   if (pc_fill_fused(c, sys)) {   // one launch: A on the Jacobian's planes, the sweeps on the filled factor's
     snprintf(buf, sizeof(buf), "k_pc_wide<%d,spmv> on the filled factor (block Jacobi, ILU(%d))", bs, pc.ilu_levels);
     return buf;
@@ -246,7 +253,7 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   LinSys& sys = c->flow;
   if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
   if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
-  if (split && (!spmv || !pc_fused(c, sys) || pc_own_factor(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
+  if (split && (!spmv || !pc_fused(c, sys) || pc_own_factor(c, sys) || pc_colour(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
     c->err = "wai_test_pc_operator: no interior / face brick lists to split the launch over";
     return -1;
   }

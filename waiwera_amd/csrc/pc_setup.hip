@@ -252,6 +252,36 @@ int lu_setup(wai_ctx* c, const LinSys& sys) {
   return 0;
 }
 
+// The multicolour ordering's symbolic phase on the device (wai_set_pc_ordering): every fact and table from build_colour_order
+// (colour_order.hpp) on the mesh's pattern and the subdomains in force, uploaded.  Neither changes after wai_ctx_create, so the
+// tables are built once, by the first set-up that needs them.  The factor goes to wai_ctx::ilu's buffers.
+static int build_colour(wai_ctx* c) {
+  ColourSchedule& k = c->colour;
+  if (k.built) return 0;
+  const Pattern& J = c->pat;
+  HostColourOrder h;
+  if (int e = build_colour_order(J.h_rowptr, J.h_colidx, c->ilu.sub, J.n, h, c->err)) return e;
+  if (k.sub_ptr.upload(c, h.sub) || k.sub_ncol.upload(c, h.ncolours) || k.rows.upload(c, h.rows) || k.slots.upload(c, h.slots) ||
+      k.counts.upload(c, h.counts))
+    return -1;
+  static_cast<ColourFacts&>(k) = std::move(h);
+  k.built = true;
+  return 0;
+}
+
+// what the multicolour ordering does not combine with, on the flow system under block Jacobi or PCASM: -2 with a text that
+// names the setting and what it met
+static int colour_refusal(wai_ctx* c, const LinSys& sys, const PcOpts& pc) {
+  const char* met = nullptr;
+  if (pc.type == WAI_PC_ASM) met = "preconditioner asm (WAI_PC_ASM)";
+  else if (pc_sub_lu(pc)) met = "sub-preconditioner lu (WAI_SUB_LU)";
+  else if (pc.ilu_levels > 0) met = "ilu_levels > 0 (ILU(k) fill)";
+  else if (pc_with_net(c, sys)) met = "source-network blocks in the factor's pattern (wai_set_network_couplings)";
+  if (!met) return 0;
+  c->err = std::string("wai_set_pc_ordering: the multicolour ordering (WAI_PC_ORDER_MULTICOLOUR) serves bjacobi with ILU(0) alone; it met ") + met;
+  return -2;
+}
+
 // Sets the preconditioner up for `sys` and records it as the owner of the (shared) factor: 0 done, 1 a pivot failed
 // (recoverable; the record stands as it did for the flags read back last), < 0 error
 int do_pc_setup(wai_ctx* c, LinSys& sys) {
@@ -267,7 +297,13 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
   {
     Prof p(c, KC_PC_SETUP);
     const Bcsr& A = sys.A;
-    if (pc_extended(c, sys)) {
+    if (c->pc_ordering == WAI_PC_ORDER_MULTICOLOUR && &sys == &c->flow) {
+      // the flow system's factor in multicolour order: refusals first, then the symbolic phase (once), then a launch per colour
+      if (int e = colour_refusal(c, sys, pc)) return e;
+      if (int e = build_colour(c)) return e == -2 ? -2 : -1;
+      c->colour.fused = pc_colour_serves(c, A, c->colour, !(c->comm && c->comm->nranks > 1));
+      if (launch_colour_factor(c, A, c->colour, c->ilu)) return -1;
+    } else if (pc_extended(c, sys)) {
       AsmSystem& as = sys.as;
       const int ov = pc.type == WAI_PC_ASM ? (pc.asm_overlap > 0 ? pc.asm_overlap : 1) : 0;
       const bool sl = pc_sub_lu(pc);

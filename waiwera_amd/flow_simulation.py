@@ -536,6 +536,20 @@ class FlowSimulation:
         self._chk(LIB.wai_set_sub_pc(self.h, _lib.SUB_PC[sub]), "set_sub_pc")
         self.sub_pc = sub
 
+    def set_pc_ordering(self, ordering):
+        """elimination order of the flow system's block-Jacobi ILU(0) (wai_set_pc_ordering): "natural" (default, the
+        reference's) or "multicolour" -- every subdomain's rows by (colour, row), two sweep levels on hexahedral and MINC
+        meshes; what it does not combine with (asm, ILU(k), sub lu, network blocks in the factor) is refused by the next set-up"""
+        if ordering not in _lib.PC_ORDER:
+            raise ValueError("pc ordering %r: one of %s" % (ordering, sorted(_lib.PC_ORDER)))
+        self._chk(LIB.wai_set_pc_ordering(self.h, _lib.PC_ORDER[ordering]), "set_pc_ordering")
+
+    def pc_ordering(self):
+        """(ordering, max_colours): the setting, and the most colours of any subdomain -- 0 before a set-up under multicolour"""
+        o, m = C.c_int(0), C.c_int(0)
+        self._chk(LIB.wai_get_pc_ordering(self.h, C.byref(o), C.byref(m)), "pc_ordering")
+        return {v: k for k, v in _lib.PC_ORDER.items()}[o.value], m.value
+
     def set_pc_tiles(self, tile_ptr):
         """tiles of the preconditioner's subdomains (wai_set_pc_tiles): contiguous owned-row ranges of 1 .. 1024 rows from 0 to
         n_owned that refine the subdomains -- the mesh's bricks under one block per rank.  A subdomain of more than 1024 rows then

@@ -28,6 +28,7 @@ pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
 THERMO = {"iapws": 0, "ifc67": 1}   # "thermodynamics" (src/thermodynamics_setup.F90)
 TRACER_SOLVE = {"per_tracer": 0, "coupled": 1}   # wai_set_tracer_solve_mode
 SUB_PC = {"ilu": 0, "lu": 1}   # wai_set_sub_pc: sub-preconditioner of bjacobi / asm
+PC_ORDER = {"natural": 0, "multicolour": 1}   # wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
 AUX_PC = dict(PC, follow=-1)   # wai_set_aux_pc: the tracer solver's own preconditioner, or the flow solver's ("follow", default)
 METHOD_KIND = {"beuler": 0, "bdf2": 1, "directss": 2}  # src/timestepper.F90:2262-2275
 
@@ -194,6 +195,8 @@ def _load():
         "wai_set_tracer_solve_mode": (i32, [vp, i32]),
         "wai_set_sub_pc": (i32, [vp, i32]),
         "wai_set_pc_tiles": (i32, [vp, i32, pi]),
+        "wai_set_pc_ordering": (i32, [vp, i32]),
+        "wai_get_pc_ordering": (i32, [vp, pi, pi]),
         "wai_set_aux_pc": (i32, [vp, i32, i32, i32, i32]),
         "wai_get_aux_pc": (i32, [vp, pi, pi, pi, pi]),
         "wai_tracer_block_system": (i32, [vp, i32, d, d, vp, vp, vp, vp]),

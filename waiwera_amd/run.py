@@ -39,6 +39,9 @@ def main(argv=None):
     ap.add_argument("--subdomains", choices=("chunks", "rank"), default="chunks",
                     help="the preconditioner's blocks: the mesh's chunks (default) or one block per rank, the reference's layout, "
                          "with the chunks as its tiles")
+    ap.add_argument("--pc-ordering", choices=("natural", "multicolour"), default="natural",
+                    help="elimination order of the flow solver's block-Jacobi ILU(0): as numbered (default, the reference's) or "
+                         "multicolour (two sweep levels per block on hexahedral and MINC meshes; bjacobi with ILU(0) only)")
     a = ap.parse_args(argv)
     import os
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -55,7 +58,7 @@ def main(argv=None):
         if os.environ.get("WAI_BENCH_LOOPBACK") != "1":
             a.device = int(os.environ.get("LOCAL_RANK", a.device))
     sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
-                               default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, **kw)
+                               default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

@@ -140,6 +140,24 @@ def linear_solver_options(obj, default_pc, sub_lu="host", defaults=None):
     return dict(opts=opts, sub_device=sub_device, pc=pct, named=pct_in is not None, note=note)
 
 
+def pc_ordering_refusal(lso, has_network):
+    """what the multicolour ordering (pc_ordering="multicolour", wai_set_pc_ordering) does not combine with, from
+    linear_solver_options' result for the flow solver and whether the input has a source network: a sentence that names the
+    setting and what it met, or None.  Pure -- the input and the arguments alone, so every rank decides alike.  Block Jacobi
+    with ILU(0) is served; under "none" and the dense "lu" the setting is ignored, as in the library."""
+    o = lso["opts"]
+    met = None
+    if o.get("pc_type") == "asm":
+        met = "preconditioner asm"
+    elif lso["sub_device"]:
+        met = "sub-preconditioner lu on the device (sub_lu='device')"
+    elif o.get("ilu_levels"):
+        met = "sub-preconditioner ilu with factor.levels %d (ILU(k))" % o["ilu_levels"]
+    elif has_network and o.get("pc_type") == "bjacobi":
+        met = "a source network (its Jacobian blocks go into the factor's pattern)"
+    return None if met is None else "pc_ordering 'multicolour' serves bjacobi with ILU(0) alone; the input and arguments give " + met
+
+
 def covers_coupled(lso):
     """does the coupled tracer solve cover the preconditioner of linear_solver_options' result: block Jacobi ILU(0) or none"""
     o = lso["opts"]
@@ -364,7 +382,7 @@ class Simulation:
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
-                 sub_lu="host", default_aux_pc=None, subdomains="chunks"):
+                 sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -391,6 +409,13 @@ class Simulation:
         if sub_lu not in ("host", "device"):
             raise ValueError("sub_lu 'host' (dense block inverses, no overlap) or 'device' (exact LU of the blocks on the device)")
         self.sub_lu = sub_lu
+        # pc_ordering: elimination order of the flow solver's block-Jacobi ILU(0) -- "natural" (the default: the reference's
+        # ILU(0)) or "multicolour" (wai_set_pc_ordering: two sweep levels per brick on hexahedral and MINC meshes; another
+        # preconditioner, so other Krylov counts).  Not a key of the input file: the reference has none.  What it does not
+        # combine with is refused when the solver options are read (pc_ordering_refusal); pc_choice records it
+        if pc_ordering not in ("natural", "multicolour"):
+            raise ValueError("pc_ordering 'natural' (the default) or 'multicolour'")
+        self.pc_ordering = pc_ordering
         # subdomains: the preconditioner's blocks on a rank -- "chunks" (the default, as before): the chunks of consecutive cells
         # the mesh builders make (mesh.sub_ptr), each on the fused one-workgroup kernels; "rank": ONE block per rank, the
         # reference's own layout (its bjacobi / asm subdomains are the ranks), with the same chunks handed to the library as
@@ -691,6 +716,13 @@ class Simulation:
             self.ode.set_opts(**opts)
         if lso["sub_device"]:
             self.ode.set_sub_pc("lu")
+        if self.pc_ordering == "multicolour":
+            net = self.inp.get("network") or {}
+            refusal = pc_ordering_refusal(lso, bool(net.get("group") or net.get("reinject")))
+            if refusal:
+                raise NotImplementedError(refusal)
+            self.ode.set_pc_ordering("multicolour")
+            self.pc_choice += ("multicolour ordering of the blocks' ILU(0) (wai_set_pc_ordering)",)
         self._pc_covers_coupled = covers_coupled(lso)
         # the auxiliary (tracer) solver: "time.step.solver.auxiliary", the same keys (src/timestepper.F90:2057-2065).  The
         # reference's defaults for it are gmres and bjacobi (:2021-2022) whatever the flow solver uses; the library's tracer
