@@ -499,6 +499,21 @@ enum { WAI_PC_ORDER_NATURAL = 0, WAI_PC_ORDER_MULTICOLOUR = 1 };
 int wai_set_pc_ordering(wai_ctx *ctx, int ordering);
 int wai_get_pc_ordering(wai_ctx *ctx, int *ordering, int *max_colours);
 
+/* Where the source network's pass (groups, limiters, separators, reinjectors) runs.  WAI_NETWORK_PASS_HOST (the default):
+ * every pass copies the sources' own rates to the host, waits, walks the network there and copies the factors back; the
+ * Jacobian's coupling blocks (wai_set_network_couplings) take three such passes and several more waits per column.
+ * WAI_NETWORK_PASS_DEVICE: one launch of one wave walks the network in LDS (k_network_pass) -- the same operations in
+ * the same order, so the same bits -- and the coupling build enqueues its columns without reading anything back: the host
+ * waits once per Jacobian, for the flag that says whether a block is nonzero.  Node states and coupling blocks are then
+ * downloaded when asked for (wai_get_source_network, wai_get_network_couplings).
+ * May be set before or after wai_set_source_network.  The device pass is in force on one rank (a matter of the
+ * communicator's size alone) for a network whose description and state fit the 64 KB of static LDS of a workgroup;
+ * otherwise the host pass runs.  wai_get_network_pass reports the setting and what runs (out-arguments may be NULL).
+ * Unknown value: -2 with a text. */
+enum { WAI_NETWORK_PASS_HOST = 0, WAI_NETWORK_PASS_DEVICE = 1 };
+int wai_set_network_pass(wai_ctx *ctx, int where);
+int wai_get_network_pass(wai_ctx *ctx, int *requested, int *in_force);
+
 /* The auxiliary (tracer) solver's own preconditioner: time.step.solver.auxiliary.preconditioner.{type, sub.preconditioner.{type,
  * factor.levels}} (timestepper_configure_auxiliary_linear_solver, src/timestepper.F90:2057-2065; the same keys as the flow
  * solver's).  pc_type: a WAI_PC_* value, or WAI_AUX_PC_FOLLOW (the default): the tracer solves use the flow solver's

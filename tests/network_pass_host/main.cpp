@@ -1,0 +1,94 @@
+// The source network's pass on its flat description (waiwera_amd/csrc/network_pass.hpp) without a device: reads a
+// network and the sources' raw rates from a text file of records "name count values...", builds the description, runs
+// network_pass and prints every double it wrote in hexadecimal.  tests/test_network_pass_host.py builds this with the
+// address and undefined-behaviour sanitizers and compares with the library's host pass.
+//   network_pass_host FILE   ->  "sources ..." (6 each), "groups ..." (6 each), "reinjectors ..." (8 each), "net ..." (2 each),
+//                                "enth ..." (1 each, started from the record enth_in), "sizes n_iw n_dw stack_frames arena lds"
+//                                or "error -2 text"
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <map>
+#include <sstream>
+#include <string>
+#include <vector>
+#include "network_pass.hpp"
+
+using namespace wai;
+
+static std::map<std::string, std::vector<std::string>> read_records(const char* path) {
+  std::map<std::string, std::vector<std::string>> rec;
+  std::ifstream in(path);
+  std::string line;
+  while (std::getline(in, line)) {
+    std::istringstream ss(line);
+    std::string name, tok;
+    size_t count = 0;
+    if (!(ss >> name >> count)) continue;
+    std::vector<std::string>& v = rec[name];
+    while (ss >> tok) v.push_back(tok);
+    if (v.size() != count) { std::fprintf(stderr, "record %s: %zu values, %zu announced\n", name.c_str(), v.size(), count); std::exit(2); }
+  }
+  return rec;
+}
+static std::vector<int> ints(const std::map<std::string, std::vector<std::string>>& rec, const char* name) {
+  std::vector<int> out;
+  auto it = rec.find(name);
+  if (it == rec.end()) { std::fprintf(stderr, "record %s is missing\n", name); std::exit(2); }
+  for (const std::string& t : it->second) out.push_back((int)std::strtol(t.c_str(), nullptr, 10));
+  return out;
+}
+static std::vector<double> dbls(const std::map<std::string, std::vector<std::string>>& rec, const char* name) {
+  std::vector<double> out;
+  auto it = rec.find(name);
+  if (it == rec.end()) { std::fprintf(stderr, "record %s is missing\n", name); std::exit(2); }
+  for (const std::string& t : it->second) out.push_back(std::strtod(t.c_str(), nullptr));   // (hexadecimal: exact)
+  return out;
+}
+static void print(const char* name, const double* v, size_t n) {
+  std::printf("%s", name);
+  for (size_t i = 0; i < n; i++) std::printf(" %a", v[i]);
+  std::printf("\n");
+}
+// arrays that may be empty still hand the builder a valid pointer
+template <class T> static const T* data(std::vector<T>& v) { if (v.empty()) v.resize(1); return v.data(); }
+
+int main(int argc, char** argv) {
+  if (argc != 2) { std::fprintf(stderr, "usage: network_pass_host FILE\n"); return 2; }
+  const auto rec = read_records(argv[1]);
+  const int n = ints(rec, "n")[0], ng = ints(rec, "n_groups")[0], nr = ints(rec, "n_reinj")[0];
+  std::vector<int> rs = ints(rec, "rate_specified"), es = ints(rec, "enthalpy_specified"), gptr = ints(rec, "grp_ptr"),
+                   gk = ints(rec, "grp_in_kind"), gi = ints(rec, "grp_in"), gs = ints(rec, "grp_scaling"),
+                   glt = ints(rec, "grp_limit_type"), rk = ints(rec, "rj_in_kind"), ri = ints(rec, "rj_in"),
+                   rptr = ints(rec, "rj_out_ptr"), of = ints(rec, "out_flow"), ok = ints(rec, "out_kind"),
+                   on = ints(rec, "out_node"), vk = ints(rec, "rj_overflow_kind"), vi = ints(rec, "rj_overflow");
+  std::vector<double> sep = dbls(rec, "src_sep"), e0 = dbls(rec, "src_enth0"), gl = dbls(rec, "grp_limit"),
+                      gsep = dbls(rec, "grp_sep"), orate = dbls(rec, "out_rate"), oprop = dbls(rec, "out_proportion"),
+                      oenth = dbls(rec, "out_enthalpy"), raw = dbls(rec, "raw"), enth = dbls(rec, "enth_in");
+  if ((int)rs.size() != n || (int)es.size() != n || (int)sep.size() != 8 * n || (int)e0.size() != n || (int)raw.size() != 2 * n ||
+      (int)enth.size() != n || (int)gptr.size() != ng + 1 || (int)rptr.size() != nr + 1) {
+    std::fprintf(stderr, "records do not fit n, n_groups, n_reinj\n");
+    return 2;
+  }
+  NetFlatHost F;
+  std::string err;
+  const int e = build_net_flat(F, n, data(rs), data(es), data(sep), data(e0), ng, data(gptr), data(gk), data(gi), data(gs), data(glt),
+                               data(gl), data(gsep), nr, data(rk), data(ri), data(rptr), data(of), data(ok), data(on), data(orate),
+                               data(oprop), data(oenth), data(vk), data(vi), err);
+  if (e) { std::printf("error %d %s\n", e, err.c_str()); return 0; }
+  // the state on one allocation of exactly the size the builder announces: the sanitizer sees a step outside it
+  std::vector<double> state((size_t)net_state_doubles(F.h), 0.0), net(2 * (size_t)n, -7.0);
+  NetState s;
+  net_state_carve(F.h, state.data(), s);
+  s.net = net.data(); s.enth = enth.data();
+  network_pass(F.view(), raw.data(), s);
+  print("sources", s.src, (size_t)NET_NODE * n);
+  print("groups", s.grp, (size_t)NET_NODE * ng);
+  std::vector<double> rj8;
+  for (int r = 0; r < nr; r++) for (int q = 0; q < 8; q++) rj8.push_back(s.rj[RJ_STATE * r + RJ_OUT_W + q]);
+  print("reinjectors", rj8.data(), rj8.size());
+  print("net", net.data(), net.size());
+  print("enth", enth.data(), enth.size());
+  std::printf("sizes %d %d %d %d %d\n", F.h.n_iw, F.h.n_dw, F.h.stack_frames, F.h.arena, net_lds_doubles(F.h));
+  return 0;
+}

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libwaiwera_hip.so")
 ASSEMBLY_UNITS = ["kernels_eos.hip", "kernels_residual.hip", "kernels_jacobian.hip", "kernels_tracer.hip"]
 SOURCES = ["capi.hip", "context.hip", "sources.hip", "tracers.hip", "krylov.hip", "pc_setup.hip", "network.hip",
            "measure.hip", "gather.hip"] + ASSEMBLY_UNITS + \
-    ["kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_tracer_block.hip", "comm.cpp"]
+    ["kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_tracer_block.hip", "kernels_network.hip", "comm.cpp"]
 import glob  # noqa: E402
 # every header any source could include: a stale object after a header edit is worse than a rebuild
 HEADERS = sorted(os.path.basename(h) for pat in ("*.h", "*.hpp") for h in glob.glob(os.path.join(CSRC, pat))) + \
@@ -30,6 +30,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # of the residual, 2.5e-8 of the entry: enough to send a failing time step of the bench window down another
 # Newton path).  WAI_ASM_CONTRACT=1 builds with the compiler's default contraction.
 PER_FILE = {} if os.environ.get("WAI_ASM_CONTRACT") == "1" else {u: ["-ffp-contract=off"] for u in ASSEMBLY_UNITS}
+# the network pass and the coupling build's column kernels round as the host pass does, whatever the assembly units do
+PER_FILE["kernels_network.hip"] = ["-ffp-contract=off"]
 
 
 def _stale(target, deps):

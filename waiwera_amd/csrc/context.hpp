@@ -10,6 +10,7 @@
 #include "devbuf.hpp"
 #include "ilu_schedule.hpp"   // ScheduleFacts
 #include "mesh_pattern.hpp"   // MAX_CELL_FACES
+#include "network_pass.hpp"   // NetFlatHost
 #include "physics.hip.h"
 #include "tile_schedule.hpp"  // TileFacts
 
@@ -181,6 +182,19 @@ struct Network {
   DevBuf<int> d_cp_cells;
   DevBuf<double> d_cp_val, d_cp_f, d_cp_g;
   DevBuf<double> d_cp_x;                           // [m * bs + 2] x at the column cells, gathered over the ranks
+  // The pass on the device (wai_set_network_pass; network_pass.hpp, k_network_pass of kernels_network.hip).  flat: the
+  // description, built with the network on one rank; flat_fits: description and state fit a workgroup's static LDS;
+  // flat_dirty: the sources' separators or specified enthalpies (h_ctl, h_enth0) changed since the upload
+  NetFlatHost flat;
+  bool flat_fits = false, flat_dirty = true;
+  DevBuf<int> d_flat_iw;
+  DevBuf<double> d_flat_dw;
+  DevBuf<double> d_state;                          // sources 6 each, groups 6 each, reinjectors 8 each: the last device pass
+  bool state_on_device = false;                    // ... is newer than src / groups / reinjectors above (network_fetch_state)
+  bool enth_stale = false;                         // the host pass hands the device every fed source's enthalpy again
+  DevBuf<double> d_cp_yh;                          // coupling build on the device: y_jk and h of the column in hand
+  DevBuf<int> d_cp_flag;                           // ... an entry of E is nonzero
+  bool cp_on_device = false;                       // d_cp_val is newer than h_cp_val (network_fetch_couplings)
 };
 
 // Block matrix in HBM: block-ELL, slot-major struct-of-arrays ("SELL" with one slice):
@@ -549,6 +563,8 @@ struct wai_ctx : wai::Handles {
   wai::EosParams ep{};
   wai_solver_opts opts{};
   int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
+  int net_pass = WAI_NETWORK_PASS_HOST;     // wai_set_network_pass: where the source network's pass runs (net_on_device: what is in force)
+  long long net_passes = 0, net_waits = 0;  // passes made / stream waits issued by network_update and network_couplings (wai_test_network_stats)
   int pc_ordering = WAI_PC_ORDER_NATURAL;   // wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
   wai::ColourSchedule colour;   // ... its symbolic phase under WAI_PC_ORDER_MULTICOLOUR, built by the first set-up that needs it
   std::vector<int> pc_tiles;    // wai_set_pc_tiles: row ranges [n_tiles + 1] of the tiles that refine the subdomains; empty: none
@@ -637,7 +653,13 @@ int launch_tracer_assemble_all(wai_ctx* c, int method, double dt, double ratio, 
 int launch_tracer_lhs(wai_ctx* c, double* Al);
 int launch_separator(wai_ctx* c, double pressure, double* out);   // out[3] on the device: hf, hg, err
 int launch_face_fluxes(wai_ctx* c, const int* face_cells, double* out);   // [face][np + nmob]
-int launch_source_rates(wai_ctx* c, double* out, bool raw = false);   // out[0..n) rates, out[n..2n) enthalpies (device); raw: before the network pass
+int launch_source_rates(wai_ctx* c, double* out, bool raw = false);
+// kernels_network.hip: one pass of the network on the device (raw: launch_source_rates(c, raw, true)), and the coupling
+// build's column steps
+int launch_network_pass(wai_ctx* c, const double* raw, double* net, double* enth, double* state_out);
+int launch_cp_perturb(wai_ctx* c, double* p, double* yh);
+int launch_cp_restore(wai_ctx* c, double* p, const double* yh);
+int launch_cp_diff(wai_ctx* c, int ml, int m, int bs, int j, int k, const double* g, const double* yh, double* val, int* flag);   // out[0..n) rates, out[n..2n) enthalpies (device); raw: before the network pass
 // X[cell][nt] <-> x[cell] of tracer it; alx = Al o X
 int launch_tracer_pick(wai_ctx* c, const double* X, int it, double* x);
 int launch_tracer_put(wai_ctx* c, const double* x, int it, double* X);

@@ -187,7 +187,14 @@ int bcgs_first_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
 int bcgs_second_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
 // ---- network.hip -------------------------------------------------------------------------------------------------
 void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n);   // separator.F90:139-166, 212-260
+// the pass on the device is in force (wai_set_network_pass): asked for, one rank -- by the communicator's size alone, so
+// every rank decides alike -- and a network whose description and state fit a workgroup's LDS
+inline bool net_on_device(const wai_ctx* c) {
+  return c->net_pass == WAI_NETWORK_PASS_DEVICE && c->net.on && c->net.flat_fits && !(c->comm && c->comm->nranks > 1);
+}
 int network_update(wai_ctx* c);
+int network_fetch_state(wai_ctx* c);       // the last device pass' node states to the host's Network
+int network_fetch_couplings(wai_ctx* c);   // the device-built coupling blocks to h_cp_val
 int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old);
 int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t);   // t = A x, + E x where the source network's blocks belong to sys
 // ---- context.hip -------------------------------------------------------------------------------------------------

@@ -196,6 +196,31 @@ void network_evaluate(Network& nw) {
     }
 }
 
+// a stream wait of network_update / network_couplings, counted (wai_test_network_stats)
+#define NET_WAIT(c) do { (c)->net_waits++; HIPCHK(c, hipStreamSynchronize((c)->stream)); } while (0)
+
+// the description on the device, with the sources' separators and specified enthalpies as they stand now
+static int network_flat_upload(wai_ctx* c) {
+  Network& nw = c->net;
+  const NetFlat& h = nw.flat.h;
+  for (int i = 0; i < h.n_src; i++) {
+    nw.flat.dw[h.src_enth0 + i] = i < (int)nw.h_enth0.size() ? nw.h_enth0[i] : 0.0;
+    SrcCtl k{};
+    if (i < (int)nw.h_ctl.size()) k = nw.h_ctl[i];
+    double* sep = &nw.flat.dw[h.src_sep + 8 * i];
+    sep[0] = k.sep_hf; sep[1] = k.sep_hg;
+    for (int q = 0; q < 6; q++) sep[2 + q] = k.sep_more[q];
+  }
+  if (!nw.d_flat_iw && (nw.d_flat_iw.alloc(c, (size_t)h.n_iw) || nw.d_flat_dw.alloc(c, (size_t)h.n_dw) ||
+                        nw.d_state.alloc(c, (size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)h.n_rj)))
+    return -1;
+  HIPCHK(c, hipMemcpyAsync(nw.d_flat_iw, nw.flat.iw.data(), sizeof(int) * (size_t)h.n_iw, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(nw.d_flat_dw, nw.flat.dw.data(), sizeof(double) * (size_t)h.n_dw, hipMemcpyHostToDevice, c->stream));
+  NET_WAIT(c);   // (only after the description changed: the host arrays are free again)
+  nw.flat_dirty = false;
+  return 0;
+}
+
 int network_update(wai_ctx* c) {
   Network& nw = c->net;
   const int n = c->src.n;           // local sources
@@ -203,11 +228,21 @@ int network_update(wai_ctx* c) {
   const bool span = nw.n_global > 0;   // (not "gidx is not empty": a rank WITHOUT sources takes part in the gather too)
   const int ng = span ? nw.n_global : n;
   if (ng == 0) return 0;
+  c->net_passes++;
+  if (net_on_device(c)) {   // k_network_pass: nothing comes to the host and nobody waits
+    if (nw.flat_dirty && network_flat_upload(c)) return -1;
+    launch_source_rates(c, nw.d_raw, true);
+    launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state);
+    nw.state_on_device = true;
+    nw.enth_stale = true;
+    return 0;
+  }
+  nw.state_on_device = false;
   // the sources' own (controlled) rates and flowing enthalpies on the current fluid
   if (n) {
     launch_source_rates(c, nw.d_raw, true);
     HIPCHK(c, hipMemcpyAsync(span ? nw.h_loc.data() : nw.h_raw.data(), nw.d_raw, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NET_WAIT(c);
   }
   if (span) {   // all ranks' sources: every rank fills its own entries, the sum is the gather (collective)
     std::fill(nw.h_raw.begin(), nw.h_raw.end(), 0.0);
@@ -215,7 +250,7 @@ int network_update(wai_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(nw.d_all, nw.h_raw.data(), sizeof(double) * 2 * ng, hipMemcpyHostToDevice, c->stream));
     if (comm_allreduce(c->comm, nw.d_all, 2 * (size_t)ng, 0, c->stream, c->err)) return -1;
     HIPCHK(c, hipMemcpyAsync(nw.h_raw.data(), nw.d_all, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NET_WAIT(c);
   }
   network_evaluate(nw);
   if (!n) return 0;
@@ -223,13 +258,15 @@ int network_update(wai_ctx* c) {
   const std::vector<char>& is_out = nw.is_out;
   // hand the result to the device: scale factors of group members, rates / enthalpies of reinjection sources
   bool enth_changed = false;
+  const bool stale = nw.enth_stale;   // device passes wrote the fed sources' enthalpies since l_enth was handed over
+  nw.enth_stale = false;
   for (int i = 0; i < n; i++) {
     const int g = span ? nw.gidx[i] : i;
     double mode = 0.0, val = 0.0;
     if (is_out[g]) {
       mode = 2.0; val = out_rate[g];
       const double e = nw.src[g].enth;
-      if (e != nw.l_enth[i]) { nw.l_enth[i] = e; enth_changed = true; }
+      if (e != nw.l_enth[i] || stale) { nw.l_enth[i] = e; enth_changed = true; }
     } else if (nw.src[g].rate != nw.h_raw[g]) {
       mode = 1.0; val = nw.h_raw[g] != 0.0 ? nw.src[g].rate / nw.h_raw[g] : 1.0;
     }
@@ -238,7 +275,35 @@ int network_update(wai_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(c->src.net, nw.l_net.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   if (enth_changed)
     HIPCHK(c, hipMemcpyAsync(c->src.enth, nw.l_enth.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // l_net / l_enth are reused by the next pass
+  NET_WAIT(c);   // l_net / l_enth are reused by the next pass
+  return 0;
+}
+
+int network_fetch_state(wai_ctx* c) {
+  Network& nw = c->net;
+  if (!nw.state_on_device || !nw.d_state) return 0;
+  const NetFlat& h = nw.flat.h;
+  std::vector<double> st((size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)h.n_rj);
+  HIPCHK(c, hipMemcpyAsync(st.data(), nw.d_state, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  auto get = [](NetNode& n, const double* o) { n.rate = o[0]; n.enth = o[1]; n.wrate = o[2]; n.wenth = o[3]; n.srate = o[4]; n.senth = o[5]; };
+  for (int i = 0; i < h.n_src; i++) get(nw.src[i], &st[(size_t)NET_NODE * i]);
+  for (int g = 0; g < h.n_grp; g++) get(nw.groups[g].node, &st[(size_t)NET_NODE * (h.n_src + g)]);
+  for (int r = 0; r < h.n_rj; r++) {
+    const double* o = &st[(size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)r];
+    NetReinjector& R = nw.reinjectors[r];
+    R.out_w = o[0]; R.out_s = o[1];
+    get(R.over, o + 2);
+  }
+  nw.state_on_device = false;
+  return 0;
+}
+int network_fetch_couplings(wai_ctx* c) {
+  Network& nw = c->net;
+  if (!nw.cp_on_device || !nw.d_cp_val || nw.h_cp_val.empty()) return 0;
+  HIPCHK(c, hipMemcpyAsync(nw.h_cp_val.data(), nw.d_cp_val, sizeof(double) * nw.h_cp_val.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  nw.cp_on_device = false;
   return 0;
 }
 
@@ -290,11 +355,43 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
       return -1;
   }
   nw.h_cp_val.assign((size_t)ml * m * bs * bs, 0.0);
-  std::vector<double> g((size_t)2 * mb), yc((size_t)bs);
+  nw.cp_on_device = false;
   const int grid = (mb + 63) / 64;
+  if (net_on_device(c)) {
+    // the same columns with nothing read back inside the loop: y_jk and h stay in device scratch, the differences go
+    // straight into d_cp_val, and the host waits once, for the flag
+    if (!nw.d_cp_yh && (nw.d_cp_yh.alloc(c, 2) || nw.d_cp_flag.alloc(c, 1))) return -1;
+    if (network_update(c)) return -1;   // the factors A was differenced with
+    HIPCHK(c, hipMemsetAsync(nw.d_cp_flag, 0, sizeof(int), c->stream));
+    for (int j = 0; j < m; j++) {
+      const int cell = nw.cp_cells[j];
+      for (int k = 0; k < bs; k++) {
+        double* p = y + (size_t)cell * bs + k;
+        launch_cp_perturb(c, p, nw.d_cp_yh);
+        launch_eos(c, y, cell, 1, false);
+        launch_residual(c, dt, lhs_old, nw.d_cp_f, nullptr, nullptr, nw.d_cp_cells, ml);   // factors held
+        hipLaunchKernelGGL(k_gather_rows, grid, 64, 0, c->stream, ml, bs, nw.d_cp_cells, nw.d_cp_f, nw.d_cp_g);
+        if (network_update(c)) return -1;
+        launch_residual(c, dt, lhs_old, nw.d_cp_f, nullptr, nullptr, nw.d_cp_cells, ml);   // network pass redone
+        hipLaunchKernelGGL(k_gather_rows, grid, 64, 0, c->stream, ml, bs, nw.d_cp_cells, nw.d_cp_f, nw.d_cp_g + mb);
+        launch_cp_diff(c, ml, m, bs, j, k, nw.d_cp_g, nw.d_cp_yh, nw.d_cp_val, nw.d_cp_flag);
+        launch_cp_restore(c, p, nw.d_cp_yh);
+        launch_eos(c, y, cell, 1, false);
+        if (network_update(c)) return -1;
+      }
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
+    int any_dev = 0;
+    HIPCHK(c, hipMemcpyAsync(&any_dev, nw.d_cp_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    NET_WAIT(c);
+    nw.cp_on_device = true;
+    nw.cp_valid = any_dev != 0;
+    return 0;
+  }
+  std::vector<double> g((size_t)2 * mb), yc((size_t)bs);
   auto set_y = [&](int cell, int k, double v) -> int {
     HIPCHK(c, hipMemcpyAsync(y + (size_t)cell * bs + k, &v, sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NET_WAIT(c);
     launch_eos(c, y, cell, 1, false);
     return 0;
   };
@@ -305,7 +402,7 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
     HIPCHK(c, hipMemcpyAsync(nw.d_cp_x, &mineval, sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (comm_allreduce(c->comm, nw.d_cp_x, 1, 0, c->stream, c->err)) return -1;
     HIPCHK(c, hipMemcpyAsync(&v, nw.d_cp_x, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NET_WAIT(c);
     return 0;
   };
   if (network_update(c)) return -1;   // the factors A was differenced with
@@ -315,7 +412,7 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
     const int cell = mine ? nw.cp_cells[j - j0] : -1;
     if (mine) {
       HIPCHK(c, hipMemcpyAsync(yc.data(), y + (size_t)cell * bs, sizeof(double) * bs, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      NET_WAIT(c);
     }
     for (int k = 0; k < bs; k++) {
       double h = 0.0;
@@ -335,7 +432,7 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
         launch_residual(c, dt, lhs_old, nw.d_cp_f, nullptr, nullptr, nw.d_cp_cells, ml);   // network pass redone
         hipLaunchKernelGGL(k_gather_rows, grid, 64, 0, c->stream, ml, bs, nw.d_cp_cells, nw.d_cp_f, nw.d_cp_g + mb);
         HIPCHK(c, hipMemcpyAsync(g.data(), nw.d_cp_g, sizeof(double) * 2 * mb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        NET_WAIT(c);
         for (int i = 0; i < ml; i++)
           for (int r = 0; r < bs; r++) {
             const double e = (g[(size_t)mb + i * bs + r] - g[(size_t)i * bs + r]) / h;
@@ -352,14 +449,14 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
   if (any) {
     HIPCHK(c, hipMemcpyAsync(nw.d_cp_val, nw.h_cp_val.data(), sizeof(double) * nw.h_cp_val.size(), hipMemcpyHostToDevice,
                              c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NET_WAIT(c);
   }
   double flag = any ? 1.0 : 0.0;   // every rank applies E (a collective gather of x) or none does
   if (span) {
     HIPCHK(c, hipMemcpyAsync(nw.d_cp_x, &flag, sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (comm_allreduce(c->comm, nw.d_cp_x, 1, 1, c->stream, c->err)) return -1;
     HIPCHK(c, hipMemcpyAsync(&flag, nw.d_cp_x, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    NET_WAIT(c);
   }
   nw.cp_valid = flag != 0.0;
   return 0;
@@ -439,21 +536,9 @@ int network_build(Network& nw, int n, const int* rate_specified, const int* enth
       R.out.push_back(o);
     }
   }
-  {   // order: a reinjector after every reinjector it delivers or overflows to
-    nw.reinj_order.clear();
-    std::vector<int> state(std::max(n_reinj, 0), 0);
-    std::function<bool(int)> visit = [&](int r) -> bool {
-      if (state[r] == 2) return true;
-      if (state[r] == 1) return false;
-      state[r] = 1;
-      const NetReinjector& R = nw.reinjectors[r];
-      for (const NetOutput& o : R.out) if (o.out.kind == 3 && !visit(o.out.index)) return false;
-      if (R.overflow.kind == 3 && !visit(R.overflow.index)) return false;
-      state[r] = 2;
-      nw.reinj_order.push_back(r);
-      return true;
-    };
-    for (int r = 0; r < n_reinj; r++) if (!visit(r)) { err = "source network reinjectors form a cycle"; return -2; }
+  // order: a reinjector after every reinjector it delivers or overflows to (network_pass.hpp: the flat description's too)
+  if (!net_reinjector_order(std::max(n_reinj, 0), rj_out_ptr, out_kind, out_node, rj_overflow_kind, rj_overflow, nw.reinj_order)) {
+    err = "source network reinjectors form a cycle"; return -2;
   }
   nw.src.assign(n, NetNode());
   nw.h_raw.assign(2 * (size_t)n, 0.0);
@@ -575,6 +660,15 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
   nw.l_enth.assign((size_t)n, 0.0);
   for (int i = 0; i < n; i++) nw.l_enth[i] = span ? nw.h_enth0[nw.gidx[i]] : (i < (int)nw.h_enth0.size() ? nw.h_enth0[i] : 0.0);
   nw.on = true;
+  if (!span) {   // the flat description of the pass on the device (wai_set_network_pass); separators and enthalpies at its upload
+    std::string e;
+    nw.flat_fits = build_net_flat(nw.flat, n, rate_specified, enthalpy_specified, nullptr, nullptr, n_groups, grp_ptr, grp_in_kind,
+                                  grp_in, grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr,
+                                  out_flow, out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind,
+                                  rj_overflow, e) == 0 &&
+                   net_lds_doubles(nw.flat.h) <= NET_LDS_DOUBLES;
+    nw.flat_dirty = true;
+  }
   if (!span) network_cells(nw, n);
   else network_cells_span(nw, ng, span_id, c->comm->rank);
   c->flow.as.overlap = -1;   // the factor's pattern carries the network's cell pairs: built again at the next set-up
@@ -606,6 +700,64 @@ int wai_set_network_couplings(wai_ctx* c, int on) {
   return 0;
 }
 
+// Where the source network's pass runs (include/waiwera_hip.h)
+int wai_set_network_pass(wai_ctx* c, int where) {
+  if (!c) return -2;
+  if (where != WAI_NETWORK_PASS_HOST && where != WAI_NETWORK_PASS_DEVICE) {
+    c->err = "unknown place for the source network's pass (WAI_NETWORK_PASS_HOST or WAI_NETWORK_PASS_DEVICE)";
+    return -2;
+  }
+  if (where != c->net_pass && network_fetch_state(c)) return -1;   // the host's copy of the node states stays the last pass'
+  c->net_pass = where;
+  return 0;
+}
+int wai_get_network_pass(wai_ctx* c, int* requested, int* in_force) {
+  if (!c) return -2;
+  if (requested) *requested = c->net_pass;
+  if (in_force) *in_force = net_on_device(c) ? WAI_NETWORK_PASS_DEVICE : WAI_NETWORK_PASS_HOST;
+  return 0;
+}
+// one pass on the device for the given raw rates (include/waiwera_hip_bench.h)
+int wai_test_network_pass(wai_ctx* c, const double* raw2n, double* sources6, double* groups6, double* reinjectors8, double* net2n,
+                          double* enth_n) {
+  if (!c || !raw2n) return -2;
+  Network& nw = c->net;
+  const int n = c->src.n;
+  if (!nw.on || !nw.flat_fits || (c->comm && c->comm->nranks > 1)) {
+    c->err = "wai_test_network_pass: a source network on one rank that fits a workgroup's LDS";
+    return -2;
+  }
+  if (nw.flat_dirty && network_flat_upload(c)) return -1;
+  const NetFlat& h = nw.flat.h;
+  HIPCHK(c, hipMemcpyAsync(nw.d_raw, raw2n, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state);
+  nw.state_on_device = true;
+  nw.enth_stale = true;
+  const size_t ns = (size_t)NET_NODE * h.n_src, ngd = (size_t)NET_NODE * h.n_grp;
+  if (sources6) HIPCHK(c, hipMemcpyAsync(sources6, nw.d_state, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+  if (groups6 && ngd) HIPCHK(c, hipMemcpyAsync(groups6, nw.d_state + ns, sizeof(double) * ngd, hipMemcpyDeviceToHost, c->stream));
+  if (reinjectors8 && h.n_rj)
+    HIPCHK(c, hipMemcpyAsync(reinjectors8, nw.d_state + ns + ngd, sizeof(double) * 8 * h.n_rj, hipMemcpyDeviceToHost, c->stream));
+  if (net2n) HIPCHK(c, hipMemcpyAsync(net2n, c->src.net, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+  if (enth_n) HIPCHK(c, hipMemcpyAsync(enth_n, c->src.enth, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+int wai_test_network_stats(wai_ctx* c, long long* passes, long long* host_waits) {
+  if (!c) return -2;
+  if (passes) *passes = c->net_passes;
+  if (host_waits) *host_waits = c->net_waits;
+  return 0;
+}
+// the most doubles of LDS a network's description and state may take for the pass on the device, and what the
+// context's network takes (0: none set, or one on several ranks)
+int wai_test_network_lds(wai_ctx* c, int* limit, int* needed) {
+  if (!c) return -2;
+  if (limit) *limit = NET_LDS_DOUBLES;
+  if (needed) *needed = c->net.on && c->net.flat.h.n_src ? net_lds_doubles(c->net.flat.h) : 0;
+  return 0;
+}
+
 int wai_get_network_couplings(wai_ctx* c, int* n_cells, int* cells, double* values) {
   if (!c || !n_cells) return -2;
   const Network& nw = c->net;
@@ -617,7 +769,10 @@ int wai_get_network_couplings(wai_ctx* c, int* n_cells, int* cells, double* valu
       const bool mine = !nw.cp_span || (j >= nw.cp_j0 && j < nw.cp_j0 + ml);
       cells[j] = mine ? nw.cp_cells[j - (nw.cp_span ? nw.cp_j0 : 0)] : -1 - nw.cp_owner[j];
     }
-  if (values && ml) std::memcpy(values, nw.h_cp_val.data(), sizeof(double) * nw.h_cp_val.size());
+  if (values && ml) {
+    if (network_fetch_couplings(c)) return -1;
+    std::memcpy(values, nw.h_cp_val.data(), sizeof(double) * nw.h_cp_val.size());
+  }
   return 0;
 }
 // The same network pass without a context or a device (host logic only; tests): the sources' own rates
@@ -686,6 +841,7 @@ int wai_network_cells(int n_sources, const int* source_cell, const int* rate_spe
 // rate, enthalpy, water rate, water enthalpy, steam rate, steam enthalpy)
 int wai_get_source_network(wai_ctx* c, double* groups, double* reinjectors) {
   if (!c) return -2;
+  if (network_fetch_state(c)) return -1;   // a pass on the device: its node states are downloaded when asked for
   const Network& nw = c->net;
   for (size_t g = 0; groups && g < nw.groups.size(); g++) {
     const NetNode& n = nw.groups[g].node;

@@ -49,6 +49,7 @@ int wai_update_sources(wai_ctx* c, const double* rate, const double* enthalpy) {
       if (g < nw.h_enth0.size()) nw.h_enth0[g] = enthalpy[i];
       if ((size_t)i < nw.l_enth.size()) nw.l_enth[i] = enthalpy[i];
     }
+    nw.flat_dirty = true;   // the device pass' copy of the specified enthalpies
   }
   return 0;
 }
@@ -89,6 +90,7 @@ int wai_set_source_controls(wai_ctx* c, const wai_source_control* controls) {
   if (c->net.gidx.empty()) c->net.h_ctl.assign(reinterpret_cast<const SrcCtl*>(controls), reinterpret_cast<const SrcCtl*>(controls) + s.n);
   else   // a network across ranks numbers its control records globally: this rank's own entries
     for (int i = 0; i < s.n; i++) c->net.h_ctl[c->net.gidx[i]] = reinterpret_cast<const SrcCtl*>(controls)[i];
+  c->net.flat_dirty = true;   // the device pass' copy of the separators
   HIPCHK(c, hipMemcpyAsync(s.ctl, controls, sizeof(SrcCtl) * (size_t)s.n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;

@@ -127,6 +127,28 @@ class FlowSimulation:
         self._chk(LIB.wai_get_source_network(self.h, G.ctypes.data_as(_lib.pd), R.ctypes.data_as(_lib.pd)), "get_source_network")
         return G[:ng], R[:nr]
 
+    def set_network_pass(self, where):
+        """where the source network's pass runs (wai_set_network_pass): "host" (default: rates to the host, the network walked
+        there, factors back -- two stream waits per pass) or "device" (one launch walks it in LDS; the coupling build then
+        waits once per Jacobian).  The same bits either way.  Before or after set_source_network"""
+        if where not in _lib.NETWORK_PASS:
+            raise ValueError("network pass %r: one of %s" % (where, sorted(_lib.NETWORK_PASS)))
+        self._chk(LIB.wai_set_network_pass(self.h, _lib.NETWORK_PASS[where]), "set_network_pass")
+
+    def network_pass(self):
+        """(requested, in_force): the setting, and what runs -- "host" on several ranks, for a network too large for a
+        workgroup's LDS, and without a network"""
+        r, f = C.c_int(0), C.c_int(0)
+        self._chk(LIB.wai_get_network_pass(self.h, C.byref(r), C.byref(f)), "network_pass")
+        name = {v: k for k, v in _lib.NETWORK_PASS.items()}
+        return name[r.value], name[f.value]
+
+    def network_stats(self):
+        """(passes, host_waits): network passes so far, and the stream waits passes and coupling builds issued"""
+        p, w = C.c_longlong(0), C.c_longlong(0)
+        self._chk(LIB.wai_test_network_stats(self.h, C.byref(p), C.byref(w)), "network_stats")
+        return p.value, w.value
+
     def set_network_couplings(self, on=True, in_preconditioner=True):
         """the network's Jacobian blocks (flow_simulation_modify_jacobian, flow_simulation.F90:3023-3084) on / off;
         in_preconditioner: also inside the factor's pattern, as PETSc factors the widened matrix (default), or in the

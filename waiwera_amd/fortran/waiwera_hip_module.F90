@@ -535,6 +535,19 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        integer(c_int), intent(out) :: ordering, max_colours
      end function wai_get_pc_ordering
+     ! where the source network's pass runs: WAI_NETWORK_PASS_HOST (0, default) | WAI_NETWORK_PASS_DEVICE (1): one launch
+     ! walks the network in LDS, and the coupling build waits once per Jacobian.  In force on one rank, for a network that fits
+     integer(c_int) function wai_set_network_pass(ctx, where) bind(c, name = "wai_set_network_pass")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: where
+     end function wai_set_network_pass
+     ! the setting, and what runs
+     integer(c_int) function wai_get_network_pass(ctx, requested, in_force) bind(c, name = "wai_get_network_pass")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: requested, in_force
+     end function wai_get_network_pass
      ! the auxiliary (tracer) solver's own preconditioner (time.step.solver.auxiliary.preconditioner): a WAI_PC_* value, or
      ! WAI_AUX_PC_FOLLOW (-1, default): the flow solver's.  The reference's default is WAI_PC_BJACOBI
      integer(c_int) function wai_set_aux_pc(ctx, pc_type, asm_overlap, ilu_levels, sub_pc) bind(c, name = "wai_set_aux_pc")
@@ -568,6 +581,7 @@ module waiwera_hip_module
   integer, parameter, public :: WAI_METHOD_BEULER = 0, WAI_METHOD_BDF2 = 1, WAI_METHOD_DIRECTSS = 2
   integer, parameter, public :: WAI_SUB_ILU = 0, WAI_SUB_LU = 1
   integer, parameter, public :: WAI_PC_ORDER_NATURAL = 0, WAI_PC_ORDER_MULTICOLOUR = 1
+  integer, parameter, public :: WAI_NETWORK_PASS_HOST = 0, WAI_NETWORK_PASS_DEVICE = 1
   integer, parameter, public :: WAI_PC_BJACOBI = 0, WAI_PC_ASM = 1, WAI_PC_NONE = 2, WAI_PC_LU = 3, WAI_AUX_PC_FOLLOW = -1
 
   type, public :: hip_flow_simulation_type
@@ -594,6 +608,7 @@ module waiwera_hip_module
      procedure, public :: set_sub_pc => hip_sim_set_sub_pc
      procedure, public :: set_pc_tiles => hip_sim_set_pc_tiles
      procedure, public :: set_pc_ordering => hip_sim_set_pc_ordering
+     procedure, public :: set_network_pass => hip_sim_set_network_pass
      procedure, public :: set_aux_pc => hip_sim_set_aux_pc
      procedure, public :: aux_lhs => hip_sim_aux_lhs
      procedure, public :: aux_solve => hip_sim_aux_solve
@@ -613,6 +628,7 @@ module waiwera_hip_module
   public :: wai_set_tracers, wai_set_tracer_bc, wai_set_tracer_injection, wai_set_aux_solver
   public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc, wai_set_aux_pc, wai_get_aux_pc
   public :: wai_set_pc_tiles, wai_set_pc_ordering, wai_get_pc_ordering
+  public :: wai_set_network_pass, wai_get_network_pass
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_gather_rows, wai_gather_fluid
@@ -870,6 +886,14 @@ contains
     integer, intent(out) :: err
     err = wai_set_pc_ordering(self%ctx, int(ordering, c_int))
   end subroutine hip_sim_set_pc_ordering
+
+  subroutine hip_sim_set_network_pass(self, where, err)
+    !! Where the source network's pass runs: WAI_NETWORK_PASS_HOST | WAI_NETWORK_PASS_DEVICE.
+    class(hip_flow_simulation_type), intent(in out) :: self
+    integer, intent(in) :: where
+    integer, intent(out) :: err
+    err = wai_set_network_pass(self%ctx, int(where, c_int))
+  end subroutine hip_sim_set_network_pass
 
   subroutine hip_sim_set_aux_pc(self, pc_type, asm_overlap, ilu_levels, sub_pc, err)
     !! Preconditioner of the auxiliary (tracer) solver (timestepper_configure_auxiliary_linear_solver,

@@ -42,6 +42,9 @@ def main(argv=None):
     ap.add_argument("--pc-ordering", choices=("natural", "multicolour"), default="natural",
                     help="elimination order of the flow solver's block-Jacobi ILU(0): as numbered (default, the reference's) or "
                          "multicolour (two sweep levels per block on hexahedral and MINC meshes; bjacobi with ILU(0) only)")
+    ap.add_argument("--network-pass", choices=("host", "device"), default="host",
+                    help="the source network's pass: on the host (default) or in one launch on the device (one rank, a network "
+                         "that fits a workgroup's LDS; the same results)")
     a = ap.parse_args(argv)
     import os
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -58,7 +61,8 @@ def main(argv=None):
         if os.environ.get("WAI_BENCH_LOOPBACK") != "1":
             a.device = int(os.environ.get("LOCAL_RANK", a.device))
     sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
-                               default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, **kw)
+                               default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, network_pass=a.network_pass,
+                               **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

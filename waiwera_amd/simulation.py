@@ -382,7 +382,7 @@ class Simulation:
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
-                 sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural"):
+                 sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural", network_pass="host"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -416,6 +416,13 @@ class Simulation:
         if pc_ordering not in ("natural", "multicolour"):
             raise ValueError("pc_ordering 'natural' (the default) or 'multicolour'")
         self.pc_ordering = pc_ordering
+        # network_pass: where the source network's pass runs -- "host" (the default, as before) or "device"
+        # (wai_set_network_pass: one launch in LDS, the coupling build without waits inside; the same bits).  Not a key of the
+        # input file.  network_pass_choice records (requested, in force) once the network is set: "host" stays in force on
+        # several ranks and for a network too large for a workgroup's LDS
+        if network_pass not in ("host", "device"):
+            raise ValueError("network_pass 'host' (the default) or 'device'")
+        self.network_pass, self.network_pass_choice = network_pass, (network_pass, "host")
         # subdomains: the preconditioner's blocks on a rank -- "chunks" (the default, as before): the chunks of consecutive cells
         # the mesh builders make (mesh.sub_ptr), each on the fused one-workgroup kernels; "rank": ONE block per rank, the
         # reference's own layout (its bjacobi / asm subdomains are the ranks), with the same chunks handed to the library as
@@ -844,6 +851,9 @@ class Simulation:
                 # without a source of the network -- `spec` depends on the input alone
                 self.ode.set_source_global_index(len(inp.get("source", []) or []), self._src_pick)
             self.ode.set_source_network(spec)
+            if self.network_pass == "device":
+                self.ode.set_network_pass("device")
+                self.network_pass_choice = self.ode.network_pass()
 
     # ---- state-dependent source controls -------------------------------------------------------
     def _setup_source_controls(self, sources, t0, collective_fluid=False):
