@@ -138,6 +138,20 @@ int wai_ctx_create(const wai_mesh_desc *mesh, const wai_eos_desc *eos,
                    const wai_solver_opts *opts, int device, wai_ctx **out);
 int wai_ctx_destroy(wai_ctx *ctx);                                 /* flow_simulation_destroy, src/flow_simulation.F90:1049-1098 */
 const char *wai_last_error(wai_ctx *ctx);                          /* text for the reference's logfile (src/logfile.F90) after a call returned < 0 */
+/* The compact cell order of a mesh BEFORE it is described to wai_ctx_create -- no context, no device.  The fast paths of
+ * the preconditioner assume that a subdomain (sub_ptr above) is a compact 3-D piece of the mesh; chunks of consecutive
+ * cells of a mesh file are slabs of one layer.  From the n_cells centroids (centroids[i * centroid_stride + a], a = 0..2;
+ * cell_geom itself with stride 4) and the n_faces interior faces' cell pairs, this gives a numbering perm[new] = old and
+ * subdomains sub_ptr[0..*n_sub] of at most max_rows cells each: recursive coordinate bisection -- a set of k cells with
+ * L = ceil(k / max_rows) > 1 is sorted along the axis of its largest extent in units of the mean centroid distance across
+ * the faces of that axis (an axis no face crosses is never chosen) and split after floor(k * (L / 2) / L) cells -- then the
+ * leaves depth-first, the cells of a leaf by (z, y, x, given index) like a brick of the structured mesh.  Ties go to the
+ * lowest axis and to the lowest given index; the result does not depend on the given numbering where all centroids differ.
+ * The host numbers its wai_mesh_desc by perm and hands sub_ptr over; the library never sees the old numbering.
+ * perm: room for n_cells, sub_ptr: for n_cells + 1.  Refused with -2: max_rows < 1, a face naming a cell outside
+ * [0, n_cells), a centroid that is not finite, null arguments; err (may be NULL, room for err_len characters) gets the text. */
+int wai_cell_order(int n_cells, int n_faces, const int *face_cells, const double *centroids, int centroid_stride, int max_rows,
+                   int *perm, int *n_sub, int *sub_ptr, char *err, int err_len);
 int wai_set_opts(wai_ctx *ctx, const wai_solver_opts *opts);       /* the "time.step.solver" block read again: timestepper_configure_linear_solver,
                                                                       src/timestepper.F90:1645-1836; nonlinear tolerances :2002-2260 */
 

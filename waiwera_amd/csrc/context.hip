@@ -2,6 +2,8 @@
 // descriptions, the solver settings, the halo and the communicator, regions, curve tables, boundary conditions and rock
 // updates.  The mesh's connectivity and matrix pattern are built on the host alone (mesh_pattern.hpp) and uploaded here.
 #include "host.hpp"
+#include "cell_order.hpp"
+#include <cstdio>
 
 using namespace wai;
 
@@ -281,6 +283,30 @@ int wai_ctx_destroy(wai_ctx* c) {
 }
 
 const char* wai_last_error(wai_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+// The compact cell order (cell_order.hpp) of a mesh a host is about to describe -- no context, no device.  perm: room for n
+// entries, sub_ptr for n + 1 (there are at most ceil(n / max_rows) subdomains, each of at least one cell); err (may be
+// NULL): room for err_len characters, the refusal's text, cut to fit and terminated
+int wai_cell_order(int n_cells, int n_faces, const int* face_cells, const double* centroids, int centroid_stride, int max_rows,
+                   int* perm, int* n_sub, int* sub_ptr, char* err, int err_len) {
+  auto refuse = [&](const std::string& text) {
+    if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", text.c_str());
+    return -2;
+  };
+  if (err && err_len > 0) err[0] = 0;
+  if (!perm || !n_sub || !sub_ptr || (n_cells > 0 && !centroids) || (n_faces > 0 && !face_cells))
+    return refuse("cell order: null argument");
+  CellOrder o;
+  std::string text;
+  if (int e = build_cell_order(n_cells, n_faces, face_cells, centroids, centroid_stride, max_rows, o, text)) {
+    refuse(text);
+    return e;
+  }
+  *n_sub = o.n_sub;
+  std::copy(o.perm.begin(), o.perm.end(), perm);
+  std::copy(o.sub_ptr.begin(), o.sub_ptr.end(), sub_ptr);
+  return 0;
+}
 
 int wai_set_opts(wai_ctx* c, const wai_solver_opts* o) {
   if (!c || !o) return -2;

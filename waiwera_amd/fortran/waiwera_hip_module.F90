@@ -180,6 +180,19 @@ module waiwera_hip_module
        integer(c_int), intent(out) :: n_cells
        integer(c_int), intent(out) :: cells(*)
      end function wai_network_cells
+     ! the compact cell order of a mesh before it is described (no context needed): perm(new) = old, 0-based, room for
+     ! n_cells; sub_ptr the subdomains of at most max_rows cells, room for n_cells + 1.  centroids(centroid_stride, n_cells)
+     ! (cell_geom itself: stride 4); face_cells(2, n_faces) the interior faces.  err: room for err_len characters
+     integer(c_int) function wai_cell_order(n_cells, n_faces, face_cells, centroids, centroid_stride, max_rows, perm, &
+          n_sub, sub_ptr, err, err_len) bind(c, name = "wai_cell_order")
+       import :: c_int, c_double, c_char
+       integer(c_int), value :: n_cells, n_faces, centroid_stride, max_rows, err_len
+       integer(c_int), intent(in) :: face_cells(*)
+       real(c_double), intent(in) :: centroids(*)
+       integer(c_int), intent(out) :: perm(*), sub_ptr(*)
+       integer(c_int), intent(out) :: n_sub
+       character(kind = c_char), intent(out) :: err(*)
+     end function wai_cell_order
      ! kernels launched / copies enqueued by the linear solver so far (a BiCGStab iteration: 4 kernels, no copy)
      integer(c_int) function wai_launch_stats(ctx, kernels, copies) bind(c, name = "wai_launch_stats")
        import :: c_int, c_ptr, c_long_long
@@ -631,7 +644,7 @@ module waiwera_hip_module
   public :: wai_set_network_pass, wai_get_network_pass
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
-  public :: wai_gather_rows, wai_gather_fluid
+  public :: wai_gather_rows, wai_gather_fluid, wai_cell_order
   public :: wai_default_eos, wai_default_opts, wai_set_bc, wai_set_sources, wai_update_sources, wai_set_source_controls, wai_get_source_rates, wai_separator_enthalpies, wai_set_regions, &
        wai_get_regions, wai_jacobian_nnzb, wai_jacobian_pattern, wai_jacobian_get_values
 

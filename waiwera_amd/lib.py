@@ -115,6 +115,7 @@ def _load():
                                  C.POINTER(vp)]),
         "wai_ctx_destroy": (i32, [vp]),
         "wai_last_error": (C.c_char_p, [vp]),
+        "wai_cell_order": (i32, [i32, i32, pi, pd, i32, i32, pi, pi, pi, C.c_char_p, i32]),
         "wai_set_opts": (i32, [vp, C.POINTER(SolverOpts)]),
         "wai_set_bc": (i32, [vp, pd, pi]),
         "wai_set_curve_table": (i32, [vp, i32, i32, i32, pd]),
@@ -289,6 +290,24 @@ def device_memory():
     if LIB.wai_test_device_memory(C.byref(n), C.byref(b)) != 0:
         raise WaiError("wai_test_device_memory failed")
     return n.value, b.value
+
+
+def cell_order(face_cells, centroids, max_rows):
+    """the compact cell order (wai_cell_order) of a mesh given by its interior faces' cell pairs (m, 2) and its cell
+    centroids (n, >= 3): (perm with perm[new] = old, sub_ptr of the subdomains of at most max_rows cells).  A refusal
+    raises WaiError with the library's text"""
+    cen = _f64(centroids)
+    if cen.ndim != 2 or cen.shape[1] < 3:
+        raise ValueError("centroids (n, 3) or wider")
+    fc = _i32(np.asarray(face_cells).reshape(-1, 2))
+    n = cen.shape[0]
+    perm, sub, ns = np.zeros(max(n, 1), dtype=np.int32), np.zeros(n + 1, dtype=np.int32), C.c_int(0)
+    err = C.create_string_buffer(256)
+    rc = LIB.wai_cell_order(n, fc.shape[0], fc.ctypes.data_as(pi), cen.ctypes.data_as(pd), cen.shape[1], int(max_rows),
+                            perm.ctypes.data_as(pi), C.byref(ns), sub.ctypes.data_as(pi), err, len(err))
+    if rc != 0:
+        raise WaiError("wai_cell_order failed (%d): %s" % (rc, err.value.decode()))
+    return perm[:n].copy(), sub[: ns.value + 1].copy()
 
 
 def comm_unique_id():

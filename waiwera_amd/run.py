@@ -45,6 +45,12 @@ def main(argv=None):
     ap.add_argument("--network-pass", choices=("host", "device"), default="host",
                     help="the source network's pass: on the host (default) or in one launch on the device (one rank, a network "
                          "that fits a workgroup's LDS; the same results)")
+    ap.add_argument("--cell-order", choices=("input", "compact"), default="input",
+                    help="the numbering the library gets: the mesh file's, with chunks of consecutive cells as the preconditioner's "
+                         "subdomains (default), or compact 3-D subdomains numbered like bricks (one rank, a mesh file, no MINC "
+                         "zones; results come back in the file's numbering)")
+    ap.add_argument("--subdomain-rows", type=int, default=None,
+                    help="most cells of a preconditioner subdomain under either cell order, 1 to 1024 (default 512, MINC cells included)")
     a = ap.parse_args(argv)
     import os
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -62,7 +68,7 @@ def main(argv=None):
             a.device = int(os.environ.get("LOCAL_RANK", a.device))
     sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
                                default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, network_pass=a.network_pass,
-                               **kw)
+                               cell_order=a.cell_order, subdomain_rows=a.subdomain_rows, **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

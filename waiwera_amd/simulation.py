@@ -60,9 +60,17 @@ sources with owned_source their numbers in the input, group and reinjector field
 for the fluid record's columns, wai_gather_rows for geometry, tracers, source and flux fields), rank 0 writes the file a
 one-rank run writes and carries output_error; save() / python -m waiwera_amd.run -o still write one .npz per rank.  NOT on
 N ranks: PCASM overlap deeper than 1, which the library refuses.
+Cell order (cell_order="compact", python -m waiwera_amd.run --cell-order compact; subdomain_rows / --subdomain-rows the cap):
+the library gets the mesh numbered by wai_cell_order -- compact 3-D preconditioner subdomains numbered inside like bricks --
+instead of the mesh file's numbering in chunks of consecutive cells.  Every cell number of the input (boundaries, sources,
+rock types, zones given as cell lists, per-cell initial conditions, a restart file's cells) goes in through the inverse
+permutation, and fields(), datasets(), the HDF5 file, save() and face_cell_1 / face_cell_2 come back in the input's numbering;
+cell_order_choice records the order, the subdomains and the share of interior faces they cut.  One rank, a mesh file and no
+MINC zones: the rest is refused by name (ValueError) from the input and the arguments alone.
 Collective-call discipline: nothing that exchanges data stands under a condition that can differ
 between ranks; what must be refused is refused from the input and the arguments alone, so on every rank alike.
 """
+import collections
 import json
 import os
 
@@ -377,12 +385,75 @@ def output_datasets(outs, n_cells, minc_level=None, minc_parent=None):
     return data
 
 
+CellOrderChoice = collections.namedtuple("CellOrderChoice", "order n_sub largest_subdomain cut_before cut_after")
+CellOrderChoice.__doc__ = """Simulation.cell_order_choice: the order taken ("input" | "compact"), the preconditioner subdomains it gives and
+the largest one's cells, and the share of interior faces cut by the input-order chunks (before) and by the subdomains taken (after)"""
+
+
+def _cut_share(interior, sub_ptr):
+    """share of the interior faces (cell pairs) whose cells lie in different subdomains"""
+    interior = np.asarray(interior).reshape(-1, 2)
+    if not len(interior):
+        return 0.0
+    owner = np.repeat(np.arange(len(sub_ptr) - 1), np.diff(np.asarray(sub_ptr, dtype=np.int64)))
+    return float(np.mean(owner[interior[:, 0]] != owner[interior[:, 1]]))
+
+
+def _face_places(input_faces, faces, perm, n):
+    """for the faces of the mesh numbered by perm[new] = old: (each one's place in the input-order mesh's face list, whether
+    it is oriented the other way round there).  Cells from n on are boundary cells, the same in both meshes"""
+    old = np.asarray(faces, dtype=np.int64).copy()
+    own = old < n
+    old[own] = np.asarray(perm, dtype=np.int64)[old[own]]
+    ref = np.asarray(input_faces, dtype=np.int64)
+    big = max(int(ref.max(initial=0)), int(old.max(initial=0))) + 1
+    key = lambda f: f.min(axis=1) * big + f.max(axis=1)     # noqa: E731
+    a, b = np.argsort(key(ref), kind="stable"), np.argsort(key(old), kind="stable")
+    if len(ref) != len(old) or not np.array_equal(key(ref)[a], key(old)[b]):
+        raise RuntimeError("the mesh in compact cell order has other faces than the mesh in input order")
+    place = np.empty(len(old), dtype=np.int64)
+    place[b] = a
+    return place, old[:, 0] != ref[place, 0]
+
+
+def renumber_input(inp, perm, inv):
+    """a copy of the input with every cell number it carries put through inv (inv[old] = new) and every per-cell array
+    listed in the new order (perm[new] = old): boundaries[].faces.cells, source[].cell, rock.types[].cells, zones given as
+    cell lists, per-cell initial.primary / region / tracer.  Pure."""
+    import copy
+    out = copy.deepcopy(inp)
+    n = len(perm)
+    renum = lambda cells: [int(inv[c]) for c in cells]      # noqa: E731
+    for b in out.get("boundaries") or []:
+        faces = b.get("faces")
+        for f in (faces if isinstance(faces, list) else [faces]):
+            if isinstance(f, dict) and f.get("cells") is not None:
+                f["cells"] = renum(f["cells"])
+    for s_ in out.get("source") or []:
+        if s_.get("cell") is not None:
+            s_["cell"] = int(inv[s_["cell"]])
+    for rt in (out.get("rock") or {}).get("types") or []:
+        if rt.get("cells") is not None:
+            rt["cells"] = renum(rt["cells"])
+    mesh = out.get("mesh")
+    for z in ((mesh.get("zones") or {}) if isinstance(mesh, dict) else {}).values():
+        if isinstance(z, dict) and z.get("cells") is not None:
+            z["cells"] = renum(z["cells"])
+    init = out.get("initial") or {}
+    for key, rank in (("primary", 2), ("region", 1), ("tracer", 2)):
+        v = init.get(key)
+        if isinstance(v, (list, tuple)) and np.ndim(v) == rank and len(v) == n:
+            init[key] = [v[p] for p in perm]
+    return out
+
+
 class Simulation:
     """One Waiwera input file -> mesh, flow simulation object and time stepper."""
 
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
-                 sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural", network_pass="host"):
+                 sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural", network_pass="host",
+                 cell_order="input", subdomain_rows=None):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -431,6 +502,19 @@ class Simulation:
         if subdomains not in ("chunks", "rank"):
             raise ValueError("subdomains 'chunks' (the mesh's chunks, the default) or 'rank' (one block per rank, the reference's layout)")
         self.subdomains, self.subdomain_choice = subdomains, None
+        # cell_order: the numbering the library gets -- "input" (the default, as before): the mesh file's, with chunks of
+        # consecutive cells as the preconditioner's subdomains; "compact" (wai_cell_order): compact 3-D subdomains of at most
+        # subdomain_rows cells, numbered inside like a brick.  Everything the input says by cell number goes in through the
+        # inverse permutation and every result comes back in the input's numbering; cell_order_choice records the order taken,
+        # the subdomains and the share of interior faces they cut.  subdomain_rows: the cap under either order (None: 512, or
+        # 512 // (1 + MINC levels)).  Not keys of the input file: the reference partitions through DMPlex
+        if cell_order not in ("input", "compact"):
+            raise ValueError("cell_order 'input' (the mesh file's numbering, the default) or 'compact' (compact subdomains, wai_cell_order)")
+        if subdomain_rows is not None and (isinstance(subdomain_rows, bool) or not isinstance(subdomain_rows, (int, np.integer))
+                                           or not 1 <= subdomain_rows <= 1024):
+            raise ValueError("subdomain_rows None (512 rows, MINC cells included) or an integer from 1 to 1024")
+        self.cell_order, self.subdomain_rows, self.cell_order_choice = cell_order, subdomain_rows, None
+        self._perm = self._inv = self._input_faces = None
         # output files go to output_dir (default: $WAIWERA_OUTPUT_DIR, else beside the input file)
         self.output_dir = output_dir or os.environ.get("WAIWERA_OUTPUT_DIR") or base_dir
         self.output_error = None
@@ -439,6 +523,13 @@ class Simulation:
         mesh = inp.get("mesh")
         if isinstance(mesh, str):
             mesh = {"filename": mesh}
+        if self.cell_order == "compact":
+            # from the arguments and the input alone, before anything is built or exchanged: each of these numbers the cells
+            # itself (partition_mesh, the mesh_builder, add_minc_zones' waiwera_order) and needs its own composition with perm
+            met = ("world = %d ranks" % self.world if self.world > 1 else "a mesh_builder" if mesh_builder is not None
+                   else "MINC zones (mesh.minc)" if (mesh or {}).get("minc") else None)
+            if met:
+                raise ValueError("cell_order 'compact' serves one rank, a mesh file and no MINC zones; the input and arguments give " + met)
         if mesh_builder is None:
             # gmsh 2.2 ASCII, or (mesh_file: the input names an ExodusII file, which cannot be read
             # here) the MULgraph geometry file the reference's benchmarks keep beside it
@@ -511,10 +602,38 @@ class Simulation:
         minc_in = [] if minc_in is None else (minc_in if isinstance(minc_in, list) else [minc_in])
         # matrix cells join their fracture cell's preconditioner subdomain (<= 1024 rows each)
         max_levels = max([len(np.atleast_1d(_get(mz, "geometry.matrix.volume", [0.9]))) for mz in minc_in] or [0])
+        chunk = int(subdomain_rows) if subdomain_rows is not None else (512 // (1 + max_levels) if max_levels else 512)
         if mesh_builder is None:
-            lm = unstructured.build_mesh(nodes, cells, dim, thickness=mesh.get("thickness", 1.0),
-                                         radial=bool(mesh.get("radial", False)), gravity=grav, boundaries=bnds,
-                                         sources=srcs, chunk=512 // (1 + max_levels) if max_levels else 512)
+            def build(cells, bnds, srcs, **kw):
+                return unstructured.build_mesh(nodes, cells, dim, thickness=mesh.get("thickness", 1.0),
+                                               radial=bool(mesh.get("radial", False)), gravity=grav, boundaries=bnds,
+                                               sources=srcs, chunk=chunk, **kw)
+            if self.cell_order == "input":
+                lm = build(cells, bnds, srcs)
+            else:
+                # The order from the centroids and interior faces of the mesh built in input order -- with canonical_faces, so
+                # that a cell's centroid is the same bits wherever the file lists it: the cells of a layer of a layered mesh
+                # then share their z exactly, and another numbering of the file gives the same order.  Then the mesh build_mesh
+                # makes of the same file with its elements listed in that order, the leaves as its subdomains, and the input
+                # renumbered.  Of the input-order mesh the face list is kept: face results are listed and oriented by it
+                from . import lib as wl
+                first = build(cells, bnds, srcs, canonical_faces=True)
+                interior = np.asarray(first.face_cells).reshape(-1, 2)[: first.n_faces - first.n_bc]
+                perm, leaves = wl.cell_order(interior, first.cell_geom[:n, :3], chunk)
+                inv = np.empty(n, dtype=np.int64)
+                inv[perm] = np.arange(n)
+                self._perm, self._inv = perm.astype(np.int64), inv
+                inp = renumber_input(inp, perm, inv)
+                mesh = inp["mesh"] if isinstance(inp.get("mesh"), dict) else mesh
+                lm = build([cells[p] for p in perm], [([int(inv[c]) for c in b[0]],) + tuple(b[1:]) for b in bnds],
+                           [dict(s, cell=int(inv[s["cell"]])) for s in srcs])
+                lm.sub_ptr = leaves.astype(np.int32)
+                faces = np.asarray(lm.face_cells).reshape(-1, 2)
+                self._input_faces = np.asarray(first.face_cells).reshape(-1, 2).copy()
+                self._face_place, self._face_flip = _face_places(self._input_faces, faces, perm, n)
+                self.cell_order_choice = CellOrderChoice("compact", len(leaves) - 1, int(np.diff(leaves).max()),
+                                                         _cut_share(interior, first.sub_ptr),
+                                                         _cut_share(faces[: lm.n_faces - lm.n_bc], lm.sub_ptr))
         else:
             lm = mesh_builder(bnds, srcs)
         cen = lm.cell_geom[:n, :3]
@@ -588,6 +707,11 @@ class Simulation:
             self._order = lm.extras["waiwera_order"]
         self.owned_gid = np.arange(lm.n_owned)
         self._src_pick = None
+        if self.cell_order_choice is None:      # the whole mesh as built, before its cells are dealt out to ranks
+            fc = np.asarray(lm.face_cells if lm.face_cells is not None else [], dtype=np.int64).reshape(-1, 2)
+            sp =np.asarray(lm.sub_ptr if lm.sub_ptr is not None else [0, lm.n_owned])
+            share = _cut_share(fc[(fc < lm.n_owned).all(axis=1)], sp)
+            self.cell_order_choice = CellOrderChoice("input", len(sp) - 1, int(np.diff(sp).max()) if len(sp) > 1 else 0, share, share)
         # what the initial conditions below need of the whole MINC mesh: its cell count, each cell's original cell and the
         # reference's cell order (on N ranks self._order becomes the rank's own)
         minc_all = (lm.n_owned, lm.extras["minc_parent"], self._order) if self._order is not None else None
@@ -650,6 +774,8 @@ class Simulation:
             elif npv > 2:
                 cols.append(st["fluid_CO2_partial_pressure" if self.eos == "wce" else "fluid_air_partial_pressure"])
             prim = np.stack(cols, axis=1)
+            if self._perm is not None and prim.shape[0] == n:      # read_state lists the file's cells by their /cell_index
+                prim, region = prim[self._perm], region[self._perm]
             if prim.shape[0] != n and not (minc_all is not None and prim.shape[0] == minc_all[0]):
                 raise ValueError("initial conditions file has %d cells, mesh has %d" % (prim.shape[0], n))
         else:
@@ -1208,6 +1334,8 @@ class Simulation:
         geom = self.mesh.cell_geom[:n]
         if self._order is not None:      # MINC: the reference's cell order (original cells, then level by level)
             fl, geom = fl[self._order], geom[self._order]
+        if self._inv is not None:        # the compact cell order: back to the input's numbering
+            fl, geom = fl[self._inv], geom[self._inv]
         cols = self._fluid_columns()
         out = {"time": self.ts.time}
         for name, col in cols[:5]:
@@ -1218,7 +1346,8 @@ class Simulation:
         if self.X is not None:
             for k, name in enumerate(self.tracer_names):
                 xk = self.X.reshape(n, -1)[:, k]
-                out["tracer_" + name] = (xk[self._order] if self._order is not None else xk).copy()
+                back = self._order if self._order is not None else self._inv
+                out["tracer_" + name] = (xk[back] if back is not None else xk).copy()
         # A source network on N ranks: reading the sources' rates runs the network pass, which gathers every rank's
         # sources -- a rank without any reads them too (`together`; decided on the input alone)
         together = self.world > 1 and bool(getattr(self, "network_names", None)) and \
@@ -1232,11 +1361,18 @@ class Simulation:
         names, flux_names = self._flux_names()
         if flux_names and hasattr(self.ode, "fluxes"):
             fx = self.ode.fluxes()
+            face_cells, face_area = self.mesh.face_cells, np.asarray(self.mesh.face_geom)[:, 0]
+            if self._input_faces is not None:
+                # the compact cell order: the faces as the input-order mesh lists and orients them
+                back, area = np.empty_like(fx), np.empty_like(face_area)
+                back[self._face_place] = np.where(self._face_flip[:, None], -fx, fx)
+                area[self._face_place] = face_area
+                fx, face_cells, face_area = back, self._input_faces, area
             for nm in flux_names:
                 out["flux_" + nm] = fx[:, names.index(nm)].copy()
             out["face_cell_1"], out["face_cell_2"], out["face_geometry_area"] = face_output(
-                self.mesh.face_cells, self.mesh.n_owned + self.mesh.n_halo, self.mesh.n_bc,
-                self.mesh.extras.get("bc_spec", np.zeros(self.mesh.n_bc, dtype=np.int64)), np.asarray(self.mesh.face_geom)[:, 0])
+                face_cells, self.mesh.n_owned + self.mesh.n_halo, self.mesh.n_bc,
+                self.mesh.extras.get("bc_spec", np.zeros(self.mesh.n_bc, dtype=np.int64)), face_area)
         # separated water / steam flows of the sources and the source network's nodes
         src_want = want.get("source") or []
         if (self.mesh.n_src or together) and hasattr(self.ode, "source_separated") and \

@@ -67,11 +67,23 @@ def _face3d(p):
     return av, cen / tot
 
 
+def _canonical_ring(ring):
+    """a face's nodes in an order that does not depend on the cell it is met from: from its smallest node, towards the
+    smaller of that node's two neighbours on the ring"""
+    k = ring.index(min(ring))
+    ring = ring[k:] + ring[:k]
+    return ring if ring[1] < ring[-1] else [ring[0]] + ring[:0:-1]
+
+
 def build_mesh(nodes, cells, dim, thickness=1.0, radial=False, gravity=None, boundaries=(), rock=None,
-               sources=None, chunk=512):
+               sources=None, chunk=512, canonical_faces=False):
     """boundaries: [(cells, normal, primary, region)]; rock: (8,) or (ncells, 8); sources:
     [{cell, rate, enthalpy, component}].  Returns a LocalMesh (single rank, natural cell order,
-    preconditioner subdomains = chunks of consecutive cells)."""
+    preconditioner subdomains = chunks of consecutive cells).
+    A face's area and centroid are summed over its nodes as the first cell that names it lists them, so they -- and the
+    cell centroids -- depend in the last bit on the order of the cells; canonical_faces=True sums over _canonical_ring
+    instead: the geometry of a cell is then the same bits wherever the file lists it (what the compact cell order is
+    computed from, waiwera_amd/simulation.py)."""
     n = len(cells)
     g = np.zeros(3)
     if gravity is not None:
@@ -103,7 +115,8 @@ def build_mesh(nodes, cells, dim, thickness=1.0, radial=False, gravity=None, bou
                 key = tuple(sorted(nd[k] for k in f))
                 facemap.setdefault(key, []).append(c)
                 if key not in fgeo:
-                    av, fc = _face3d(nodes[[nd[k] for k in f]])
+                    ring = [nd[k] for k in f]
+                    av, fc = _face3d(nodes[_canonical_ring(ring) if canonical_faces else ring])
                     area = np.linalg.norm(av)
                     fgeo[key] = [area, fc, av / area]
                 fl.append(key)
