@@ -528,6 +528,26 @@ enum { WAI_NETWORK_PASS_HOST = 0, WAI_NETWORK_PASS_DEVICE = 1 };
 int wai_set_network_pass(wai_ctx *ctx, int where);
 int wai_get_network_pass(wai_ctx *ctx, int *requested, int *in_force);
 
+/* How wai_jacobian builds the source network's coupling blocks E (wai_set_network_couplings).  WAI_COUPLING_BUILD_COLUMNS
+ * (the default): one column -- network cell j, primary k -- at a time, on the global state: y_jk is perturbed in place, the
+ * cell's fluid record evaluated again, the network's rows differenced around a network pass, and everything restored;
+ * about thirteen launches per column with the device pass, several stream waits per column with the host pass.
+ * WAI_COUPLING_BUILD_BATCHED: all m * bs columns at once, each on private copies of what a column changes -- the
+ * perturbed cell's record, the sources' own rates, the pass' factors and enthalpies, the rows with the factors held --
+ * in five launches whatever m is (k_cb_states, k_cb_raw, k_cb_rows, k_cb_pass, k_cb_rows; one network pass per column, each
+ * one wave on LDS).  y, the fluid record and the network's factors are read and never written; the host waits once, for
+ * the flag.  The same operations in the same order as the column loop: the same bits.  The scratch (one column: 1 + the
+ * record + 5 n + m * bs doubles, n sources) is allocated by the first build and kept; where all columns would take more than
+ * 256 MiB they run in chunks of as many as fit, five launches each, and a column that does not fit alone is refused (-2
+ * with a text, from wai_jacobian).
+ * May be set before or after wai_set_source_network.  The batched build is in force exactly where the device pass is
+ * (wai_set_network_pass: WAI_NETWORK_PASS_DEVICE asked for, one rank, a network that fits a workgroup's LDS) and the
+ * couplings are on; otherwise the column loop of the pass in force runs, and no error is raised.
+ * wai_get_coupling_build reports the setting and what runs (out-arguments may be NULL).  Unknown value: -2 with a text. */
+enum { WAI_COUPLING_BUILD_COLUMNS = 0, WAI_COUPLING_BUILD_BATCHED = 1 };
+int wai_set_coupling_build(wai_ctx *ctx, int how);
+int wai_get_coupling_build(wai_ctx *ctx, int *requested, int *in_force);
+
 /* The auxiliary (tracer) solver's own preconditioner: time.step.solver.auxiliary.preconditioner.{type, sub.preconditioner.{type,
  * factor.levels}} (timestepper_configure_auxiliary_linear_solver, src/timestepper.F90:2057-2065; the same keys as the flow
  * solver's).  pc_type: a WAI_PC_* value, or WAI_AUX_PC_FOLLOW (the default): the tracer solves use the flow solver's

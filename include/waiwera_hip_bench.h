@@ -42,8 +42,12 @@ int wai_test_drop_stream_wait(wai_ctx *ctx, int which);
  * pass touches the entries of the sources a reinjector feeds alone.  Out-arguments may be NULL. */
 int wai_test_network_pass(wai_ctx *ctx, const double *raw2n, double *sources6, double *groups6, double *reinjectors8,
                           double *net2n, double *enth_n);
-/* network passes made so far, and the stream waits the passes and the coupling build issued (either mode) */
+/* network passes made so far, and the stream waits the passes and the coupling build issued (either mode).  A batched
+ * coupling build (wai_set_coupling_build) counts 1 + m * bs passes: the one before it and one per column */
 int wai_test_network_stats(wai_ctx *ctx, long long *passes, long long *host_waits);
+/* the last coupling build of wai_jacobian, whichever way it ran: kernel launches (the column loops': counted from their
+ * text), columns (m * bs; 0: no build) and chunks of the batched build (0 for a column loop).  Out-arguments may be NULL */
+int wai_test_coupling_build_stats(wai_ctx *ctx, long long *launches, long long *columns, long long *chunks);
 /* doubles of LDS the pass on the device may take (description + raw rates + state), and what the context's network
  * takes (0: none, or one on several ranks): a network that needs more keeps the host pass */
 int wai_test_network_lds(wai_ctx *ctx, int *limit, int *needed);

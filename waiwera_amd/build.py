@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwaiwera_hip.so")
 # the cell/face assembly sweeps: every unit that includes assembly_device.hip.h (tests/test_abi.py holds the list complete)
-ASSEMBLY_UNITS = ["kernels_eos.hip", "kernels_residual.hip", "kernels_jacobian.hip", "kernels_tracer.hip"]
+ASSEMBLY_UNITS = ["kernels_eos.hip", "kernels_residual.hip", "kernels_jacobian.hip", "kernels_tracer.hip",
+                  "kernels_coupling.hip"]
 SOURCES = ["capi.hip", "context.hip", "sources.hip", "tracers.hip", "krylov.hip", "pc_setup.hip", "network.hip",
            "measure.hip", "gather.hip"] + ASSEMBLY_UNITS + \
     ["kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_tracer_block.hip", "kernels_network.hip", "comm.cpp"]

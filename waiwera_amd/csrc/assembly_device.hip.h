@@ -1,6 +1,6 @@
 // What the cell/face assembly sweeps for gfx950 share: constants, the XCD-aware cell mapping, the mesh view, the face and
 // source terms of one row, the residual forms, the records parked in LDS, and the host helpers every launcher starts from.
-// Included by the four assembly units (waiwera_amd/build.py: ASSEMBLY_UNITS, all built without FMA contraction) and by
+// Included by the five assembly units (waiwera_amd/build.py: ASSEMBLY_UNITS, all built without FMA contraction) and by
 // nothing else:
 //   kernels_eos.hip       k_eos / k_eos_pert (K1), k_transitions (K11), k_separator
 //   kernels_residual.hip  k_residual_tile -- the default full sweep, the workgroup's own cells staged in LDS -- and
@@ -10,6 +10,8 @@
 //                         LDS -- and the row-wise k_jacobian_park / k_jacobian (WAI_JAC_SYM=0, WAI_JAC_PARK=0) that the
 //                         tests compare it with (K5)
 //   kernels_tracer.hip    the tracers' scalar systems, one per tracer or all in one sweep, and their copies
+//   kernels_coupling.hip  the batched build of the source network's coupling blocks: k_eos, k_source_rates and k_residual's
+//                         row list per column on private scratch, around k_network_pass per column
 //
 // Reference loops replaced (the reference's src/):
 //   flow_simulation.F90:2291-2415 fluid_properties     -> k_eos / k_eos_pert

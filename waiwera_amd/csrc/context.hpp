@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/waiwera_hip.h"
 #include "colour_order.hpp"   // ColourFacts
+#include "coupling_batch.hpp" // CouplingBatch
 #include "devbuf.hpp"
 #include "ilu_schedule.hpp"   // ScheduleFacts
 #include "mesh_pattern.hpp"   // MAX_CELL_FACES
@@ -195,6 +196,10 @@ struct Network {
   DevBuf<double> d_cp_yh;                          // coupling build on the device: y_jk and h of the column in hand
   DevBuf<int> d_cp_flag;                           // ... an entry of E is nonzero
   bool cp_on_device = false;                       // d_cp_val is newer than h_cp_val (network_fetch_couplings)
+  // the batched coupling build (wai_set_coupling_build; coupling_batch.hpp): one chunk's columns of private scratch,
+  // allocated by the first batched build and kept while it is large enough
+  DevBuf<double> d_cb_scratch;
+  long long cb_doubles = 0;                        // ... its size
 };
 
 // Block matrix in HBM: block-ELL, slot-major struct-of-arrays ("SELL" with one slice):
@@ -565,6 +570,8 @@ struct wai_ctx : wai::Handles {
   int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
   int net_pass = WAI_NETWORK_PASS_HOST;     // wai_set_network_pass: where the source network's pass runs (net_on_device: what is in force)
   long long net_passes = 0, net_waits = 0;  // passes made / stream waits issued by network_update and network_couplings (wai_test_network_stats)
+  int cp_build = WAI_COUPLING_BUILD_COLUMNS;   // wai_set_coupling_build: how the network's Jacobian blocks are built (cp_batched: what is in force)
+  long long cp_launches = 0, cp_columns = 0, cp_chunks = 0;   // kernel launches, columns and chunks of the last coupling build (wai_test_coupling_build_stats)
   int pc_ordering = WAI_PC_ORDER_NATURAL;   // wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
   wai::ColourSchedule colour;   // ... its symbolic phase under WAI_PC_ORDER_MULTICOLOUR, built by the first set-up that needs it
   std::vector<int> pc_tiles;    // wai_set_pc_tiles: row ranges [n_tiles + 1] of the tiles that refine the subdomains; empty: none
@@ -660,6 +667,10 @@ int launch_network_pass(wai_ctx* c, const double* raw, double* net, double* enth
 int launch_cp_perturb(wai_ctx* c, double* p, double* yh);
 int launch_cp_restore(wai_ctx* c, double* p, const double* yh);
 int launch_cp_diff(wai_ctx* c, int ml, int m, int bs, int j, int k, const double* g, const double* yh, double* val, int* flag);   // out[0..n) rates, out[n..2n) enthalpies (device); raw: before the network pass
+// kernels_coupling.hip: the columns col0 .. col0 + ncol - 1 of the batched coupling build on the scratch plan b -- five
+// launches whatever ncol is; launches: counted
+int launch_coupling_batch(wai_ctx* c, const CouplingBatch& b, int col0, int ncol, double dt, const double* y, const double* lhs_old,
+                          long long* launches);
 // X[cell][nt] <-> x[cell] of tracer it; alx = Al o X
 int launch_tracer_pick(wai_ctx* c, const double* X, int it, double* x);
 int launch_tracer_put(wai_ctx* c, const double* x, int it, double* X);

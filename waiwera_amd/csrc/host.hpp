@@ -192,6 +192,11 @@ void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n);   // s
 inline bool net_on_device(const wai_ctx* c) {
   return c->net_pass == WAI_NETWORK_PASS_DEVICE && c->net.on && c->net.flat_fits && !(c->comm && c->comm->nranks > 1);
 }
+// Is the batched coupling build (wai_set_coupling_build) in force: asked for, the device pass in force, the couplings on
+inline bool cp_batched(const wai_ctx* c) {
+  return c->cp_build == WAI_COUPLING_BUILD_BATCHED && net_on_device(c) && c->net.coupling;
+}
+constexpr long long COUPLING_BATCH_BYTES = 256LL << 20;   // the most scratch one chunk of its columns takes (coupling_batch.hpp)
 int network_update(wai_ctx* c);
 int network_fetch_state(wai_ctx* c);       // the last device pass' node states to the host's Network
 int network_fetch_couplings(wai_ctx* c);   // the device-built coupling blocks to h_cp_val

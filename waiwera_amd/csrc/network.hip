@@ -316,6 +316,9 @@ int network_fetch_couplings(wai_ctx* c) {
 // columns), E[:, j][:, k] = (R(network pass redone) - R(factors held)) / h on the rows of those cells.
 // Two residual launches on the network's rows alone (k_residual's row list: the same code path per row, so
 // the same bits as a full sweep) and three host passes per column: the cost does not grow with the mesh.
+// wai_set_coupling_build, WAI_COUPLING_BUILD_BATCHED (where the device pass is in force): the columns are independent, so
+// all of them run at once on private scratch in five launches (kernels_coupling.hip; the plan: coupling_batch.hpp, its byte
+// cap COUPLING_BATCH_BYTES or, for the tests, the environment's WAI_COUPLING_BATCH_BYTES) -- the same bits.
 __global__ void k_gather_rows(int m, int bs, const int* __restrict__ cells, const double* __restrict__ f,
                               double* __restrict__ out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -342,6 +345,7 @@ __global__ void k_coupling_apply(int mr, int mc, int bs, const int* __restrict__
 int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
   Network& nw = c->net;
   nw.cp_valid = false;
+  c->cp_launches = c->cp_columns = c->cp_chunks = 0;
   const bool span = nw.cp_span;
   const int ml = (int)nw.cp_cells.size(), m = span ? nw.cp_m : ml, j0 = span ? nw.cp_j0 : 0;
   if (!nw.on || !nw.coupling || m == 0) return 0;
@@ -363,7 +367,27 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
     if (!nw.d_cp_yh && (nw.d_cp_yh.alloc(c, 2) || nw.d_cp_flag.alloc(c, 1))) return -1;
     if (network_update(c)) return -1;   // the factors A was differenced with
     HIPCHK(c, hipMemsetAsync(nw.d_cp_flag, 0, sizeof(int), c->stream));
-    for (int j = 0; j < m; j++) {
+    c->cp_columns = (long long)m * bs;
+    c->cp_launches = 2;   // network_update above: k_source_rates and k_network_pass
+    const bool batched = cp_batched(c);
+    if (batched) {
+      // all columns at once, each on private scratch (kernels_coupling.hip): y, the fluid record and the factors are read
+      // and never written, so nothing is perturbed, restored or passed again -- five launches per chunk whatever m is
+      CouplingBatch b;
+      long long cap = COUPLING_BATCH_BYTES;
+      if (const char* ev = getenv("WAI_COUPLING_BATCH_BYTES")) cap = atoll(ev);   // read per build: the tests force several chunks
+      if (int e = coupling_batch_plan(m, ml, bs, c->df, c->src.n, cap, b, c->err)) return e;
+      if (b.doubles > nw.cb_doubles) {
+        if (nw.d_cb_scratch.alloc(c, (size_t)b.doubles)) return -1;
+        nw.cb_doubles = b.doubles;
+      }
+      for (int ch = 0; ch < b.n_chunks; ch++)
+        if (launch_coupling_batch(c, b, ch * b.chunk, ch + 1 < b.n_chunks ? b.chunk : b.last, dt, y, lhs_old, &c->cp_launches))
+          return -1;
+      c->net_passes += b.ncol;   // one pass per column, in k_cb_pass
+      c->cp_chunks = b.n_chunks;
+    } else c->cp_launches += 13 * c->cp_columns;   // counted from the loop below (each network_update in it: two launches)
+    for (int j = 0; j < m && !batched; j++) {
       const int cell = nw.cp_cells[j];
       for (int k = 0; k < bs; k++) {
         double* p = y + (size_t)cell * bs + k;
@@ -406,6 +430,9 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
     return 0;
   };
   if (network_update(c)) return -1;   // the factors A was differenced with
+  c->cp_columns = (long long)m * bs;
+  // counted from the loop below: per column two residuals and gathers, two k_source_rates, and two k_eos on its owner
+  c->cp_launches = (c->src.n ? 1 : 0) + ((ml ? 4 : 0) + (c->src.n ? 2 : 0)) * c->cp_columns + 2LL * ml * bs;
   bool any = false;
   for (int j = 0; j < m; j++) {       // every rank walks the same columns: the network passes are collective
     const bool mine = !span || nw.cp_owner[j] == me;
@@ -715,6 +742,29 @@ int wai_get_network_pass(wai_ctx* c, int* requested, int* in_force) {
   if (!c) return -2;
   if (requested) *requested = c->net_pass;
   if (in_force) *in_force = net_on_device(c) ? WAI_NETWORK_PASS_DEVICE : WAI_NETWORK_PASS_HOST;
+  return 0;
+}
+// How the network's Jacobian blocks are built (include/waiwera_hip.h)
+int wai_set_coupling_build(wai_ctx* c, int how) {
+  if (!c) return -2;
+  if (how != WAI_COUPLING_BUILD_COLUMNS && how != WAI_COUPLING_BUILD_BATCHED) {
+    c->err = "unknown way to build the source network's coupling blocks (WAI_COUPLING_BUILD_COLUMNS or WAI_COUPLING_BUILD_BATCHED)";
+    return -2;
+  }
+  c->cp_build = how;
+  return 0;
+}
+int wai_get_coupling_build(wai_ctx* c, int* requested, int* in_force) {
+  if (!c) return -2;
+  if (requested) *requested = c->cp_build;
+  if (in_force) *in_force = cp_batched(c) ? WAI_COUPLING_BUILD_BATCHED : WAI_COUPLING_BUILD_COLUMNS;
+  return 0;
+}
+int wai_test_coupling_build_stats(wai_ctx* c, long long* launches, long long* columns, long long* chunks) {
+  if (!c) return -2;
+  if (launches) *launches = c->cp_launches;
+  if (columns) *columns = c->cp_columns;
+  if (chunks) *chunks = c->cp_chunks;
   return 0;
 }
 // one pass on the device for the given raw rates (include/waiwera_hip_bench.h)

@@ -149,6 +149,28 @@ class FlowSimulation:
         self._chk(LIB.wai_test_network_stats(self.h, C.byref(p), C.byref(w)), "network_stats")
         return p.value, w.value
 
+    def set_coupling_build(self, how):
+        """how wai_jacobian builds the network's coupling blocks (wai_set_coupling_build): "columns" (default: one column at a
+        time on the global state) or "batched" (all columns at once on private scratch, five launches whatever the number of
+        network cells).  The same bits either way.  Before or after set_source_network"""
+        if how not in _lib.COUPLING_BUILD:
+            raise ValueError("coupling build %r: one of %s" % (how, sorted(_lib.COUPLING_BUILD)))
+        self._chk(LIB.wai_set_coupling_build(self.h, _lib.COUPLING_BUILD[how]), "set_coupling_build")
+
+    def coupling_build(self):
+        """(requested, in_force): the setting, and what runs -- "batched" where the device pass is in force (network_pass)
+        and the couplings are on, "columns" otherwise"""
+        r, f = C.c_int(0), C.c_int(0)
+        self._chk(LIB.wai_get_coupling_build(self.h, C.byref(r), C.byref(f)), "coupling_build")
+        name = {v: k for k, v in _lib.COUPLING_BUILD.items()}
+        return name[r.value], name[f.value]
+
+    def coupling_build_stats(self):
+        """(launches, columns, chunks) of the last coupling build (wai_test_coupling_build_stats)"""
+        a, b, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        self._chk(LIB.wai_test_coupling_build_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "coupling_build_stats")
+        return a.value, b.value, c.value
+
     def set_network_couplings(self, on=True, in_preconditioner=True):
         """the network's Jacobian blocks (flow_simulation_modify_jacobian, flow_simulation.F90:3023-3084) on / off;
         in_preconditioner: also inside the factor's pattern, as PETSc factors the widened matrix (default), or in the

@@ -561,6 +561,19 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        integer(c_int), intent(out) :: requested, in_force
      end function wai_get_network_pass
+     ! how wai_jacobian builds the network's coupling blocks: WAI_COUPLING_BUILD_COLUMNS (0, default) one column at a time |
+     ! WAI_COUPLING_BUILD_BATCHED (1): all columns at once on private scratch.  In force where the device pass is
+     integer(c_int) function wai_set_coupling_build(ctx, how) bind(c, name = "wai_set_coupling_build")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: how
+     end function wai_set_coupling_build
+     ! the setting, and what runs
+     integer(c_int) function wai_get_coupling_build(ctx, requested, in_force) bind(c, name = "wai_get_coupling_build")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: requested, in_force
+     end function wai_get_coupling_build
      ! the auxiliary (tracer) solver's own preconditioner (time.step.solver.auxiliary.preconditioner): a WAI_PC_* value, or
      ! WAI_AUX_PC_FOLLOW (-1, default): the flow solver's.  The reference's default is WAI_PC_BJACOBI
      integer(c_int) function wai_set_aux_pc(ctx, pc_type, asm_overlap, ilu_levels, sub_pc) bind(c, name = "wai_set_aux_pc")
@@ -595,6 +608,7 @@ module waiwera_hip_module
   integer, parameter, public :: WAI_SUB_ILU = 0, WAI_SUB_LU = 1
   integer, parameter, public :: WAI_PC_ORDER_NATURAL = 0, WAI_PC_ORDER_MULTICOLOUR = 1
   integer, parameter, public :: WAI_NETWORK_PASS_HOST = 0, WAI_NETWORK_PASS_DEVICE = 1
+  integer, parameter, public :: WAI_COUPLING_BUILD_COLUMNS = 0, WAI_COUPLING_BUILD_BATCHED = 1
   integer, parameter, public :: WAI_PC_BJACOBI = 0, WAI_PC_ASM = 1, WAI_PC_NONE = 2, WAI_PC_LU = 3, WAI_AUX_PC_FOLLOW = -1
 
   type, public :: hip_flow_simulation_type
@@ -622,6 +636,7 @@ module waiwera_hip_module
      procedure, public :: set_pc_tiles => hip_sim_set_pc_tiles
      procedure, public :: set_pc_ordering => hip_sim_set_pc_ordering
      procedure, public :: set_network_pass => hip_sim_set_network_pass
+     procedure, public :: set_coupling_build => hip_sim_set_coupling_build
      procedure, public :: set_aux_pc => hip_sim_set_aux_pc
      procedure, public :: aux_lhs => hip_sim_aux_lhs
      procedure, public :: aux_solve => hip_sim_aux_solve
@@ -642,6 +657,7 @@ module waiwera_hip_module
   public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc, wai_set_aux_pc, wai_get_aux_pc
   public :: wai_set_pc_tiles, wai_set_pc_ordering, wai_get_pc_ordering
   public :: wai_set_network_pass, wai_get_network_pass
+  public :: wai_set_coupling_build, wai_get_coupling_build
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_gather_rows, wai_gather_fluid, wai_cell_order
@@ -907,6 +923,14 @@ contains
     integer, intent(out) :: err
     err = wai_set_network_pass(self%ctx, int(where, c_int))
   end subroutine hip_sim_set_network_pass
+
+  subroutine hip_sim_set_coupling_build(self, how, err)
+    !! How the network's Jacobian blocks are built: WAI_COUPLING_BUILD_COLUMNS | WAI_COUPLING_BUILD_BATCHED.
+    class(hip_flow_simulation_type), intent(in out) :: self
+    integer, intent(in) :: how
+    integer, intent(out) :: err
+    err = wai_set_coupling_build(self%ctx, int(how, c_int))
+  end subroutine hip_sim_set_coupling_build
 
   subroutine hip_sim_set_aux_pc(self, pc_type, asm_overlap, ilu_levels, sub_pc, err)
     !! Preconditioner of the auxiliary (tracer) solver (timestepper_configure_auxiliary_linear_solver,

@@ -45,6 +45,9 @@ def main(argv=None):
     ap.add_argument("--network-pass", choices=("host", "device"), default="host",
                     help="the source network's pass: on the host (default) or in one launch on the device (one rank, a network "
                          "that fits a workgroup's LDS; the same results)")
+    ap.add_argument("--coupling-build", choices=("columns", "batched"), default="columns",
+                    help="the Jacobian's blocks through the source network: one column at a time (default) or all columns at "
+                         "once on private scratch (in force with --network-pass device; the same results)")
     ap.add_argument("--cell-order", choices=("input", "compact"), default="input",
                     help="the numbering the library gets: the mesh file's, with chunks of consecutive cells as the preconditioner's "
                          "subdomains (default), or compact 3-D subdomains numbered like bricks (one rank, a mesh file, no MINC "
@@ -68,7 +71,8 @@ def main(argv=None):
             a.device = int(os.environ.get("LOCAL_RANK", a.device))
     sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
                                default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, network_pass=a.network_pass,
-                               cell_order=a.cell_order, subdomain_rows=a.subdomain_rows, **kw)
+                               cell_order=a.cell_order, subdomain_rows=a.subdomain_rows,
+                               coupling_build=a.coupling_build, **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

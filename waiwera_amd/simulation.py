@@ -453,7 +453,7 @@ class Simulation:
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
                  sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural", network_pass="host",
-                 cell_order="input", subdomain_rows=None):
+                 cell_order="input", subdomain_rows=None, coupling_build="columns"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -494,6 +494,13 @@ class Simulation:
         if network_pass not in ("host", "device"):
             raise ValueError("network_pass 'host' (the default) or 'device'")
         self.network_pass, self.network_pass_choice = network_pass, (network_pass, "host")
+        # coupling_build: how the Jacobian's blocks through the source network are built -- "columns" (the default, as
+        # before: one column at a time) or "batched" (wai_set_coupling_build: all columns at once on private scratch; the
+        # same bits).  Not a key of the input file.  coupling_build_choice records (requested, in force) once the network is
+        # set: "batched" is in force where network_pass "device" is
+        if coupling_build not in ("columns", "batched"):
+            raise ValueError("coupling_build 'columns' (the default) or 'batched'")
+        self.coupling_build, self.coupling_build_choice = coupling_build, (coupling_build, "columns")
         # subdomains: the preconditioner's blocks on a rank -- "chunks" (the default, as before): the chunks of consecutive cells
         # the mesh builders make (mesh.sub_ptr), each on the fused one-workgroup kernels; "rank": ONE block per rank, the
         # reference's own layout (its bjacobi / asm subdomains are the ranks), with the same chunks handed to the library as
@@ -980,6 +987,9 @@ class Simulation:
             if self.network_pass == "device":
                 self.ode.set_network_pass("device")
                 self.network_pass_choice = self.ode.network_pass()
+            if self.coupling_build == "batched":
+                self.ode.set_coupling_build("batched")
+                self.coupling_build_choice = self.ode.coupling_build()
 
     # ---- state-dependent source controls -------------------------------------------------------
     def _setup_source_controls(self, sources, t0, collective_fluid=False):
