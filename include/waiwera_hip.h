@@ -163,6 +163,13 @@ int wai_set_opts(wai_ctx *ctx, const wai_solver_opts *opts);       /* the "time.
  * cp_type = WAI_CP_TABLE; call before wai_set_bc (the boundary fluid is evaluated there). */
 int wai_set_curve_table(wai_ctx *ctx, int which, int interpolation, int n, const double *xy);
 
+/* "thermodynamics.extrapolate" (src/thermodynamics_setup.F90:57-89): on != 0 raises region 1's upper temperature bound
+ * from 350 to 360 deg C for both formulations (src/IAPWS.F90:449-482, src/IFC67.F90:228-248); the formulas and every other
+ * region are unchanged.  Off after wai_ctx_create.  Every launch that evaluates region 1 reads the bound from the EOS
+ * description it carries; call before wai_set_bc (the boundary fluid is evaluated there). */
+int wai_set_thermo_extrapolate(wai_ctx *ctx, int on);
+int wai_get_thermo_extrapolate(wai_ctx *ctx, int *on);
+
 /* boundary-condition ghost cells: unscaled primaries + region per bc cell
  * (mesh_set_boundary_conditions, src/mesh.F90:1069-1264; fluid filled once :1199-1202) */
 int wai_set_bc(wai_ctx *ctx, const double *primary, const int *region);
@@ -173,6 +180,12 @@ int wai_update_rock(wai_ctx *ctx, int field, int n, const int *cells, const doub
 /* constant-rate sources (src/source.F90:386-480, source_network.F90:296-355) */
 int wai_set_sources(wai_ctx *ctx, int n, const int *cell, const double *rate,
                     const double *enthalpy, const int *component);
+/* "source.production_component" (src/source.F90:340-366, 403-453), one per source in wai_set_sources order, after it (which
+ * resets them); NULL: none.  A producing source (rate < 0) with c > 0 puts its whole rate into component c instead of
+ * dividing it among the mass components by their flow fractions; the flowing enthalpy is formed and enthalpy * rate added
+ * to the energy equation only for c < np; c = np (the block size) produces heat alone.  c <= 0: production follows
+ * `component` as before.  Injection takes `component` either way.  c > np: -2. */
+int wai_set_source_production_component(wai_ctx *ctx, const int *component);
 /* new rates / enthalpies for the sources in force, in wai_set_sources order; either may be NULL
  * (kept).  What the reference's table controls do to their sources before each residual
  * (source_network%update, src/flow_simulation.F90:1469; table_object_control_update,

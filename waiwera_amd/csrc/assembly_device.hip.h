@@ -69,7 +69,7 @@ struct MeshView {
   const int* adj_face; const int* adj_other; const int* adj_blk; const int* diag_blk;
   const int* adj_tblk;     // slot of THIS cell's column in the neighbour's block row (-1: the neighbour is no owned row)
   const int* cell_src;
-  const int* src_next; const int* src_comp; const double* src_rate; const double* src_enth;
+  const int* src_next; const int* src_comp; const int* src_pcomp; const double* src_rate; const double* src_enth;
   SrcCtl* src_ctl;         // null: all rates as given (the unperturbed residual sweep notes threshold indices into the records)
   const double* src_net;   // null: no source network (source_network_rate)
   int n_owned, n_local, n_faces, max_deg;
@@ -102,7 +102,7 @@ __device__ __forceinline__ void source_terms(const MeshView& m, int c, const Cel
   using E = EosT<KIND>;
   for (int si = m.cell_src[c]; si >= 0; si = m.src_next[si]) {
     double flow[E::np];
-    source_flow<KIND>(s, source_rate<KIND>(s, m.src_ctl, si, m.src_rate[si], m.src_net, commit), m.src_enth[si], m.src_comp[si], flow);
+    source_flow<KIND>(s, source_rate<KIND>(s, m.src_ctl, si, m.src_rate[si], m.src_net, commit), m.src_enth[si], m.src_comp[si], m.src_pcomp[si], flow);
 #pragma unroll
     for (int k = 0; k < E::np; k++) R[k] += flow[k] / vol;
   }
@@ -183,7 +183,7 @@ static inline MeshView view(wai_ctx* c) {
   m.rock = c->mesh.rock; m.vol = c->mesh.vol; m.fgeom = c->mesh.fgeom; m.fdir = c->mesh.fdir;
   m.adj_face = c->mesh.adj_face; m.adj_other = c->mesh.adj_other; m.adj_blk = c->mesh.adj_blk;
   m.diag_blk = c->mesh.diag_blk; m.cell_src = c->mesh.cell_src; m.adj_tblk = c->mesh.adj_tblk;
-  m.src_next = c->src.next; m.src_comp = c->src.comp; m.src_rate = c->src.rate;
+  m.src_next = c->src.next; m.src_comp = c->src.comp; m.src_pcomp = c->src.pcomp; m.src_rate = c->src.rate;
   m.src_enth = c->src.enth; m.src_ctl = c->src.ctl; m.src_net = c->src.net;
   m.n_owned = c->mesh.n_owned; m.n_local = c->mesh.n_local; m.n_faces = c->mesh.n_faces;
   m.max_deg = c->mesh.max_deg;

@@ -96,6 +96,7 @@ static int create_eos(wai_ctx* c, const wai_eos_desc* ed) {
   c->ep.rp_type = ed->rp_type; c->ep.cp_type = ed->cp_type;
   if (ed->thermo != WAI_THERMO_IAPWS && ed->thermo != WAI_THERMO_IFC67) { c->err = "unknown thermodynamic formulation"; return -2; }
   c->ep.thermo = ed->thermo;
+  c->ep.t1_max = 350.0;   // wai_set_thermo_extrapolate raises it
   if (ed->perm_type < 0 || ed->perm_type > 2) { c->err = "unknown permeability modifier"; return -2; }
   c->ep.perm_type = ed->perm_type;
   for (int i = 0; i < 3; i++) c->ep.perm_par[i] = ed->perm_par[i];
@@ -427,6 +428,20 @@ int wai_set_curve_table(wai_ctx* c, int which, int interpolation, int n, const d
     if (i > 0 && !(t.x[i] > t.x[i - 1])) { c->err = "curve table coordinates must increase strictly"; return -2; }
   }
   if (interpolation == WAI_INTERP_PCHIP) pchip_derivatives(n, t.x, t.v, t.d);
+  return 0;
+}
+
+// "thermodynamics.extrapolate" (thermodynamics_setup.F90:57-89): region 1's upper temperature bound 360 instead of 350 deg C
+// (IAPWS.F90:449-482, IFC67.F90:228-248), the formulas as they are; a field of the EOS description every launch carries
+int wai_set_thermo_extrapolate(wai_ctx* c, int on) {
+  if (!c) return -2;
+  c->ep.t1_max = on ? 360.0 : 350.0;
+  return 0;
+}
+
+int wai_get_thermo_extrapolate(wai_ctx* c, int* on) {
+  if (!c || !on) return -2;
+  *on = c->ep.t1_max > 350.0 ? 1 : 0;
   return 0;
 }
 

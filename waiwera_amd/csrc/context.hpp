@@ -108,7 +108,7 @@ struct DeviceMesh {
 
 struct Sources {
   int n = 0;
-  DevBuf<int> cell, comp, next;
+  DevBuf<int> cell, comp, pcomp, next;   // pcomp: production components (wai_set_source_production_component), 0: none
   DevBuf<double> rate, enth;
   DevBuf<SrcCtl> ctl;      // state-dependent controls (wai_set_source_controls), null: none
   DevBuf<double> net;      // [2 n] what the source network does to each source (source_network_rate), null: no network

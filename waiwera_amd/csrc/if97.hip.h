@@ -45,8 +45,8 @@ __device__ __forceinline__ void r1_sums(double a, double b, double binv, double&
 }
 
 // Region 1 (liquid): density and internal energy from (P [Pa], T [deg C]); returns error flag
-__device__ __forceinline__ int region1(double p, double t, double& rho, double& u) {
-  if (!((t <= 350.0) && (p <= 100.e6))) return 1;
+__device__ __forceinline__ int region1(double p, double t, double t_max, double& rho, double& u) {
+  if (!((t <= t_max) && (p <= 100.e6))) return 1;
   constexpr double pstar = 16.53e6, tstar = 1386.0;
   const double tk = t + TC_K, rt = RCONST * tk, pi = p / pstar, tau = tstar / tk;
   const double a = 7.1 - pi, b = tau - 1.222, binv = 1.0 / b;

@@ -26,8 +26,8 @@ __device__ constexpr double SA[12] = {8.438375405e-1, 5.362162162e-4, 1.72, 7.34
                                       4.975858870e-2, 6.537154300e-1, 1.150e-6, 1.51080e-5,
                                       1.41880e-1, 7.002753165, 2.995284926e-4, 2.040e-1};
 
-__device__ __forceinline__ int region1(double p, double t, double& rho, double& u) {
-  if (!(t <= 350.0 && p <= 100.0e6)) return 1;
+__device__ __forceinline__ int region1(double p, double t, double t_max, double& rho, double& u) {
+  if (!(t <= t_max && p <= 100.0e6)) return 1;
   const double th = (t + TC_K) / TCK;
   const double th2 = th * th, th4 = th2 * th2, th6 = th4 * th2, th7 = th6 * th, th8 = th4 * th4;
   const double th10 = th8 * th2, th11 = th10 * th, th18 = th10 * th8, th19 = th18 * th, th20 = th10 * th10;

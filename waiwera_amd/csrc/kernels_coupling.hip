@@ -87,9 +87,11 @@ __global__ __launch_bounds__(TPB) void k_cb_raw(MeshView m, CbView v, const int*
 #pragma unroll
     for (int p = 0; p < E::nph; p++) if (phases & (1 << p)) sum += s.kr[p] * s.rho[p] / s.mu[p];
     if constexpr (!E::isothermal) {
+      if (m.src_pcomp[si] < E::np) {   // a production component np produces heat alone: no enthalpy is formed (source.F90:419-425)
 #pragma unroll
-      for (int p = 0; p < E::nph; p++)
-        if (phases & (1 << p)) h += (s.kr[p] * s.rho[p] / s.mu[p] / sum) * s.h[p];
+        for (int p = 0; p < E::nph; p++)
+          if (phases & (1 << p)) h += (s.kr[p] * s.rho[p] / s.mu[p] / sum) * s.h[p];
+      }
     }
   }
   col[v.off_raw + si] = q;

@@ -96,12 +96,12 @@ __global__ __launch_bounds__(TPB) void k_transitions(EosParams ep, int n_owned,
 
 // separator_stage_init (separator.F90:108-136): enthalpies of saturated water and steam at the
 // separator pressure; out = {hf, hg, err}
-__global__ void k_separator(int thermo, double pressure, double* __restrict__ out) {
+__global__ void k_separator(int thermo, double t1_max, double pressure, double* __restrict__ out) {
   double ts = 0.0, rho = 0.0, u = 0.0;
   int err = th::sat_temperature(thermo, pressure, ts);
-  if (!err) err = th::props(thermo, 1, pressure, ts, rho, u);
+  if (!err) err = th::props(thermo, t1_max, 1, pressure, ts, rho, u);
   out[0] = u + pressure / rho;
-  if (!err) err = th::props(thermo, 2, pressure, ts, rho, u);
+  if (!err) err = th::props(thermo, t1_max, 2, pressure, ts, rho, u);
   out[1] = u + pressure / rho;
   out[2] = (double)err;
 }
@@ -134,7 +134,7 @@ int launch_transitions(wai_ctx* c, const double* y_old, double* search, double* 
 }
 
 int launch_separator(wai_ctx* c, double pressure, double* out) {
-  hipLaunchKernelGGL(k_separator, 1, 1, 0, c->stream, c->ep.thermo, pressure, out);
+  hipLaunchKernelGGL(k_separator, 1, 1, 0, c->stream, c->ep.thermo, c->ep.t1_max, pressure, out);
   return launched(c, "k_separator");
 }
 

@@ -163,9 +163,11 @@ __global__ __launch_bounds__(TPB) void k_source_rates(MeshView m, const int* __r
 #pragma unroll
     for (int p = 0; p < E::nph; p++) if (phases & (1 << p)) sum += s.kr[p] * s.rho[p] / s.mu[p];
     if constexpr (!E::isothermal) {
+      if (m.src_pcomp[si] < E::np) {   // a production component np produces heat alone: no enthalpy is formed (source.F90:419-425)
 #pragma unroll
-      for (int p = 0; p < E::nph; p++)
-        if (phases & (1 << p)) h += (s.kr[p] * s.rho[p] / s.mu[p] / sum) * s.h[p];
+        for (int p = 0; p < E::nph; p++)
+          if (phases & (1 << p)) h += (s.kr[p] * s.rho[p] / s.mu[p] / sum) * s.h[p];
+      }
     }
   }
   out[si] = q;

@@ -95,8 +95,7 @@ __global__ __launch_bounds__(TPB) void k_tracer_assemble(MeshView m, const doubl
   // sources (tracer_source_iterator, flow_simulation.F90:1722-1772)
   for (int si = m.cell_src[c]; si >= 0; si = m.src_next[si]) {
     const double rate = source_rate<KIND>(own, m.src_ctl, si, m.src_rate[si], m.src_net);
-    const int comp = m.src_comp[si];
-    const int component = rate > 0.0 ? (comp <= 0 ? 1 : comp) : (comp <= 0 ? 0 : comp);
+    const int component = source_component(rate, m.src_comp[si], m.src_pcomp[si]);
     if (!(component < E::np)) continue;
     if (rate < 0.0) {
       const int ph = (int)own.phases;
@@ -232,8 +231,7 @@ __global__ __launch_bounds__(TPB) void k_tracer_assemble_all(MeshView m, const d
   // sources (tracer_source_iterator, flow_simulation.F90:1722-1772)
   for (int si = m.cell_src[c]; si >= 0; si = m.src_next[si]) {
     const double rate = source_rate<KIND>(own, m.src_ctl, si, m.src_rate[si], m.src_net);
-    const int comp = m.src_comp[si];
-    const int component = rate > 0.0 ? (comp <= 0 ? 1 : comp) : (comp <= 0 ? 0 : comp);
+    const int component = source_component(rate, m.src_comp[si], m.src_pcomp[si]);
     if (!(component < E::np)) continue;
     if (rate < 0.0) {
       const int ph = (int)own.phases;

@@ -82,6 +82,8 @@ struct EosParams {
   double temperature;     // eos_w
   double scale[9][4];     // primary_scale(var, region)  (eos_we.F90:104-109; eos_wse: regions 1..8); a zero partial-
                           // pressure scale selects adaptive scaling Pg/P (eos_wge.F90:639-674)
+  double t1_max;          // region 1's upper temperature bound, deg C: 350, or 360 under "thermodynamics.extrapolate"
+                          // (IAPWS.F90:449-482, IFC67.F90:228-248; wai_set_thermo_extrapolate)
   int rp_type, cp_type;
   double rp_par[6], cp_par[6];
   int thermo;             // "thermodynamics": THERMO_IAPWS (default) | THERMO_IFC67
@@ -91,12 +93,12 @@ struct EosParams {
 };
 
 // thermodynamic formulation dispatch (thermodynamics_type: src/thermodynamics.F90, IAPWS.F90,
-// IFC67.F90); `thermo` is uniform over a launch.  region 1 = liquid water, 2 = steam.
+// IFC67.F90); `thermo` and region 1's bound `t1_max` are uniform over a launch.  region 1 = liquid water, 2 = steam.
 enum { THERMO_IAPWS = 0, THERMO_IFC67 = 1 };
 namespace th {
-__device__ __forceinline__ int props(int thermo, int region, double p, double t, double& rho, double& u) {
-  if (thermo == THERMO_IFC67) return region == 1 ? ifc67::region1(p, t, rho, u) : ifc67::region2(p, t, rho, u);
-  return region == 1 ? if97::region1(p, t, rho, u) : if97::region2(p, t, rho, u);
+__device__ __forceinline__ int props(int thermo, double t1_max, int region, double p, double t, double& rho, double& u) {
+  if (thermo == THERMO_IFC67) return region == 1 ? ifc67::region1(p, t, t1_max, rho, u) : ifc67::region2(p, t, rho, u);
+  return region == 1 ? if97::region1(p, t, t1_max, rho, u) : if97::region2(p, t, rho, u);
 }
 __device__ __forceinline__ double viscosity(int thermo, int region, double t, double p, double rho) {
   return thermo == THERMO_IFC67 ? ifc67::viscosity(region, t, p, rho) : if97::viscosity(t, rho);
@@ -427,7 +429,7 @@ __device__ __forceinline__ int eos_eval(const EosParams& e, const double* y, int
     if (ph <= 0) return 1;
     s.phases = (double)ph;
     double rho, u;
-    const int err = th::props(e.thermo, region == 1 ? 1 : 2, s.P, s.T, rho, u);
+    const int err = th::props(e.thermo, e.t1_max, region == 1 ? 1 : 2, s.P, s.T, rho, u);
     if (err) return err;
     s.rho[0] = rho; s.u[0] = u; s.h[0] = u + s.P / rho;
     s.kr[0] = 1.0; s.pc[0] = 0.0;
@@ -480,11 +482,11 @@ __device__ __forceinline__ int eos_eval(const EosParams& e, const double* y, int
       if (ph & (1 << p)) {
         double rho, u, mu;
         const double bp = (p == 0 || !gas) ? s.P : pw;
-        const int err = (p == 0) ? salt::brine_properties(e.thermo, bp, s.T, xs, rho, u)
-                                 : th::props(e.thermo, 2, bp, s.T, rho, u);
+        const int err = (p == 0) ? salt::brine_properties(e.thermo, e.t1_max, bp, s.T, xs, rho, u)
+                                 : th::props(e.thermo, e.t1_max, 2, bp, s.T, rho, u);
         if (err) return err;
         const double xp = (p == 0) ? xs : 0.0;
-        if (p == 0) { if (salt::brine_viscosity(e.thermo, s.T, s.P, xs, mu)) return 1; }
+        if (p == 0) { if (salt::brine_viscosity(e.thermo, e.t1_max, s.T, s.P, xs, mu)) return 1; }
         else mu = th::viscosity(e.thermo, 2, s.T, s.P, rho);
         double xg = 0.0, grho = 0.0, esol = 0.0;
         if constexpr (gas) {
@@ -565,7 +567,7 @@ __device__ __forceinline__ int eos_eval(const EosParams& e, const double* y, int
       if (ph & (1 << p)) {
         const double wpres = (p == 0) ? s.P : Pw;
         double wrho, wu;
-        const int err = th::props(e.thermo, p == 0 ? 1 : 2, wpres, s.T, wrho, wu);
+        const int err = th::props(e.thermo, e.t1_max, p == 0 ? 1 : 2, wpres, s.T, wrho, wu);
         if (err) return err;
         const double grho = (p == 0) ? 0.0 : gas_rho;
         double xg, esol = 0.0;
@@ -627,7 +629,7 @@ __device__ __forceinline__ int eos_eval(const EosParams& e, const double* y, int
     for (int p = 0; p < E::nph; p++) {
       if (ph & (1 << p)) {
         double rho, u;
-        const int err = th::props(e.thermo, p == 0 ? 1 : 2, s.P, s.T, rho, u);
+        const int err = th::props(e.thermo, e.t1_max, p == 0 ? 1 : 2, s.P, s.T, rho, u);
         if (err) return err;
         s.rho[p] = rho; s.u[p] = u; s.h[p] = u + s.P / rho;
         s.kr[p] = (p == 0) ? kl : kv;
@@ -940,24 +942,30 @@ __device__ inline double source_rate(const CellState<KIND>& s, SrcCtl* ctl, int 
   return source_network_rate(net, si, rate);
 }
 
+// the component a source's flow goes to (source.F90:340-366): injection takes `comp` (default 1: water); production takes
+// the production component `pcomp` where one is set (wai_set_source_production_component), and `comp` as before where
+// none is (default 0: all mass components by their flow fractions).  np is heat alone
+__device__ __forceinline__ int source_component(double rate, int comp, int pcomp) {
+  if (rate > 0.0) return comp <= 0 ? 1 : comp;
+  return pcomp > 0 ? pcomp : (comp <= 0 ? 0 : comp);
+}
+
 // source term (source.F90:386-480, fluid.F90:377-453): flow[np] for one source
 template <int KIND>
 __device__ __forceinline__ void source_flow(const CellState<KIND>& s, double rate, double enth,
-                                            int comp, double* flow) {
+                                            int comp, int pcomp, double* flow) {
   using E = EosT<KIND>;
 #pragma unroll
   for (int k = 0; k < E::np; k++) flow[k] = 0.0;
   double h = 0.0;
-  int component;
+  const int component = source_component(rate, comp, pcomp);
   if (rate > 0.0) {
-    component = comp <= 0 ? 1 : comp;
     h = enth;
     if (component - 1 < E::np) {
 #pragma unroll
       for (int k = 0; k < E::np; k++) if (k == component - 1) flow[k] = rate;
     }
   } else {
-    component = comp <= 0 ? 0 : comp;
     const int phases = (int)s.phases;
     double frac[E::nph] = {}, sum = 0.0;
     if (component < E::np) {

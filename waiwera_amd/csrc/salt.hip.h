@@ -107,7 +107,7 @@ __device__ inline int halite_solubility_two_phase(int thermo, double p, double& 
 }
 
 // brine_properties :221-389: density and internal energy
-__device__ inline int brine_properties(int thermo, double p, double t, double xs, double& rho_out, double& u_out) {
+__device__ inline int brine_properties(int thermo, double t1_max, double p, double t, double xs, double& rho_out, double& u_out) {
   const double pbar = p / 1.0e5;
   const double f = 1.0 / (xs + (1.0 - xs) * SALT_MW / WATER_MW);
   const double xmol = xs * f, xmol1 = 1.0 - xmol, xmol12 = xmol1 * xmol1;
@@ -145,10 +145,10 @@ __device__ inline int brine_properties(int thermo, double p, double t, double xs
   if (err) return err;
   if (extrapolate) {                                      // eq. 17
     const double dt = 0.2;
-    err = th::props(thermo, 1, p, ts, rw, uw);
+    err = th::props(thermo, t1_max, 1, p, ts, rw, uw);
     if (err) return err;
     const double vws = 1.0e3 * WATER_MW / rw;
-    err = th::props(thermo, 1, p, ts - dt, rw, uw);
+    err = th::props(thermo, t1_max, 1, p, ts - dt, rw, uw);
     if (err) return err;
     const double vws1 = 1.0e3 * WATER_MW / rw;
     const double dvdt = (vws - vws1) / dt, logp = log(pbar);
@@ -159,7 +159,7 @@ __device__ inline int brine_properties(int thermo, double p, double t, double xs
     const double cv[4] = {o0, o1, 0.0, o2};
     rho = 1.0e3 * bmw / poly(cv, tstar_v);
   } else {
-    err = th::props(thermo, 1, p, tstar_v, rw, uw);
+    err = th::props(thermo, t1_max, 1, p, tstar_v, rw, uw);
     if (err) return err;
     rho = rw * bmw / WATER_MW;
   }
@@ -175,7 +175,7 @@ __device__ inline int brine_properties(int thermo, double p, double t, double xs
   const double q23 = q2x1 - q20 - q21 * sqrt(1.0 + q22);
   const double q1 = q10 + q11 * xmol1 + q12 * xmol12;
   const double q2 = q20 + q21 * sqrt(xmol + q22) + q23 * xmol;
-  err = th::props(thermo, 1, p, q1 + q2 * t, rw, uw);
+  err = th::props(thermo, t1_max, 1, p, q1 + q2 * t, rw, uw);
   if (err) return err;
   rho_out = rho;
   u_out = (uw + p / rw) - p / rho;
@@ -183,12 +183,12 @@ __device__ inline int brine_properties(int thermo, double p, double t, double xs
 }
 
 // brine_viscosity :393-423
-__device__ inline int brine_viscosity(int thermo, double t, double p, double xs, double& mu) {
+__device__ inline int brine_viscosity(int thermo, double t1_max, double t, double p, double xs, double& mu) {
   const double cv[4] = {1.0, 0.0816, 0.0122, 1.28e-4};
   const double smol = mole_fraction(xs);
   const double factor = poly(cv, smol) + 6.29e-4 * t * (1.0 - exp(-0.7 * smol));
   double rw, uw;
-  const int err = th::props(thermo, 1, p, t, rw, uw);
+  const int err = th::props(thermo, t1_max, 1, p, t, rw, uw);
   if (err) return err;
   mu = factor * th::viscosity(thermo, 1, t, p, rw);
   return 0;

@@ -24,7 +24,7 @@ int wai_set_sources(wai_ctx* c, int n, const int* cell, const double* rate, cons
     vc[i] = cell[i]; vk[i] = component ? component[i] : 0; vr[i] = rate[i]; ve[i] = enthalpy ? enthalpy[i] : 0.0;
   }
   HIPCHK(c, hipMemcpy(c->mesh.cell_src, head.data(), N * sizeof(int), hipMemcpyHostToDevice));
-  if (s.cell.upload(c, vc) || s.comp.upload(c, vk) || s.next.upload(c, next) || s.rate.upload(c, vr) || s.enth.upload(c, ve)) return -1;
+  if (s.cell.upload(c, vc) || s.comp.upload(c, vk) || s.pcomp.upload(c, std::vector<int>(std::max(n, 1), 0)) || s.next.upload(c, next) || s.rate.upload(c, vr) || s.enth.upload(c, ve)) return -1;
   const bool coupling = c->net.coupling, cp_in_pc = c->net.cp_in_pc;
   c->net = Network();   // a network refers to sources by index: set it again after the sources
   c->net.h_enth0 = ve;
@@ -51,6 +51,22 @@ int wai_update_sources(wai_ctx* c, const double* rate, const double* enthalpy) {
     }
     nw.flat_dirty = true;   // the device pass' copy of the specified enthalpies
   }
+  return 0;
+}
+
+// production components beside wai_set_sources' `component` (source.F90:340-366, 403-453): a producing source with c > 0
+// puts its whole rate into component c -- c = np: heat alone, and no enthalpy is formed -- instead of `component`'s
+int wai_set_source_production_component(wai_ctx* c, const int* component) {
+  if (!c) return -2;
+  Sources& s = c->src;
+  std::vector<int> v(std::max(s.n, 1), 0);
+  for (int i = 0; i < s.n && component; i++) {
+    if (component[i] > c->np) { c->err = "production component above the number of primary variables"; return -2; }
+    v[i] = std::max(component[i], 0);
+  }
+  if (!s.pcomp) return component && s.n ? (c->err = "production components: wai_set_sources first", -2) : 0;
+  HIPCHK(c, hipMemcpyAsync(s.pcomp, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 

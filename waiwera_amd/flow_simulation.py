@@ -18,7 +18,7 @@ from .lib import LIB, WaiError
 class FlowSimulation:
     def __init__(self, mesh, eos="we", opts=None, device=0, temperature=20.0,
                  relperm=("linear", [0.0, 1.0, 0.0, 1.0]), capillary=("zero", []), thermo="iapws",
-                 permeability_modifier=None):
+                 permeability_modifier=None, thermo_extrapolate=False):
         self.mesh = mesh
         self.eos_name = eos
         self._keep = dict(
@@ -52,6 +52,8 @@ class FlowSimulation:
                     xy = _lib._f64(spec[1].get(key, default))
                     self._chk(LIB.wai_set_curve_table(h, which, _lib.INTERP[spec[1].get("interpolation", "linear")],
                                                       len(xy), xy.ctypes.data_as(_lib.pd)), "set_curve_table")
+        if thermo_extrapolate:      # before the boundary fluid is evaluated, like the curve tables
+            self.set_thermo_extrapolate(True)
         self.num_primary_variables = LIB.wai_block_size(h)
         self.fluid_dof = LIB.wai_num_fluid_dof(h)
         self.n_owned, self.n_prim, self.n_local = mesh.n_owned, mesh.n_prim, mesh.n_local
@@ -74,6 +76,30 @@ class FlowSimulation:
             si, rp = _lib._i32(mesh.send_idx), _lib._i32(mesh.recv_ptr)
             self._chk(LIB.wai_set_halo(h, nr.size, nr.ctypes.data_as(_lib.pi), sp.ctypes.data_as(_lib.pi),
                                        si.ctypes.data_as(_lib.pi), rp.ctypes.data_as(_lib.pi)), "set_halo")
+
+    def set_thermo_extrapolate(self, on):
+        """"thermodynamics.extrapolate" (wai_set_thermo_extrapolate): region 1 (liquid water) is evaluated up to 360 deg C
+        instead of 350, the formulas as they are.  The boundary cells' fluid is evaluated when the object is made: a mesh
+        with boundary cells hotter than 350 deg C needs the constructor's thermo_extrapolate=True"""
+        self._chk(LIB.wai_set_thermo_extrapolate(self.h, 1 if on else 0), "set_thermo_extrapolate")
+
+    def thermo_extrapolate(self):
+        on = C.c_int(0)
+        self._chk(LIB.wai_get_thermo_extrapolate(self.h, C.byref(on)), "thermo_extrapolate")
+        return bool(on.value)
+
+    def set_source_production_component(self, components):
+        """"source.production_component" (wai_set_source_production_component), one integer per source or None: a
+        producing source with c > 0 puts its whole rate into component c (c = the number of primary variables: heat alone,
+        no enthalpy formed); c <= 0 keeps production on the source's `component` as before"""
+        if components is None:
+            self._chk(LIB.wai_set_source_production_component(self.h, None), "set_source_production_component")
+            return
+        pc = _lib._i32(components)
+        if pc.size != self.mesh.n_src:
+            raise ValueError("one production component per source")
+        self._chk(LIB.wai_set_source_production_component(self.h, pc.ctypes.data_as(_lib.pi) if pc.size else None),
+                  "set_source_production_component")
 
     def update_rock(self, field, cells, values):
         """rock controls: one field of the rock record (0..2 permeability, 3 wet, 4 dry conductivity, 5 porosity,

@@ -380,6 +380,25 @@ module waiwera_hip_module
        integer(c_int), value :: which, interpolation, n
        real(c_double), intent(in) :: xy(*)
      end function wai_set_curve_table
+     ! "thermodynamics.extrapolate" (thermodynamics_setup.F90:57-89): region 1 up to 360 instead of 350 deg C; before wai_set_bc
+     integer(c_int) function wai_set_thermo_extrapolate(ctx, on) bind(c, name = "wai_set_thermo_extrapolate")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: on
+     end function wai_set_thermo_extrapolate
+     integer(c_int) function wai_get_thermo_extrapolate(ctx, on) bind(c, name = "wai_get_thermo_extrapolate")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: on
+     end function wai_get_thermo_extrapolate
+     ! "source.production_component" (source.F90:340-366, 403-453): one per source after wai_set_sources; c_null_ptr through
+     ! an absent actual argument is not possible here: pass zeros for none
+     integer(c_int) function wai_set_source_production_component(ctx, component) &
+          bind(c, name = "wai_set_source_production_component")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(in) :: component(*)
+     end function wai_set_source_production_component
      integer(c_int) function wai_block_size(ctx) bind(c, name = "wai_block_size")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -658,6 +677,7 @@ module waiwera_hip_module
   public :: wai_set_pc_tiles, wai_set_pc_ordering, wai_get_pc_ordering
   public :: wai_set_network_pass, wai_get_network_pass
   public :: wai_set_coupling_build, wai_get_coupling_build
+  public :: wai_set_thermo_extrapolate, wai_get_thermo_extrapolate, wai_set_source_production_component
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
   public :: wai_gather_rows, wai_gather_fluid, wai_cell_order

@@ -206,6 +206,9 @@ def _load():
         "wai_test_network_stats": (i32, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "wai_test_network_lds": (i32, [vp, pi, pi]),
         "wai_set_coupling_build": (i32, [vp, i32]),
+        "wai_set_thermo_extrapolate": (i32, [vp, i32]),
+        "wai_get_thermo_extrapolate": (i32, [vp, pi]),
+        "wai_set_source_production_component": (i32, [vp, pi]),
         "wai_get_coupling_build": (i32, [vp, pi, pi]),
         "wai_test_coupling_build_stats": (i32, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "wai_set_aux_pc": (i32, [vp, i32, i32, i32, i32]),

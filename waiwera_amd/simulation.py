@@ -6,10 +6,11 @@ Input keys handled, with the reference's defaults (src/flow_simulation.F90:296-6
 src/mesh.F90:270-300, 1640-1800; src/rock_setup.F90; src/initial.F90:421-677; src/source_setup.F90;
 src/timestepper.F90:1960-2275; src/tracer.F90:63-140; utils/input_schema.json):
 
-  mesh        filename (gmsh MSH 2.2), thickness, radial, zones (all / box ranges on x, y, z)
+  mesh        filename (gmsh MSH 2.2), thickness, radial, zones (all / box ranges on x, y, z), permeability_angle,
+              faces [cells, permeability_direction]
   gravity     number | vector | null
   eos         name w | we | wce | wae | wse | wsce | wsae, temperature, permeability_modifier
-  thermodynamics  iapws | ifc67
+  thermodynamics  iapws | ifc67, or {name, extrapolate}
   rock        types [cells | zones, permeability, porosity, density, specific_heat, wet / dry
               conductivity], relative_permeability, capillary_pressure
   initial     primary (one record or one per cell), region (one or per cell), tracer; or
@@ -18,7 +19,8 @@ src/timestepper.F90:1960-2275; src/tracer.F90:63-140; utils/input_schema.json):
   mesh        filename (gmsh 2.2 ASCII; or mesh_file=: a MULgraph geometry file), thickness, radial,
               zones (boxes, cell lists), minc {geometry, rock {fracture, matrix, zones | types}}
   source      cell, rate, enthalpy, tracer (constants or [[t, v], ...] tables with "interpolation":
-              linear|step and "averaging": integrate|endpoint), component, deliverability {productivity,
+              linear|step and "averaging": integrate|endpoint), component, production_component (integers or the
+              component's name; "energy": the heat equation), deliverability {productivity,
               pressure}, recharge | injectivity {coefficient, pressure}, limiter {type, limit,
               separator_pressure}, separator {pressure}, direction, factor
   time        start, stop, step {size, adapt, maximum, method, solver.nonlinear, solver.linear, solver.auxiliary}
@@ -27,8 +29,13 @@ src/timestepper.F90:1960-2275; src/tracer.F90:63-140; utils/input_schema.json):
   output      filename, initial, final, frequency, checkpoint {time, tolerance} (cell fields, source
               rate and enthalpy)
 
-Anything else that changes results (deliverability thresholds, ...) raises
-NotImplementedError instead of being ignored.
+Every key of the reference's schema stands in KEY_TABLE below as handled, without effect on the numbers (title, logfile.*,
+output.flush, mesh.rebalance) or refused with the reason (REFUSED_KEYS: eos.primary.scale.*, initial.minc, zones made of other
+zones or by radius, mesh.minc.rock.cells, output.checkpoint.step, output.jacobian, source.cells / zones, source.rate.time /
+enthalpy.time, reference pressure against enthalpy under recharge / injectivity, source.tracer.<name>,
+time.step.solver.nonlinear.jacobian.differencing.* and tolerance.update.*, time.step.stop.size.*).  check_input_keys walks
+the input before anything is read or built and raises NotImplementedError with the full path for a refused key and for a key
+the schema does not have; values a handled key can carry but this front end does not cover are refused where they are read.
 
 Sub-preconditioner "lu" ("preconditioner": {"sub": {"preconditioner": {"type": "lu"}}}) under bjacobi or asm has two
 mappings.  The default (sub_lu="host") takes the library's pc_type "lu": dense block inverses formed on the host, block
@@ -89,6 +96,200 @@ def _get(d, path, default=None):
             return default
         d = d[k]
     return d
+
+
+# ---- every key of an input file: honoured, without effect on the numbers, or refused by name ---------------------------
+# One entry per key path of the reference's schema (utils/input_schema.json; tests/golden/input_schema_paths.txt lists them).
+# Normal form of a path: keys joined by dots, an array's elements under the array's own path (source[2].rate and a single
+# tracer object's tracer.name alike: "source.rate", "tracer.name"), "*" for a name the user chooses (zones, tracers).
+# HANDLED: read by this front end (which may still refuse a VALUE it does not cover, by name, where it reads it).
+# NO_EFFECT: changes no computed number -- titles, the log, flushing, load balancing.
+# REFUSED: would change the results or the files written and nothing here reads it.
+HANDLED_KEYS = """
+boundaries boundaries.faces boundaries.faces.cells boundaries.faces.normal boundaries.primary boundaries.region boundaries.tracer
+eos eos.name eos.temperature eos.permeability_modifier eos.permeability_modifier.exponent eos.permeability_modifier.gamma
+eos.permeability_modifier.phir eos.permeability_modifier.type eos.primary eos.primary.scale
+gravity initial initial.filename initial.index initial.primary initial.region initial.tracer
+mesh mesh.filename mesh.radial mesh.thickness mesh.permeability_angle mesh.faces mesh.faces.cells mesh.faces.permeability_direction
+mesh.zones mesh.zones.* mesh.zones.*.cells mesh.zones.*.type mesh.zones.*.x mesh.zones.*.y mesh.zones.*.z
+mesh.minc mesh.minc.geometry mesh.minc.geometry.fracture mesh.minc.geometry.fracture.connection
+mesh.minc.geometry.fracture.planes mesh.minc.geometry.fracture.spacing mesh.minc.geometry.fracture.volume
+mesh.minc.geometry.matrix mesh.minc.geometry.matrix.volume mesh.minc.rock mesh.minc.rock.fracture mesh.minc.rock.fracture.type
+mesh.minc.rock.matrix mesh.minc.rock.matrix.type mesh.minc.rock.types mesh.minc.rock.zones
+network network.group network.group.in network.group.limiter network.group.limiter.averaging
+network.group.limiter.interpolation network.group.limiter.limit network.group.limiter.steam network.group.limiter.total
+network.group.limiter.type network.group.limiter.water network.group.name network.group.scaling network.group.separator
+network.group.separator.pressure network.reinject network.reinject.in network.reinject.name network.reinject.overflow
+network.reinject.overflow.out network.reinject.steam network.reinject.steam.averaging network.reinject.steam.enthalpy
+network.reinject.steam.interpolation network.reinject.steam.out network.reinject.steam.proportion network.reinject.steam.rate
+network.reinject.water network.reinject.water.averaging network.reinject.water.enthalpy network.reinject.water.interpolation
+network.reinject.water.out network.reinject.water.proportion network.reinject.water.rate
+output output.checkpoint output.checkpoint.repeat output.checkpoint.time output.checkpoint.tolerance output.fields
+output.fields.cell_geometry output.fields.face_geometry output.fields.fluid output.fields.flux output.fields.network_group
+output.fields.network_reinject output.fields.source output.filename output.final output.frequency output.initial
+rock rock.capillary_pressure rock.capillary_pressure.P0 rock.capillary_pressure.Pmax rock.capillary_pressure.interpolation
+rock.capillary_pressure.lambda rock.capillary_pressure.pressure rock.capillary_pressure.saturation_limits
+rock.capillary_pressure.slr rock.capillary_pressure.sls rock.capillary_pressure.type rock.relative_permeability
+rock.relative_permeability.interpolation rock.relative_permeability.lambda rock.relative_permeability.liquid
+rock.relative_permeability.power rock.relative_permeability.slr rock.relative_permeability.sls rock.relative_permeability.ssr
+rock.relative_permeability.sum_unity rock.relative_permeability.type rock.relative_permeability.vapour
+rock.types rock.types.cells rock.types.density rock.types.dry_conductivity rock.types.interpolation rock.types.name
+rock.types.permeability rock.types.porosity rock.types.specific_heat rock.types.wet_conductivity rock.types.zones
+source source.averaging source.cell source.component source.production_component source.deliverability
+source.deliverability.pressure source.deliverability.pressure.enthalpy source.deliverability.pressure.pressure
+source.deliverability.pressure.time source.deliverability.productivity source.deliverability.productivity.time
+source.deliverability.threshold source.direction source.enthalpy source.factor source.factor.averaging
+source.factor.interpolation source.factor.time source.injectivity source.injectivity.coefficient
+source.injectivity.coefficient.time source.injectivity.pressure source.injectivity.pressure.time source.interpolation
+source.limiter source.limiter.averaging source.limiter.interpolation source.limiter.limit source.limiter.separator_pressure
+source.limiter.steam source.limiter.total source.limiter.type source.limiter.water source.name source.rate source.recharge
+source.recharge.coefficient source.recharge.coefficient.time source.recharge.pressure source.recharge.pressure.time
+source.separator source.separator.pressure source.tracer
+thermodynamics thermodynamics.name thermodynamics.extrapolate
+time time.start time.stop time.step time.step.adapt time.step.adapt.amplification time.step.adapt.maximum
+time.step.adapt.method time.step.adapt.minimum time.step.adapt.on time.step.adapt.reduction time.step.maximum
+time.step.maximum.number time.step.maximum.size time.step.maximum.tries time.step.method time.step.size time.step.solver
+time.step.solver.auxiliary time.step.solver.auxiliary.maximum time.step.solver.auxiliary.maximum.iterations
+time.step.solver.auxiliary.options time.step.solver.auxiliary.options.gmres time.step.solver.auxiliary.options.gmres.restart
+time.step.solver.auxiliary.preconditioner time.step.solver.auxiliary.preconditioner.sub
+time.step.solver.auxiliary.preconditioner.sub.preconditioner time.step.solver.auxiliary.preconditioner.sub.preconditioner.factor
+time.step.solver.auxiliary.preconditioner.sub.preconditioner.factor.levels
+time.step.solver.auxiliary.preconditioner.sub.preconditioner.type time.step.solver.auxiliary.preconditioner.type
+time.step.solver.auxiliary.tolerance time.step.solver.auxiliary.tolerance.relative time.step.solver.auxiliary.type
+time.step.solver.linear time.step.solver.linear.maximum time.step.solver.linear.maximum.iterations
+time.step.solver.linear.options time.step.solver.linear.options.gmres time.step.solver.linear.options.gmres.restart
+time.step.solver.linear.preconditioner time.step.solver.linear.preconditioner.sub
+time.step.solver.linear.preconditioner.sub.preconditioner time.step.solver.linear.preconditioner.sub.preconditioner.factor
+time.step.solver.linear.preconditioner.sub.preconditioner.factor.levels
+time.step.solver.linear.preconditioner.sub.preconditioner.type time.step.solver.linear.preconditioner.type
+time.step.solver.linear.tolerance time.step.solver.linear.tolerance.relative time.step.solver.linear.type
+time.step.solver.nonlinear time.step.solver.nonlinear.maximum time.step.solver.nonlinear.maximum.iterations
+time.step.solver.nonlinear.minimum time.step.solver.nonlinear.minimum.iterations time.step.solver.nonlinear.tolerance
+time.step.solver.nonlinear.tolerance.function time.step.solver.nonlinear.tolerance.function.absolute
+time.step.solver.nonlinear.tolerance.function.relative
+tracer tracer.activation tracer.decay tracer.diffusion tracer.name tracer.phase
+"""
+NO_EFFECT_KEYS = """
+title logfile logfile.echo logfile.filename logfile.format logfile.format.max_num_length logfile.format.num_real_digits
+output.flush mesh.rebalance
+"""
+# why each is refused, for the message
+REFUSED_KEYS = {
+    "eos.primary.scale.pressure": "the library's pressure scale stays 1e6 (another scaling, another Newton path)",
+    "eos.primary.scale.temperature": "the library's temperature scale stays 100 (another scaling, another Newton path)",
+    "eos.primary.scale.partial_pressure": "the gas partial pressure keeps its adaptive scaling",
+    "initial.minc": "whether the initial conditions hold the MINC cells is read off their size",
+    "mesh.minc.additionalProperties": "the schema lists it; the reference reads no such key",
+    "mesh.minc.rock.cells": "MINC zones are given by rock types or zones",
+    "mesh.zones.*.*": "zones made of other zones", "mesh.zones.*.+": "zones made of other zones",
+    "mesh.zones.*.-": "zones made of other zones", "mesh.zones.*.r": "zones by radius",
+    "output.checkpoint.step": "output checkpoints by step size",
+    "output.jacobian": "no Jacobian file is written", "output.jacobian.filename": "no Jacobian file is written",
+    "source.cells": "sources given by cell lists", "source.zones": "sources given by zones",
+    "source.rate.time": "source rate given as an object", "source.enthalpy.time": "source enthalpy given as an object",
+    "source.injectivity.pressure.enthalpy": "injectivity reference pressure against enthalpy",
+    "source.recharge.pressure.enthalpy": "recharge reference pressure against enthalpy",
+    "source.tracer.*": "tracer injection rates given by tracer name",
+    "time.step.solver.nonlinear.jacobian": "finite-difference increments of the Jacobian",
+    "time.step.solver.nonlinear.jacobian.differencing": "finite-difference increments of the Jacobian",
+    "time.step.solver.nonlinear.jacobian.differencing.increment": "finite-difference increments of the Jacobian",
+    "time.step.solver.nonlinear.jacobian.differencing.tolerance": "finite-difference increments of the Jacobian",
+    "time.step.solver.nonlinear.tolerance.update": "convergence on the size of the Newton update",
+    "time.step.solver.nonlinear.tolerance.update.absolute": "convergence on the size of the Newton update",
+    "time.step.solver.nonlinear.tolerance.update.relative": "convergence on the size of the Newton update",
+    "time.step.stop": "stopping on the step size", "time.step.stop.size": "stopping on the step size",
+    "time.step.stop.size.maximum": "stopping on the step size", "time.step.stop.size.minimum": "stopping on the step size",
+}
+KEY_TABLE = dict({k: "handled" for k in HANDLED_KEYS.split()}, **{k: "no effect" for k in NO_EFFECT_KEYS.split()})
+KEY_TABLE.update({k: "refused" for k in REFUSED_KEYS})
+
+
+def schema_path(path):
+    """a key path as the schema's walk writes it ("source[].rate", "boundaries[].faces[].cells") in KEY_TABLE's normal form"""
+    return path.replace("[]", "")
+
+
+def check_input_keys(inp):
+    """walks an input and raises NotImplementedError, naming the full path, for the first key that is refused or that
+    KEY_TABLE does not hold (no key of the reference's schema: nothing would read it).  A key whose value is null counts
+    as absent, as everywhere here.  Pure: the input alone, so before any library and the same on every rank."""
+    def walk(node, shown, norm):
+        if isinstance(node, dict):
+            for k, v in node.items():
+                if v is None:
+                    continue
+                p = norm + "." + k if norm else k
+                if p not in KEY_TABLE and norm + ".*" in KEY_TABLE:
+                    p = norm + ".*"
+                s = shown + "." + k if shown else k
+                kind = KEY_TABLE.get(p)
+                if kind is None:
+                    raise NotImplementedError("input key %s (%s) is no key of the reference's input schema: nothing reads it" % (s, p))
+                if kind == "refused":
+                    raise NotImplementedError("input key %s (%s) is not supported: %s" % (s, p, REFUSED_KEYS[p]))
+                walk(v, s, p)
+        elif isinstance(node, (list, tuple)):
+            for i, v in enumerate(node):
+                walk(v, "%s[%d]" % (shown, i), norm)
+    walk(inp, "", "")
+
+
+def component_index(name, eos, key="component"):
+    """"component" / "production_component" of a source as the reference's get_component takes it (src/source_setup.F90:2030-
+    2049, eos_component_index, src/eos.F90:261-281): an integer, or a name -- "water", the EOS's second and third mass
+    components by name ("gas" for the non-condensible gas whichever it is), "energy" for the last, heat, equation"""
+    if isinstance(name, (int, np.integer)) and not isinstance(name, bool):
+        return int(name)
+    names = {"w": ["water"], "we": ["water"], "wce": ["water", "co2"], "wae": ["water", "air"], "wse": ["water", "salt"],
+             "wsce": ["water", "salt", "co2"], "wsae": ["water", "salt", "air"]}[eos]
+    low = str(name).strip().lower()
+    if low == "energy" and eos != "w":
+        return len(names) + 1
+    if low == "gas" and names[-1] in ("co2", "air"):
+        return len(names)
+    if low in names:
+        return names.index(low) + 1
+    raise ValueError("source %s %r: eos %s has the components %s%s" % (key, name, eos, names, "" if eos == "w" else " and energy"))
+
+
+def production_components(inp, eos):
+    """"source[].production_component" of every source as integers (0: none named, production follows "component" as
+    before), and what the key does not combine with here refused by name, from the input alone.  In the reference a
+    production component only chooses where the produced rate goes (source.F90:403-453): deliverability, recharge, a limiter on
+    the total flow, direction and factor set the RATE and combine with it as they are.  A separator, a limiter on separated
+    water or steam and a source network separate or pass on the flow by its enthalpy, which a heat-only source does not
+    form: not built, refused."""
+    sources = inp.get("source", []) or []
+    net = inp.get("network") or {}
+    members = set()
+    for g in net.get("group") or []:
+        members.update(g.get("in") or [])
+    for r in net.get("reinject") or []:
+        members.add(r.get("in"))
+        for key in ("water", "steam"):
+            members.update(o.get("out") for o in r.get(key) or [])
+        over = r.get("overflow")
+        members.add(over.get("out") if isinstance(over, dict) else over)
+    np_ = {"w": 1, "we": 2, "wce": 3, "wse": 3, "wae": 3, "wsce": 4, "wsae": 4}[eos]
+    out = []
+    for i, s in enumerate(sources):
+        if s.get("production_component") is None:
+            out.append(0)
+            continue
+        c = component_index(s["production_component"], eos, "production_component")
+        if c > np_:
+            raise ValueError("source[%d].production_component %r: eos %s has %d equations" % (i, s["production_component"], eos, np_))
+        lim = s.get("limiter") or {}
+        met = ("source[%d].separator" % i if s.get("separator") not in (None, False)
+               else "source[%d].limiter on separated %s" % (i, lim.get("type") if lim.get("type") in ("water", "steam") else
+                                                             "water" if "water" in lim else "steam")
+               if (lim.get("type") in ("water", "steam") or "water" in lim or "steam" in lim or "separator_pressure" in lim)
+               else "membership of the source network (network.group / network.reinject)" if s.get("name") is not None and s["name"] in members
+               else None)
+        if c > 0 and met:
+            raise NotImplementedError("source[%d].production_component together with %s" % (i, met))
+        out.append(max(c, 0))
+    return out
 
 
 # the reference's defaults of the auxiliary (tracer) solver where its "auxiliary" object leaves a key out
@@ -418,8 +619,8 @@ def _face_places(input_faces, faces, perm, n):
 
 def renumber_input(inp, perm, inv):
     """a copy of the input with every cell number it carries put through inv (inv[old] = new) and every per-cell array
-    listed in the new order (perm[new] = old): boundaries[].faces.cells, source[].cell, rock.types[].cells, zones given as
-    cell lists, per-cell initial.primary / region / tracer.  Pure."""
+    listed in the new order (perm[new] = old): boundaries[].faces.cells, source[].cell, rock.types[].cells, mesh.faces[].cells,
+    zones given as cell lists, per-cell initial.primary / region / tracer.  Pure."""
     import copy
     out = copy.deepcopy(inp)
     n = len(perm)
@@ -439,6 +640,9 @@ def renumber_input(inp, perm, inv):
     for z in ((mesh.get("zones") or {}) if isinstance(mesh, dict) else {}).values():
         if isinstance(z, dict) and z.get("cells") is not None:
             z["cells"] = renum(z["cells"])
+    for f in ((mesh.get("faces") or []) if isinstance(mesh, dict) else []):
+        if f.get("cells") is not None:
+            f["cells"] = renum(f["cells"])
     init = out.get("initial") or {}
     for key, rank in (("primary", 2), ("region", 1), ("tracer", 2)):
         v = init.get(key)
@@ -461,6 +665,9 @@ class Simulation:
         what DMPlexDistribute (src/mesh.F90:143-171) does for the reference.  What N ranks cover: the module docstring
         (fields() returns the rank's cells, self.owned_gid their index in the one-rank output's numbering)."""
         self.rank, self.world = int(rank), int(world)
+        # every key of the input is honoured, without effect or refused by name (KEY_TABLE): before anything is read, built
+        # or handed to the library, and from the input alone, so on every rank alike
+        check_input_keys(inp)
         # tracer_solve: "per_tracer" (one scalar solve per tracer) or "coupled" (all tracers in one Krylov solve, as the
         # reference; needs the bjacobi or no preconditioner).  Not a key of the input file: the reference has none
         if tracer_solve not in ("per_tracer", "coupled"):
@@ -576,6 +783,8 @@ class Simulation:
                 raise NotImplementedError("permeability modifier %r" % pm["type"])
         th = inp.get("thermodynamics", "iapws")
         self.thermo = (th.get("name", "iapws") if isinstance(th, dict) else th).lower()
+        # "thermodynamics.extrapolate" (thermodynamics_setup.F90:57-89): region 1 up to 360 deg C; a bare name leaves it off
+        self.thermo_extrapolate = bool(th.get("extrapolate", False)) if isinstance(th, dict) else False
         if self.eos not in ("w", "we", "wce", "wse", "wae", "wsce", "wsae") or self.thermo not in ("iapws", "ifc67"):
             raise NotImplementedError("eos %r / thermodynamics %r" % (self.eos, self.thermo))
         # geometry first without rock (centroids are needed for zones), rock filled in below
@@ -585,6 +794,7 @@ class Simulation:
             for f in (faces if isinstance(faces, list) else [faces]):
                 bnds.append((list(f["cells"]), list(f.get("normal", [0.0, 0.0, 1.0])), b["primary"], b.get("region", 1)))
         srcs, self._tables = [], []
+        self._production_components = production_components(inp, self.eos)
         for s in inp.get("source", []) or []:
             bad = [k for k in UNSUPPORTED_SOURCE_KEYS if k in s]
             if bad:
@@ -604,7 +814,7 @@ class Simulation:
                     v = float(tab.interpolate(_get(inp, "time.start", 0.0))[0])
                 vals[key] = v
             srcs.append(dict(cell=s["cell"], rate=vals["rate"], enthalpy=vals["enthalpy"],
-                             component=s.get("component", 0)))
+                             component=component_index(s.get("component", 0), self.eos)))
         minc_in = (mesh or {}).get("minc")
         minc_in = [] if minc_in is None else (minc_in if isinstance(minc_in, list) else [minc_in])
         # matrix cells join their fracture cell's preconditioner subdomain (<= 1024 rows each)
@@ -614,7 +824,9 @@ class Simulation:
             def build(cells, bnds, srcs, **kw):
                 return unstructured.build_mesh(nodes, cells, dim, thickness=mesh.get("thickness", 1.0),
                                                radial=bool(mesh.get("radial", False)), gravity=grav, boundaries=bnds,
-                                               sources=srcs, chunk=chunk, **kw)
+                                               sources=srcs, chunk=chunk, permeability_angle=float(mesh.get("permeability_angle") or 0.0),
+                                               face_directions=[(int(f["cells"][0]), int(f["cells"][1]), f.get("permeability_direction", 1))
+                                                                for f in mesh.get("faces") or [] if len(f.get("cells") or []) == 2], **kw)
             if self.cell_order == "input":
                 lm = build(cells, bnds, srcs)
             else:
@@ -642,6 +854,10 @@ class Simulation:
                                                          _cut_share(interior, first.sub_ptr),
                                                          _cut_share(faces[: lm.n_faces - lm.n_bc], lm.sub_ptr))
         else:
+            # (a mesh_builder makes its own face records: the two keys that change them cannot be honoured through it)
+            for key in ("permeability_angle", "faces"):
+                if (mesh or {}).get(key):
+                    raise NotImplementedError("mesh.%s together with a mesh_builder" % key)
             lm = mesh_builder(bnds, srcs)
         cen = lm.cell_geom[:n, :3]
         rock = inp.get("rock", {}) or {}
@@ -817,7 +1033,11 @@ class Simulation:
             from .flow_simulation import FlowSimulation
             self.ode = FlowSimulation(lm, eos=self.eos, device=device, temperature=temperature,
                                       relperm=self.relperm, capillary=self.capillary, thermo=self.thermo,
-                                      permeability_modifier=self.permeability_modifier)
+                                      permeability_modifier=self.permeability_modifier, thermo_extrapolate=self.thermo_extrapolate)
+        elif self.thermo_extrapolate:
+            # (an ode_factory evaluates the boundary fluid when it makes the object: the bound has to be part of that call)
+            self.ode = ode_factory(lm, self.eos, self.thermo, self.relperm, self.capillary, temperature,
+                                   permeability_modifier=self.permeability_modifier, thermo_extrapolate=True)
         elif self.permeability_modifier is not None:
             self.ode = ode_factory(lm, self.eos, self.thermo, self.relperm, self.capillary, temperature,
                                    permeability_modifier=self.permeability_modifier)
@@ -826,6 +1046,9 @@ class Simulation:
         if tiles is not None:
             self.ode.set_pc_tiles(tiles)
         self.ode.set_regions(region)
+        if any(self._production_components):      # the rank's own sources, in the rank's order (like owned_source below)
+            pc = self._production_components
+            self.ode.set_source_production_component(pc if self._src_pick is None else [pc[i] for i in self._src_pick])
         if self.world > 1:
             if comm_id is None:
                 raise ValueError("several ranks need the communicator id of rank 0 (waiwera_amd.lib.comm_unique_id)")

@@ -75,15 +75,32 @@ def _canonical_ring(ring):
     return ring if ring[1] < ring[-1] else [ring[0]] + ring[:0:-1]
 
 
+def permeability_direction(normal, dim, angle=0.0):
+    """the permeability axis (1..3) a face's flow goes along: the coordinate axis most closely aligned with the normal once
+    the horizontal axes are turned by "mesh.permeability_angle" degrees anti-clockwise from x
+    (face_calculate_permeability_direction, src/face.F90:210-226; mesh_set_permeability_rotation, src/mesh.F90:316-336:
+    d = R n with R = [[c, s], [-s, c]]; the first of equal components wins, as maxloc does).  Angle 0 reads the bare normal"""
+    d = np.array(normal[:dim], dtype=np.float64)
+    if angle:
+        a = np.deg2rad(float(angle))
+        c, s = np.cos(a), np.sin(a)
+        d[0], d[1] = c * normal[0] + s * normal[1], -s * normal[0] + c * normal[1]
+    return int(np.argmax(np.abs(d))) + 1
+
+
 def build_mesh(nodes, cells, dim, thickness=1.0, radial=False, gravity=None, boundaries=(), rock=None,
-               sources=None, chunk=512, canonical_faces=False):
+               sources=None, chunk=512, canonical_faces=False, permeability_angle=0.0, face_directions=()):
     """boundaries: [(cells, normal, primary, region)]; rock: (8,) or (ncells, 8); sources:
     [{cell, rate, enthalpy, component}].  Returns a LocalMesh (single rank, natural cell order,
     preconditioner subdomains = chunks of consecutive cells).
     A face's area and centroid are summed over its nodes as the first cell that names it lists them, so they -- and the
     cell centroids -- depend in the last bit on the order of the cells; canonical_faces=True sums over _canonical_ring
     instead: the geometry of a cell is then the same bits wherever the file lists it (what the compact cell order is
-    computed from, waiwera_amd/simulation.py)."""
+    computed from, waiwera_amd/simulation.py).
+    permeability_angle: "mesh.permeability_angle" in degrees (permeability_direction).  face_directions: "mesh.faces" as
+    [(cell, cell, direction)] -- the interior face between the two cells, named in either order, takes that direction
+    whatever its normal (mesh_override_face_properties, src/mesh.F90:1286-1405); a pair that shares no face is passed
+    over, as the reference does (:1330-1345, a warning in its log)."""
     n = len(cells)
     g = np.zeros(3)
     if gravity is not None:
@@ -155,7 +172,7 @@ def build_mesh(nodes, cells, dim, thickness=1.0, radial=False, gravity=None, bou
         rec[4:7] = nrm
         rec[7] = np.dot(g, nrm)
         rec[8:11] = fc
-        rec[11] = int(np.argmax(np.abs(nrm[:dim]))) + 1
+        rec[11] = permeability_direction(nrm, dim, permeability_angle)
         return rec
 
     fc_list, fg_list = [], []
@@ -163,6 +180,14 @@ def build_mesh(nodes, cells, dim, thickness=1.0, radial=False, gravity=None, bou
         if len(cs) == 2:
             fc_list.append((cs[0], cs[1]))
             fg_list.append(face_record(key, cs[0], cs[1]))
+    if len(face_directions):
+        place = {(min(a, b), max(a, b)): k for k, (a, b) in enumerate(fc_list)}
+        for a, b, direction in face_directions:
+            if int(direction) not in (1, 2, 3):
+                raise ValueError("mesh.faces: permeability_direction %r of cells [%d, %d] is not 1, 2 or 3" % (direction, a, b))
+            k = place.get((min(a, b), max(a, b)))
+            if k is not None:
+                fg_list[k][11] = int(direction)
     # open boundaries
     bc_prim, bc_region, bc_cen = [], [], []
     cell_bfaces = {}
