@@ -400,11 +400,16 @@ int wai_jacobian_set_values(wai_ctx *ctx, const double *val);      /* drops the 
 /* MatMult_SeqBAIJ / MPIBAIJ: y = J x (x haloed internally); J = A + the source network's blocks
  * (wai_get_network_couplings) when wai_jacobian assembled any */
 int wai_spmv(wai_ctx *ctx, const double *x, double *y);
-/* PCSetUp / PCApply of bjacobi | asm + ilu(0), or none (:1668-1669,1745-1757,1789-1834) */
+/* PCSetUp / PCApply of bjacobi | asm + ilu(0), or none (:1668-1669,1745-1757,1789-1834).
+ * wai_pc_setup: 0 done, 1 a pivot block of the factorisation is exactly singular (recoverable: no factor is in force, and
+ * every later wai_pc_setup, wai_pc_apply and wai_ksp_solve on the same values sets up again and reports it again; new
+ * values -- wai_jacobian, wai_jacobian_set_values -- clear it), < 0 error.  wai_pc_apply sets up first where no factor is
+ * in force: 1 on a failed pivot, z left as it was.  Collective over ranks: every rank returns 1 when any rank's pivot failed */
 int wai_pc_setup(wai_ctx *ctx);
 int wai_pc_apply(wai_ctx *ctx, const double *r, double *z);
 /* KSPSolve (:1645-1836): left-preconditioned BiCGStab / GMRES(m), zero initial guess.
- * reason follows KSPConvergedReason: 2 rtol, 3 atol, -3 its, -4 dtol, -5 breakdown, -9 nan */
+ * reason follows KSPConvergedReason: 2 rtol, 3 atol, -3 its, -4 dtol, -5 breakdown, -9 nan,
+ * -11 the preconditioner's set-up failed (KSP_DIVERGED_PC_FAILED: a singular pivot; its = 0, rnorm = 0, x = 0) */
 int wai_ksp_solve(wai_ctx *ctx, const double *b, double *x, int *its, int *reason,
                   double *rnorm);
 /* vec_max_pointwise_abs_scale (src/dm_utils.F90:644-685) */

@@ -727,7 +727,11 @@ int do_ksp(wai_ctx* c, LinSys& sys, const double* b, double* x, int* its, int* r
   if (c->ilu.owner != &sys) {
     const int e = do_pc_setup(c, sys);
     if (e < 0) return -1;
-    if (e > 0) { *reason = -11; *its = 0; *rnorm = 0.0; return 0; }
+    if (e > 0) {   // a pivot failed: KSP_DIVERGED_PC_FAILED, nothing iterated, x = 0 (the zero initial guess)
+      vec_zero(c, x, sys.n);
+      *reason = -11; *its = 0; *rnorm = 0.0;
+      return 0;
+    }
   }
   if (sys.ksp.type == WAI_KSP_GMRES) return ksp_gmres(c, sys, b, x, its, reason, rnorm);
   if (sys.ksp.type == WAI_KSP_BCGSL) return ksp_bcgsl(c, sys, b, x, its, reason, rnorm);

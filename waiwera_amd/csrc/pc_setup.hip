@@ -291,7 +291,7 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
   if (pc.type == WAI_PC_LU) {
     Prof p(c, KC_PC_SETUP);
     const int e = lu_setup(c, sys);
-    if (e == 0) c->ilu.owner = &sys;
+    c->ilu.owner = e == 0 ? &sys : nullptr;
     return e;
   }
   {
@@ -326,11 +326,15 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
       launch_asm_gather_matrix(c, A, as);
       if (launch_ilu_factor_on(c, as.E, as.sched)) return -1;
     } else if (launch_ilu_factor_on(c, A, c->ilu)) return -1;
-    c->ilu.owner = &sys;
   }
+  // The factor buffers are overwritten either way, so whoever owned them owns them no longer; `sys` owns them only when
+  // every pivot inverted.  After a failed pivot the next solve, application or measurement sets up again and reports it.
+  c->ilu.owner = nullptr;
   int fl[4];
   if (fetch_flags(c, fl)) return -1;
-  return fl[0] ? 1 : 0;
+  if (fl[0]) return 1;
+  c->ilu.owner = &sys;
+  return 0;
 }
 
 }  // namespace wai

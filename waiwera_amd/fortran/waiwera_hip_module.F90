@@ -289,6 +289,8 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        real(c_double), intent(out) :: val(*)
      end function wai_jacobian_get_values
+     ! reason follows KSPConvergedReason: 2 rtol, 3 atol, -3 its, -4 dtol, -5 breakdown, -9 nan, -11 the preconditioner's
+     ! set-up failed (a singular pivot: its = 0, rnorm = 0, x = 0)
      integer(c_int) function wai_ksp_solve(ctx, b, x, its, reason, rnorm) bind(c, name = "wai_ksp_solve")
        import :: c_int, c_ptr, c_double
        type(c_ptr), value :: ctx
@@ -494,7 +496,9 @@ module waiwera_hip_module
        real(c_double), intent(in) :: x(*)
        real(c_double), intent(out) :: y(*)
      end function wai_spmv
-     ! PCSetUp / PCApply (timestepper.F90:1668-1669,1745-1757,1789-1834)
+     ! PCSetUp / PCApply (timestepper.F90:1668-1669,1745-1757,1789-1834).  Both return 1 when a pivot block is exactly
+     ! singular (recoverable; on every rank): no factor is in force, wai_pc_apply leaves z as it was, and every later call
+     ! on the same values sets up and reports it again
      integer(c_int) function wai_pc_setup(ctx) bind(c, name = "wai_pc_setup")
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
