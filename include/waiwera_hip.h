@@ -539,12 +539,30 @@ int wai_get_pc_ordering(wai_ctx *ctx, int *ordering, int *max_colours);
  * waits once per Jacobian, for the flag that says whether a block is nonzero.  Node states and coupling blocks are then
  * downloaded when asked for (wai_get_source_network, wai_get_network_couplings).
  * May be set before or after wai_set_source_network.  The device pass is in force on one rank (a matter of the
- * communicator's size alone) for a network whose description and state fit the 64 KB of static LDS of a workgroup;
- * otherwise the host pass runs.  wai_get_network_pass reports the setting and what runs (out-arguments may be NULL).
+ * communicator's size alone) for a network whose description and state fit the 64 KB of static LDS of a workgroup (160 KiB
+ * of dynamic LDS under wai_set_network_walk's wave walk); otherwise the host pass runs.  wai_get_network_pass reports the setting and what runs (out-arguments may be NULL).
  * Unknown value: -2 with a text. */
 enum { WAI_NETWORK_PASS_HOST = 0, WAI_NETWORK_PASS_DEVICE = 1 };
 int wai_set_network_pass(wai_ctx *ctx, int where);
 int wai_get_network_pass(wai_ctx *ctx, int *requested, int *in_force);
+
+/* How the device pass walks groups and reinjectors.  WAI_NETWORK_WALK_LANE (the default): one lane of the wave walks them
+ * (k_network_pass, k_cb_pass); description and state take the 64 KB of static LDS at most.  WAI_NETWORK_WALK_WAVE: the
+ * wave's 64 lanes gather the terms of every sum into a staging run of LDS and the additions are chained over it in input
+ * order, one sum per lane; scaling what is below a limited group and delivering to injection sources is strided over the lanes
+ * (k_network_pass_wave, k_cb_pass_wave; network_wave.hpp).  The same roundings in the same order as the host pass: the same
+ * bits.  The wave walk takes dynamic LDS of the network's own size, up to the 160 KiB of a gfx950 workgroup, so it holds
+ * networks on the device that the lane walk leaves to the host pass.
+ * May be set before or after wai_set_source_network.  The wave walk is in force only where the device pass is
+ * (WAI_NETWORK_PASS_DEVICE asked for, one rank) and its schedule accepts the network: no source or group taken in by more
+ * than one group (or twice by one), and a need of at most 160 KiB.  Otherwise what ran before runs -- the lane walk where the
+ * network fits it, else the host pass -- and no error is raised.  Outputs and overflows of reinjectors that share a target
+ * source are accepted: one lane delivers them in output order.  The batched coupling build (wai_set_coupling_build) uses the
+ * walk in force.  wai_get_network_walk reports the setting and what runs (out-arguments may be NULL).  Unknown value: -2 with
+ * a text. */
+enum { WAI_NETWORK_WALK_LANE = 0, WAI_NETWORK_WALK_WAVE = 1 };
+int wai_set_network_walk(wai_ctx *ctx, int how);
+int wai_get_network_walk(wai_ctx *ctx, int *requested, int *in_force);
 
 /* How wai_jacobian builds the source network's coupling blocks E (wai_set_network_couplings).  WAI_COUPLING_BUILD_COLUMNS
  * (the default): one column -- network cell j, primary k -- at a time, on the global state: y_jk is perturbed in place, the

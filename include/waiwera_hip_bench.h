@@ -35,8 +35,9 @@ int wai_test_drop_partials(wai_ctx *ctx, int n);
  * is enqueued WITHOUT waiting for the event behind the unpack on the communication stream.  Over a stream-asynchronous
  * transport a multi-rank solve must then go wrong (tests/test_hip_multirank.py); 0 restores the product's ordering */
 int wai_test_drop_stream_wait(wai_ctx *ctx, int which);
-/* one pass of the context's source network on the device (k_network_pass; a network on one rank that fits LDS, else -2),
- * whatever wai_set_network_pass says: raw2n (host) = the sources' own rates [n], then their flowing enthalpies [n].
+/* one pass of the context's source network on the device (a network on one rank that fits LDS, else -2), whatever
+ * wai_set_network_pass says, with the walk wai_set_network_walk leaves in force (k_network_pass_wave where the wave walk is
+ * asked for and its schedule accepts the network, else k_network_pass): raw2n (host) = the sources' own rates [n], then their flowing enthalpies [n].
  * Returns the node states -- sources and groups 6 doubles each, reinjectors 8 each, as wai_network_evaluate -- and what
  * the pass wrote for the residual kernel: the (mode, value) pairs [2 n] and the sources' enthalpy array [n], of which the
  * pass touches the entries of the sources a reinjector feeds alone.  Out-arguments may be NULL. */
@@ -49,7 +50,9 @@ int wai_test_network_stats(wai_ctx *ctx, long long *passes, long long *host_wait
  * text), columns (m * bs; 0: no build) and chunks of the batched build (0 for a column loop).  Out-arguments may be NULL */
 int wai_test_coupling_build_stats(wai_ctx *ctx, long long *launches, long long *columns, long long *chunks);
 /* doubles of LDS the pass on the device may take (description + raw rates + state), and what the context's network
- * takes (0: none, or one on several ranks): a network that needs more keeps the host pass */
+ * takes (0: none, or one on several ranks): a network that needs more keeps the host pass.  8192 and the lane walk's need
+ * under WAI_NETWORK_WALK_LANE; under WAI_NETWORK_WALK_WAVE, for a network whose topology the wave schedule accepts, 20480 and
+ * the wave walk's need (staging run and schedule included) */
 int wai_test_network_lds(wai_ctx *ctx, int *limit, int *needed);
 /* device allocations the library holds in this process now, over all contexts and its temporaries, and their bytes: what
  * a context allocated is returned when it is destroyed, and setting something again does not grow it (tests/test_hip_memory.py) */

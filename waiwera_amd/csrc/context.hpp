@@ -12,6 +12,7 @@
 #include "ilu_schedule.hpp"   // ScheduleFacts
 #include "mesh_pattern.hpp"   // MAX_CELL_FACES
 #include "network_pass.hpp"   // NetFlatHost
+#include "network_wave.hpp"   // NetWaveHost
 #include "physics.hip.h"
 #include "tile_schedule.hpp"  // TileFacts
 
@@ -189,6 +190,13 @@ struct Network {
   NetFlatHost flat;
   bool flat_fits = false, flat_dirty = true;
   DevBuf<int> d_flat_iw;
+  // The wave-wide walk (wai_set_network_walk; network_wave.hpp): its schedule, built with the flat description whatever walk
+  // is asked for.  wave_built: the topology was accepted (the schedule's lists and its need of LDS stand); wave_ok: and the
+  // need fits 160 KiB; wave_err: why not
+  NetWaveHost wave;
+  bool wave_built = false, wave_ok = false;
+  std::string wave_err;
+  DevBuf<int> d_wave_ww;
   DevBuf<double> d_flat_dw;
   DevBuf<double> d_state;                          // sources 6 each, groups 6 each, reinjectors 8 each: the last device pass
   bool state_on_device = false;                    // ... is newer than src / groups / reinjectors above (network_fetch_state)
@@ -569,6 +577,8 @@ struct wai_ctx : wai::Handles {
   wai_solver_opts opts{};
   int sub_pc = WAI_SUB_ILU;     // sub-preconditioner of bjacobi / asm (wai_set_sub_pc): ILU(ilu_levels) or the blocks' exact LU
   int net_pass = WAI_NETWORK_PASS_HOST;     // wai_set_network_pass: where the source network's pass runs (net_on_device: what is in force)
+  int net_walk = WAI_NETWORK_WALK_LANE;     // wai_set_network_walk: how the device pass walks groups and reinjectors (net_walk_wave: what is in force)
+  int net_wave_attr = 0;                    // the wave kernels that were allowed their dynamic LDS above 64 KB (bit 0 k_network_pass_wave, 1 k_cb_pass_wave)
   long long net_passes = 0, net_waits = 0;  // passes made / stream waits issued by network_update and network_couplings (wai_test_network_stats)
   int cp_build = WAI_COUPLING_BUILD_COLUMNS;   // wai_set_coupling_build: how the network's Jacobian blocks are built (cp_batched: what is in force)
   long long cp_launches = 0, cp_columns = 0, cp_chunks = 0;   // kernel launches, columns and chunks of the last coupling build (wai_test_coupling_build_stats)
@@ -663,14 +673,15 @@ int launch_face_fluxes(wai_ctx* c, const int* face_cells, double* out);   // [fa
 int launch_source_rates(wai_ctx* c, double* out, bool raw = false);
 // kernels_network.hip: one pass of the network on the device (raw: launch_source_rates(c, raw, true)), and the coupling
 // build's column steps
-int launch_network_pass(wai_ctx* c, const double* raw, double* net, double* enth, double* state_out);
+int launch_network_pass(wai_ctx* c, const double* raw, double* net, double* enth, double* state_out, bool wave);
+int net_wave_allow_lds(wai_ctx* c, const void* kernel, int bit, size_t* bytes);
 int launch_cp_perturb(wai_ctx* c, double* p, double* yh);
 int launch_cp_restore(wai_ctx* c, double* p, const double* yh);
 int launch_cp_diff(wai_ctx* c, int ml, int m, int bs, int j, int k, const double* g, const double* yh, double* val, int* flag);   // out[0..n) rates, out[n..2n) enthalpies (device); raw: before the network pass
 // kernels_coupling.hip: the columns col0 .. col0 + ncol - 1 of the batched coupling build on the scratch plan b -- five
 // launches whatever ncol is; launches: counted
 int launch_coupling_batch(wai_ctx* c, const CouplingBatch& b, int col0, int ncol, double dt, const double* y, const double* lhs_old,
-                          long long* launches);
+                          long long* launches, bool wave);
 // X[cell][nt] <-> x[cell] of tracer it; alx = Al o X
 int launch_tracer_pick(wai_ctx* c, const double* X, int it, double* x);
 int launch_tracer_put(wai_ctx* c, const double* x, int it, double* X);

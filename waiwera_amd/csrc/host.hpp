@@ -189,9 +189,17 @@ int bcgs_second_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
 void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n);   // separator.F90:139-166, 212-260
 // the pass on the device is in force (wai_set_network_pass): asked for, one rank -- by the communicator's size alone, so
 // every rank decides alike -- and a network whose description and state fit a workgroup's LDS
-inline bool net_on_device(const wai_ctx* c) {
-  return c->net_pass == WAI_NETWORK_PASS_DEVICE && c->net.on && c->net.flat_fits && !(c->comm && c->comm->nranks > 1);
+// The wave-wide walk (wai_set_network_walk) can run: asked for, one rank, and a network its schedule accepts.  It holds
+// networks of up to 160 KiB on the device, where the lane walk stops at NET_LDS_DOUBLES
+inline bool net_wave_usable(const wai_ctx* c) {
+  return c->net_walk == WAI_NETWORK_WALK_WAVE && c->net.on && c->net.wave_ok && !(c->comm && c->comm->nranks > 1);
 }
+inline bool net_on_device(const wai_ctx* c) {
+  return c->net_pass == WAI_NETWORK_PASS_DEVICE && c->net.on && (c->net.flat_fits || net_wave_usable(c)) &&
+         !(c->comm && c->comm->nranks > 1);
+}
+// ... is in force: where the device pass is
+inline bool net_walk_wave(const wai_ctx* c) { return net_wave_usable(c) && net_on_device(c); }
 // Is the batched coupling build (wai_set_coupling_build) in force: asked for, the device pass in force, the couplings on
 inline bool cp_batched(const wai_ctx* c) {
   return c->cp_build == WAI_COUPLING_BUILD_BATCHED && net_on_device(c) && c->net.coupling;

@@ -11,6 +11,7 @@
 // assembly unit, waiwera_amd/build.py): the column loop is the oracle, bit for bit.
 #include "assembly_device.hip.h"
 #include "network_pass.hpp"
+#include "network_wave.hpp"
 
 namespace wai {
 
@@ -177,8 +178,20 @@ __global__ __launch_bounds__(64) void k_cb_pass(NetFlat h, const int* __restrict
   network_pass_final(fv, sraw, s, t, 64);
 }
 
+// k_cb_pass with the wave-wide walk (wai_set_network_walk; network_wave.hpp), as k_network_pass_wave:
+//   [ dw | raw 2n | state | staging | iw | ww ]   net_wave_lds_doubles(h, w) doubles, up to 160 KiB
+__global__ __launch_bounds__(64) void k_cb_pass_wave(NetFlat h, NetWave w, const int* __restrict__ iw, const double* __restrict__ dw,
+                                                     const int* __restrict__ ww, CbView v) {
+  extern __shared__ double lds[];
+  if ((int)blockIdx.x >= v.ncol) return;   // (the whole workgroup alike)
+  double* col = v.scratch + (size_t)blockIdx.x * v.per_col;
+  NetState s;
+  net_wave_pass_lds(h, w, iw, dw, ww, col + v.off_raw, col + v.off_net, col + v.off_enth, lds, s);
+}
+
+// wave: k_cb_pass_wave stands in for k_cb_pass (net_wave_usable, host.hpp); the scratch plan is the same
 int launch_coupling_batch(wai_ctx* c, const CouplingBatch& b, int col0, int ncol, double dt, const double* y, const double* lhs_old,
-                          long long* launches) {
+                          long long* launches, bool wave) {
   const Network& nw = c->net;
   const int ml = (int)nw.cp_cells.size(), n = c->src.n;
   if (ncol <= 0 || ncol > b.chunk || col0 < 0 || col0 + ncol > b.ncol || (long long)ncol * b.per_col > nw.cb_doubles ||
@@ -195,7 +208,8 @@ int launch_coupling_batch(wai_ctx* c, const CouplingBatch& b, int col0, int ncol
   mraw.src_net = nullptr;
   const size_t stride = c->mesh.n_local;
   const ResForm rf = res_form_of(c, dt, lhs_old);
-  const size_t lds = sizeof(double) * (size_t)net_lds_doubles(nw.flat.h);
+  size_t lds = sizeof(double) * (size_t)net_lds_doubles(nw.flat.h);
+  if (wave && net_wave_allow_lds(c, reinterpret_cast<const void*>(&k_cb_pass_wave), 2, &lds)) return -1;
   const char* kernel = "k_cb_states";
   int e = with_eos(c->kind, [&](auto k) {
     constexpr int K = decltype(k)::value;
@@ -211,7 +225,11 @@ int launch_coupling_batch(wai_ctx* c, const CouplingBatch& b, int col0, int ncol
                        (double*)nw.d_cp_val, (int*)nw.d_cp_flag);
     if (launched(c, kernel)) return;
     kernel = "k_cb_pass";
-    hipLaunchKernelGGL(k_cb_pass, ncol, 64, lds, c->stream, nw.flat.h, (const int*)nw.d_flat_iw, (const double*)nw.d_flat_dw, v);
+    if (wave)
+      hipLaunchKernelGGL(k_cb_pass_wave, ncol, 64, lds, c->stream, nw.flat.h, nw.wave.w, (const int*)nw.d_flat_iw,
+                         (const double*)nw.d_flat_dw, (const int*)nw.d_wave_ww, v);
+    else
+      hipLaunchKernelGGL(k_cb_pass, ncol, 64, lds, c->stream, nw.flat.h, (const int*)nw.d_flat_iw, (const double*)nw.d_flat_dw, v);
     if (launched(c, kernel)) return;
     kernel = "k_cb_rows";
     hipLaunchKernelGGL((k_cb_rows<K, 1>), grid_for((size_t)ncol * ml), TPB, 0, c->stream, m, v, (const double*)c->flu, stride, rf,

@@ -4,6 +4,7 @@
 // restore y.  Built without FMA contraction, like the assembly units: the host pass is the oracle, bit for bit.
 #include "context.hpp"
 #include "network_pass.hpp"
+#include "network_wave.hpp"
 
 namespace wai {
 
@@ -40,6 +41,21 @@ __global__ __launch_bounds__(64) void k_network_pass(NetFlat h, const int* __res
   for (int i = t; i < 8 * h.n_rj; i += 64) state_out[nn + i] = s.rj[RJ_STATE * (i >> 3) + RJ_OUT_W + (i & 7)];
 }
 
+// The same pass with the wave-wide walk (wai_set_network_walk, WAI_NETWORK_WALK_WAVE; network_wave.hpp): one wave, dynamic
+// LDS of the network's own size plus the staging run and the schedule (ww), up to 160 KiB
+__global__ __launch_bounds__(64) void k_network_pass_wave(NetFlat h, NetWave w, const int* __restrict__ iw, const double* __restrict__ dw,
+                                                          const int* __restrict__ ww, const double* __restrict__ raw,
+                                                          double* __restrict__ net, double* __restrict__ enth,
+                                                          double* __restrict__ state_out) {
+  extern __shared__ double lds[];
+  const int t = threadIdx.x;
+  NetState s;
+  net_wave_pass_lds(h, w, iw, dw, ww, raw, net, enth, lds, s);   // (ends with a barrier)
+  const int nn = NET_NODE * (h.n_src + h.n_grp);
+  for (int i = t; i < nn; i += 64) state_out[i] = s.src[i];
+  for (int i = t; i < 8 * h.n_rj; i += 64) state_out[nn + i] = s.rj[RJ_STATE * (i >> 3) + RJ_OUT_W + (i & 7)];
+}
+
 // y_jk + h, with h by the Jacobian's rule (MatFDColoring "ds", as fd_step of the assembly sweeps); yh keeps y_jk and h
 __global__ void k_cp_perturb(double* __restrict__ p, double* __restrict__ yh, double umin, double eps) {
   if (threadIdx.x || blockIdx.x) return;
@@ -66,8 +82,26 @@ __global__ void k_cp_diff(int ml, int m, int bs, int j, int k, const double* __r
   if (e != 0.0) atomicOr(flag, 1);
 }
 
-int launch_network_pass(wai_ctx* c, const double* raw, double* net, double* enth, double* state_out) {
+// the wave kernels take dynamic LDS of the network's own size; above 64 KB a kernel has to be allowed it, once (bit: which)
+int net_wave_allow_lds(wai_ctx* c, const void* kernel, int bit, size_t* bytes) {
   const Network& nw = c->net;
+  *bytes = sizeof(double) * (size_t)net_wave_lds_doubles(nw.flat.h, nw.wave.w);
+  if (!nw.wave_ok || !nw.d_wave_ww || !nw.d_flat_iw || *bytes > sizeof(double) * (size_t)NET_WAVE_LDS_DOUBLES) { c->err = "network wave walk: a network its schedule refused"; return -1; }
+  if (c->net_wave_attr & bit) return 0;
+  HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NET_WAVE_LDS_DOUBLES)));
+  c->net_wave_attr |= bit;
+  return 0;
+}
+// wave: the wave-wide walk (net_wave_usable, host.hpp)
+int launch_network_pass(wai_ctx* c, const double* raw, double* net, double* enth, double* state_out, bool wave) {
+  const Network& nw = c->net;
+  if (wave) {
+    size_t lds = 0;
+    if (net_wave_allow_lds(c, reinterpret_cast<const void*>(&k_network_pass_wave), 1, &lds)) return -1;
+    hipLaunchKernelGGL(k_network_pass_wave, 1, 64, lds, c->stream, nw.flat.h, nw.wave.w, (const int*)nw.d_flat_iw,
+                       (const double*)nw.d_flat_dw, (const int*)nw.d_wave_ww, raw, net, enth, state_out);
+    return 0;
+  }
   hipLaunchKernelGGL(k_network_pass, 1, 64, 0, c->stream, nw.flat.h, (const int*)nw.d_flat_iw, (const double*)nw.d_flat_dw, raw, net,
                      enth, state_out);
   return 0;

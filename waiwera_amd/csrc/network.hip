@@ -214,6 +214,10 @@ static int network_flat_upload(wai_ctx* c) {
   if (!nw.d_flat_iw && (nw.d_flat_iw.alloc(c, (size_t)h.n_iw) || nw.d_flat_dw.alloc(c, (size_t)h.n_dw) ||
                         nw.d_state.alloc(c, (size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)h.n_rj)))
     return -1;
+  if (nw.wave_ok && !nw.d_wave_ww) {   // the wave walk's schedule: it changes with the description alone
+    if (nw.d_wave_ww.alloc(c, (size_t)std::max(nw.wave.w.n_ww, 1))) return -1;
+    HIPCHK(c, hipMemcpyAsync(nw.d_wave_ww, nw.wave.ww.data(), sizeof(int) * (size_t)nw.wave.w.n_ww, hipMemcpyHostToDevice, c->stream));
+  }
   HIPCHK(c, hipMemcpyAsync(nw.d_flat_iw, nw.flat.iw.data(), sizeof(int) * (size_t)h.n_iw, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(nw.d_flat_dw, nw.flat.dw.data(), sizeof(double) * (size_t)h.n_dw, hipMemcpyHostToDevice, c->stream));
   NET_WAIT(c);   // (only after the description changed: the host arrays are free again)
@@ -232,7 +236,7 @@ int network_update(wai_ctx* c) {
   if (net_on_device(c)) {   // k_network_pass: nothing comes to the host and nobody waits
     if (nw.flat_dirty && network_flat_upload(c)) return -1;
     launch_source_rates(c, nw.d_raw, true);
-    launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state);
+    if (launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state, net_wave_usable(c))) return -1;
     nw.state_on_device = true;
     nw.enth_stale = true;
     return 0;
@@ -382,7 +386,8 @@ int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old) {
         nw.cb_doubles = b.doubles;
       }
       for (int ch = 0; ch < b.n_chunks; ch++)
-        if (launch_coupling_batch(c, b, ch * b.chunk, ch + 1 < b.n_chunks ? b.chunk : b.last, dt, y, lhs_old, &c->cp_launches))
+        if (launch_coupling_batch(c, b, ch * b.chunk, ch + 1 < b.n_chunks ? b.chunk : b.last, dt, y, lhs_old, &c->cp_launches,
+                                  net_wave_usable(c)))
           return -1;
       c->net_passes += b.ncol;   // one pass per column, in k_cb_pass
       c->cp_chunks = b.n_chunks;
@@ -695,6 +700,14 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
                                   rj_overflow, e) == 0 &&
                    net_lds_doubles(nw.flat.h) <= NET_LDS_DOUBLES;
     nw.flat_dirty = true;
+    // the wave walk's schedule (wai_set_network_walk), whatever walk is asked for now: it may be asked for later
+    const bool flat_ok = nw.flat.h.n_src == n;   // (the builder fills the header only behind its refusals)
+    nw.wave_built = nw.wave_ok = false;
+    if (!flat_ok) nw.wave_err = e;
+    else {
+      nw.wave_ok = build_net_wave(nw.flat, nw.wave, nw.wave_err) == 0;
+      nw.wave_built = nw.wave_ok || nw.wave.w.n_ww > 0;
+    }
   }
   if (!span) network_cells(nw, n);
   else network_cells_span(nw, ng, span_id, c->comm->rank);
@@ -744,6 +757,24 @@ int wai_get_network_pass(wai_ctx* c, int* requested, int* in_force) {
   if (in_force) *in_force = net_on_device(c) ? WAI_NETWORK_PASS_DEVICE : WAI_NETWORK_PASS_HOST;
   return 0;
 }
+// How the device pass walks groups and reinjectors (include/waiwera_hip.h)
+int wai_set_network_walk(wai_ctx* c, int how) {
+  if (!c) return -2;
+  if (how != WAI_NETWORK_WALK_LANE && how != WAI_NETWORK_WALK_WAVE) {
+    c->err = "unknown walk of the source network's device pass (WAI_NETWORK_WALK_LANE or WAI_NETWORK_WALK_WAVE)";
+    return -2;
+  }
+  // a network only the wave walk holds on the device goes back to the host pass: its copy of the node states stays the last pass'
+  if (how != c->net_walk && network_fetch_state(c)) return -1;
+  c->net_walk = how;
+  return 0;
+}
+int wai_get_network_walk(wai_ctx* c, int* requested, int* in_force) {
+  if (!c) return -2;
+  if (requested) *requested = c->net_walk;
+  if (in_force) *in_force = net_walk_wave(c) ? WAI_NETWORK_WALK_WAVE : WAI_NETWORK_WALK_LANE;
+  return 0;
+}
 // How the network's Jacobian blocks are built (include/waiwera_hip.h)
 int wai_set_coupling_build(wai_ctx* c, int how) {
   if (!c) return -2;
@@ -773,14 +804,16 @@ int wai_test_network_pass(wai_ctx* c, const double* raw2n, double* sources6, dou
   if (!c || !raw2n) return -2;
   Network& nw = c->net;
   const int n = c->src.n;
-  if (!nw.on || !nw.flat_fits || (c->comm && c->comm->nranks > 1)) {
+  const bool wave = net_wave_usable(c);
+  if (!nw.on || !(nw.flat_fits || wave) || (c->comm && c->comm->nranks > 1)) {
     c->err = "wai_test_network_pass: a source network on one rank that fits a workgroup's LDS";
+    if (c->net_walk == WAI_NETWORK_WALK_WAVE && !nw.wave_err.empty()) c->err += " (" + nw.wave_err + ")";
     return -2;
   }
   if (nw.flat_dirty && network_flat_upload(c)) return -1;
   const NetFlat& h = nw.flat.h;
   HIPCHK(c, hipMemcpyAsync(nw.d_raw, raw2n, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-  launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state);
+  if (launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state, wave)) return -1;
   nw.state_on_device = true;
   nw.enth_stale = true;
   const size_t ns = (size_t)NET_NODE * h.n_src, ngd = (size_t)NET_NODE * h.n_grp;
@@ -803,8 +836,15 @@ int wai_test_network_stats(wai_ctx* c, long long* passes, long long* host_waits)
 // context's network takes (0: none set, or one on several ranks)
 int wai_test_network_lds(wai_ctx* c, int* limit, int* needed) {
   if (!c) return -2;
+  const Network& nw = c->net;
+  const bool have = nw.on && nw.flat.h.n_src;
+  if (c->net_walk == WAI_NETWORK_WALK_WAVE && have && nw.wave_built) {   // the wave walk's own limit and need
+    if (limit) *limit = NET_WAVE_LDS_DOUBLES;
+    if (needed) *needed = net_wave_lds_doubles(nw.flat.h, nw.wave.w);
+    return 0;
+  }
   if (limit) *limit = NET_LDS_DOUBLES;
-  if (needed) *needed = c->net.on && c->net.flat.h.n_src ? net_lds_doubles(c->net.flat.h) : 0;
+  if (needed) *needed = have ? net_lds_doubles(nw.flat.h) : 0;
   return 0;
 }
 

@@ -169,6 +169,22 @@ class FlowSimulation:
         name = {v: k for k, v in _lib.NETWORK_PASS.items()}
         return name[r.value], name[f.value]
 
+    def set_network_walk(self, how):
+        """how the device pass walks groups and reinjectors (wai_set_network_walk): "lane" (default: one lane of the wave, a
+        network of at most 64 KB of LDS) or "wave" (the 64 lanes gather every sum's terms and one chains them in input order;
+        dynamic LDS up to 160 KiB).  The same bits either way.  Before or after set_source_network"""
+        if how not in _lib.NETWORK_WALK:
+            raise ValueError("network walk %r: one of %s" % (how, sorted(_lib.NETWORK_WALK)))
+        self._chk(LIB.wai_set_network_walk(self.h, _lib.NETWORK_WALK[how]), "set_network_walk")
+
+    def network_walk(self):
+        """(requested, in_force): the setting, and what runs -- "wave" where the device pass is in force (network_pass) and
+        the wave schedule accepts the network, "lane" otherwise"""
+        r, f = C.c_int(0), C.c_int(0)
+        self._chk(LIB.wai_get_network_walk(self.h, C.byref(r), C.byref(f)), "network_walk")
+        name = {v: k for k, v in _lib.NETWORK_WALK.items()}
+        return name[r.value], name[f.value]
+
     def network_stats(self):
         """(passes, host_waits): network passes so far, and the stream waits passes and coupling builds issued"""
         p, w = C.c_longlong(0), C.c_longlong(0)

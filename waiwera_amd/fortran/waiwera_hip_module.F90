@@ -584,6 +584,19 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        integer(c_int), intent(out) :: requested, in_force
      end function wai_get_network_pass
+     ! how the device pass walks groups and reinjectors: WAI_NETWORK_WALK_LANE (0, default) one lane | WAI_NETWORK_WALK_WAVE
+     ! (1): the wave's lanes gather, one chains; networks of up to 160 KiB of LDS.  In force where the device pass is
+     integer(c_int) function wai_set_network_walk(ctx, how) bind(c, name = "wai_set_network_walk")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: how
+     end function wai_set_network_walk
+     ! the setting, and what runs
+     integer(c_int) function wai_get_network_walk(ctx, requested, in_force) bind(c, name = "wai_get_network_walk")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: requested, in_force
+     end function wai_get_network_walk
      ! how wai_jacobian builds the network's coupling blocks: WAI_COUPLING_BUILD_COLUMNS (0, default) one column at a time |
      ! WAI_COUPLING_BUILD_BATCHED (1): all columns at once on private scratch.  In force where the device pass is
      integer(c_int) function wai_set_coupling_build(ctx, how) bind(c, name = "wai_set_coupling_build")
@@ -632,6 +645,7 @@ module waiwera_hip_module
   integer, parameter, public :: WAI_PC_ORDER_NATURAL = 0, WAI_PC_ORDER_MULTICOLOUR = 1
   integer, parameter, public :: WAI_NETWORK_PASS_HOST = 0, WAI_NETWORK_PASS_DEVICE = 1
   integer, parameter, public :: WAI_COUPLING_BUILD_COLUMNS = 0, WAI_COUPLING_BUILD_BATCHED = 1
+  integer, parameter, public :: WAI_NETWORK_WALK_LANE = 0, WAI_NETWORK_WALK_WAVE = 1
   integer, parameter, public :: WAI_PC_BJACOBI = 0, WAI_PC_ASM = 1, WAI_PC_NONE = 2, WAI_PC_LU = 3, WAI_AUX_PC_FOLLOW = -1
 
   type, public :: hip_flow_simulation_type
@@ -660,6 +674,7 @@ module waiwera_hip_module
      procedure, public :: set_pc_ordering => hip_sim_set_pc_ordering
      procedure, public :: set_network_pass => hip_sim_set_network_pass
      procedure, public :: set_coupling_build => hip_sim_set_coupling_build
+     procedure, public :: set_network_walk => hip_sim_set_network_walk
      procedure, public :: set_aux_pc => hip_sim_set_aux_pc
      procedure, public :: aux_lhs => hip_sim_aux_lhs
      procedure, public :: aux_solve => hip_sim_aux_solve
@@ -681,6 +696,7 @@ module waiwera_hip_module
   public :: wai_set_pc_tiles, wai_set_pc_ordering, wai_get_pc_ordering
   public :: wai_set_network_pass, wai_get_network_pass
   public :: wai_set_coupling_build, wai_get_coupling_build
+  public :: wai_set_network_walk, wai_get_network_walk
   public :: wai_set_thermo_extrapolate, wai_get_thermo_extrapolate, wai_set_source_production_component
   public :: wai_set_source_network, wai_get_source_network, wai_set_network_couplings, wai_get_network_couplings
   public :: wai_set_source_global_index, wai_launch_stats, wai_update_rock, wai_network_cells
@@ -947,6 +963,14 @@ contains
     integer, intent(out) :: err
     err = wai_set_network_pass(self%ctx, int(where, c_int))
   end subroutine hip_sim_set_network_pass
+
+  subroutine hip_sim_set_network_walk(self, how, err)
+    !! How the device pass walks groups and reinjectors: WAI_NETWORK_WALK_LANE | WAI_NETWORK_WALK_WAVE.
+    class(hip_flow_simulation_type), intent(in out) :: self
+    integer, intent(in) :: how
+    integer, intent(out) :: err
+    err = wai_set_network_walk(self%ctx, int(how, c_int))
+  end subroutine hip_sim_set_network_walk
 
   subroutine hip_sim_set_coupling_build(self, how, err)
     !! How the network's Jacobian blocks are built: WAI_COUPLING_BUILD_COLUMNS | WAI_COUPLING_BUILD_BATCHED.

@@ -30,6 +30,7 @@ TRACER_SOLVE = {"per_tracer": 0, "coupled": 1}   # wai_set_tracer_solve_mode
 SUB_PC = {"ilu": 0, "lu": 1}   # wai_set_sub_pc: sub-preconditioner of bjacobi / asm
 PC_ORDER = {"natural": 0, "multicolour": 1}   # wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
 NETWORK_PASS = {"host": 0, "device": 1}   # wai_set_network_pass: where the source network's pass runs
+NETWORK_WALK = {"lane": 0, "wave": 1}   # wai_set_network_walk: how the device pass walks groups and reinjectors
 COUPLING_BUILD = {"columns": 0, "batched": 1}   # wai_set_coupling_build: how the network's Jacobian blocks are built
 AUX_PC = dict(PC, follow=-1)   # wai_set_aux_pc: the tracer solver's own preconditioner, or the flow solver's ("follow", default)
 METHOD_KIND = {"beuler": 0, "bdf2": 1, "directss": 2}  # src/timestepper.F90:2262-2275
@@ -202,6 +203,8 @@ def _load():
         "wai_get_pc_ordering": (i32, [vp, pi, pi]),
         "wai_set_network_pass": (i32, [vp, i32]),
         "wai_get_network_pass": (i32, [vp, pi, pi]),
+        "wai_set_network_walk": (i32, [vp, i32]),
+        "wai_get_network_walk": (i32, [vp, pi, pi]),
         "wai_test_network_pass": (i32, [vp, pd, pd, pd, pd, pd, pd]),
         "wai_test_network_stats": (i32, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "wai_test_network_lds": (i32, [vp, pi, pi]),

@@ -48,6 +48,9 @@ def main(argv=None):
     ap.add_argument("--coupling-build", choices=("columns", "batched"), default="columns",
                     help="the Jacobian's blocks through the source network: one column at a time (default) or all columns at "
                          "once on private scratch (in force with --network-pass device; the same results)")
+    ap.add_argument("--network-walk", choices=("lane", "wave"), default="lane",
+                    help="how the device pass walks groups and reinjectors: one lane (default) or the whole wave (in force with "
+                         "--network-pass device; networks of up to 160 KiB of LDS; the same results)")
     ap.add_argument("--cell-order", choices=("input", "compact"), default="input",
                     help="the numbering the library gets: the mesh file's, with chunks of consecutive cells as the preconditioner's "
                          "subdomains (default), or compact 3-D subdomains numbered like bricks (one rank, a mesh file, no MINC "
@@ -72,7 +75,7 @@ def main(argv=None):
     sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
                                default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, network_pass=a.network_pass,
                                cell_order=a.cell_order, subdomain_rows=a.subdomain_rows,
-                               coupling_build=a.coupling_build, **kw)
+                               coupling_build=a.coupling_build, network_walk=a.network_walk, **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

@@ -657,7 +657,7 @@ class Simulation:
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
                  sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural", network_pass="host",
-                 cell_order="input", subdomain_rows=None, coupling_build="columns"):
+                 cell_order="input", subdomain_rows=None, coupling_build="columns", network_walk="lane"):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -708,6 +708,13 @@ class Simulation:
         if coupling_build not in ("columns", "batched"):
             raise ValueError("coupling_build 'columns' (the default) or 'batched'")
         self.coupling_build, self.coupling_build_choice = coupling_build, (coupling_build, "columns")
+        # network_walk: how the device pass walks groups and reinjectors -- "lane" (the default, as before: one lane) or "wave"
+        # (wai_set_network_walk: the wave's lanes gather, one chains; networks of up to 160 KiB of LDS; the same bits).  Not a
+        # key of the input file.  network_walk_choice records (requested, in force) once the network is set: "wave" is in
+        # force where network_pass "device" is and the wave schedule accepts the network
+        if network_walk not in ("lane", "wave"):
+            raise ValueError("network_walk 'lane' (the default) or 'wave'")
+        self.network_walk, self.network_walk_choice = network_walk, (network_walk, "lane")
         # subdomains: the preconditioner's blocks on a rank -- "chunks" (the default, as before): the chunks of consecutive cells
         # the mesh builders make (mesh.sub_ptr), each on the fused one-workgroup kernels; "rank": ONE block per rank, the
         # reference's own layout (its bjacobi / asm subdomains are the ranks), with the same chunks handed to the library as
@@ -1207,12 +1214,16 @@ class Simulation:
                 # without a source of the network -- `spec` depends on the input alone
                 self.ode.set_source_global_index(len(inp.get("source", []) or []), self._src_pick)
             self.ode.set_source_network(spec)
+            if self.network_walk == "wave":      # (before the pass' place is read back: the wave walk holds larger networks)
+                self.ode.set_network_walk("wave")
             if self.network_pass == "device":
                 self.ode.set_network_pass("device")
                 self.network_pass_choice = self.ode.network_pass()
             if self.coupling_build == "batched":
                 self.ode.set_coupling_build("batched")
                 self.coupling_build_choice = self.ode.coupling_build()
+            if self.network_walk == "wave":
+                self.network_walk_choice = self.ode.network_walk()
 
     # ---- state-dependent source controls -------------------------------------------------------
     def _setup_source_controls(self, sources, t0, collective_fluid=False):
