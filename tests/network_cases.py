@@ -1,7 +1,12 @@
 """Source networks for the tests of the flat pass (csrc/network_pass.hpp: tests/test_network_pass_host.py on the host,
 tests/test_hip_network_device.py on the device).  A case is dict(spec, rate, enth, sep): the description of
-lib.network_arrays, the sources' own rates and flowing enthalpies, and their separators (8 doubles each).  The oracle of
-every case is the library's host pass, wai_network_evaluate, whose specified enthalpies are the flowing ones handed in."""
+lib.network_arrays, the sources' own rates and flowing enthalpies, and their separators (8 doubles each).
+
+The oracle of the host tests is tests/golden/network_pass_bits.json: what wai_network_evaluate gave for every case while the
+library still had a second, recursive pass on a network of structs (the commit the file names) -- today the library's host
+pass is network_pass itself, so comparing the two would compare a text with itself.  The specified enthalpies of a case
+are the flowing ones handed in."""
+import hashlib
 import json
 import os
 
@@ -193,3 +198,45 @@ def with_sources(c, n):
                 enthalpy_specified=list(c["spec"]["enthalpy_specified"]) + [0] * extra, groups=list(c["spec"]["groups"]) + more)
     return case(spec, np.concatenate([c["rate"], -0.25 * (1 + k % 3)]), np.concatenate([c["enth"], 9.0e5 + 1.0e4 * k]),
                 np.concatenate([c["sep"], separators(extra, range(0, extra, 2))]))
+
+
+# ---- the recorded bits ----------------------------------------------------------------------------------------------
+_RECORDED = {}
+
+
+def recorded(name):
+    if not _RECORDED:
+        _RECORDED.update(json.load(open(os.path.join(HERE, "golden", "network_pass_bits.json")))["cases"])
+    return _RECORDED[name]
+
+
+def _digest(*arrays):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a, dtype="<f8").tobytes() for a in arrays)).hexdigest()
+
+
+def on_recorded_inputs(c, name="reference_fixture"):
+    """case c with the numeric inputs the bits of `name` were recorded on (separator enthalpies come out of the oracle's
+    libm: the same formulas elsewhere may differ in the last place), after checking that c's own agree with them"""
+    out = dict(c)
+    for key, hexes in recorded(name)["inputs"].items():
+        out[key] = np.array([float.fromhex(x) for x in hexes])
+        assert out[key].shape == c[key].shape, (name, key)
+        # 1e-12 relative: the same formulas through a possibly different libm
+        assert np.all(np.abs(out[key] - c[key]) <= 1e-12 * np.abs(out[key])), (name, key, out[key], c[key])
+    return out
+
+
+def assert_recorded(name, c, S, G, R, who):
+    """the node states (sources, groups, reinjectors) `who` gave for case c are the recorded ones, bit for bit"""
+    rec = recorded(name)
+    assert _digest(c["rate"], c["enth"], c["sep"]) == rec["inputs_sha256"], \
+        "%s: the case's numeric inputs are not the ones its bits were recorded on -- the generator drifted, not the pass" % name
+    got = np.concatenate([np.ravel(np.asarray(x, dtype=float)) for x in (S, G, R)])
+    if "hex" in rec:
+        want = np.array([float.fromhex(x) for x in rec["hex"]])
+        assert got.shape == want.shape, (name, who, got.shape, want.shape)
+        bad = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
+        assert bad.size == 0, "%s: %s differs from the recorded bits at doubles %s: %s, recorded %s" % (
+            name, who, bad[:8], [float(x).hex() for x in got[bad[:8]]], [rec["hex"][i] for i in bad[:8]])
+    else:
+        assert _digest(got) == rec["sha256"], "%s: %s differs from the recorded bits (digest of %d doubles)" % (name, who, got.size)

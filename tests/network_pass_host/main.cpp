@@ -1,7 +1,7 @@
 // The source network's pass on its flat description (waiwera_amd/csrc/network_pass.hpp) without a device: reads a
 // network and the sources' raw rates from a text file of records "name count values...", builds the description, runs
 // network_pass and prints every double it wrote in hexadecimal.  tests/test_network_pass_host.py builds this with the
-// address and undefined-behaviour sanitizers and compares with the library's host pass.
+// address and undefined-behaviour sanitizers and compares with the recorded bits (tests/golden/network_pass_bits.json).
 //   network_pass_host FILE   ->  "sources ..." (6 each), "groups ..." (6 each), "reinjectors ..." (8 each), "net ..." (2 each),
 //                                "enth ..." (1 each, started from the record enth_in), "sizes n_iw n_dw stack_frames arena lds"
 //                                or "error -2 text"

@@ -3,7 +3,7 @@
 // description and the wave schedule, and runs network_pass_wave over 64 EMULATED lanes three times -- lanes ascending,
 // descending and in a seeded shuffle.  Every double each run wrote is printed in hexadecimal; a difference between the three
 // is a race between the lanes of one phase.  tests/test_network_wave_host.py builds this with the address and
-// undefined-behaviour sanitizers and compares with the library's host pass.
+// undefined-behaviour sanitizers and compares with the recorded bits (tests/golden/network_pass_bits.json).
 //   network_wave_host FILE [SEED]  ->  "schedule.NAME ints..." for fan_in stage lds ds_ptr ds dg_ptr dg an_ptr an gc_ptr gc out_shared,
 //                                      then per ORDER in ascending, descending, shuffled: "sources.ORDER ..." (6 each),
 //                                      "groups.ORDER ..." (6 each), "reinjectors.ORDER ..." (8 each), "net.ORDER ..." (2 each),

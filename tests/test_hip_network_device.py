@@ -1,5 +1,6 @@
 """The source network's pass on the device (wai_set_network_pass, k_network_pass) and the coupling build without host waits:
-the host pass is the oracle, BIT FOR BIT -- one pass (wai_test_network_pass against wai_network_evaluate), a residual, the
+the host pass (the same network_pass, run on the host) must give the same bits -- one pass (wai_test_network_pass against
+wai_network_evaluate, which tests/test_network_pass_host.py holds to the recorded bits of the former recursion), a residual, the
 rates, the network's state and coupling blocks, a Newton step and whole input runs, host mode against device mode -- and the
 stream waits the passes and the coupling build issue are counted in both modes."""
 import ctypes as C
@@ -121,7 +122,7 @@ def fixture_case(oracle):
     return nc.reference_fixture(sep_enth)
 
 
-# ---- 1. one pass against the oracle ------------------------------------------------------------------------------------------
+# ---- 1. one pass against the host's ------------------------------------------------------------------------------------------
 def test_pass_reference_fixture(small, oracle):
     sim, lm = small
     c = fixture_case(oracle)

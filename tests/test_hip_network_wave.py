@@ -1,5 +1,6 @@
 """The source network's device pass with the wave-wide walk (wai_set_network_walk, WAI_NETWORK_WALK_WAVE: k_network_pass_wave,
-k_cb_pass_wave).  The host pass is the oracle, BIT FOR BIT: one pass through wai_test_network_pass against
+k_cb_pass_wave).  The host pass (the lane walk's network_pass, run on the host; tests/test_network_wave_host.py holds both
+walks to the recorded bits of the former recursion) must give the same bits: one pass through wai_test_network_pass against
 wai_network_evaluate with guard elements behind every output; a residual, the rates, the node states, the coupling blocks of
 the column loop and of the batched build, a Newton step and whole input runs with walk=wave against walk=lane and host mode.
 A network that needs more than the lane walk's 64 KB runs its pass on the device under the wave walk alone; one above 160 KiB
@@ -48,7 +49,7 @@ def check_wave_pass(sim, lm, c):
     return fed
 
 
-# ---- 1. one pass against the oracle ------------------------------------------------------------------------------------------
+# ---- 1. one pass against the host's ------------------------------------------------------------------------------------------
 def test_pass_reference_fixture(wave, oracle):
     sim, lm = wave
     c = fixture_case(oracle)

@@ -1,5 +1,5 @@
-"""Host logic of the source network (groups, reinjectors: csrc/capi.hip network_evaluate, reached through
-the context-free C-ABI entry wai_network_evaluate) against the known answers of the reference's own unit
+"""Host logic of the source network (groups, reinjectors: network_pass of csrc/network_pass.hpp, reached through
+the context-free C-ABI entry wai_network_evaluate of csrc/network.hip) against the known answers of the reference's own unit
 test test/unit/src/source_network_reinjector_test.F90: 39 sources, 6 groups (five with their own
 separator), 10 reinjectors with rate / proportion / unrated / node-less outputs, time tables, reinjector ->
 reinjector outputs and overflow chains.  No GPU involved: the library is only loaded."""

@@ -2,9 +2,11 @@
 program (tests/network_pass_host/main.cpp) built with the address and undefined-behaviour sanitizers builds the description
 from a text file, runs network_pass -- the text k_network_pass runs on the device -- and prints every double in hex.
 
-The oracle is the library's host pass, wai_network_evaluate (the library is only loaded): node states of sources and
-groups (6 doubles each) and reinjectors (8 each) must be equal BIT FOR BIT, and the (mode, value) pairs and enthalpies the
-pass hands the residual kernel must follow network_update's rule on those states."""
+The oracle is tests/golden/network_pass_bits.json: the node states of sources and groups (6 doubles each) and reinjectors
+(8 each) that the library's former recursive host pass gave for every case here, recorded before it was deleted.  The
+program's states AND those of the library's host pass, wai_network_evaluate (the same network_pass, built into the library;
+only loaded), must equal them BIT FOR BIT, and the (mode, value) pairs and enthalpies the pass hands the residual kernel
+must follow the hand-over rule (tests/network_cases.py, handed_over) on those states."""
 import inspect
 import os
 import re
@@ -70,16 +72,17 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
-def check(program, tmp_path, c, tag="case"):
+def check(program, tmp_path, c, name):
+    """case c, recorded under `name`: the program and the library against the recorded bits, then the hand-over"""
     from waiwera_amd import lib as wl
+    tag = re.sub(r"\W+", "_", name)
     path = tmp_path / (tag + ".txt")
     write_case(path, c)
     got = run(program, path)
     assert "error" not in got, got
+    nc.assert_recorded(name, c, got["sources"], got["groups"], got["reinjectors"], "the stand-alone program")
     S, G, R = wl.network_evaluate(c["spec"], c["rate"], c["enth"], c["sep"])
-    assert same_bits(got["sources"], S), (tag, np.argwhere(got["sources"].reshape(S.shape) != S))
-    assert same_bits(got["groups"], G), (tag, got["groups"], G)
-    assert same_bits(got["reinjectors"], R), (tag, got["reinjectors"], R)
+    nc.assert_recorded(name, c, S, G, R, "wai_network_evaluate")
     net, fed, enth = nc.handed_over(c, S)
     assert same_bits(got["net"], net), (tag, got["net"].reshape(-1, 2), net)
     want = np.full(len(c["rate"]), ENTH_IN)
@@ -98,23 +101,23 @@ def test_reference_reinjector_fixture(program, tmp_path, oracle):
         hf, hg = np.zeros(1), np.zeros(1)
         assert oracle.wo_separator_enthalpies(C.byref(e), float(p), ol.dp(hf), ol.dp(hg)) == 0
         return float(hf[0]), float(hg[0])
-    c = nc.reference_fixture(sep_enth)
-    got = check(program, tmp_path, c)
+    c = nc.on_recorded_inputs(nc.reference_fixture(sep_enth))
+    got = check(program, tmp_path, c, "reference_fixture")
     assert np.count_nonzero(got["net"].reshape(-1, 2)[:, 0] == 2.0) == len(nc.fed_sources(c["spec"])) > 0
 
 
 @pytest.mark.parametrize("scaling", [0, 1])
 def test_three_well_limiters(program, tmp_path, scaling):
-    got = check(program, tmp_path, nc.three_wells(scaling))
+    got = check(program, tmp_path, nc.three_wells(scaling), "three_wells(%d)" % scaling)
     assert np.allclose(got["sources"].reshape(3, 6)[:, 0], [[-4.0 * 6 / 9, -3.0 * 6 / 9, -2.0 * 6 / 9], [-4.0, -2.0, 0.0]][scaling], atol=1e-12)
 
 
 @pytest.mark.parametrize("outer", [7.0, 3.0, 100.0])
 def test_nested_three_deep(program, tmp_path, outer):
     """a progressive limit outside, a progressive group between, a uniform limit inside: the explicit stack and the arena of
-    node_limit tables against the recursion (outer 3.0 cuts into the inner groups, 100.0 leaves the outer limit idle)"""
+    node_limit tables against the recorded recursion (outer 3.0 cuts into the inner groups, 100.0 leaves the outer limit idle)"""
     c = nc.nested(outer)
-    got = check(program, tmp_path, c)
+    got = check(program, tmp_path, c, "nested(%g)" % outer)
     n_iw, n_dw, frames, arena, lds = got["sizes"]
     assert frames == 2 * 3 + 2 and arena == 3 + 9 + 9   # three levels; the outer and the middle group's tables [3][3]
     if outer < 100.0:
@@ -124,23 +127,26 @@ def test_nested_three_deep(program, tmp_path, outer):
 @pytest.mark.parametrize("flow", [1, 2])
 @pytest.mark.parametrize("scaling", [0, 1])
 def test_limit_behind_group_separator(program, tmp_path, flow, scaling):
-    got = check(program, tmp_path, nc.separated_limit(flow, scaling))
+    got = check(program, tmp_path, nc.separated_limit(flow, scaling), "separated_limit(%d,%d)" % (flow, scaling))
     if scaling == 0:   # one factor for every member scales the separated flows with the total: the limit is met exactly.
         # (progressive scaling shares the limit out by the MEMBERS' separated flows, which these wells without separators of
         # their own do not have: the oracle's bits are the check there)
         assert abs(got["groups"].reshape(1, 6)[0, 2 * flow]) <= 1.25 * (1 + 1e-12)
 
 
-@pytest.mark.parametrize("rates", [(-6.0, -4.0, 0.0, 1.5, 0.0, 0.0), (-6.0, -4.0, 0.0, 0.2, 0.0, 0.0), (0.0, 0.0, 0.0, 1.5, 0.0, 0.0)])
+CHAINS = [(-6.0, -4.0, 0.0, 1.5, 0.0, 0.0), (-6.0, -4.0, 0.0, 0.2, 0.0, 0.0), (0.0, 0.0, 0.0, 1.5, 0.0, 0.0)]
+
+
+@pytest.mark.parametrize("rates", CHAINS)
 def test_reinjector_chain(program, tmp_path, rates):
     """proportion, unrated and rate outputs, an output to a second reinjector, overflow to a source and down the chain"""
-    got = check(program, tmp_path, nc.chain(rates))
+    got = check(program, tmp_path, nc.chain(rates), "chain(%d)" % CHAINS.index(rates))
     assert list(np.flatnonzero(got["net"].reshape(-1, 2)[:, 0] == 2.0)) == [2, 3, 4, 5, 6]
 
 
 def test_zero_and_positive_totals(program, tmp_path):
     for k, c in enumerate(nc.signs()):
-        check(program, tmp_path, c, "signs%d" % k)
+        check(program, tmp_path, c, "signs(%d)" % k)
 
 
 def test_random_networks(program, tmp_path):
@@ -150,7 +156,7 @@ def test_random_networks(program, tmp_path):
         c = nc.random_network(seed)
         spec = c["spec"]
         assert len(c["rate"]) <= 12 and len(spec["groups"]) <= 4 and len(spec["reinjectors"]) <= 4
-        check(program, tmp_path, c, "random")
+        check(program, tmp_path, c, "random_network(%d)" % seed)
         seen["groups"] += bool(spec["groups"])
         seen["reinj"] += bool(spec["reinjectors"])
         seen["limited"] += any(g["limits"] for g in spec["groups"])
@@ -166,7 +172,7 @@ def test_cyclic_reinjectors_are_refused(program, tmp_path):
     write_case(path, c)
     assert run(program, path) == {"error": "source network reinjectors form a cycle"}
     from waiwera_amd import lib as wl
-    with pytest.raises(wl.WaiError):   # the host pass refuses it too (the same order function serves both)
+    with pytest.raises(wl.WaiError):   # the library refuses it too (the same builder serves both)
         wl.network_evaluate(c["spec"], c["rate"], c["enth"], c["sep"])
 
 

@@ -4,8 +4,10 @@ the wave schedule from a text file and runs network_pass_wave -- the text the wa
 times: lanes ascending, descending and in a seeded shuffle.
 
 The three runs must print the same bits (a difference is a race between the lanes of one phase), and those bits must be the
-library's host pass', wai_network_evaluate (the library is only loaded): node states of sources, groups and reinjectors, the
-(mode, value) pairs and the fed sources' enthalpies.  The schedule is checked against a construction from its definition
+recorded ones of tests/golden/network_pass_bits.json (the library's former recursive host pass; tests/network_cases.py), as
+must those of the library's host pass, wai_network_evaluate (the lane walk's network_pass; the library is only loaded):
+node states of sources, groups and reinjectors, then the (mode, value) pairs and the fed sources' enthalpies by the
+hand-over rule on those states.  The schedule is checked against a construction from its definition
 (tests/network_wave_cases.py), the refusals with their texts, the switch's values, names and defaults without a device."""
 import inspect
 import os
@@ -17,7 +19,7 @@ import pytest
 
 from tests import network_cases as nc
 from tests import network_wave_cases as wc
-from tests.test_network_pass_host import ENTH_IN, same_bits, write_case
+from tests.test_network_pass_host import CHAINS, ENTH_IN, same_bits, write_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORDERS = ("ascending", "descending", "shuffled")
@@ -47,17 +49,23 @@ def run(program, path, seed=7):
     return out
 
 
-def check(program, tmp_path, c, tag="case", seed=7):
+def check(program, tmp_path, c, name, seed=7):
+    """case c, recorded under `name`"""
     from waiwera_amd import lib as wl
+    tag = re.sub(r"\W+", "_", name)
     path = tmp_path / (tag + ".txt")
     write_case(path, c)
     got = run(program, path, seed)
     assert "error" not in got and "refused" not in got, got
     S, G, R = wl.network_evaluate(c["spec"], c["rate"], c["enth"], c["sep"])
+    nc.assert_recorded(name, c, S, G, R, "wai_network_evaluate")
+    for order in ORDERS:
+        nc.assert_recorded(name, c, *(got["%s.%s" % (k, order)] for k in ("sources", "groups", "reinjectors")),
+                           "the wave walk, lanes " + order)
     net, fed, enth = nc.handed_over(c, S)
     want_enth = np.full(len(c["rate"]), ENTH_IN)
     want_enth[fed] = enth
-    for order in ORDERS:      # the oracle's bits in every lane order: then the three are the same bits too
+    for order in ORDERS:      # the recorded bits in every lane order: then the three are the same bits too
         for name, want in (("sources", S), ("groups", G), ("reinjectors", R), ("net", net), ("enth", want_enth)):
             have = got["%s.%s" % (name, order)]
             assert same_bits(have, want), (tag, order, name, np.argwhere(have != np.ravel(want))[:8].ravel())
@@ -78,34 +86,35 @@ def test_reference_reinjector_fixture(program, tmp_path, oracle):
         hf, hg = np.zeros(1), np.zeros(1)
         assert oracle.wo_separator_enthalpies(C.byref(e), float(p), ol.dp(hf), ol.dp(hg)) == 0
         return float(hf[0]), float(hg[0])
-    c = nc.reference_fixture(sep_enth)
-    got = check(program, tmp_path, c)
+    c = nc.on_recorded_inputs(nc.reference_fixture(sep_enth))
+    got = check(program, tmp_path, c, "reference_fixture")
     assert np.count_nonzero(got["net.ascending"].reshape(-1, 2)[:, 0] == 2.0) == len(nc.fed_sources(c["spec"])) > 0
     for n in (63, 64, 65, 130):
-        check(program, tmp_path, nc.with_sources(c, n), "fixture%d" % n)
+        check(program, tmp_path, nc.with_sources(c, n), "with_sources(reference_fixture,%d)" % n)
 
 
 def test_cases_of_the_lane_walk(program, tmp_path):
     """every hand-made case of tests/network_cases.py"""
-    cases = [nc.three_wells(0), nc.three_wells(1)] + [nc.nested(o) for o in (7.0, 3.0, 100.0)]
-    cases += [nc.separated_limit(f, s) for f in (1, 2) for s in (0, 1)]
-    cases += [nc.chain(r) for r in [(-6.0, -4.0, 0.0, 1.5, 0.0, 0.0), (-6.0, -4.0, 0.0, 0.2, 0.0, 0.0), (0.0, 0.0, 0.0, 1.5, 0.0, 0.0)]]
-    cases += nc.signs()
-    for k, c in enumerate(cases):
-        check(program, tmp_path, c, "lane%d" % k)
+    cases = [("three_wells(%d)" % s, nc.three_wells(s)) for s in (0, 1)] + [("nested(%g)" % o, nc.nested(o)) for o in (7.0, 3.0, 100.0)]
+    cases += [("separated_limit(%d,%d)" % (f, s), nc.separated_limit(f, s)) for f in (1, 2) for s in (0, 1)]
+    cases += [("chain(%d)" % k, nc.chain(r)) for k, r in enumerate(CHAINS)]
+    cases += [("signs(%d)" % k, c) for k, c in enumerate(nc.signs())]
+    assert len(cases) == 16
+    for name, c in cases:
+        check(program, tmp_path, c, name)
 
 
 def test_random_networks_of_the_lane_walk(program, tmp_path):
     """the 200 seeded networks of tests/test_network_pass_host.py: none is refused"""
     for seed in range(200):
-        check(program, tmp_path, nc.random_network(seed), "random", seed)
+        check(program, tmp_path, nc.random_network(seed), "random_network(%d)" % seed, seed)
 
 
 @pytest.mark.parametrize("scaling", [0, 1])
 @pytest.mark.parametrize("m", [1, 63, 64, 65, 130])
 def test_wide_groups_at_the_staging_loops_edges(program, tmp_path, m, scaling):
     c = wc.wide_group(m, scaling)
-    got = check(program, tmp_path, c)
+    got = check(program, tmp_path, c, "wide_group(%d,%d)" % (m, scaling))
     S = got["sources.ascending"].reshape(m, 6)
     assert got["schedule.fan_in"][0] == m and got["schedule.stage"][0] == 8 + 6 * m
     assert not same_bits(S[:, 0], c["rate"])      # the limit is at work
@@ -117,14 +126,14 @@ def test_wide_groups_at_the_staging_loops_edges(program, tmp_path, m, scaling):
 
 @pytest.mark.parametrize("outer", [20.0, 6.0, 1000.0])
 def test_nested_three_deep_with_a_wide_inner_group(program, tmp_path, outer):
-    got = check(program, tmp_path, wc.nested_wide(70, outer))
+    got = check(program, tmp_path, wc.nested_wide(70, outer), "nested_wide(70,%g)" % outer)
     assert list(got["schedule.an"]) == [1, 2, 2] and list(got["schedule.dg"]) == [0, 0, 1]
     assert abs(got["groups.ascending"].reshape(3, 6)[0, 4]) <= 3.0 * (1 + 1e-12)      # the inner steam limit holds
 
 
 def test_reinjector_with_65_outputs_and_an_overflow(program, tmp_path):
     c = wc.wide_reinjector(65)
-    got = check(program, tmp_path, c)
+    got = check(program, tmp_path, c, "wide_reinjector(65)")
     assert got["schedule.fan_in"][0] == 65 and not got["schedule.out_shared"].any()
     R = got["reinjectors.ascending"].reshape(1, 8)
     assert R[0, 0] > 0 and R[0, 1] > 0 and R[0, 2] > 0      # water and steam delivered, and something left for the overflow
@@ -134,7 +143,7 @@ def test_two_outputs_onto_one_source_are_delivered_in_order(program, tmp_path):
     """the wave walk does not refuse them: the schedule flags every output onto a source with more than one writer, and the
     lane that runs the balance chain delivers those in output order"""
     c = wc.two_outputs_one_source()
-    got = check(program, tmp_path, c)
+    got = check(program, tmp_path, c, "two_outputs_one_source")
     assert list(got["schedule.out_shared"]) == [1, 0, 1, 0]
 
 
@@ -145,7 +154,7 @@ def test_wide_random_networks(program, tmp_path):
         c = wc.wide_random(seed)
         spec = c["spec"]
         assert len(c["rate"]) <= 200 and len(spec["groups"]) <= 6 and len(spec["reinjectors"]) <= 4
-        got = check(program, tmp_path, c, "wide", seed)
+        got = check(program, tmp_path, c, "wide_random(%d)" % seed, seed)
         seen["groups"] += bool(spec["groups"])
         seen["reinj"] += bool(spec["reinjectors"])
         seen["limited"] += any(g["limits"] for g in spec["groups"])

@@ -116,45 +116,25 @@ struct Sources {
 };
 
 // Source network: groups and reinjectors (src/source_network_group.F90, source_network_reinjector.F90),
-// evaluated on the host between the EOS sweep and the residual kernel of every residual evaluation,
-// as source_network%update is (src/source_network.F90:90-130).  Nodes carry the six flow values of
-// source_network_node_type.
-struct NetNode { double rate = 0, enth = 0, wrate = 0, wenth = 0, srate = 0, senth = 0; };
-struct NetRef { int kind = 0, index = -1; };       // 0 none, 1 source, 2 group, 3 reinjector
-struct NetGroup {
-  std::vector<NetRef> in;
-  int scaling = 0;                                 // 0 uniform, 1 progressive
-  int n_limit = 0, limit_type[3] = {0, 0, 0};      // 0 total, 1 water, 2 steam
-  double limit[3] = {0, 0, 0};
-  SrcCtl sep{};                                    // the group's own separator (sep_hf, sep_hg, sep_more); sep_hg = 0: none
-  NetNode node;
-};
-struct NetOutput {
-  int flow = 1;                                    // 1 water, 2 steam
-  NetRef out;
-  double rate = -1.0, proportion = -1.0, enthalpy = -1.0;
-  NetNode node;
-};
-struct NetReinjector {
-  NetRef in;                                       // source / group; none: fed by another reinjector
-  std::vector<NetOutput> out;
-  NetRef overflow;
-  NetNode node;                                    // water / steam rate = capacity (-1 unrated)
-  double in_w = 0, in_wh = 0, in_s = 0, in_sh = 0; // input flows
-  double out_w = 0, out_s = 0;                     // delivered
-  NetNode over;                                    // overflow
-  bool fed = false;                                // input set by an upstream reinjector this pass
-};
+// evaluated between the EOS sweep and the residual kernel of every residual evaluation, as source_network%update is
+// (src/source_network.F90:90-130) -- on the host unless wai_set_network_pass asks for the device.  One description
+// (flat: network_pass.hpp, built and validated by build_net_flat) and one pass (network_pass) serve both places; what is
+// kept of a pass is one run of doubles (net_state_keep: the six flow values of source_network_node_type per source and
+// group, eight doubles per reinjector), h_state on the host and d_state on the device.
 struct Network {
   bool on = false;
-  std::vector<NetGroup> groups;
-  std::vector<NetReinjector> reinjectors;
-  std::vector<int> reinj_order;                    // outputs / overflow targets before their feeders
-  std::vector<int> rate_specified, enth_specified; // per source
-  std::vector<NetNode> src;                        // per source, last pass
-  std::vector<double> h_enth0, h_raw, out_rate, out_enth;
-  std::vector<char> is_out;                        // sources a reinjector feeds (last pass)
+  // flat: the description, numbered by global source index where the network spans several ranks.  Its doubles carry the
+  // sources' separators and specified enthalpies (h_ctl, h_enth0): flat_gen counts their changes, flat_host_gen /
+  // flat_dev_gen say which of them flat.dw and the device's copy hold (network_flat_refresh, network_flat_upload).
+  // flat_fits: description and state fit a workgroup's static LDS (one rank only: the pass on the device)
+  NetFlatHost flat;
+  int flat_gen = 1, flat_host_gen = 0, flat_dev_gen = 0;
+  bool flat_fits = false;
+  std::vector<double> h_enth0, h_raw;              // per source: specified enthalpies; raw rates, then enthalpies (2 n)
   std::vector<SrcCtl> h_ctl;                       // host copy of the control records (separators)
+  // the host pass: its working state (net_state_carve), what it hands over per source of the network -- (mode, value)
+  // pairs and the fed sources' enthalpies -- and the state kept of the last pass, host or device (network_fetch_state)
+  std::vector<double> h_work, h_net, h_enth, h_state;
   DevBuf<double> d_raw;                            // device scratch: raw rates and enthalpies, 2 n
   // A network whose sources live on several ranks (source_network_group.F90:494-515, 579-596: gathers over the
   // group's communicator): every rank holds the whole description, numbered by GLOBAL source index; the sources' own
@@ -184,11 +164,7 @@ struct Network {
   DevBuf<int> d_cp_cells;
   DevBuf<double> d_cp_val, d_cp_f, d_cp_g;
   DevBuf<double> d_cp_x;                           // [m * bs + 2] x at the column cells, gathered over the ranks
-  // The pass on the device (wai_set_network_pass; network_pass.hpp, k_network_pass of kernels_network.hip).  flat: the
-  // description, built with the network on one rank; flat_fits: description and state fit a workgroup's static LDS;
-  // flat_dirty: the sources' separators or specified enthalpies (h_ctl, h_enth0) changed since the upload
-  NetFlatHost flat;
-  bool flat_fits = false, flat_dirty = true;
+  // The pass on the device (wai_set_network_pass; k_network_pass of kernels_network.hip): the description's two arrays
   DevBuf<int> d_flat_iw;
   // The wave-wide walk (wai_set_network_walk; network_wave.hpp): its schedule, built with the flat description whatever walk
   // is asked for.  wave_built: the topology was accepted (the schedule's lists and its need of LDS stand); wave_ok: and the
@@ -198,8 +174,8 @@ struct Network {
   std::string wave_err;
   DevBuf<int> d_wave_ww;
   DevBuf<double> d_flat_dw;
-  DevBuf<double> d_state;                          // sources 6 each, groups 6 each, reinjectors 8 each: the last device pass
-  bool state_on_device = false;                    // ... is newer than src / groups / reinjectors above (network_fetch_state)
+  DevBuf<double> d_state;                          // what the last device pass kept (net_state_keep)
+  bool state_on_device = false;                    // ... is newer than h_state (network_fetch_state)
   bool enth_stale = false;                         // the host pass hands the device every fed source's enthalpy again
   DevBuf<double> d_cp_yh;                          // coupling build on the device: y_jk and h of the column in hand
   DevBuf<int> d_cp_flag;                           // ... an entry of E is nonzero

@@ -186,7 +186,11 @@ BcgsPlan bcgs_plan(const wai_ctx* c, const LinSys& sys);
 int bcgs_first_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
 int bcgs_second_half(wai_ctx* c, LinSys& sys, const BcgsPlan& pl);
 // ---- network.hip -------------------------------------------------------------------------------------------------
-void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n);   // separator.F90:139-166, 212-260
+// a control record's separator as the pass reads it: hf, hg of stage 1, then (hf, hg) of stages 2..4
+inline void src_separator(const SrcCtl& k, double* sep8) {
+  sep8[0] = k.sep_hf; sep8[1] = k.sep_hg;
+  for (int q = 0; q < 6; q++) sep8[2 + q] = k.sep_more[q];
+}
 // the pass on the device is in force (wai_set_network_pass): asked for, one rank -- by the communicator's size alone, so
 // every rank decides alike -- and a network whose description and state fit a workgroup's LDS
 // The wave-wide walk (wai_set_network_walk) can run: asked for, one rank, and a network its schedule accepts.  It holds
@@ -206,7 +210,7 @@ inline bool cp_batched(const wai_ctx* c) {
 }
 constexpr long long COUPLING_BATCH_BYTES = 256LL << 20;   // the most scratch one chunk of its columns takes (coupling_batch.hpp)
 int network_update(wai_ctx* c);
-int network_fetch_state(wai_ctx* c);       // the last device pass' node states to the host's Network
+int network_fetch_state(wai_ctx* c);       // what the last device pass kept to Network::h_state
 int network_fetch_couplings(wai_ctx* c);   // the device-built coupling blocks to h_cp_val
 int network_couplings(wai_ctx* c, double dt, double* y, const double* lhs_old);
 int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t);   // t = A x, + E x where the source network's blocks belong to sys

@@ -1,7 +1,7 @@
 // The source network on the device (wai_set_network_pass, WAI_NETWORK_PASS_DEVICE): k_network_pass runs the pass of
 // network_pass.hpp -- the text the host runs too -- in one wave on LDS, and three small kernels keep the coupling build's
 // column loop (network_couplings, network.hip) on the stream: perturb y, difference the gathered rows into the blocks,
-// restore y.  Built without FMA contraction, like the assembly units: the host pass is the oracle, bit for bit.
+// restore y.  Built without FMA contraction, like the assembly units: the host pass gives the same bits.
 #include "context.hpp"
 #include "network_pass.hpp"
 #include "network_wave.hpp"
@@ -12,7 +12,7 @@ namespace wai {
 //   [ dw | raw 2n | state (net_state_carve) | iw ]          net_lds_doubles(h) <= NET_LDS_DOUBLES, decided by the builder
 // The per-source parts are strided over the 64 lanes; lane 0 walks groups and reinjectors.
 // raw: launch_source_rates(c, raw, true); net, enth: Sources::net, Sources::enth (enth: fed sources only);
-// state_out: sources 6 each, groups 6 each, reinjectors 8 each (as wai_get_source_network)
+// state_out: sources 6 each, groups 6 each, reinjectors 8 each (net_state_keep)
 __global__ __launch_bounds__(64) void k_network_pass(NetFlat h, const int* __restrict__ iw, const double* __restrict__ dw,
                                                      const double* __restrict__ raw, double* __restrict__ net,
                                                      double* __restrict__ enth, double* __restrict__ state_out) {
@@ -36,9 +36,7 @@ __global__ __launch_bounds__(64) void k_network_pass(NetFlat h, const int* __res
   __syncthreads();
   network_pass_final(v, sraw, s, t, 64);
   __syncthreads();
-  const int nn = NET_NODE * (n + h.n_grp);   // sources and groups are one run of the state
-  for (int i = t; i < nn; i += 64) state_out[i] = s.src[i];
-  for (int i = t; i < 8 * h.n_rj; i += 64) state_out[nn + i] = s.rj[RJ_STATE * (i >> 3) + RJ_OUT_W + (i & 7)];
+  net_state_keep(h, s, state_out, t, 64);
 }
 
 // The same pass with the wave-wide walk (wai_set_network_walk, WAI_NETWORK_WALK_WAVE; network_wave.hpp): one wave, dynamic
@@ -51,9 +49,7 @@ __global__ __launch_bounds__(64) void k_network_pass_wave(NetFlat h, NetWave w, 
   const int t = threadIdx.x;
   NetState s;
   net_wave_pass_lds(h, w, iw, dw, ww, raw, net, enth, lds, s);   // (ends with a barrier)
-  const int nn = NET_NODE * (h.n_src + h.n_grp);
-  for (int i = t; i < nn; i += 64) state_out[i] = s.src[i];
-  for (int i = t; i < 8 * h.n_rj; i += 64) state_out[nn + i] = s.rj[RJ_STATE * (i >> 3) + RJ_OUT_W + (i & 7)];
+  net_state_keep(h, s, state_out, t, 64);
 }
 
 // y_jk + h, with h by the Jacobian's rule (MatFDColoring "ds", as fd_step of the assembly sweeps); yh keeps y_jk and h

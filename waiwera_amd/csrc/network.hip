@@ -7,212 +7,46 @@ using namespace wai;
 
 namespace wai {
 
-// ---- source network: groups and reinjectors, one pass on the host -------------------------------
+// ---- source network: groups and reinjectors, one pass --------------------------------------------
 // source_network%update (src/source_network.F90:90-130) after the sources' own controls: group sums
 // (source_network_group.F90:239-287) and limiters with uniform (:479-534) or progressive (:652-763;
 // array_progressive_limit, utils.F90:607-647) scaling, reinjector capacities
-// (source_network_reinjector.F90:1014-1112) and distribution with overflow (:1115-1292, :970-1010).
-// Serial: every source of the network lives on this rank.
-void net_separate(const SrcCtl& k, double rate, double enth, NetNode& n) {   // separator.F90:139-166, 212-260
-  double q = rate, h = enth, steam_m = 0.0, steam_e = 0.0;
-  for (int st = 0; st < 4; st++) {
-    const double hf = st == 0 ? k.sep_hf : k.sep_more[2 * (st - 1)], hg = st == 0 ? k.sep_hg : k.sep_more[2 * (st - 1) + 1];
-    if (st > 0 && !(hg > 0.0)) break;
-    double f, hw, hs;
-    if (h <= hf) { f = 0.0; hw = h; hs = 0.0; }
-    else if (h <= hg) { f = (h - hf) / (hg - hf); hw = hf; hs = hg; }
-    else { f = 1.0; hw = 0.0; hs = h; }
-    const double sr = f * q;
-    steam_m += sr; steam_e += sr * hs;
-    q = (1.0 - f) * q; h = hw;
-  }
-  n.wrate = q; n.wenth = h; n.srate = steam_m;
-  n.senth = std::fabs(steam_m) > 1.e-9 ? steam_e / steam_m : 0.0;
-}
-void net_zero_separated(NetNode& n) { n.wrate = n.wenth = n.srate = n.senth = 0.0; }
-void net_source_set_rate(Network& nw, int i, double rate) {   // source_network_node_set_rate + get_separated_flows
-  NetNode& n = nw.src[i];
-  n.rate = rate;
-  if (rate < 0.0 && i < (int)nw.h_ctl.size() && nw.h_ctl[i].sep_hg > 0.0) net_separate(nw.h_ctl[i], rate, n.enth, n);
-  else net_zero_separated(n);
-}
-NetNode& net_node(Network& nw, const NetRef& r) { return r.kind == 1 ? nw.src[r.index] : nw.groups[r.index].node; }
-double net_rate_by_type(const NetNode& n, int type) { return type == 1 ? n.wrate : (type == 2 ? n.srate : n.rate); }
-void net_group_sum(Network& nw, NetGroup& g) {   // source_network_group_sum + default_separated_flows
-  double q = 0.0, qh = 0.0;
-  for (const NetRef& r : g.in) { const NetNode& n = net_node(nw, r); q += n.rate; qh += n.rate * n.enth; }
-  g.node.enth = std::fabs(q) > 1.e-9 ? qh / q : 0.0;
-  g.node.rate = q;
-  if (q < 0.0 && g.sep.sep_hg > 0.0) net_separate(g.sep, q, g.node.enth, g.node);   // the group's own separator (:375-403)
-  else if (q < 0.0) {
-    double wq = 0, wqh = 0, sq = 0, sqh = 0;
-    for (const NetRef& r : g.in) {
-      const NetNode& n = net_node(nw, r);
-      wq += n.wrate; wqh += n.wrate * n.wenth; sq += n.srate; sqh += n.srate * n.senth;
-    }
-    g.node.wrate = wq; g.node.srate = sq;
-    g.node.wenth = std::fabs(wq) > 1.e-9 ? wqh / wq : 0.0;
-    g.node.senth = std::fabs(sq) > 1.e-9 ? sqh / sq : 0.0;
-  } else net_zero_separated(g.node);
-}
-void net_scale(Network& nw, const NetRef& r, double scale) {   // scale_rate, recursive through groups
-  if (r.kind == 1) { net_source_set_rate(nw, r.index, nw.src[r.index].rate * scale); return; }
-  NetGroup& g = nw.groups[r.index];
-  for (const NetRef& q : g.in) net_scale(nw, q, scale);
-  net_group_sum(nw, g);
-}
-bool net_min_limit_scale(const NetNode& n, int nl, const int* type, const double* limit, double& scale) {
-  bool over = false;
-  scale = 1.0;
-  for (int i = 0; i < nl; i++) {
-    const double a = std::fabs(net_rate_by_type(n, type[i]));
-    if (a > limit[i]) { over = true; if (a > 1.e-6) scale = std::min(scale, limit[i] / a); }
-  }
-  return over;
-}
-void net_limit_inputs(Network& nw, const NetRef& r, int nl, const int* type, const double* limit);
-void net_limit_rate(Network& nw, const NetRef& r, int nl, const int* type, const double* limit) {
-  double scale;
-  if (r.kind == 1 || nw.groups[r.index].scaling == 0) {   // node / uniform group: one factor for everything below
-    if (net_min_limit_scale(net_node(nw, r), nl, type, limit, scale)) net_scale(nw, r, scale);
-    return;
-  }
-  bool over = false;
-  for (int i = 0; i < nl; i++) over = over || std::fabs(net_rate_by_type(nw.groups[r.index].node, type[i])) > limit[i];
-  if (over) net_limit_inputs(nw, r, nl, type, limit);
-}
-void net_limit_inputs(Network& nw, const NetRef& r, int nl, const int* type, const double* limit) {
-  if (r.kind == 1 || nw.groups[r.index].scaling == 0) { net_limit_rate(nw, r, nl, type, limit); return; }
-  NetGroup& g = nw.groups[r.index];   // progressive: inputs are limited in order until the total is met
-  const size_t m = g.in.size();
-  std::vector<double> node_limit(m * 3, 0.0);
-  for (int il = 0; il < nl; il++) {
-    double sum = 0.0;
-    for (size_t i = 0; i < m; i++) {
-      const double a = std::fabs(net_rate_by_type(net_node(nw, g.in[i]), type[il]));
-      if (sum + a > limit[il]) { node_limit[i * 3 + il] = limit[il] - sum; break; }
-      node_limit[i * 3 + il] = a;
-      sum += a;
-    }
-  }
-  for (size_t i = 0; i < m; i++) net_limit_inputs(nw, g.in[i], nl, type, &node_limit[i * 3]);
-  net_group_sum(nw, g);
-}
-void net_node_limit_rate(double node_rate, double& rate) {   // reinjector.F90:199-215
-  if (node_rate > -1.0) rate = rate > -1.0 ? std::min(rate, node_rate) : node_rate;
-}
-void net_total(double wr, double wh, double sr, double sh, double& rate, double& enth) {
-  rate = wr + sr;
-  enth = rate > 1.e-6 ? (wr * wh + sr * sh) / rate : 0.0;
-}
-
-// one pass of the network on the host: nw.h_raw (rates, then enthalpies of the sources' own controls) ->
-// node states, nw.is_out / out_rate / out_enth for the sources the reinjectors feed
-void network_evaluate(Network& nw) {
-  const int n = (int)nw.src.size();
-  for (int i = 0; i < n; i++) { nw.src[i].enth = nw.h_raw[n + i]; net_source_set_rate(nw, i, nw.h_raw[i]); }
-  for (NetGroup& g : nw.groups) net_group_sum(nw, g);
-  for (size_t gi = 0; gi < nw.groups.size(); gi++) {
-    NetGroup& g = nw.groups[gi];
-    if (!g.n_limit) continue;
-    NetRef self; self.kind = 2; self.index = (int)gi;
-    net_limit_rate(nw, self, g.n_limit, g.limit_type, g.limit);
-    for (size_t gj = gi + 1; gj < nw.groups.size(); gj++) net_group_sum(nw, nw.groups[gj]);   // sum_out
-  }
-  // what the injection sources can take: their own specified rate, -1 if none
-  auto specified = [&](int i) { return nw.rate_specified[i] ? nw.h_raw[i] : -1.0; };
-  std::vector<double>& out_rate = nw.out_rate;
-  std::vector<double>& out_enth = nw.out_enth;
-  std::vector<char>& is_out = nw.is_out;
-  out_rate.assign(n, 0.0); out_enth.assign(n, 0.0); is_out.assign(n, 0);
-  for (NetReinjector& r : nw.reinjectors) r.fed = false;
-  for (int ri : nw.reinj_order) {   // capacities, downstream first
-    NetReinjector& r = nw.reinjectors[ri];
-    double cap[3] = {0.0, 0.0, 0.0};
-    for (const NetOutput& o : r.out) {
-      double node_rate = -1.0;
-      if (o.out.kind == 1) node_rate = specified(o.out.index);
-      else if (o.out.kind == 3) node_rate = o.flow == 1 ? nw.reinjectors[o.out.index].node.wrate : nw.reinjectors[o.out.index].node.srate;
-      else continue;
-      double& cc = cap[o.flow];
-      if (node_rate > -1.0) { if (cc > -1.0) cc += node_rate; } else cc = -1.0;
-    }
-    r.node.wrate = cap[1]; r.node.srate = cap[2];
-  }
-  for (auto it = nw.reinj_order.rbegin(); it != nw.reinj_order.rend(); ++it) {   // distribution, upstream first
-    NetReinjector& r = nw.reinjectors[*it];
-    if (r.in.kind == 1 || r.in.kind == 2) {
-      const NetNode& in = net_node(nw, r.in);
-      r.in_w = std::fabs(in.wrate); r.in_wh = in.wenth; r.in_s = std::fabs(in.srate); r.in_sh = in.senth;
-    } else if (!r.fed) { r.in_w = r.in_wh = r.in_s = r.in_sh = 0.0; }
-    double wbal = r.in_w, sbal = r.in_s;
-    r.out_w = r.out_s = 0.0;
-    for (NetOutput& o : r.out) {
-      double qw = 0.0, qs = 0.0;
-      double& q = o.flow == 1 ? qw : qs;
-      if (o.rate > -1.0) q = o.rate;                                              // rate output (:463-480)
-      else if (o.proportion >= 0.0) q = o.proportion * (o.flow == 1 ? r.in_w : r.in_s);   // proportion output (:484-501)
-      else q = -1.0;                                                              // whatever is left
-      double node_rate = -1.0;
-      if (o.out.kind == 1) node_rate = specified(o.out.index);
-      else if (o.out.kind == 3) node_rate = o.flow == 1 ? nw.reinjectors[o.out.index].node.wrate : nw.reinjectors[o.out.index].node.srate;
-      if (o.out.kind) net_node_limit_rate(node_rate, q);
-      double& bal = o.flow == 1 ? wbal : sbal;
-      double& tot = o.flow == 1 ? r.out_w : r.out_s;
-      if (q < 0.0) q = bal;
-      q = std::min(q, bal);
-      bal = std::max(bal - q, 0.0);
-      tot += q;
-      // enthalpies: specified for this flow type, or the input's
-      const double wh = (o.enthalpy > 0.0 && o.flow == 1) ? o.enthalpy : (o.enthalpy > 0.0 ? 0.0 : r.in_wh);
-      const double sh = (o.enthalpy > 0.0 && o.flow == 2) ? o.enthalpy : (o.enthalpy > 0.0 ? 0.0 : r.in_sh);
-      o.node.wrate = qw; o.node.wenth = wh; o.node.srate = qs; o.node.senth = sh;
-      net_total(qw, wh, qs, sh, o.node.rate, o.node.enth);
-      if (o.out.kind == 1) {
-        const int i = o.out.index;
-        is_out[i] = 1; out_rate[i] = o.node.rate; out_enth[i] = o.node.enth;
-        nw.src[i].wrate = qw; nw.src[i].wenth = wh; nw.src[i].srate = qs; nw.src[i].senth = sh;
-      } else if (o.out.kind == 3) {
-        NetReinjector& d = nw.reinjectors[o.out.index];
-        if (!d.fed) { d.in_w = d.in_wh = d.in_s = d.in_sh = 0.0; d.fed = true; }
-        if (o.flow == 1) { d.in_w += qw; d.in_wh = wh; } else { d.in_s += qs; d.in_sh = sh; }
-      }
-    }
-    r.over.wrate = wbal; r.over.wenth = r.in_wh; r.over.srate = sbal; r.over.senth = r.in_sh;
-    net_total(wbal, r.in_wh, sbal, r.in_sh, r.over.rate, r.over.enth);
-    if (r.overflow.kind == 3) {
-      NetReinjector& d = nw.reinjectors[r.overflow.index];
-      d.in_w = wbal; d.in_wh = r.in_wh; d.in_s = sbal; d.in_sh = r.in_sh; d.fed = true;
-    } else if (r.overflow.kind == 1) {   // an overflow source takes what is left, whatever its own rate says (:1002-1006)
-      const int i = r.overflow.index;
-      is_out[i] = 1; out_rate[i] = r.over.rate; out_enth[i] = r.over.enth;
-      nw.src[i].wrate = wbal; nw.src[i].wenth = r.in_wh; nw.src[i].srate = sbal; nw.src[i].senth = r.in_sh;
-    }
-  }
-  for (int i = 0; i < n; i++)
-    if (is_out[i]) {   // reinjector_output_update (:283-320): rate always, enthalpy unless the source has its own
-      nw.src[i].rate = out_rate[i];
-      nw.src[i].enth = (nw.enth_specified[i] && i < (int)nw.h_enth0.size()) ? nw.h_enth0[i] : out_enth[i];
-    }
+// (source_network_reinjector.F90:1014-1112) and distribution with overflow (:1115-1292, :970-1010): network_pass of
+// network_pass.hpp, here on the host.  raw: rates, then enthalpies of the sources' own controls; work: the pass' scratch;
+// net, enth (null: not wanted): what the residual kernel is handed, per source of the description; kept: net_state_keep.
+// Returns the working state (is_out: the sources a reinjector feeds)
+static NetState network_pass_host(const NetFlatHost& F, const double* raw, std::vector<double>& work, double* net, double* enth,
+                                  double* kept) {
+  work.resize((size_t)net_state_doubles(F.h));
+  NetState s;
+  net_state_carve(F.h, work.data(), s);
+  s.net = net; s.enth = enth;
+  network_pass(F.view(), raw, s);
+  net_state_keep(F.h, s, kept, 0, 1);
+  return s;
 }
 
 // a stream wait of network_update / network_couplings, counted (wai_test_network_stats)
 #define NET_WAIT(c) do { (c)->net_waits++; HIPCHK(c, hipStreamSynchronize((c)->stream)); } while (0)
 
-// the description on the device, with the sources' separators and specified enthalpies as they stand now
-static int network_flat_upload(wai_ctx* c) {
-  Network& nw = c->net;
+// the sources' separators and specified enthalpies as they stand now, in the description's doubles
+static void network_flat_refresh(Network& nw) {
+  if (nw.flat_host_gen == nw.flat_gen) return;
   const NetFlat& h = nw.flat.h;
   for (int i = 0; i < h.n_src; i++) {
     nw.flat.dw[h.src_enth0 + i] = i < (int)nw.h_enth0.size() ? nw.h_enth0[i] : 0.0;
-    SrcCtl k{};
-    if (i < (int)nw.h_ctl.size()) k = nw.h_ctl[i];
-    double* sep = &nw.flat.dw[h.src_sep + 8 * i];
-    sep[0] = k.sep_hf; sep[1] = k.sep_hg;
-    for (int q = 0; q < 6; q++) sep[2 + q] = k.sep_more[q];
+    src_separator(i < (int)nw.h_ctl.size() ? nw.h_ctl[i] : SrcCtl{}, &nw.flat.dw[h.src_sep + 8 * i]);
   }
+  nw.flat_host_gen = nw.flat_gen;
+}
+// ... and the description on the device, where that is older
+static int network_flat_upload(wai_ctx* c) {
+  Network& nw = c->net;
+  if (nw.flat_dev_gen == nw.flat_gen) return 0;
+  network_flat_refresh(nw);
+  const NetFlat& h = nw.flat.h;
   if (!nw.d_flat_iw && (nw.d_flat_iw.alloc(c, (size_t)h.n_iw) || nw.d_flat_dw.alloc(c, (size_t)h.n_dw) ||
-                        nw.d_state.alloc(c, (size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)h.n_rj)))
+                        nw.d_state.alloc(c, (size_t)net_kept_doubles(h))))
     return -1;
   if (nw.wave_ok && !nw.d_wave_ww) {   // the wave walk's schedule: it changes with the description alone
     if (nw.d_wave_ww.alloc(c, (size_t)std::max(nw.wave.w.n_ww, 1))) return -1;
@@ -221,7 +55,7 @@ static int network_flat_upload(wai_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(nw.d_flat_iw, nw.flat.iw.data(), sizeof(int) * (size_t)h.n_iw, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(nw.d_flat_dw, nw.flat.dw.data(), sizeof(double) * (size_t)h.n_dw, hipMemcpyHostToDevice, c->stream));
   NET_WAIT(c);   // (only after the description changed: the host arrays are free again)
-  nw.flat_dirty = false;
+  nw.flat_dev_gen = nw.flat_gen;
   return 0;
 }
 
@@ -234,7 +68,7 @@ int network_update(wai_ctx* c) {
   if (ng == 0) return 0;
   c->net_passes++;
   if (net_on_device(c)) {   // k_network_pass: nothing comes to the host and nobody waits
-    if (nw.flat_dirty && network_flat_upload(c)) return -1;
+    if (network_flat_upload(c)) return -1;
     launch_source_rates(c, nw.d_raw, true);
     if (launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state, net_wave_usable(c))) return -1;
     nw.state_on_device = true;
@@ -256,25 +90,18 @@ int network_update(wai_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(nw.h_raw.data(), nw.d_all, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, c->stream));
     NET_WAIT(c);
   }
-  network_evaluate(nw);
+  network_flat_refresh(nw);
+  const NetState s = network_pass_host(nw.flat, nw.h_raw.data(), nw.h_work, nw.h_net.data(), nw.h_enth.data(), nw.h_state.data());
   if (!n) return 0;
-  const std::vector<double>& out_rate = nw.out_rate;
-  const std::vector<char>& is_out = nw.is_out;
-  // hand the result to the device: scale factors of group members, rates / enthalpies of reinjection sources
+  // hand the result to the device: this rank's (mode, value) pairs -- scale factors of group members, rates of reinjection
+  // sources -- and the enthalpies of the sources a reinjector feeds
   bool enth_changed = false;
   const bool stale = nw.enth_stale;   // device passes wrote the fed sources' enthalpies since l_enth was handed over
   nw.enth_stale = false;
   for (int i = 0; i < n; i++) {
     const int g = span ? nw.gidx[i] : i;
-    double mode = 0.0, val = 0.0;
-    if (is_out[g]) {
-      mode = 2.0; val = out_rate[g];
-      const double e = nw.src[g].enth;
-      if (e != nw.l_enth[i] || stale) { nw.l_enth[i] = e; enth_changed = true; }
-    } else if (nw.src[g].rate != nw.h_raw[g]) {
-      mode = 1.0; val = nw.h_raw[g] != 0.0 ? nw.src[g].rate / nw.h_raw[g] : 1.0;
-    }
-    nw.l_net[2 * i] = mode; nw.l_net[2 * i + 1] = val;
+    nw.l_net[2 * i] = nw.h_net[2 * g]; nw.l_net[2 * i + 1] = nw.h_net[2 * g + 1];
+    if (s.is_out[g] != 0.0 && (nw.h_enth[g] != nw.l_enth[i] || stale)) { nw.l_enth[i] = nw.h_enth[g]; enth_changed = true; }
   }
   HIPCHK(c, hipMemcpyAsync(c->src.net, nw.l_net.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   if (enth_changed)
@@ -286,19 +113,8 @@ int network_update(wai_ctx* c) {
 int network_fetch_state(wai_ctx* c) {
   Network& nw = c->net;
   if (!nw.state_on_device || !nw.d_state) return 0;
-  const NetFlat& h = nw.flat.h;
-  std::vector<double> st((size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)h.n_rj);
-  HIPCHK(c, hipMemcpyAsync(st.data(), nw.d_state, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(nw.h_state.data(), nw.d_state, sizeof(double) * nw.h_state.size(), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  auto get = [](NetNode& n, const double* o) { n.rate = o[0]; n.enth = o[1]; n.wrate = o[2]; n.wenth = o[3]; n.srate = o[4]; n.senth = o[5]; };
-  for (int i = 0; i < h.n_src; i++) get(nw.src[i], &st[(size_t)NET_NODE * i]);
-  for (int g = 0; g < h.n_grp; g++) get(nw.groups[g].node, &st[(size_t)NET_NODE * (h.n_src + g)]);
-  for (int r = 0; r < h.n_rj; r++) {
-    const double* o = &st[(size_t)NET_NODE * (h.n_src + h.n_grp) + 8 * (size_t)r];
-    NetReinjector& R = nw.reinjectors[r];
-    R.out_w = o[0]; R.out_s = o[1];
-    get(R.over, o + 2);
-  }
   nw.state_on_device = false;
   return 0;
 }
@@ -515,94 +331,32 @@ int apply_operator(wai_ctx* c, const LinSys& sys, const double* x, double* t) {
   return 0;
 }
 
-// the flat description of wai_set_source_network -> Network (no device involved)
-int network_build(Network& nw, int n, const int* rate_specified, const int* enthalpy_specified, int n_groups,
-                  const int* grp_ptr, const int* grp_in_kind, const int* grp_in, const int* grp_scaling,
-                  const int* grp_limit_type, const double* grp_limit, const double* grp_sep, int n_reinj,
-                  const int* rj_in_kind, const int* rj_in, const int* rj_out_ptr, const int* out_flow,
-                  const int* out_kind, const int* out_node, const double* out_rate, const double* out_proportion,
-                  const double* out_enthalpy, const int* rj_overflow_kind, const int* rj_overflow, std::string& err) {
-  if (!n || !rate_specified || !enthalpy_specified) { err = "source network without sources"; return -2; }
-  auto ok = [&](int kind, int idx) {
-    return kind == 0 || (kind == 1 && idx >= 0 && idx < n) || (kind == 2 && idx >= 0 && idx < n_groups) ||
-           (kind == 3 && idx >= 0 && idx < n_reinj);
-  };
-  nw.rate_specified.assign(rate_specified, rate_specified + n);
-  nw.enth_specified.assign(enthalpy_specified, enthalpy_specified + n);
-  nw.groups.assign(std::max(n_groups, 0), NetGroup());
-  for (int g = 0; g < n_groups; g++) {
-    NetGroup& G = nw.groups[g];
-    for (int q = grp_ptr[g]; q < grp_ptr[g + 1]; q++) {
-      if (!ok(grp_in_kind[q], grp_in[q]) || grp_in_kind[q] == 0 || grp_in_kind[q] == 3 || (grp_in_kind[q] == 2 && grp_in[q] >= g)) {
-        err = "source network group: inputs are sources or earlier groups"; return -2;
-      }
-      NetRef r; r.kind = grp_in_kind[q]; r.index = grp_in[q];
-      G.in.push_back(r);
-    }
-    G.scaling = grp_scaling ? grp_scaling[g] : 0;
-    for (int l = 0; l < 3; l++)
-      if (grp_limit_type && grp_limit_type[3 * g + l] >= 0) {
-        G.limit_type[G.n_limit] = grp_limit_type[3 * g + l]; G.limit[G.n_limit] = grp_limit[3 * g + l]; G.n_limit++;
-      }
-    std::memset(&G.sep, 0, sizeof(G.sep));
-    if (grp_sep) {
-      G.sep.sep_hf = grp_sep[8 * g]; G.sep.sep_hg = grp_sep[8 * g + 1];
-      for (int q = 0; q < 6; q++) G.sep.sep_more[q] = grp_sep[8 * g + 2 + q];
-    }
-  }
-  nw.reinjectors.assign(std::max(n_reinj, 0), NetReinjector());
-  for (int r = 0; r < n_reinj; r++) {
-    NetReinjector& R = nw.reinjectors[r];
-    if (!ok(rj_in_kind[r], rj_in[r]) || rj_in_kind[r] == 3 || !ok(rj_overflow_kind[r], rj_overflow[r]) || rj_overflow_kind[r] == 2) {
-      err = "source network reinjector: bad input / overflow reference"; return -2;
-    }
-    R.in.kind = rj_in_kind[r]; R.in.index = rj_in[r];
-    R.overflow.kind = rj_overflow_kind[r]; R.overflow.index = rj_overflow[r];
-    for (int q = rj_out_ptr[r]; q < rj_out_ptr[r + 1]; q++) {
-      if (!ok(out_kind[q], out_node[q]) || out_kind[q] == 2 || (out_flow[q] != 1 && out_flow[q] != 2)) {
-        err = "source network reinjector: bad output"; return -2;
-      }
-      NetOutput o;
-      o.flow = out_flow[q]; o.out.kind = out_kind[q]; o.out.index = out_node[q];
-      o.rate = out_rate[q]; o.proportion = out_proportion[q]; o.enthalpy = out_enthalpy[q];
-      R.out.push_back(o);
-    }
-  }
-  // order: a reinjector after every reinjector it delivers or overflows to (network_pass.hpp: the flat description's too)
-  if (!net_reinjector_order(std::max(n_reinj, 0), rj_out_ptr, out_kind, out_node, rj_overflow_kind, rj_overflow, nw.reinj_order)) {
-    err = "source network reinjectors form a cycle"; return -2;
-  }
-  nw.src.assign(n, NetNode());
-  nw.h_raw.assign(2 * (size_t)n, 0.0);
-  if (nw.h_enth0.size() != (size_t)n) nw.h_enth0.assign(n, 0.0);
-  return 0;
-}
 // the cells whose equations and unknowns the network ties together: every source a group, a reinjector input,
 // output or overflow names (source_network_identify_source_dependencies, source_network.F90:359-498, walks the
 // same lists: production cells of a reinjector's input x cells of the sources it -- or the reinjectors
 // it delivers or overflows to -- feeds; the members of a limited group among each other).  The coupling
 // blocks E cover all pairs of these cells, a superset of the reference's dependency list.
-void network_cells(Network& nw, int n) {
-  std::vector<char> in_net((size_t)n, 0);
-  auto mark = [&](const NetRef& r) { if (r.kind == 1 && r.index >= 0 && r.index < n) in_net[r.index] = 1; };
-  for (const NetGroup& g : nw.groups) for (const NetRef& r : g.in) mark(r);
-  for (const NetReinjector& r : nw.reinjectors) { mark(r.in); mark(r.overflow); for (const NetOutput& o : r.out) mark(o.out); }
-  nw.cp_cells.clear();
-  for (int i = 0; i < n && i < (int)nw.h_cell.size(); i++) if (in_net[i]) nw.cp_cells.push_back(nw.h_cell[i]);
-  std::sort(nw.cp_cells.begin(), nw.cp_cells.end());
-  nw.cp_cells.erase(std::unique(nw.cp_cells.begin(), nw.cp_cells.end()), nw.cp_cells.end());
-}
-// the same over several ranks: the network's cells of all ranks, ordered by (owner rank, local cell); this rank's own
-// are then one contiguous run of the columns and, in that order, the rows it differences and applies
-void network_cells_span(Network& nw, int ng, const std::vector<double>& id, int rank) {
-  std::vector<char> in_net((size_t)ng, 0);
-  auto mark = [&](const NetRef& r) { if (r.kind == 1 && r.index >= 0 && r.index < ng) in_net[r.index] = 1; };
-  for (const NetGroup& g : nw.groups) for (const NetRef& r : g.in) mark(r);
-  for (const NetReinjector& r : nw.reinjectors) { mark(r.in); mark(r.overflow); for (const NetOutput& o : r.out) mark(o.out); }
-  std::vector<double> u;
-  for (int g = 0; g < ng; g++) if (in_net[g]) u.push_back(id[g]);
+// key[i]: what stands for source i's cell; the distinct keys of the named sources, ascending
+template <class T>
+static std::vector<T> network_cells(const NetFlatHost& F, const T* key, int n_key) {
+  const NetFlat& h = F.h;
+  const int* iw = F.iw.data();
+  std::vector<char> in_net((size_t)h.n_src, 0);
+  auto mark = [&](int kind, int index) { if (kind == NET_SOURCE && index >= 0 && index < h.n_src) in_net[index] = 1; };
+  for (int q = 0; q < h.n_in; q++) mark(iw[h.in_kind + q], iw[h.in_index + q]);
+  for (int r = 0; r < h.n_rj; r++) { mark(iw[h.rj_in_kind + r], iw[h.rj_in + r]); mark(iw[h.rj_over_kind + r], iw[h.rj_over + r]); }
+  for (int q = 0; q < h.n_out; q++) mark(iw[h.out_kind + q], iw[h.out_node + q]);
+  std::vector<T> u;
+  for (int i = 0; i < h.n_src && i < n_key; i++) if (in_net[i]) u.push_back(key[i]);
   std::sort(u.begin(), u.end());
   u.erase(std::unique(u.begin(), u.end()), u.end());
+  return u;
+}
+// the same over several ranks: the network's cells of all ranks (id: rank * 2^32 + local cell, per global source), so
+// ordered by (owner rank, local cell); this rank's own are then one contiguous run of the columns and, in that order, the
+// rows it differences and applies
+static void network_cells_span(Network& nw, const std::vector<double>& id, int rank) {
+  const std::vector<double> u = network_cells(nw.flat, id.data(), (int)id.size());
   nw.cp_span = true;
   nw.cp_m = (int)u.size();
   nw.cp_owner.resize(u.size());
@@ -659,10 +413,7 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
     for (int i = 0; i < n; i++) {
       const int g = nw.gidx[i];
       const int k = (int)was.size() == n ? was[i] : i;   // source i in ctl and e0
-      if (k < (int)ctl.size()) {
-        all[(size_t)NG * g] = ctl[k].sep_hf; all[(size_t)NG * g + 1] = ctl[k].sep_hg;
-        for (int q = 0; q < 6; q++) all[(size_t)NG * g + 2 + q] = ctl[k].sep_more[q];
-      }
+      if (k < (int)ctl.size()) src_separator(ctl[k], &all[(size_t)NG * g]);
       all[(size_t)NG * g + 8] = k < (int)e0.size() ? e0[k] : 0.0;
       all[(size_t)NG * g + 9] = (double)c->comm->rank * 4294967296.0 + (double)(i < (int)cells.size() ? cells[i] : 0);
     }
@@ -680,37 +431,33 @@ int wai_set_source_network(wai_ctx* c, const int* rate_specified, const int* ent
       span_id[g] = all[(size_t)NG * g + 9];
     }
   }
-  if (int e = network_build(nw, ng, rate_specified, enthalpy_specified, n_groups, grp_ptr, grp_in_kind, grp_in, grp_scaling,
-                            grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow, out_kind,
-                            out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, c->err))
+  // the description (every refusal is the builder's); the sources' separators and specified enthalpies come into it from
+  // h_ctl and h_enth0, now and whenever they change (network_flat_refresh)
+  if (int e = build_net_flat(nw.flat, ng, rate_specified, enthalpy_specified, nullptr, nullptr, n_groups, grp_ptr, grp_in_kind, grp_in,
+                             grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow,
+                             out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, c->err))
     return e;
+  const NetFlat& h = nw.flat.h;
+  nw.h_raw.assign(2 * (size_t)ng, 0.0);
+  if (nw.h_enth0.size() != (size_t)ng) nw.h_enth0.assign((size_t)ng, 0.0);
+  nw.h_net.assign(2 * (size_t)ng, 0.0);
+  nw.h_enth.assign((size_t)ng, 0.0);
+  nw.h_state.assign((size_t)net_kept_doubles(h), 0.0);
   if (nw.d_raw.alloc(c, 2 * (size_t)std::max(n, 1)) || c->src.net.alloc(c, 2 * (size_t)std::max(n, 1))) return -1;
   if (span && nw.d_all.alloc(c, 2 * (size_t)ng)) return -1;
   HIPCHK(c, hipMemset(c->src.net, 0, sizeof(double) * 2 * std::max(n, 1)));
   nw.h_loc.assign(2 * (size_t)n, 0.0);
   nw.l_net.assign(2 * (size_t)n, 0.0);
   nw.l_enth.assign((size_t)n, 0.0);
-  for (int i = 0; i < n; i++) nw.l_enth[i] = span ? nw.h_enth0[nw.gidx[i]] : (i < (int)nw.h_enth0.size() ? nw.h_enth0[i] : 0.0);
+  for (int i = 0; i < n; i++) nw.l_enth[i] = nw.h_enth0[span ? nw.gidx[i] : i];
   nw.on = true;
-  if (!span) {   // the flat description of the pass on the device (wai_set_network_pass); separators and enthalpies at its upload
-    std::string e;
-    nw.flat_fits = build_net_flat(nw.flat, n, rate_specified, enthalpy_specified, nullptr, nullptr, n_groups, grp_ptr, grp_in_kind,
-                                  grp_in, grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr,
-                                  out_flow, out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind,
-                                  rj_overflow, e) == 0 &&
-                   net_lds_doubles(nw.flat.h) <= NET_LDS_DOUBLES;
-    nw.flat_dirty = true;
-    // the wave walk's schedule (wai_set_network_walk), whatever walk is asked for now: it may be asked for later
-    const bool flat_ok = nw.flat.h.n_src == n;   // (the builder fills the header only behind its refusals)
-    nw.wave_built = nw.wave_ok = false;
-    if (!flat_ok) nw.wave_err = e;
-    else {
-      nw.wave_ok = build_net_wave(nw.flat, nw.wave, nw.wave_err) == 0;
-      nw.wave_built = nw.wave_ok || nw.wave.w.n_ww > 0;
-    }
-  }
-  if (!span) network_cells(nw, n);
-  else network_cells_span(nw, ng, span_id, c->comm->rank);
+  if (!span) {   // the pass on the device (wai_set_network_pass) and its wave walk (wai_set_network_walk): one rank only
+    nw.flat_fits = net_lds_doubles(h) <= NET_LDS_DOUBLES;
+    // the wave walk's schedule, whatever walk is asked for now: it may be asked for later
+    nw.wave_ok = build_net_wave(nw.flat, nw.wave, nw.wave_err) == 0;
+    nw.wave_built = nw.wave_ok || nw.wave.w.n_ww > 0;
+    nw.cp_cells = network_cells(nw.flat, nw.h_cell.data(), (int)nw.h_cell.size());
+  } else network_cells_span(nw, span_id, c->comm->rank);
   c->flow.as.overlap = -1;   // the factor's pattern carries the network's cell pairs: built again at the next set-up
   return 0;
 }
@@ -810,7 +557,7 @@ int wai_test_network_pass(wai_ctx* c, const double* raw2n, double* sources6, dou
     if (c->net_walk == WAI_NETWORK_WALK_WAVE && !nw.wave_err.empty()) c->err += " (" + nw.wave_err + ")";
     return -2;
   }
-  if (nw.flat_dirty && network_flat_upload(c)) return -1;
+  if (network_flat_upload(c)) return -1;
   const NetFlat& h = nw.flat.h;
   HIPCHK(c, hipMemcpyAsync(nw.d_raw, raw2n, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
   if (launch_network_pass(c, nw.d_raw, c->src.net, c->src.enth, nw.d_state, wave)) return -1;
@@ -837,7 +584,7 @@ int wai_test_network_stats(wai_ctx* c, long long* passes, long long* host_waits)
 int wai_test_network_lds(wai_ctx* c, int* limit, int* needed) {
   if (!c) return -2;
   const Network& nw = c->net;
-  const bool have = nw.on && nw.flat.h.n_src;
+  const bool have = nw.on && !nw.n_global;
   if (c->net_walk == WAI_NETWORK_WALK_WAVE && have && nw.wave_built) {   // the wave walk's own limit and need
     if (limit) *limit = NET_WAVE_LDS_DOUBLES;
     if (needed) *needed = net_wave_lds_doubles(nw.flat.h, nw.wave.w);
@@ -865,7 +612,7 @@ int wai_get_network_couplings(wai_ctx* c, int* n_cells, int* cells, double* valu
   }
   return 0;
 }
-// The same network pass without a context or a device (host logic only; tests): the sources' own rates
+// The network pass without a context or a device (the host pass of network_update; tests): the sources' own rates
 // and enthalpies and their separators (8 doubles per source: hf, hg of stage 1, then (hf, hg) of stages
 // 2..4, hg = 0: no separator / no further stage) in, node states out -- sources and groups 6 doubles each
 // (rate, enthalpy, water_rate, water_enthalpy, steam_rate, steam_enthalpy), reinjectors 8 each as
@@ -879,28 +626,19 @@ int wai_network_evaluate(int n_sources, const double* rate, const double* enthal
                          const double* out_proportion, const double* out_enthalpy, const int* rj_overflow_kind,
                          const int* rj_overflow, double* sources_out, double* groups_out, double* reinjectors_out) {
   if (!rate || !enthalpy || n_sources <= 0) return -2;
-  Network nw;
+  NetFlatHost F;
   std::string err;
-  nw.h_enth0.assign(enthalpy, enthalpy + n_sources);
-  if (int e = network_build(nw, n_sources, rate_specified, enthalpy_specified, n_groups, grp_ptr, grp_in_kind, grp_in,
-                            grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow,
-                            out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, err))
+  if (int e = build_net_flat(F, n_sources, rate_specified, enthalpy_specified, src_sep, enthalpy, n_groups, grp_ptr, grp_in_kind, grp_in,
+                             grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow,
+                             out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, err))
     return e;
-  nw.h_ctl.assign(n_sources, SrcCtl{});
-  for (int i = 0; i < n_sources && src_sep; i++) {
-    nw.h_ctl[i].sep_hf = src_sep[8 * i]; nw.h_ctl[i].sep_hg = src_sep[8 * i + 1];
-    for (int q = 0; q < 6; q++) nw.h_ctl[i].sep_more[q] = src_sep[8 * i + 2 + q];
-  }
-  for (int i = 0; i < n_sources; i++) { nw.h_raw[i] = rate[i]; nw.h_raw[n_sources + i] = enthalpy[i]; }
-  network_evaluate(nw);
-  auto put = [](const NetNode& n, double* o) { o[0] = n.rate; o[1] = n.enth; o[2] = n.wrate; o[3] = n.wenth; o[4] = n.srate; o[5] = n.senth; };
-  for (int i = 0; sources_out && i < n_sources; i++) put(nw.src[i], sources_out + 6 * i);
-  for (size_t g = 0; groups_out && g < nw.groups.size(); g++) put(nw.groups[g].node, groups_out + 6 * g);
-  for (size_t r = 0; reinjectors_out && r < nw.reinjectors.size(); r++) {
-    const NetReinjector& R = nw.reinjectors[r];
-    const double v[8] = {R.out_w, R.out_s, R.over.rate, R.over.enth, R.over.wrate, R.over.wenth, R.over.srate, R.over.senth};
-    std::memcpy(reinjectors_out + 8 * r, v, sizeof(v));
-  }
+  std::vector<double> raw(rate, rate + n_sources), work, kept((size_t)net_kept_doubles(F.h));
+  raw.insert(raw.end(), enthalpy, enthalpy + n_sources);
+  network_pass_host(F, raw.data(), work, nullptr, nullptr, kept.data());
+  const size_t ns = (size_t)NET_NODE * F.h.n_src, ngd = (size_t)NET_NODE * F.h.n_grp;
+  if (sources_out) std::memcpy(sources_out, kept.data(), sizeof(double) * ns);
+  if (groups_out) std::memcpy(groups_out, kept.data() + ns, sizeof(double) * ngd);
+  if (reinjectors_out) std::memcpy(reinjectors_out, kept.data() + ns + ngd, sizeof(double) * 8 * (size_t)F.h.n_rj);
   return 0;
 }
 // The cells between which wai_jacobian forms the network's coupling blocks, for the given sources' cells and
@@ -914,16 +652,15 @@ int wai_network_cells(int n_sources, const int* source_cell, const int* rate_spe
                       const double* out_enthalpy, const int* rj_overflow_kind, const int* rj_overflow, int* n_cells,
                       int* cells) {
   if (!source_cell || !n_cells || !cells || n_sources <= 0) return -2;
-  Network nw;
+  NetFlatHost F;
   std::string err;
-  if (int e = network_build(nw, n_sources, rate_specified, enthalpy_specified, n_groups, grp_ptr, grp_in_kind, grp_in,
-                            grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow,
-                            out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, err))
+  if (int e = build_net_flat(F, n_sources, rate_specified, enthalpy_specified, nullptr, nullptr, n_groups, grp_ptr, grp_in_kind, grp_in,
+                             grp_scaling, grp_limit_type, grp_limit, grp_sep, n_reinj, rj_in_kind, rj_in, rj_out_ptr, out_flow,
+                             out_kind, out_node, out_rate, out_proportion, out_enthalpy, rj_overflow_kind, rj_overflow, err))
     return e;
-  nw.h_cell.assign(source_cell, source_cell + n_sources);
-  network_cells(nw, n_sources);
-  *n_cells = (int)nw.cp_cells.size();
-  for (size_t i = 0; i < nw.cp_cells.size(); i++) cells[i] = nw.cp_cells[i];
+  const std::vector<int> u = network_cells(F, source_cell, n_sources);
+  *n_cells = (int)u.size();
+  std::copy(u.begin(), u.end(), cells);
   return 0;
 }
 // state of the network after the last pass: groups 6 doubles each (rate, enthalpy, water_rate,
@@ -933,16 +670,11 @@ int wai_get_source_network(wai_ctx* c, double* groups, double* reinjectors) {
   if (!c) return -2;
   if (network_fetch_state(c)) return -1;   // a pass on the device: its node states are downloaded when asked for
   const Network& nw = c->net;
-  for (size_t g = 0; groups && g < nw.groups.size(); g++) {
-    const NetNode& n = nw.groups[g].node;
-    const double v[6] = {n.rate, n.enth, n.wrate, n.wenth, n.srate, n.senth};
-    std::memcpy(groups + 6 * g, v, sizeof(v));
-  }
-  for (size_t r = 0; reinjectors && r < nw.reinjectors.size(); r++) {
-    const NetReinjector& R = nw.reinjectors[r];
-    const double v[8] = {R.out_w, R.out_s, R.over.rate, R.over.enth, R.over.wrate, R.over.wenth, R.over.srate, R.over.senth};
-    std::memcpy(reinjectors + 8 * r, v, sizeof(v));
-  }
+  if (nw.h_state.empty()) return 0;   // no network
+  const NetFlat& h = nw.flat.h;
+  const double* kept = nw.h_state.data() + (size_t)NET_NODE * h.n_src;
+  if (groups) std::memcpy(groups, kept, sizeof(double) * NET_NODE * (size_t)h.n_grp);
+  if (reinjectors) std::memcpy(reinjectors, kept + (size_t)NET_NODE * h.n_grp, sizeof(double) * 8 * (size_t)h.n_rj);
   return 0;
 }
 

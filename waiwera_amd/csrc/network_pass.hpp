@@ -1,13 +1,13 @@
-// One pass of the source network (groups, limiters, separators, reinjectors, overflow chains) on a FLAT description:
-// what network_evaluate (network.hip) does on a Network of vectors, written so that the same text runs on the host and
-// inside a kernel (k_network_pass, kernels_network.hip).  Host-only compatible, like mesh_pattern.hpp, ilu_schedule.hpp
-// and colour_order.hpp: no HIP header; tests/network_pass_host runs it without a device.
+// One pass of the source network (groups, limiters, separators, reinjectors, overflow chains) on a FLAT description: one
+// array of ints, one of doubles.  THE pass of the library: the same text runs on the host (network_update and
+// wai_network_evaluate, network.hip) and inside a kernel (k_network_pass, kernels_network.hip), and build_net_flat below is
+// the one place a description is validated.  Host-only compatible, like mesh_pattern.hpp, ilu_schedule.hpp and
+// colour_order.hpp: no HIP header; tests/network_pass_host runs it without a device.
 //
-// The same floating-point operations in the same order as network_evaluate, every sum over a group's inputs in input
-// order, and no contraction of a product and a sum into one rounding: host and device then give the same bits.
-// No recursion and no allocation: net_scale / net_limit_rate / net_limit_inputs of network.hip walk nested groups by
-// recursion; here an explicit stack of frames does, and the progressive limiter's node_limit tables live in a scratch
-// arena -- build_net_flat sizes both from the nesting.
+// Every sum over a group's inputs runs in input order, and no product and sum are contracted into one rounding: host and
+// device then give the same bits -- those recorded in tests/golden/network_pass_bits.json from the recursive pass on a
+// network of structs this one replaced.  No recursion and no allocation: an explicit stack of frames walks nested groups,
+// and the progressive limiter's node_limit tables live in a scratch arena -- build_net_flat sizes both from the nesting.
 #pragma once
 #include <string>
 #include <vector>
@@ -96,7 +96,7 @@ WAI_NET_HD inline double dmin(double a, double b) { return b < a ? b : a; }   //
 WAI_NET_HD inline double dmax(double a, double b) { return a < b ? b : a; }   // std::max
 WAI_NET_HD inline double dabs(double a) { WAI_NET_FP return __builtin_fabs(a); }
 
-// separator.F90:139-166, 212-260 (net_separate): sep = hf, hg of stage 1, then (hf, hg) of stages 2..4
+// separator.F90:139-166, 212-260: sep = hf, hg of stage 1, then (hf, hg) of stages 2..4
 WAI_NET_HD inline void separate(const double* sep, double rate, double enth, double* n) {
   WAI_NET_FP
   double q = rate, h = enth, steam_m = 0.0, steam_e = 0.0;
@@ -151,7 +151,7 @@ WAI_NET_HD inline void group_sum(const NetFlatView& v, NetState& s, int g) {
   } else G[2] = G[3] = G[4] = G[5] = 0.0;
 }
 
-// net_scale: everything below (kind, index) times `scale`, the groups summed again on the way up.  Frames above sp.
+// scale_rate: everything below (kind, index) times `scale`, the groups summed again on the way up.  Frames above sp.
 WAI_NET_HD inline void scale_run(const NetFlatView& v, NetState& s, int& sp, int kind, int index, double scale) {
   WAI_NET_FP
   if (kind == NET_SOURCE) { source_set_rate(v, s, index, s.src[NET_NODE * index] * scale); return; }
@@ -170,7 +170,7 @@ WAI_NET_HD inline void scale_run(const NetFlatView& v, NetState& s, int& sp, int
     } else { group_sum(v, s, g); sp--; }
   }
 }
-// a source or a uniform group under limits: one factor for everything below (net_limit_rate's first branch)
+// a source or a uniform group under limits: one factor for everything below
 WAI_NET_HD inline void limit_leaf(const NetFlatView& v, NetState& s, int& sp, int kind, int index, int nl, const int* type,
                                   const double* limit) {
   WAI_NET_FP
@@ -187,7 +187,7 @@ WAI_NET_HD inline bool is_leaf(const NetFlatView& v, int kind, int index) {
   WAI_NET_FP
   return kind == NET_SOURCE || v.iw[v.h.grp_scaling + index] == 0;
 }
-// net_limit_inputs: a progressive group's inputs are limited in order until the total is met; the limits of (kind, index)
+// a progressive group's inputs are limited in order until the total is met; the limits of (kind, index)
 // are the three doubles at arena[lim]; atop: the arena's first free double
 WAI_NET_HD inline void limit_inputs_run(const NetFlatView& v, NetState& s, int& sp, int atop, int kind, int index, int lim, int nl,
                                         const int* type) {
@@ -343,7 +343,7 @@ WAI_NET_HD inline void network_pass_serial(const NetFlatView& v, const double* r
     }
   }
 }
-// reinjector_output_update for the fed sources, then what the residual kernel is handed (network_update's rule): mode 2
+// reinjector_output_update for the fed sources, then what the residual kernel is handed (source_network_rate): mode 2
 // with the output rate for fed sources, mode 1 with rate / raw where the rate changed, otherwise 0; the enthalpy of fed
 // sources, and of those only
 WAI_NET_HD inline void network_pass_final(const NetFlatView& v, const double* raw, NetState& s, int i0, int stride) {
@@ -368,6 +368,15 @@ WAI_NET_HD inline void network_pass(const NetFlatView& v, const double* raw, Net
   network_pass_sources(v, raw, s, 0, 1);
   network_pass_serial(v, raw, s);
   network_pass_final(v, raw, s, 0, 1);
+}
+// What is kept of a pass, on the host and on the device alike (Network::h_state, d_state; wai_get_source_network,
+// wai_network_evaluate): sources NET_NODE doubles each, groups NET_NODE each, reinjectors 8 each (delivered water and steam,
+// then the overflow node).  Entries i0, i0 + stride, ..
+WAI_NET_HD inline int net_kept_doubles(const NetFlat& h) { return NET_NODE * (h.n_src + h.n_grp) + 8 * h.n_rj; }
+WAI_NET_HD inline void net_state_keep(const NetFlat& h, const NetState& s, double* out, int i0, int stride) {
+  const int nn = NET_NODE * (h.n_src + h.n_grp);   // sources and groups are one run of the state
+  for (int i = i0; i < nn; i += stride) out[i] = s.src[i];
+  for (int i = i0; i < 8 * h.n_rj; i += stride) out[nn + i] = s.rj[RJ_STATE * (i >> 3) + RJ_OUT_W + (i & 7)];
 }
 
 // ---- the builder (host) ---------------------------------------------------------------------------------------------
@@ -404,8 +413,8 @@ struct NetFlatHost {
   NetFlatView view() const { return NetFlatView{h, iw.data(), dw.data()}; }
 };
 
-// The flat description from the arrays of wai_set_source_network (validated as network_build validates them: the same
-// refusals with the same texts), the sources' separators (8 doubles each, null: none) and specified enthalpies (null: 0).
+// The flat description from the arrays of wai_set_source_network, validated here and nowhere else (the refusals' texts are
+// the library's), the sources' separators (8 doubles each, null: none) and specified enthalpies (null: 0).
 // 0, or -2 with a text
 inline int build_net_flat(NetFlatHost& F, int n, const int* rate_specified, const int* enthalpy_specified, const double* src_sep,
                           const double* src_enth0, int n_groups, const int* grp_ptr, const int* grp_in_kind, const int* grp_in,

@@ -180,7 +180,7 @@ WAI_NET_HD inline void group_sum(Ex& ex, const NetFlatView& v, NetState& s, doub
   });
 }
 
-// net_scale: the sources below, lane-strided (each is below exactly once: build_net_wave); then the groups below in schedule
+// scale_run: the sources below, lane-strided (each is below exactly once: build_net_wave); then the groups below in schedule
 // order and the group itself.  A group's sum is a function of its inputs' states alone, so the order among groups that do not
 // contain one another is free; no stack
 template <class Ex>

@@ -49,7 +49,7 @@ int wai_update_sources(wai_ctx* c, const double* rate, const double* enthalpy) {
       if (g < nw.h_enth0.size()) nw.h_enth0[g] = enthalpy[i];
       if ((size_t)i < nw.l_enth.size()) nw.l_enth[i] = enthalpy[i];
     }
-    nw.flat_dirty = true;   // the device pass' copy of the specified enthalpies
+    nw.flat_gen++;   // the pass' copies of the specified enthalpies, host and device
   }
   return 0;
 }
@@ -106,7 +106,7 @@ int wai_set_source_controls(wai_ctx* c, const wai_source_control* controls) {
   if (c->net.gidx.empty()) c->net.h_ctl.assign(reinterpret_cast<const SrcCtl*>(controls), reinterpret_cast<const SrcCtl*>(controls) + s.n);
   else   // a network across ranks numbers its control records globally: this rank's own entries
     for (int i = 0; i < s.n; i++) c->net.h_ctl[c->net.gidx[i]] = reinterpret_cast<const SrcCtl*>(controls)[i];
-  c->net.flat_dirty = true;   // the device pass' copy of the separators
+  c->net.flat_gen++;   // the pass' copies of the separators, host and device
   HIPCHK(c, hipMemcpyAsync(s.ctl, controls, sizeof(SrcCtl) * (size_t)s.n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -151,11 +151,13 @@ int wai_get_source_separated(wai_ctx* c, double* out4) {
   std::vector<double> q(std::max(n, 1)), h(std::max(n, 1));
   if (int e = wai_get_source_rates(c, q.data(), h.data())) return e;   // (the network pass in it: made without sources too)
   for (int i = 0; i < n; i++) {
-    NetNode nd;
-    nd.rate = q[i]; nd.enth = h[i];
+    double nd[NET_NODE] = {q[i], h[i], 0.0, 0.0, 0.0, 0.0}, sep[8];
     const int g = c->net.gidx.empty() ? i : c->net.gidx[i];   // the network's control records are numbered globally
-    if (q[i] < 0.0 && g < (int)c->net.h_ctl.size() && c->net.h_ctl[g].sep_hg > 0.0) net_separate(c->net.h_ctl[g], q[i], h[i], nd);
-    out4[4 * i] = nd.wrate; out4[4 * i + 1] = nd.wenth; out4[4 * i + 2] = nd.srate; out4[4 * i + 3] = nd.senth;
+    if (q[i] < 0.0 && g < (int)c->net.h_ctl.size() && c->net.h_ctl[g].sep_hg > 0.0) {
+      src_separator(c->net.h_ctl[g], sep);
+      netpass::separate(sep, q[i], h[i], nd);
+    }
+    for (int k = 0; k < 4; k++) out4[4 * i + k] = nd[2 + k];
   }
   return 0;
 }
