@@ -531,6 +531,29 @@ enum { WAI_PC_ORDER_NATURAL = 0, WAI_PC_ORDER_MULTICOLOUR = 1 };
 int wai_set_pc_ordering(wai_ctx *ctx, int ordering);
 int wai_get_pc_ordering(wai_ctx *ctx, int *ordering, int *max_colours);
 
+/* A second level for the flow system's preconditioner: one coarse level, piecewise constant over aggregates of cells.
+ * agg[n_owned] names every owned cell's aggregate, 0 <= agg[i] < nc.  The prolongation P has P[(i,k),(I,k)] = 1 where
+ * agg[i] = I -- every component is prolonged by its own constant --, the coarse matrix is the Galerkin product
+ * Ac = P^T A P (block (I, J): the sum of the blocks A_ij over i in I, j in J), formed densely on the device at every set-up
+ * and inverted there by Gauss-Jordan elimination with partial pivoting.  With M^-1 the one-level preconditioner in force
+ * (bjacobi or asm, ILU(k) or sub-preconditioner lu, tiles or none):
+ *   WAI_PC_COARSE_ADDITIVE   z = M^-1 r + P Ac^-1 P^T r
+ *   WAI_PC_COARSE_DEFLATED   y = Ac^-1 P^T r, z = M^-1 (r - A P y) + P y      (one more operator application)
+ * Both are fixed linear operators, so every Krylov method takes them.  Every sum is taken in a fixed order: two set-ups
+ * on the same values, and two applications to the same vector, give the same bits.  While a coarse level is on the flow system
+ * takes the unfused route: the operator, the one-level preconditioner, three short launches for the coarse correction
+ * (restriction, dense product, prolongation), then the reductions.  NOT the reference's preconditioner; off by default
+ * (WAI_PC_COARSE_OFF: nc and agg are ignored).  A zero pivot of Ac is reported like ILU's: wai_pc_setup returns 1 and the
+ * solve's reason is PC_FAILED.
+ * Refused with -2 and a text that names what it met, with what was in force staying in force: more than one rank,
+ * source-network couplings in the operator, WAI_PC_NONE, WAI_PC_LU, WAI_PC_ORDER_MULTICOLOUR, auxiliary (tracer) systems,
+ * nc * block size > 1024, an agg value outside [0, nc), an empty aggregate; the set-up refuses the same way what was set
+ * since.  The preconditioner is set up again by its next use.  wai_get_pc_coarse returns the mode and nc (0 while off;
+ * out-arguments may be NULL). */
+enum { WAI_PC_COARSE_OFF = 0, WAI_PC_COARSE_ADDITIVE = 1, WAI_PC_COARSE_DEFLATED = 2 };
+int wai_set_pc_coarse(wai_ctx *ctx, int mode, int nc, const int *agg);
+int wai_get_pc_coarse(wai_ctx *ctx, int *mode, int *nc);
+
 /* Where the source network's pass (groups, limiters, separators, reinjectors) runs.  WAI_NETWORK_PASS_HOST (the default):
  * every pass copies the sources' own rates to the host, waits, walks the network there and copies the factors back; the
  * Jacobian's coupling blocks (wai_set_network_couplings) take three such passes and several more waits per column.

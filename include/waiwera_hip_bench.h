@@ -115,6 +115,19 @@ enum { WAI_KV_DOT = 0, WAI_KV_DOTS, WAI_KV_WAXPY, WAI_KV_BCGS_P, WAI_KV_BCGS_S, 
        WAI_KV_BCGS_XRP_DERIVE, WAI_KV_SCALARS, WAI_KV_MDOT, WAI_KV_MAXPY_NORM, WAI_KV_SCALE_TO, WAI_KV_UPDATE_X };
 int wai_test_krylov_vec(wai_ctx *ctx, int op, int variant, int n, int k, long long ld, long long len, double alpha,
                         double *vecs, double *basis, const double *coef, double *scal, double *post);
+/* the coarse level of the two-level preconditioner (wai_set_pc_coarse, which must be on), one piece at a time, each kernel
+ * through the launcher the drivers use.  n = bs * n_owned, m = nc * bs; vectors are host or device memory, and a device
+ * vector goes to the launcher as it is (so what lies behind its last entry is the caller's to check).
+ *   RESTRICT      out[m] = P^T in[n]                  k_coarse_restrict
+ *   GEMV          out[m] = Ac^-1 in[m]                k_coarse_gemv (sets the preconditioner up if it is not in force)
+ *   PROLONG_ADD   out[n] += P in[m]                   k_coarse_prolong, the additive mode's and both modes' last launch
+ *   PROLONG_SET   out[n] = P in[m]                    k_coarse_prolong, the deflated mode's first
+ *   AC / AINV     out[m * m] = Ac / Ac^-1, row-major, of the set-up in force (made if there is none; 1: a pivot failed)
+ *   TIMES         out[2] (host) = ms of the last set-up's Galerkin product and of its inversion, 0 unless profiling was on
+ *                 (wai_profile_enable) */
+enum { WAI_COARSE_RESTRICT = 0, WAI_COARSE_GEMV, WAI_COARSE_PROLONG_ADD, WAI_COARSE_PROLONG_SET, WAI_COARSE_AC, WAI_COARSE_AINV,
+       WAI_COARSE_TIMES };
+int wai_test_coarse(wai_ctx *ctx, int what, const double *in, double *out);
 /* bytes this rank sends per halo exchange of a dof-per-cell vector, and its number of neighbours */
 int wai_halo_size(wai_ctx *ctx, int dof, long long *bytes_sent, int *n_neighbours);
 

@@ -15,7 +15,7 @@ ASSEMBLY_UNITS = ["kernels_eos.hip", "kernels_residual.hip", "kernels_jacobian.h
                   "kernels_coupling.hip"]
 SOURCES = ["capi.hip", "context.hip", "sources.hip", "tracers.hip", "krylov.hip", "pc_setup.hip", "network.hip",
            "measure.hip", "gather.hip"] + ASSEMBLY_UNITS + \
-    ["kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_tracer_block.hip", "kernels_network.hip", "comm.cpp"]
+    ["kernels_matrix.hip", "kernels_factor.hip", "kernels_fused.hip", "kernels_coarse.hip", "kernels_tracer_block.hip", "kernels_network.hip", "comm.cpp"]
 import glob  # noqa: E402
 # every header any source could include: a stale object after a header edit is worse than a rebuild
 HEADERS = sorted(os.path.basename(h) for pat in ("*.h", "*.hpp") for h in glob.glob(os.path.join(CSRC, pat))) + \

@@ -349,6 +349,44 @@ int wai_get_pc_ordering(wai_ctx* c, int* ordering, int* max_colours) {
   return 0;
 }
 
+int wai_set_pc_coarse(wai_ctx* c, int mode, int nc, const int* agg) {
+  if (!c) return -2;
+  if (mode != WAI_PC_COARSE_OFF && mode != WAI_PC_COARSE_ADDITIVE && mode != WAI_PC_COARSE_DEFLATED) {
+    c->err = "unknown coarse-level mode (WAI_PC_COARSE_OFF, WAI_PC_COARSE_ADDITIVE or WAI_PC_COARSE_DEFLATED)";
+    return -2;
+  }
+  if (mode == WAI_PC_COARSE_OFF) {
+    if (c->coarse.mode != mode) pc_invalidate(c);
+    c->coarse.mode = mode;
+    return 0;
+  }
+  // refused by name, from the arguments and settings alone; what was in force stays in force
+  if (const char* met = coarse_refusal(c, false)) {
+    c->err = std::string("wai_set_pc_coarse: the coarse level serves the flow system under bjacobi or asm on one rank; it met ") + met;
+    return -2;
+  }
+  if (!agg) { c->err = "wai_set_pc_coarse: no aggregates"; return -2; }
+  const Pattern& J = c->pat;
+  CoarseSpace h;
+  std::string text;
+  if (int e = build_coarse_space(J.h_rowptr, J.h_colidx, J.n, std::vector<int>(agg, agg + J.n), nc, c->np, h, text)) {
+    c->err = "wai_set_pc_coarse: " + text;
+    return e;
+  }
+  pc_invalidate(c);
+  c->coarse.mode = WAI_PC_COARSE_OFF;   // (nothing half-made is in force if the upload fails)
+  c->coarse.h = std::move(h);
+  if (coarse_upload(c)) return -1;
+  c->coarse.mode = mode;
+  return 0;
+}
+int wai_get_pc_coarse(wai_ctx* c, int* mode, int* nc) {
+  if (!c) return -2;
+  if (mode) *mode = c->coarse.mode;
+  if (nc) *nc = c->coarse.mode != WAI_PC_COARSE_OFF ? c->coarse.h.nc : 0;
+  return 0;
+}
+
 int wai_set_pc_tiles(wai_ctx* c, int n_tiles, const int* tile_ptr) {
   if (!c) return -2;
   if (n_tiles < 0) { c->err = "wai_set_pc_tiles: n_tiles < 0"; return -1; }

@@ -6,6 +6,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/waiwera_hip.h"
+#include "coarse_space.hpp"   // CoarseSpace
 #include "colour_order.hpp"   // ColourFacts
 #include "coupling_batch.hpp" // CouplingBatch
 #include "devbuf.hpp"
@@ -290,6 +291,23 @@ struct ColourSchedule : ColourFacts {
   DevBuf<unsigned long long> slots;   // per row: its in-subdomain slots in elimination order, 4 bits each, lower ones first
   DevBuf<int> counts;       // per row: lower | upper << 8 | diagonal slot << 16 | colour << 24
 };
+// The coarse level of the two-level preconditioner (wai_set_pc_coarse; coarse_space.hpp, where build_coarse_space makes every
+// list on the host): the lists on the device, the dense Galerkin matrix and its inverse, and the work vectors of an
+// application.  The flow system's alone.  mode: WAI_PC_COARSE_OFF | _ADDITIVE | _DEFLATED; the lists stand from the call
+// that set them, Ac and Ainv from the set-up in force (IluSchedule::owner)
+struct CoarseLevel {
+  int mode = 0;
+  CoarseSpace h;            // what the device's lists were made from
+  int m = 0, nblk = 0;      // coarse unknowns nc * bs, blocks of the coarse pattern
+  DevBuf<int> agg, agg_ptr, agg_rows;                       // [n], [nc + 1], [n]
+  DevBuf<int> blk_row, blk_col, ent_ptr, ent_row, ent_slot; // per coarse block: its place in Ac and its contribution list
+  DevBuf<double> Ac, W, Ainv;                               // [m][m] row-major: Galerkin matrix, elimination workspace, inverse
+  DevBuf<double> prow, pcol;                                // [m] the elimination's scaled pivot row and pivot column
+  DevBuf<int> perm, src;                                    // [m] row exchanges of the elimination; columns of W that make Ainv
+  DevBuf<double> rc, yc;                                    // [m] restricted residual, coarse correction
+  DevBuf<double> t, w;                                      // deflated mode: P yc (halo room) and A P yc, then r - A P yc
+  float ms_galerkin = 0.f, ms_inverse = 0.f;                // the last set-up's two parts, timed while profiling is on
+};
 // threads of a brick kernel's workgroup: one per row of the largest subdomain, whole waves
 inline int pc_threads(const IluSchedule& s) { return ((s.max_rows + 63) / 64) * 64; }
 
@@ -560,6 +578,7 @@ struct wai_ctx : wai::Handles {
   long long cp_launches = 0, cp_columns = 0, cp_chunks = 0;   // kernel launches, columns and chunks of the last coupling build (wai_test_coupling_build_stats)
   int pc_ordering = WAI_PC_ORDER_NATURAL;   // wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
   wai::ColourSchedule colour;   // ... its symbolic phase under WAI_PC_ORDER_MULTICOLOUR, built by the first set-up that needs it
+  wai::CoarseLevel coarse;      // wai_set_pc_coarse: the flow system's coarse level (pc_coarse: is it in force)
   std::vector<int> pc_tiles;    // wai_set_pc_tiles: row ranges [n_tiles + 1] of the tiles that refine the subdomains; empty: none
   wai::DeviceMesh mesh;
   wai::Sources src;
@@ -600,6 +619,8 @@ struct wai_ctx : wai::Handles {
     bool fin_separate = false; bool no_col16 = false; bool scalar_kernels = false; bool iluk_level_path = false;
     bool asm_unfused = false; bool no_desc_share = false; bool no_pack = false;
     bool colour_sweeps = false;
+    bool pc_unfused = false;   // WAI_PC_UNFUSED: pc_amul takes its unfused route (t = A x, then pc_solve) where a fused launch would serve -- the
+                               // route a coarse level puts the flow system on, without one (tools/pc_coarse_timing.py)
     int park_stage = -1;   // WAI_PARK_STAGE: 0 / 1 k_pc_park's staged operand off / on for every launch kind, -1 the compiled-in defaults
   } env;
   int test_drop_wait = 0;   // fault injection (wai_test_drop_stream_wait): 1 the face bricks' launch does not wait for the halo
@@ -695,6 +716,13 @@ int launch_colour_solve(wai_ctx* c, const Bcsr& M, const ColourSchedule& k, cons
 bool pc_colour_serves(const wai_ctx* c, const Bcsr& M, const ColourSchedule& k, bool one_rank);
 int launch_pc_colour(wai_ctx* c, const Bcsr& M, const ColourSchedule& k, const IluSchedule& s, bool spmv, const double* in, double* z,
                      int dot_mode, const double* aux, const Fin* fin = nullptr);
+// the coarse level (kernels_coarse.hip): Ac from the system's value planes; Ainv from Ac (2 m + 2 launches; a zero pivot raises
+// d_flags[0]); rc = P^T r; yc = Ainv rc; z += P yc (add) or z = P yc
+int launch_coarse_galerkin(wai_ctx* c, const Bcsr& A, CoarseLevel& k);
+int launch_coarse_invert(wai_ctx* c, CoarseLevel& k);
+int launch_coarse_restrict(wai_ctx* c, const CoarseLevel& k, const double* r, double* rc);
+int launch_coarse_gemv(wai_ctx* c, const CoarseLevel& k, const double* rc, double* yc);
+int launch_coarse_prolong(wai_ctx* c, const CoarseLevel& k, const double* yc, double* z, bool add);
 // sub-preconditioner lu (IluSchedule::sublu): both substitutions of every block in one launch, in place on z
 int launch_sublu_solve(wai_ctx* c, const Bcsr& M, const IluSchedule& s, double* z);
 bool sublu_vector_in_lds(const IluSchedule& s, int bs);   // does k_sublu_solve hold a block's part of the vector in LDS

@@ -149,6 +149,10 @@ inline bool pc_extended(const wai_ctx* c, const LinSys& sys) {
   const PcOpts p = pc_of(c, sys);
   return p.type == WAI_PC_ASM || (p.type == WAI_PC_BJACOBI && (p.ilu_levels > 0 || pc_with_net(c, sys) || pc_sub_lu(p)));
 }
+// the two-level preconditioner's coarse level is in force for `sys` (wai_set_pc_coarse): the flow system's alone.  The system
+// then takes the unfused route -- pc_amul computes t = A x and calls pc_solve, which applies the one-level preconditioner and
+// the coarse correction and reduces the inner products of the final z; no composed operand (pc_axpy_ok)
+inline bool pc_coarse(const wai_ctx* c, const LinSys& sys) { return c->coarse.mode != WAI_PC_COARSE_OFF && &sys == &c->flow; }
 // the preconditioner set up for `sys` no longer stands (its values changed); without a system: nobody's does
 inline void pc_invalidate(wai_ctx* c, const LinSys& sys) { if (c->ilu.owner == &sys) c->ilu.owner = nullptr; }
 inline void pc_invalidate(wai_ctx* c) { c->ilu.owner = nullptr; }
@@ -159,6 +163,9 @@ int build_schedule(wai_ctx* c, IluSchedule& s, const std::vector<int>& rowptr, c
                    bool fill = false, const std::vector<int>* row_tile = nullptr);
 int ensure_halo_dof(wai_ctx* c, int dof);   // halo buffers wide enough for `dof` doubles per cell
 int do_pc_setup(wai_ctx* c, LinSys& sys);
+// what the coarse level does not combine with, from the settings alone: null, or the party it met
+const char* coarse_refusal(const wai_ctx* c, bool at_setup);
+int coarse_upload(wai_ctx* c);    // the lists of c->coarse.h to the device, the matrices and work vectors allocated
 // ---- krylov.hip --------------------------------------------------------------------------------------------------
 int halo_exchange(wai_ctx* c, double* vec, int dof);
 // the two launches of the overlapped halo exchange on the compute stream: interior bricks, then face bricks behind `after`

@@ -27,6 +27,7 @@ void read_env(wai_ctx* c) {
   c->env.no_desc_share = getenv("WAI_NO_DESC_SHARE") != nullptr;
   c->env.no_pack = getenv("WAI_NO_PACK") != nullptr;
   c->env.colour_sweeps = getenv("WAI_COLOUR_SWEEPS") != nullptr;
+  c->env.pc_unfused = getenv("WAI_PC_UNFUSED") != nullptr;
   const char* st = getenv("WAI_PARK_STAGE");
   c->env.park_stage = st && (st[0] == '0' || st[0] == '1') ? st[0] - '0' : -1;
 }

@@ -94,7 +94,7 @@ int pc_finalize(wai_ctx* c, int dot_mode, int phase) {
 // z = B^-1 r; dot_mode as launch_pc, with `x` the partner of mode 2.  fin_phase >= -1: the partial sums of
 // the dot products are summed into the device scalars (and the BiCGStab scalars of that phase derived) --
 // in the fused kernel's last workgroup, or by a k_finalize launch on the general path; -2: left as partials
-int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase) {
+static int pc_solve_one(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase) {
   if (pc_fused(c, sys)) {
     // the fused kernels take the partner of modes 2 and 4 from their own input vector (the x of
     // z = B^-1 A x); here the input is r = (A + E) x, so those inner products are reduced separately
@@ -137,6 +137,27 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
   return fin_phase >= -1 ? pc_finalize(c, dot_mode, fin_phase) : 0;
 }
 
+// The same with the coarse level where it is in force (wai_set_pc_coarse; kernels_coarse.hip): M^-1 is the one-level
+// preconditioner above, applied without inner products (a fused kernel with PC_DOT_NONE), yc = Ac^-1 P^T r three short launches.
+//   additive   z = M^-1 r + P yc
+//   deflated   z = M^-1 (r - A P yc) + P yc      (one more operator application: apply_operator)
+// The inner products are reduced from the final z by separate launches, as the general path reduces them
+int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, const double* x, const double* aux, int fin_phase) {
+  if (!pc_coarse(c, sys)) return pc_solve_one(c, sys, r, z, dot_mode, x, aux, fin_phase);
+  CoarseLevel& k = c->coarse;
+  if (launch_coarse_restrict(c, k, r, k.rc)) return -1;   // (before z is written: r and z may be one vector)
+  if (launch_coarse_gemv(c, k, k.rc, k.yc)) return -1;
+  if (k.mode == WAI_PC_COARSE_DEFLATED) {
+    if (launch_coarse_prolong(c, k, k.yc, k.t, false)) return -1;
+    if (apply_operator(c, sys, k.t, k.w)) return -1;
+    vec_waxpy(c, k.w, -1.0, k.w, r, sys.n);   // w = r - A P yc
+    if (int e = pc_solve_one(c, sys, k.w, z, PC_DOT_NONE, nullptr, nullptr, -2)) return e;
+  } else if (int e = pc_solve_one(c, sys, r, z, PC_DOT_NONE, nullptr, nullptr, -2)) return e;
+  if (launch_coarse_prolong(c, k, k.yc, z, true)) return -1;
+  if (pc_dots(c, sys.n, dot_mode, x, z, aux)) return -1;
+  return fin_phase >= -1 ? pc_finalize(c, dot_mode, fin_phase) : 0;
+}
+
 // z = B^-1 A x  (x has halo room); optional fused dot products of the result, summed as pc_solve sums them.
 // x2 (optional; fused kernels only, pc_axpy_ok): the operand is x - alpha x2 with alpha the device scalar S_ALPHA, formed
 // inside the kernel (BiCGStab's S = R - alpha V); both vectors have halo room, the operand's ghost values are packed as
@@ -144,7 +165,7 @@ int pc_solve(wai_ctx* c, LinSys& sys, const double* r, double* z, int dot_mode, 
 int pc_amul(wai_ctx* c, LinSys& sys, double* x, double* z, int dot_mode, const double* aux, int fin_phase, const double* x2, bool post) {
   const IluSchedule& s = c->ilu;
   const int bs = sys.A.bs;
-  if (!pc_fused(c, sys) || net_in_operator(c, sys)) {   // unfused: t = A x (+ the network's blocks), then the preconditioner
+  if (!pc_fused(c, sys) || net_in_operator(c, sys) || pc_coarse(c, sys) || c->env.pc_unfused) {   // unfused: t = A x (+ the network's blocks), then the preconditioner
     if (x2) { c->err = "pc_amul: composed operand on the unfused path"; return -1; }
     if (halo_exchange(c, x, bs)) return -1;
     { Prof p(c, KC_SPMV); if (apply_operator(c, sys, x, sys.kv->tmp)) return -1; }
@@ -258,7 +279,9 @@ int bcgs_mode(const wai_ctx* c) {
 // (profiles/compose_full_c4c5_ab_r5.log): C4 1.303 -> 1.265, C5 0.486 -> 0.467.  WAI_BCGS_COMPOSE=0 / 1 forces it off / on
 // (k_pc_rows -- 4 x 4 blocks, MINC inside 3-D bricks -- not measured: on request).
 bool pc_axpy_ok(const wai_ctx* c, const LinSys& sys) {
-  if (!(pc_fused(c, sys) && !pc_own_factor(c, sys) && !pc_colour(c, sys) && !net_in_operator(c, sys) && pc_axpy_capable(c, sys.A))) return false;
+  if (!(pc_fused(c, sys) && !pc_own_factor(c, sys) && !pc_colour(c, sys) && !net_in_operator(c, sys) && !pc_coarse(c, sys) &&
+        !c->env.pc_unfused && pc_axpy_capable(c, sys.A)))
+    return false;
   if (const char* e = getenv("WAI_BCGS_COMPOSE")) return e[0] == '1';
   return pc_axpy_default(c, sys.A);
 }

@@ -31,7 +31,8 @@ __global__ __launch_bounds__(256) void k_stream_read(const stream_d2* __restrict
 }
 // can pc_amul form its operand x - alpha x2 inside the launch?  (pc_axpy_ok without the switch and the default)
 bool pc_operand_composable(const wai_ctx* c) {
-  return pc_fused(c, c->flow) && !pc_own_factor(c, c->flow) && !pc_colour(c, c->flow) && !net_in_operator(c, c->flow) && pc_axpy_capable(c, c->flow.A);
+  return pc_fused(c, c->flow) && !pc_own_factor(c, c->flow) && !pc_colour(c, c->flow) && !net_in_operator(c, c->flow) && !pc_coarse(c, c->flow) &&
+         !c->env.pc_unfused && pc_axpy_capable(c, c->flow.A);
 }
 }  // namespace
 
@@ -253,7 +254,8 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   LinSys& sys = c->flow;
   if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
   if (x2 && (!spmv || !pc_operand_composable(c))) { c->err = "wai_test_pc_operator: composed operand asked of a kernel that cannot form it"; return -1; }
-  if (split && (!spmv || !pc_fused(c, sys) || pc_own_factor(c, sys) || pc_colour(c, sys) || net_in_operator(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 || !c->ilu.sub_int)) {
+  if (split && (!spmv || !pc_fused(c, sys) || pc_own_factor(c, sys) || pc_colour(c, sys) || net_in_operator(c, sys) || pc_coarse(c, sys) || c->ilu.n_int <= 0 || c->ilu.n_bnd <= 0 ||
+                !c->ilu.sub_int)) {
     c->err = "wai_test_pc_operator: no interior / face brick lists to split the launch over";
     return -1;
   }
@@ -290,6 +292,44 @@ int wai_test_pc_operator(wai_ctx* c, int spmv, const double* x, const double* x2
   HIPCHK(c, hipMemcpyAsync(s, c->ks.scal, sizeof(s), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < 16; i++) scal_out[i] = s[i];
+  return 0;
+}
+// one launch of the coarse level through the launcher pc_solve itself uses, or a download of its matrices
+// (waiwera_hip_bench.h).  Vectors are host or device memory; a device vector is handed to the launcher as it is
+int wai_test_coarse(wai_ctx* c, int what, const double* in, double* out) {
+  if (!c || !out || what < WAI_COARSE_RESTRICT || what > WAI_COARSE_TIMES) return -2;
+  if (!in && what <= WAI_COARSE_PROLONG_SET) return -2;
+  LinSys& sys = c->flow;
+  CoarseLevel& k = c->coarse;
+  if (!pc_coarse(c, sys)) { c->err = "wai_test_coarse: no coarse level is in force (wai_set_pc_coarse)"; return -2; }
+  read_env(c);
+  if (what == WAI_COARSE_GEMV || what == WAI_COARSE_AC || what == WAI_COARSE_AINV || what == WAI_COARSE_TIMES)
+    if (c->ilu.owner != &sys) { const int e = do_pc_setup(c, sys); if (e) return e < 0 ? -1 : e; }
+  const size_t n = (size_t)sys.n, m = (size_t)k.m;
+  if (what == WAI_COARSE_TIMES) { out[0] = k.ms_galerkin; out[1] = k.ms_inverse; return 0; }
+  if (what == WAI_COARSE_AC || what == WAI_COARSE_AINV) {
+    HIPCHK(c, hipMemcpyAsync(out, what == WAI_COARSE_AC ? k.Ac.get() : k.Ainv.get(), m * m * sizeof(double), hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  VecArg vi{c}, vo{c};
+  int e = 0;
+  switch (what) {
+    case WAI_COARSE_RESTRICT:
+      if (vi.in(in, n, 0) || vo.out_only(out, m, 1)) return -1;
+      e = launch_coarse_restrict(c, k, vi.dev, vo.dev);
+      break;
+    case WAI_COARSE_GEMV:
+      if (vi.in(in, m, 0) || vo.out_only(out, m, 1)) return -1;
+      e = launch_coarse_gemv(c, k, vi.dev, vo.dev);
+      break;
+    default:
+      if (vi.in(in, m, 0) || vo.in(out, n, 1)) return -1;
+      e = launch_coarse_prolong(c, k, vi.dev, vo.dev, what == WAI_COARSE_PROLONG_ADD);
+  }
+  if (e) return e;
+  if (vo.back()) return -1;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 int wai_pc_axpy_capable(wai_ctx* c) { return c ? (pc_operand_composable(c) ? 1 : 0) : -2; }

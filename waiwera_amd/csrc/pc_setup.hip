@@ -282,11 +282,72 @@ static int colour_refusal(wai_ctx* c, const LinSys& sys, const PcOpts& pc) {
   return -2;
 }
 
+// What the coarse level (wai_set_pc_coarse) does not combine with, from the settings alone -- so every caller decides alike,
+// wai_set_pc_coarse when it is asked and the set-up for what was set since: null, or the party it met
+const char* coarse_refusal(const wai_ctx* c, bool at_setup) {
+  if (c->comm && c->comm->nranks > 1) return "more than one rank";
+  if (at_setup ? net_in_operator(c, c->flow) : (c->net.on && c->net.coupling))
+    return "source-network couplings in the operator (wai_set_network_couplings)";
+  if (c->opts.pc_type == WAI_PC_NONE) return "preconditioner none (WAI_PC_NONE)";
+  if (c->opts.pc_type == WAI_PC_LU) return "preconditioner lu (WAI_PC_LU)";
+  if (c->pc_ordering == WAI_PC_ORDER_MULTICOLOUR) return "the multicolour ordering (WAI_PC_ORDER_MULTICOLOUR)";
+  if (c->tr.nt > 0) return "auxiliary (tracer) systems (wai_set_tracers)";
+  return nullptr;
+}
+
+// The coarse level's lists on the device (c->coarse.h: build_coarse_space), its matrices and its work vectors
+int coarse_upload(wai_ctx* c) {
+  CoarseLevel& k = c->coarse;
+  const CoarseSpace& h = k.h;
+  k.m = h.nc * h.bs;
+  k.nblk = (int)h.c_colidx.size();
+  std::vector<int> blk_row(k.nblk);
+  for (int I = 0; I < h.nc; I++)
+    for (int b = h.c_rowptr[I]; b < h.c_rowptr[I + 1]; b++) blk_row[b] = I;
+  if (k.agg.upload(c, h.agg) || k.agg_ptr.upload(c, h.agg_ptr) || k.agg_rows.upload(c, h.agg_rows) || k.blk_row.upload(c, blk_row) ||
+      k.blk_col.upload(c, h.c_colidx) || k.ent_ptr.upload(c, h.ent_ptr) || k.ent_row.upload(c, h.ent_row) ||
+      k.ent_slot.upload(c, h.ent_slot))
+    return -1;
+  const size_t mm = (size_t)k.m * k.m;
+  if (k.Ac.alloc_zeroed(c, mm) || k.W.alloc_zeroed(c, mm) || k.Ainv.alloc_zeroed(c, mm) || k.prow.alloc_zeroed(c, k.m) ||
+      k.pcol.alloc_zeroed(c, k.m) || k.perm.alloc_zeroed(c, k.m) || k.src.alloc_zeroed(c, k.m) || k.rc.alloc_zeroed(c, k.m) ||
+      k.yc.alloc_zeroed(c, k.m) || k.t.alloc_zeroed(c, (size_t)c->flow.nl + 16) || k.w.alloc_zeroed(c, (size_t)c->flow.nl + 16))
+    return -1;
+  return 0;
+}
+
+// the coarse level's numeric set-up on the values in force: Ac = P^T A P, then its inverse (a zero pivot raises d_flags[0],
+// which do_pc_setup reads once for both levels).  The two parts are timed apart while profiling is on
+static int coarse_numeric(wai_ctx* c, const LinSys& sys) {
+  CoarseLevel& k = c->coarse;
+  k.ms_galerkin = k.ms_inverse = 0.f;   // (what an unprofiled set-up reports: WAI_COARSE_TIMES)
+  auto timed = [&](float& ms, auto&& run) -> int {
+    if (c->prof_on) (void)hipEventRecord(c->pev0, c->stream);
+    const int e = run();
+    if (c->prof_on) {
+      (void)hipEventRecord(c->pev1, c->stream);
+      (void)hipEventSynchronize(c->pev1);
+      (void)hipEventElapsedTime(&ms, c->pev0, c->pev1);
+      c->prof_ms[KC_PC_SETUP] += ms;
+      c->prof_n[KC_PC_SETUP] += 1;
+    }
+    return e;
+  };
+  if (timed(k.ms_galerkin, [&] { return launch_coarse_galerkin(c, sys.A, k); })) return -1;
+  return timed(k.ms_inverse, [&] { return launch_coarse_invert(c, k); });
+}
+
 // Sets the preconditioner up for `sys` and records it as the owner of the (shared) factor: 0 done, 1 a pivot failed
 // (recoverable; the record stands as it did for the flags read back last), < 0 error
 int do_pc_setup(wai_ctx* c, LinSys& sys) {
   read_env(c);
   const PcOpts pc = pc_of(c, sys);   // the system's own choice, or the flow solver's
+  if (pc_coarse(c, sys)) {
+    if (const char* met = coarse_refusal(c, true)) {
+      c->err = std::string("wai_set_pc_coarse: the coarse level serves the flow system under bjacobi or asm on one rank; it met ") + met;
+      return -2;
+    }
+  }
   if (pc.type == WAI_PC_NONE) { c->ilu.owner = &sys; return 0; }
   if (pc.type == WAI_PC_LU) {
     Prof p(c, KC_PC_SETUP);
@@ -327,6 +388,7 @@ int do_pc_setup(wai_ctx* c, LinSys& sys) {
       if (launch_ilu_factor_on(c, as.E, as.sched)) return -1;
     } else if (launch_ilu_factor_on(c, A, c->ilu)) return -1;
   }
+  if (pc_coarse(c, sys) && coarse_numeric(c, sys)) return -1;
   // The factor buffers are overwritten either way, so whoever owned them owns them no longer; `sys` owns them only when
   // every pivot inverted.  After a failed pivot the next solve, application or measurement sets up again and reports it.
   c->ilu.owner = nullptr;

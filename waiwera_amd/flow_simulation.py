@@ -15,6 +15,20 @@ from . import lib as _lib
 from .lib import LIB, WaiError
 
 
+def box_aggregates(ijk, boxes):
+    """aggregate of every cell of a structured mesh for set_pc_coarse: the cells' index range along every axis cut into
+    boxes[a] equal parts (the last ones shorter where it does not divide), numbered x-major; ijk: (n, 3) cell indices"""
+    ijk = np.asarray(ijk, dtype=np.int64)
+    boxes = tuple(int(b) for b in boxes)
+    if len(boxes) != 3 or min(boxes) < 1:
+        raise ValueError("boxes: three positive counts (nx, ny, nz)")
+    lo, hi = ijk.min(axis=0), ijk.max(axis=0) + 1
+    if any(boxes[a] > hi[a] - lo[a] for a in range(3)):
+        raise ValueError("boxes %r: more boxes than cells along an axis of extent %r" % (boxes, tuple((hi - lo).tolist())))
+    idx = [(ijk[:, a] - lo[a]) * boxes[a] // (hi[a] - lo[a]) for a in range(3)]
+    return ((idx[0] * boxes[1] + idx[1]) * boxes[2] + idx[2]).astype(np.int32)
+
+
 class FlowSimulation:
     def __init__(self, mesh, eos="we", opts=None, device=0, temperature=20.0,
                  relperm=("linear", [0.0, 1.0, 0.0, 1.0]), capillary=("zero", []), thermo="iapws",
@@ -635,6 +649,42 @@ class FlowSimulation:
         o, m = C.c_int(0), C.c_int(0)
         self._chk(LIB.wai_get_pc_ordering(self.h, C.byref(o), C.byref(m)), "pc_ordering")
         return {v: k for k, v in _lib.PC_ORDER.items()}[o.value], m.value
+
+    def set_pc_coarse(self, mode, aggregates=None, boxes=None):
+        """a coarse level for the flow system's preconditioner (wai_set_pc_coarse): mode "additive", "deflated" or "off"
+        (also None / False).  aggregates: the 0-based aggregate of every owned cell; or boxes=(nx, ny, nz) on a structured
+        mesh: the mesh cut into that many boxes per axis (box_aggregates).  One level, piecewise constant, Galerkin, the
+        coarse matrix inverted densely on the device: at most 1024 / block size aggregates.  What it does not combine with
+        is refused by name, and what was in force stays in force"""
+        mode = "off" if mode in (None, False) else mode
+        if mode not in _lib.PC_COARSE:
+            raise ValueError("pc coarse mode %r: one of %s" % (mode, sorted(_lib.PC_COARSE)))
+        if mode == "off":
+            self._chk(LIB.wai_set_pc_coarse(self.h, 0, 0, None), "set_pc_coarse")
+            return
+        if (aggregates is None) == (boxes is None):
+            raise ValueError("set_pc_coarse: give either aggregates or boxes")
+        if boxes is not None:
+            if getattr(self.mesh, "owned_ijk", None) is None:
+                raise ValueError("set_pc_coarse: boxes need a structured mesh (owned_ijk); give aggregates")
+            aggregates = box_aggregates(self.mesh.owned_ijk, boxes)
+        agg = _lib._i32(aggregates)
+        if agg.size != self.n_owned:
+            raise ValueError("set_pc_coarse: %d aggregates for %d owned cells" % (agg.size, self.n_owned))
+        nc = int(agg.max()) + 1 if agg.size else 0
+        self._chk(LIB.wai_set_pc_coarse(self.h, _lib.PC_COARSE[mode], nc, agg.ctypes.data_as(_lib.pi)), "set_pc_coarse")
+
+    def pc_coarse(self):
+        """(mode, nc): the coarse level's setting and its number of aggregates, ("off", 0) by default"""
+        m, nc = C.c_int(0), C.c_int(0)
+        self._chk(LIB.wai_get_pc_coarse(self.h, C.byref(m), C.byref(nc)), "pc_coarse")
+        return {v: k for k, v in _lib.PC_COARSE.items()}[m.value], nc.value
+
+    def test_coarse(self, what, vin, out):
+        """one piece of the coarse level alone (wai_test_coarse): what is a key of lib.COARSE_WHAT; vin / out are float64
+        numpy arrays or torch tensors on the device, out written in place; returns the library's code (1: a pivot failed)"""
+        return self._chk(LIB.wai_test_coarse(self.h, _lib.COARSE_WHAT[what], None if vin is None else _lib.ptr(vin), _lib.ptr(out)),
+                         "test_coarse")
 
     def set_pc_tiles(self, tile_ptr):
         """tiles of the preconditioner's subdomains (wai_set_pc_tiles): contiguous owned-row ranges of 1 .. 1024 rows from 0 to

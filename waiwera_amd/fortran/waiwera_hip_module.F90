@@ -571,6 +571,20 @@ module waiwera_hip_module
        type(c_ptr), value :: ctx
        integer(c_int), intent(out) :: ordering, max_colours
      end function wai_get_pc_ordering
+     ! a coarse level for the flow system's preconditioner: mode WAI_PC_COARSE_OFF (0, default) | _ADDITIVE (1) | _DEFLATED (2),
+     ! agg(n_owned) the 0-based aggregate of every owned cell, 0 <= agg < nc, nc * block size <= 1024.  Not the reference's
+     integer(c_int) function wai_set_pc_coarse(ctx, mode, nc, agg) bind(c, name = "wai_set_pc_coarse")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: mode, nc
+       integer(c_int), intent(in) :: agg(*)
+     end function wai_set_pc_coarse
+     ! the mode, and the number of aggregates (0 while off)
+     integer(c_int) function wai_get_pc_coarse(ctx, mode, nc) bind(c, name = "wai_get_pc_coarse")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int), intent(out) :: mode, nc
+     end function wai_get_pc_coarse
      ! where the source network's pass runs: WAI_NETWORK_PASS_HOST (0, default) | WAI_NETWORK_PASS_DEVICE (1): one launch
      ! walks the network in LDS, and the coupling build waits once per Jacobian.  In force on one rank, for a network that fits
      integer(c_int) function wai_set_network_pass(ctx, where) bind(c, name = "wai_set_network_pass")
@@ -693,7 +707,7 @@ module waiwera_hip_module
        wai_max_scaled, wai_tracer_system, wai_synchronize, wai_network_evaluate
   public :: wai_set_tracers, wai_set_tracer_bc, wai_set_tracer_injection, wai_set_aux_solver
   public :: wai_set_tracer_solve_mode, wai_tracer_block_system, wai_set_sub_pc, wai_set_aux_pc, wai_get_aux_pc
-  public :: wai_set_pc_tiles, wai_set_pc_ordering, wai_get_pc_ordering
+  public :: wai_set_pc_tiles, wai_set_pc_ordering, wai_get_pc_ordering, wai_set_pc_coarse, wai_get_pc_coarse
   public :: wai_set_network_pass, wai_get_network_pass
   public :: wai_set_coupling_build, wai_get_coupling_build
   public :: wai_set_network_walk, wai_get_network_walk

@@ -29,6 +29,8 @@ THERMO = {"iapws": 0, "ifc67": 1}   # "thermodynamics" (src/thermodynamics_setup
 TRACER_SOLVE = {"per_tracer": 0, "coupled": 1}   # wai_set_tracer_solve_mode
 SUB_PC = {"ilu": 0, "lu": 1}   # wai_set_sub_pc: sub-preconditioner of bjacobi / asm
 PC_ORDER = {"natural": 0, "multicolour": 1}   # wai_set_pc_ordering: elimination order of the flow system's block-Jacobi ILU(0)
+PC_COARSE = {"off": 0, "additive": 1, "deflated": 2}   # wai_set_pc_coarse: the flow preconditioner's coarse level
+COARSE_WHAT = {"restrict": 0, "gemv": 1, "prolong_add": 2, "prolong_set": 3, "ac": 4, "ainv": 5, "times": 6}   # wai_test_coarse
 NETWORK_PASS = {"host": 0, "device": 1}   # wai_set_network_pass: where the source network's pass runs
 NETWORK_WALK = {"lane": 0, "wave": 1}   # wai_set_network_walk: how the device pass walks groups and reinjectors
 COUPLING_BUILD = {"columns": 0, "batched": 1}   # wai_set_coupling_build: how the network's Jacobian blocks are built
@@ -201,6 +203,9 @@ def _load():
         "wai_set_pc_tiles": (i32, [vp, i32, pi]),
         "wai_set_pc_ordering": (i32, [vp, i32]),
         "wai_get_pc_ordering": (i32, [vp, pi, pi]),
+        "wai_set_pc_coarse": (i32, [vp, i32, i32, pi]),
+        "wai_get_pc_coarse": (i32, [vp, pi, pi]),
+        "wai_test_coarse": (i32, [vp, i32, vp, vp]),
         "wai_set_network_pass": (i32, [vp, i32]),
         "wai_get_network_pass": (i32, [vp, pi, pi]),
         "wai_set_network_walk": (i32, [vp, i32]),

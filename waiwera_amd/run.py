@@ -42,6 +42,11 @@ def main(argv=None):
     ap.add_argument("--pc-ordering", choices=("natural", "multicolour"), default="natural",
                     help="elimination order of the flow solver's block-Jacobi ILU(0): as numbered (default, the reference's) or "
                          "multicolour (two sweep levels per block on hexahedral and MINC meshes; bjacobi with ILU(0) only)")
+    ap.add_argument("--pc-coarse", choices=("additive", "deflated"), default=None,
+                    help="a coarse level for the flow solver's preconditioner: piecewise constant over aggregates of cells, Galerkin, "
+                         "added to (additive) or deflating (deflated) the one-level preconditioner (default: none; one rank, bjacobi or asm)")
+    ap.add_argument("--coarse-aggregates", type=int, default=64,
+                    help="aggregates of the coarse level, from the coordinate bisection of the cells (default 64; at most 1024 / block size)")
     ap.add_argument("--network-pass", choices=("host", "device"), default="host",
                     help="the source network's pass: on the host (default) or in one launch on the device (one rank, a network "
                          "that fits a workgroup's LDS; the same results)")
@@ -75,7 +80,8 @@ def main(argv=None):
     sim = Simulation.from_json(a.input, device=a.device, tracer_solve=a.tracer_solve, sub_lu=a.sub_lu, subdomains=a.subdomains,
                                default_aux_pc=None if a.aux_pc == "follow" else a.aux_pc, pc_ordering=a.pc_ordering, network_pass=a.network_pass,
                                cell_order=a.cell_order, subdomain_rows=a.subdomain_rows,
-                               coupling_build=a.coupling_build, network_walk=a.network_walk, **kw)
+                               coupling_build=a.coupling_build, network_walk=a.network_walk, pc_coarse=a.pc_coarse,
+                               coarse_aggregates=a.coarse_aggregates, **kw)
     out = sim.run()
     if rank != 0:
         if a.output:

@@ -349,6 +349,39 @@ def linear_solver_options(obj, default_pc, sub_lu="host", defaults=None):
     return dict(opts=opts, sub_device=sub_device, pc=pct, named=pct_in is not None, note=note)
 
 
+def pc_coarse_refusal(lso, has_network, world, has_tracers, multicolour):
+    """what the coarse level (pc_coarse="additive" | "deflated", wai_set_pc_coarse) does not combine with, from the input's
+    solver object and the arguments alone, so every rank decides alike: None, or the refusal's text"""
+    met = None
+    if world > 1:
+        met = "more than one rank"
+    elif has_network:
+        met = "a source network (its couplings are part of the operator)"
+    elif lso["opts"].get("pc_type") in ("none", "lu"):
+        met = "preconditioner %r" % lso["opts"]["pc_type"]
+    elif multicolour:
+        met = "pc_ordering 'multicolour'"
+    elif has_tracers:
+        met = "tracers (the auxiliary systems)"
+    return None if met is None else "pc_coarse serves the flow solver under bjacobi or asm on one rank; the input and arguments give " + met
+
+
+def coarse_aggregates_of(lm, n_aggregates):
+    """aggregates for the coarse level from the library's coordinate bisection (wai_cell_order with the cap
+    ceil(n / n_aggregates)): the aggregate of every owned cell, its leaves numbered in order.  The cell order handed to the
+    library is not changed"""
+    from . import lib as wl
+    n = lm.n_owned
+    if n_aggregates < 1:
+        raise ValueError("coarse_aggregates: at least 1")
+    faces = np.asarray(lm.face_cells).reshape(-1, 2)
+    interior = faces[(faces[:, 0] < n) & (faces[:, 1] < n)]
+    perm, leaves = wl.cell_order(interior, np.asarray(lm.cell_geom)[:n, :3], -(-n // int(n_aggregates)))
+    agg = np.empty(n, dtype=np.int32)
+    agg[perm] = np.repeat(np.arange(len(leaves) - 1), np.diff(leaves))
+    return agg
+
+
 def pc_ordering_refusal(lso, has_network):
     """what the multicolour ordering (pc_ordering="multicolour", wai_set_pc_ordering) does not combine with, from
     linear_solver_options' result for the flow solver and whether the input has a source network: a sentence that names the
@@ -657,7 +690,8 @@ class Simulation:
     def __init__(self, inp, base_dir=".", ode_factory=None, device=0, mesh_builder=None, mesh_file=None,
                  output_dir=None, rank=0, world=1, comm_id=None, owner=None, default_pc="asm", tracer_solve="per_tracer",
                  sub_lu="host", default_aux_pc=None, subdomains="chunks", pc_ordering="natural", network_pass="host",
-                 cell_order="input", subdomain_rows=None, coupling_build="columns", network_walk="lane"):
+                 cell_order="input", subdomain_rows=None, coupling_build="columns", network_walk="lane", pc_coarse=None,
+                 coarse_aggregates=64):
         """rank / world / comm_id (wai_comm_unique_id of rank 0, handed round by the host): one process per rank, each
         reads the whole input, keeps its own cells with one ghost layer (waiwera_amd.partition.partition_mesh; owner: rank of
         every cell, default contiguous blocks of the input's numbering; a MINC mesh: per input cell, or per cell in the
@@ -694,6 +728,14 @@ class Simulation:
         if pc_ordering not in ("natural", "multicolour"):
             raise ValueError("pc_ordering 'natural' (the default) or 'multicolour'")
         self.pc_ordering = pc_ordering
+        # pc_coarse: a coarse level for the flow solver's preconditioner -- None (the default: one level, as before),
+        # "additive" or "deflated" (wai_set_pc_coarse: piecewise constant over coarse_aggregates aggregates from the library's
+        # coordinate bisection, Galerkin, inverted densely on the device; another preconditioner, so other Krylov counts).
+        # Not a key of the input file: the reference has none.  What it does not combine with is refused when the solver
+        # options are read (pc_coarse_refusal); pc_choice records the mode and the number of aggregates
+        if pc_coarse not in (None, "additive", "deflated"):
+            raise ValueError("pc_coarse None (the default), 'additive' or 'deflated'")
+        self.pc_coarse, self.coarse_aggregates = pc_coarse, int(coarse_aggregates)
         # network_pass: where the source network's pass runs -- "host" (the default, as before) or "device"
         # (wai_set_network_pass: one launch in LDS, the coupling build without waits inside; the same bits).  Not a key of the
         # input file.  network_pass_choice records (requested, in force) once the network is set: "host" stays in force on
@@ -1093,6 +1135,14 @@ class Simulation:
                 raise NotImplementedError(refusal)
             self.ode.set_pc_ordering("multicolour")
             self.pc_choice += ("multicolour ordering of the blocks' ILU(0) (wai_set_pc_ordering)",)
+        if self.pc_coarse is not None:
+            net = self.inp.get("network") or {}
+            refusal = pc_coarse_refusal(lso, bool(net.get("group") or net.get("reinject")), self.world, bool(self.inp.get("tracer")),
+                                        self.pc_ordering == "multicolour")
+            if refusal:
+                raise NotImplementedError(refusal)
+            self.ode.set_pc_coarse(self.pc_coarse, aggregates=coarse_aggregates_of(lm, self.coarse_aggregates))
+            self.pc_choice += ("coarse level %s over %d aggregates (wai_set_pc_coarse)" % self.ode.pc_coarse(),)
         self._pc_covers_coupled = covers_coupled(lso)
         # the auxiliary (tracer) solver: "time.step.solver.auxiliary", the same keys (src/timestepper.F90:2057-2065).  The
         # reference's defaults for it are gmres and bjacobi (:2021-2022) whatever the flow solver uses; the library's tracer
